@@ -13,6 +13,12 @@ frame is split into N row bands (rank r owns rows [r*H/N, (r+1)*H/N)), every
 rank bins all triangles against its band, and the colour strips are gathered
 to rank 0 over RCCL ("scaling": "strong": total work fixed).
 
+A plain run sets up, warms up, times `--steps` frames and prints the result
+line.  `--full` adds everything that takes runs of its own: the serial
+per-kernel frames, the frame download timing, the roofline's committed
+counter figures, the CPU baseline and (`--check 1`) the oracle comparison.
+`--dump-outputs DIR` writes what the last timed frame left in the target.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -40,15 +46,24 @@ def parse():
     ap.add_argument("--radius", type=float, default=16.0)
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--tile", type=str, default="")
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU path (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: serial per-kernel frames, frame "
+                         "download, roofline counter figures, the CPU baseline, --check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last frame's colour and z (what the caller's target "
+                         "holds) as DIR/color.npy, DIR/z.npy (float32; a seeded pixel sample of a large frame)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU path (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-max-tris", type=int, default=1_000_000,
                     help="bound on the CPU sample (triangles of the same scene)")
-    ap.add_argument("--check", type=int, default=0, help="compare the frame with the oracle")
+    ap.add_argument("--check", type=int, default=0, help="with --full: compare the frame with the oracle")
     ap.add_argument("--comm", choices=("torch", "prk"), default="torch",
                     help="N > 1 strip gather: torch.distributed P2P (RCCL) or the C-ABI's prk_gather_frame "
                          "(RCCL from libprk_hip.so)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.check and not a.full:
+        ap.error("--check needs --full")
+    return a
 
 
 def algorithmic_bytes(T, W, rows, tex_texels):
@@ -237,6 +252,35 @@ def cpu_baseline(scene, threads, max_tris, frames=3, scan=(16, 64)):
                 span_pixels=st["span_pixels"] if n == T else None, **topo)
 
 
+DUMP_MAX_PIXELS = 1 << 21  # 20 B a pixel dumped (4 colour bytes + z, float32): 42 MB at most
+
+
+def _dump_pixels(flat, seed=0):
+    """Every pixel of a frame of at most DUMP_MAX_PIXELS, else a fixed sample
+    of that many (seeded indices: the same pixels in every run)."""
+    n = flat.shape[0]
+    if n <= DUMP_MAX_PIXELS:
+        return flat
+    return flat[np.random.default_rng(seed).integers(0, n, size=DUMP_MAX_PIXELS)]
+
+
+def dump_outputs(path, color, z):
+    """The caller's target after the last timed frame: `color` (int32 pixels,
+    rank 0's band or the gathered frame) as float32 [..., 4] of its four
+    bytes in memory order, `z` (rank 0's band) as float32.  Frames of more than
+    DUMP_MAX_PIXELS are written as [DUMP_MAX_PIXELS(, 4)] samples."""
+    os.makedirs(path, exist_ok=True)
+    c = color.cpu().numpy()
+    zz = z.cpu().numpy()
+    if c.size <= DUMP_MAX_PIXELS:
+        cb = c.view(np.uint8).reshape(c.shape + (4,))
+    else:
+        cb = _dump_pixels(c.reshape(-1)).view(np.uint8).reshape(-1, 4)
+        zz = _dump_pixels(zz.reshape(-1))
+    np.save(os.path.join(path, "color.npy"), cb.astype(np.float32))
+    np.save(os.path.join(path, "z.npy"), np.ascontiguousarray(zz, dtype=np.float32))
+
+
 def main():
     a = parse()
     import torch
@@ -361,19 +405,26 @@ def main():
     ms_vis = stats["sum_ms_vis"] / nt
     ms_span = stats["sum_ms_span"] / nt
     ms_pix = ms_raster - ms_vis - ms_span
+    if a.dump_outputs:  # the last timed frame, before --full draws any more
+        r.synchronize()  # the frame's bin count is read (an overflowed frame re-run) before torch reads the target
+        if rank == 0:
+            last = (nstep[0] - 1) % nbuf
+            dump_outputs(a.dump_outputs, frames[last] if world > 1 else colors[last], zbuf)
     # Serial kernel times (outside the timed region): the same frame with the
     # host waiting for each frame, so no kernel overlaps another frame's.
-    r.timing_reset()
-    for _ in range(5):
-        step()
-        drain()
-        torch.cuda.synchronize()
-    ss = r.stats()
-    ns = max(1, ss["frames_timed"])
-    serial = {"k_bin_phase": ss["sum_ms_bin"] / ns, "k_vis": ss["sum_ms_vis"] / ns,
-              "k_walk": ss["sum_ms_span"] / ns,
-              "k_pix": (ss["sum_ms_raster"] - ss["sum_ms_vis"] - ss["sum_ms_span"]) / ns,
-              "raster": ss["sum_ms_raster"] / ns}
+    serial = None
+    if a.full:
+        r.timing_reset()
+        for _ in range(5):
+            step()
+            drain()
+            torch.cuda.synchronize()
+        ss = r.stats()
+        ns = max(1, ss["frames_timed"])
+        serial = {"k_bin_phase": ss["sum_ms_bin"] / ns, "k_vis": ss["sum_ms_vis"] / ns,
+                  "k_walk": ss["sum_ms_span"] / ns,
+                  "k_pix": (ss["sum_ms_raster"] - ss["sum_ms_vis"] - ss["sum_ms_span"]) / ns,
+                  "raster": ss["sum_ms_raster"] / ns}
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -382,17 +433,19 @@ def main():
     # Frame download (colour + z of this rank's band, HBM -> host), outside
     # the timed region: reported separately.
     r.synchronize()  # the last frame's bin count is read (an overflowed frame re-run) before torch reads the target
-    host_c = torch.empty(color.shape, dtype=color.dtype, pin_memory=True)
-    host_z = torch.empty(zbuf.shape, dtype=zbuf.dtype, pin_memory=True)
-    torch.cuda.synchronize()
-    t_dn = time.perf_counter()
-    host_c.copy_(color, non_blocking=True)
-    host_z.copy_(zbuf, non_blocking=True)
-    torch.cuda.synchronize()
-    ms_download = (time.perf_counter() - t_dn) * 1e3
+    ms_download = None
+    if a.full:
+        host_c = torch.empty(color.shape, dtype=color.dtype, pin_memory=True)
+        host_z = torch.empty(zbuf.shape, dtype=zbuf.dtype, pin_memory=True)
+        torch.cuda.synchronize()
+        t_dn = time.perf_counter()
+        host_c.copy_(color, non_blocking=True)
+        host_z.copy_(zbuf, non_blocking=True)
+        torch.cuda.synchronize()
+        ms_download = (time.perf_counter() - t_dn) * 1e3
 
     check = None
-    if a.check and rank == 0 and world == 1:
+    if a.full and a.check and rank == 0 and world == 1:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
         oc, oz, _, _ = O.render(scene, threads=min(16, os.cpu_count() or 1), winners=False)
@@ -413,8 +466,6 @@ def main():
     # Roofline of the whole frame (every kernel of the step): SURVEY §8(d)'s
     # algorithmic bytes per frame over the measured time per frame.
     achieved = alg / (ms * 1e-3) / 1e9
-    cfg_key = "%dx%d_T%d_r%g_N%d" % (W, H, T, a.radius, world)
-    traffic, traffic_src = load_traffic(cfg_key)
     out = {
         "metric": "Mpixels/s shaded (+ Mtri/s) at 4096x4096, 1M tris; 1/2/4/8 GPUs",
         "value": W * H / (ms * 1e-3) / 1e6,
@@ -445,11 +496,11 @@ def main():
         "ms_bin_overlapped": ms_bin,
         "ms_raster_overlapped": ms_raster,
         "ms_kernels_overlapped": {"k_vis": ms_vis, "k_walk": ms_span, "k_pix": ms_pix},
-        # serial: 5 more frames with the host waiting after each one
+        # serial (--full): 5 more frames with the host waiting after each one
         "ms_kernels_serial": serial,
         "bin_entries": int(stats["bin_entries"]),
         "ms_upload": ms_upload,
-        "ms_download": ms_download,
+        "ms_download": ms_download,  # --full
         # Whole frame against HBM: SURVEY §8(d) algorithmic bytes / ms_per_step.
         # `bound` names the roofline `frac` is priced on (the contract's
         # hbm|mfma); what actually limits the frame is `limiter`: the dominant
@@ -459,24 +510,29 @@ def main():
         "roofline": {"bound": "hbm", "limiter": "valu-issue (k_vis); no kernel of the frame is HBM-bound",
                      "kernel": "whole frame (binning + k_vis + k_walk + k_pix)",
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes": alg,
-                     "dominant_kernel": {"name": "k_vis", "ms_serial": serial["k_vis"],
-                                         "share_of_serial_frame": serial["k_vis"] / max(
-                                             1e-9, serial["raster"] + serial["k_bin_phase"])},
-                     # the frame's algorithmic bytes over the dominant kernel's
-                     # own serial time (HIP events on its stream, host-synchronised
-                     # frames; rocprofv3 of the same frames:
-                     # profiles/r06/kernel_stats_serial.csv)
-                     "dominant_frac": alg / (serial["k_vis"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     # the binding resource of the dominant kernel: issued VALU
-                     # (SQ counters of the committed round profile)
-                     "valu": load_valu(cfg_key, "k_vis", ms),
-                     # every kernel's VALU time over the frame (SQ counters)
-                     "valu_frame": load_valu_frame(cfg_key, ms)},
+                     "algorithmic_bytes": alg},
     }
+    if a.full:
+        cfg_key = "%dx%d_T%d_r%g_N%d" % (W, H, T, a.radius, world)
+        traffic, traffic_src = load_traffic(cfg_key)
+        out["roofline"].update({
+            "traffic": traffic, "traffic_source": traffic_src,
+            "dominant_kernel": {"name": "k_vis", "ms_serial": serial["k_vis"],
+                                "share_of_serial_frame": serial["k_vis"] / max(
+                                    1e-9, serial["raster"] + serial["k_bin_phase"])},
+            # the frame's algorithmic bytes over the dominant kernel's
+            # own serial time (HIP events on its stream, host-synchronised
+            # frames; rocprofv3 of the same frames:
+            # profiles/r06/kernel_stats_serial.csv)
+            "dominant_frac": alg / (serial["k_vis"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            # the binding resource of the dominant kernel: issued VALU
+            # (SQ counters of the committed round profile)
+            "valu": load_valu(cfg_key, "k_vis", ms),
+            # every kernel's VALU time over the frame (SQ counters)
+            "valu_frame": load_valu_frame(cfg_key, ms)})
     if check is not None:
         out["check"] = check
-    if a.cpu_baseline and world == 1:
+    if a.full and a.cpu_baseline and world == 1:
         threads = a.cpu_threads or len(os.sched_getaffinity(0))
         cb = cpu_baseline(scene, threads, a.cpu_max_tris)
         out["cpu_baseline"] = cb

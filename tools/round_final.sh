@@ -8,7 +8,7 @@ o=gpurun_out/final_$tag
 mkdir -p $o
 exec tools/gpu_run.sh \
   "600|final_gt|python -u -m pytest tests -m gpu -q -x --timeout 200 --timeout-method thread" \
-  "300|final_bench|python3 bench.py > $o/bench.log 2>&1 && tail -1 $o/bench.log" \
+  "300|final_bench|python3 bench.py --full > $o/bench.log 2>&1 && tail -1 $o/bench.log" \
   "300|final_band_c3b|python3 tools/time_band.py --scene c3b --json $o/band_c3b_final.json" \
   "300|final_band_c5|python3 tools/time_band.py --scene c5 --json $o/band_c5_final.json" \
   "300|final_objects|python3 tools/time_objects.py --json $o/objects_final.json" \
