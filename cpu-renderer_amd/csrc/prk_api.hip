@@ -336,6 +336,11 @@ struct prk_context {
         uint32_t *h_rb = nullptr;  // pinned readback words
         char *h_cls = nullptr;     // pinned: the large objects' most active entries, then their walk groups
         size_t cls_cap = 0;
+        // debug (prk_debug_walk_routes): the last pass with large objects --
+        // objects per walk class, objects sized by k_maxact_huge_*, and the
+        // first large object's (most, rows, entries) as read back
+        uint32_t walk_routes[9] = {};
+        int32_t walk_sizes[3] = {};
     } spans;
 };
 
@@ -1247,6 +1252,14 @@ int prk_debug_counters(prk_context *c, uint64_t *out, int32_t n) {
     return PRK_OK;
 }
 
+int prk_debug_walk_routes(prk_context *c, uint32_t *out, int32_t n) {
+    if (!c || !out || n < 0 || n > 12) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);
+    const prk_context::SpanScratch &S = c->spans;
+    for (int i = 0; i < n; ++i) out[i] = i < 9 ? S.walk_routes[i] : (uint32_t)S.walk_sizes[i - 9];
+    return PRK_OK;
+}
+
 // The frame parameters every pass of a flush shares (camera, lights, target, tiling).
 static void frame_params(const prk_context *c, prk::FrameParams &fp) {
     fp = prk::FrameParams{};
@@ -1939,8 +1952,10 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         const uint32_t kMaxactHugeEdges = henv ? (uint32_t)std::max(1l, std::atol(henv)) : (1u << 18);
         PRK_TRY(prk_obj_maxact(&fp, d_objs, d_big, nbig_all, escan, total0p, S.d_work.p, (int32_t *)S.d_most.p,
                                kMaxactHugeEdges, s));
+        for (uint32_t &r : S.walk_routes) r = 0;  // (prk_debug_walk_routes: this pass's)
         for (uint32_t b = 0; b < nbig_all; ++b)
             if (big_edges[b] >= kMaxactHugeEdges) {
+                ++S.walk_routes[8];
                 PRK_TRY(S.d_mhuge.ensure(prk_maxact_huge_scratch()));
                 PRK_TRY(prk_obj_maxact_huge(&fp, d_objs, d_big, b, nbig_all, big_edges[b], escan, total0p,
                                             S.d_work.p, (int32_t *)S.d_most.p, S.d_mhuge.p, s));
@@ -1999,6 +2014,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         const bool big_on = !(benv && benv[0] == '0'), lds_on = !(lenv && lenv[0] == '0');
         const int64_t big_min = menv ? std::atoll(menv) : INT64_MAX;
         const int32_t *h_rows = h_most + nbig_all, *h_ents = h_most + 2 * (size_t)nbig_all;
+        if (nbig_all) {
+            S.walk_sizes[0] = h_most[0];
+            S.walk_sizes[1] = h_rows[0];
+            S.walk_sizes[2] = h_ents[0];
+        }
         static const uint32_t kCaps[] = {62, 126, 254, 510, 1022};
         uint32_t k = 0, b = 0;
         for (int mo = 0; mo < prk::MODE_COUNT; ++mo) {
@@ -2038,6 +2058,7 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                         pool += huge ? prk_big_slice_ints(cap, (uint32_t)rows, (uint32_t)ents)
                                      : (uint64_t)kWaveListArrays * (cap + 2);
                     if (huge) gmax = std::max(gmax, (uint32_t)rows);
+                    ++S.walk_routes[ci];
                     ++k;
                 }
                 if (k > start) groups.push_back(Group{mo, capc, start, k - start, ci == 5 || ci == 6, gmax, ci == 5});

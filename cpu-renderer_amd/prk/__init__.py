@@ -90,6 +90,7 @@ _SIGS = {
     "prk_set_early_z": (C.c_int, [C.c_void_p, C.c_int]),
     "prk_download_winners": (C.c_int, [C.c_void_p, C.c_void_p]),
     "prk_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
+    "prk_debug_walk_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]),
     "prk_set_tile": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "prk_construct_sphere": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_uint32)]),
@@ -585,10 +586,28 @@ class Renderer:
         _check("prk_debug_counters", self._L.prk_debug_counters(self._h, out, n))
         return list(out)
 
+    def walk_routes(self):
+        """Which walk the large objects of the last flush that had any took
+        (prk_debug_walk_routes): objects per class -- slots (the five LDS slot
+        classes), huge_lds, huge_mem, wave -- how many were sized by the
+        many-workgroup histogram (sized_huge), and the first large object's
+        sizes as the device counted them (most, rows, ents)."""
+        out = (C.c_uint32 * 12)()
+        _check("prk_debug_walk_routes", self._L.prk_debug_walk_routes(self._h, out, 12))
+        sizes = [v - (1 << 32) if v >> 31 else v for v in out[9:12]]  # (int32_t bits)
+        return dict(slots=tuple(out[0:5]), huge_lds=out[5], huge_mem=out[6], wave=out[7], sized_huge=out[8],
+                    most=sizes[0], rows=sizes[1], ents=sizes[2])
+
     def stats(self):
         s = abi.PrkStats()
         _check("prk_get_stats", self._L.prk_get_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in abi.PrkStats._fields_}
+
+
+class Stats(dict):
+    """render_scene's stats: prk_get_stats as a dict, and the flush's walk
+    routes (Renderer.walk_routes) as the attribute walk_routes."""
+    walk_routes = None
 
 
 def render_scene(scene, semantics=abi.PRK_SEM_AVX, phong=True, device=0, tile=None, debug=True,
@@ -635,6 +654,8 @@ def render_scene(scene, semantics=abi.PRK_SEM_AVX, phong=True, device=0, tile=No
         r.synchronize()
         col, zb = r.download()
         win = r.winners() if debug else None
-        return col, zb, win, r.stats()
+        st = Stats(r.stats())
+        st.walk_routes = r.walk_routes()
+        return col, zb, win, st
     finally:
         r.close()

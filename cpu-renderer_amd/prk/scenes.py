@@ -240,6 +240,70 @@ def slivers(n_tris, width, height, seed=0, textured=True):
                  name="slivers%d_%dx%d_s%d" % (n, width, height, seed), meta=dict(kind="slivers", seed=seed))
 
 
+def comb(groups, width, height, seed=0, textured=True, kink=0.03):
+    """Long active edge lists with many insertions on chosen rows: groups of
+    tall thin slivers, apex up.  groups: [(count, apex_row, base_lo, base_hi),
+    ...] -- a group's `count` slivers have their apexes in row `apex_row` (two
+    edges each enter the list there, so a group of 512 or more outgrows one
+    insertion window of 1024) and their bases uniform over rows [base_lo,
+    base_hi), where the edges expire one by one.  Centres are uniform in x
+    across the screen, so a group's edges interleave with the listed ones;
+    half-widths of 0.3 to 3 px and a lean of up to 4 px make neighbours cross
+    on the way down (the swap passes).  A `kink` fraction have their apex
+    one row higher and one base vertex pulled up into the apex row: two edges
+    enter on the row above and one on the apex row, so per-row counts of
+    either parity can be had.  The
+    triangle order is shuffled.  z, normals, uvs, colours and texture as in
+    random_soup / slivers.  Exact per-row counts come from a census of the
+    edge table, not from these parameters (rounding decides an edge's row)."""
+    rng = np.random.default_rng(seed)
+    cam = default_camera(width, height)
+    parts = []
+    for count, apex_row, base_lo, base_hi in groups:
+        n = int(count)
+        cx = rng.uniform(2.0, width - 2.0, n)
+        lean = rng.uniform(-4.0, 4.0, n)
+        hw = rng.uniform(0.3, 3.0, n)
+        ya = apex_row + rng.uniform(-0.35, 0.35, n)
+        yb = rng.uniform(base_lo, base_hi, n)
+        s = np.empty((n, 3, 2))
+        s[:, 0] = np.stack([cx, ya], 1)
+        s[:, 1] = np.stack([cx + lean - hw, yb + rng.uniform(-0.45, 0.45, n)], 1)
+        s[:, 2] = np.stack([cx + lean + hw, yb + rng.uniform(-0.45, 0.45, n)], 1)
+        k = rng.random(n) < kink
+        s[k, 1, 0] = cx[k] - 0.25 * hw[k]
+        s[k, 1, 1] = ya[k]
+        s[k, 0, 1] = ya[k] - 1.0
+        parts.append(s)
+    s = np.concatenate(parts)
+    s = s[rng.permutation(len(s))]
+    n = len(s)
+    e1 = s[:, 1] - s[:, 0]
+    e2 = s[:, 2] - s[:, 0]
+    flip = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0] > 0
+    s[flip, 1], s[flip, 2] = s[flip, 2].copy(), s[flip, 1].copy()
+    z = rng.uniform(-0.8, 0.8, n)[:, None] + rng.uniform(-0.1, 0.1, (n, 3))
+    x, y = _unproject(s[..., 0], s[..., 1], z, cam)
+    verts = np.stack([x, y, z], -1).reshape(-1, 3).astype(np.float32)
+    nrm = rng.normal(size=(3 * n, 3))
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    uvs = rng.uniform(0.0, 1.0, (3 * n, 2)).astype(np.float32)
+    cols = rng.uniform(0.0, 1.0, (3 * n, 4)).astype(np.float32)
+    cols[:, 3] = 1.0
+    tex = random_texture(rng, 64, 64) if textured else None
+    return Scene(width, height, verts, cols, nrm.astype(np.float32), uvs, cam, LIGHTS_ONE, AMBIENT_ONE, tex,
+                 name="comb%d_%dx%d_s%d" % (n, width, height, seed), meta=dict(kind="comb", seed=seed))
+
+
+def select_triangles(scene, keep):
+    """The scene with the triangles whose indices `keep` lists, in that order."""
+    k = np.asarray(keep, np.int64)
+    pick = lambda a: a.reshape(scene.tri_count, 3, -1)[k].reshape(3 * len(k), -1).copy()  # noqa: E731
+    return Scene(scene.width, scene.height, pick(scene.vertices), pick(scene.colors), pick(scene.normals),
+                 pick(scene.uvs), scene.transform, scene.lights, scene.ambient, scene.texture, scene.P,
+                 scene.name + "[%d kept]" % len(k), dict(scene.meta))
+
+
 def procedural_texture(rng, size, kind):
     """A 1024^2-style material texture (uint32 ARGB, zeroed guard row):
     checker / brick / stripes / noise patterns with per-texel noise."""

@@ -412,6 +412,16 @@ int prk_download_winners(prk_context *ctx, int32_t *winners_host);
 /* Debug: the raster kernels' phase cycle counters (written only by builds
  * with -DPRK_PROF; zeroed by prk_timing_reset), n <= 16. */
 int prk_debug_counters(prk_context *ctx, uint64_t *out, int32_t n);
+/* Debug/test: which walk the large objects (whole-object draws of 64
+ * triangles or more) of the most recent flush that had any were given, from
+ * the host's bookkeeping (no kernel reports in).  out[0..4]: objects in the
+ * workgroup walk's LDS slot classes of 62 / 126 / 254 / 510 / 1022 entries;
+ * out[5]: the huge-object walk with the list in LDS; out[6]: the same with
+ * the list in device memory; out[7]: one wave each; out[8]: objects whose
+ * sizes the many-workgroup histogram counted; out[9..11]: the first large
+ * object's most active edges, rows and list entries as read back (int32_t
+ * bits; INT32_MAX: past the histogram).  n <= 12 words are written. */
+int prk_debug_walk_routes(prk_context *ctx, uint32_t *out, int32_t n);
 
 /* Test: the raster kernels divide several values by one divisor through a
  * shared reciprocal; this checks n hashed (x, d) draws and

@@ -220,6 +220,29 @@ def fill_edge_table_words(scene, tri0=0, n=1, phong=True, semantics=abi.PRK_SEM_
     return words.reshape(-1, 27)[: cnt.value].copy()
 
 
+def edge_rows_per_triangle(scene, phong=True, semantics=abi.PRK_SEM_AVX):
+    """FillEdgeTable on each triangle alone: (tri, YMin, YMax) int32 arrays,
+    one entry per edge it makes (culled triangles make none).  What a
+    whole-object draw lists, by the triangle it came from: scene builders drop
+    triangles by it until a census (tests/census.py) shows the wanted sizes."""
+    k = _Keep(scene, semantics, phong, 1)
+    words = np.zeros(27 * 4, np.uint32)
+    rows = words.reshape(-1, 27).view(np.int32)
+    cnt = C.c_uint32(0)
+    fn, p = lib().oracle_fill_edge_table, _ptr(words)
+    tri, y0, y1 = [], [], []
+    for t in range(scene.tri_count):
+        rc = fn(C.byref(k.desc), C.c_uint32(t), C.c_uint32(1), C.byref(k.transform), C.byref(k.lights), p,
+                C.byref(cnt))
+        if rc != 0:
+            raise RuntimeError("oracle_fill_edge_table failed: %d" % rc)
+        for e in range(cnt.value):
+            tri.append(t)
+            y0.append(int(rows[e, 7]))
+            y1.append(int(rows[e, 0]))
+    return np.array(tri, np.int32), np.array(y0, np.int32), np.array(y1, np.int32)
+
+
 def advance_edges(edge_words, height):
     """What DrawModel* leaves in the caller's edge list ([n, 27] prk_edge
     words, sorted as FillEdgeTable leaves them) after walking it over a frame

@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import census as Cn
 import oracle as O
 import prk
 from prk import abi, scenes
@@ -1075,9 +1076,13 @@ def test_whole_object_big_walk(gpu, sem, lds, monkeypatch):
     for s, tpo in ((sph, sph.tri_count), (soup, 700), (soup, 64)):
         label = "big walk %s tpo=%d sem=%d" % (s.name, tpo, sem)
         g, o = run_both(s, semantics=sem, phong=True, tris_per_object=tpo, threads=1, label=label)
+        wr = g[3].walk_routes  # the forced walk took them, none stayed in a slot class
+        assert wr["huge_lds" if lds == "1" else "huge_mem"] >= 1 and sum(wr["slots"]) == 0, (label, wr)
+        assert wr["huge_mem" if lds == "1" else "huge_lds"] == 0, (label, wr)
         monkeypatch.setenv("PRK_OBJ_BIG", "0")
         w = prk.render_scene(s, semantics=sem, phong=True, tris_per_object=tpo)
         monkeypatch.delenv("PRK_OBJ_BIG")
+        assert w[3].walk_routes["wave"] >= 1 and w[3].walk_routes["huge_lds"] + w[3].walk_routes["huge_mem"] == 0
         for k in range(3):
             assert np.array_equal(g[k].view(np.uint32), w[k].view(np.uint32)), (label, k)
     oc, oz, ow, _ = O.render(soup, semantics=sem, phong=True, threads=1, tris_per_object=700)
@@ -1165,6 +1170,164 @@ def test_c3b_one_object_golden(gpu):
         if got != want:
             bad.append(b)
     assert not bad, "bands differing from the oracle's frame: %s" % bad[:16]
+
+
+# ---- the huge-object walks at multi-window list sizes (tests/census.py) ------
+# Each case renders one comb scene as ONE object and asserts three things: the
+# census of the scene (test_census.py asserts the same figures without a GPU),
+# the walk the host chose and the sizes the device counted
+# (Renderer.walk_routes), and the oracle's frame bit for bit.
+
+ROUTES = ("huge_lds", "huge_mem", "wave")
+
+
+def _huge_render(s, sem, rows=None):
+    if sem == abi.PRK_SEM_SCALAR:
+        s = Cn.untextured(s)
+    return prk.render_scene(s, semantics=sem, phong=sem != abi.PRK_SEM_SCALAR, tris_per_object=s.tri_count, rows=rows)
+
+
+def _huge_case(name, sem, route, monkeypatch, rows=None, other_form=True, wave=True, sized_huge=0, sizes=True):
+    """Scene `name` of tests/census.py (Cn.SCENES) as one object: the route
+    report names `route` (one of ROUTES, or a tuple of allowed ones) for its
+    one object and (sizes) the device's (most, rows, ents) equal the
+    census's; z, winners and colour equal the oracle's (rows: a band); and,
+    where asked, the one-wave walk's and the other memory form's frames equal
+    this one's word for word."""
+    s = Cn.scene(name)
+    c = Cn.census(s, rows)
+    o = Cn.reference(name, sem)
+    if rows is not None:
+        o = tuple(a[rows[0]:rows[1]] for a in o[:3]) + (None,)
+    label = "%s sem=%d rows=%s" % (name, sem, rows)
+    g = _huge_render(s, sem, rows)
+    wr = g[3].walk_routes
+    allowed = (route,) if isinstance(route, str) else route
+    took = [r for r in ROUTES if wr[r]]
+    assert took and took[0] in allowed and sum(wr[r] for r in ROUTES) + sum(wr["slots"]) == 1, (label, wr)
+    if sizes:
+        assert wr["sized_huge"] == sized_huge, (label, wr)
+        assert (wr["most"], wr["rows"], wr["ents"]) == Cn.device_sizes(c), (label, wr, Cn.device_sizes(c))
+    compare(g, o, label=label)
+    variants = []
+    if wave:
+        variants.append(("PRK_OBJ_BIG", "0", "wave"))
+    if other_form:
+        assert took[0] == "huge_lds"  # (a list the LDS holds: the device-memory form is the other one)
+        variants.append(("PRK_OBJ_LDSWALK", "0", "huge_mem"))
+    for env, value, vroute in variants:
+        monkeypatch.setenv(env, value)
+        v = _huge_render(s, sem, rows)
+        monkeypatch.delenv(env)
+        assert v[3].walk_routes[vroute] == 1, (label, env, v[3].walk_routes)
+        for k in range(3):
+            assert np.array_equal(g[k].view(np.uint32), v[k].view(np.uint32)), (label, env, k)
+    return c, wr
+
+
+@pytest.mark.parametrize("k,lds", [(1023, "1"), (1024, "1"), (1025, "1"), (2048, "1"), (2049, "1"),
+                                   (1024, "0"), (2049, "0")])
+def test_huge_walk_window_edges(gpu, k, lds, monkeypatch):
+    """A. One row takes exactly k new edges: one short of the insertion
+    window of 1024, the window exactly (the next window is empty: expiry runs
+    alone after it), one more, and the same at two windows -- through the LDS
+    walk, and 1024 / 2049 through the device-memory walk too."""
+    monkeypatch.setenv("PRK_OBJ_LDSWALK", lds)
+    c, _ = _huge_case("window_%d" % k, abi.PRK_SEM_AVX, "huge_lds" if lds == "1" else "huge_mem",
+                      monkeypatch, other_form=False)
+    assert Cn.busiest(c)[1] == k and c["most"] > Cn.SLOT_CAP
+
+
+@pytest.mark.parametrize("sem,name", [(abi.PRK_SEM_AVX, "lds"), (abi.PRK_SEM_AVX_ST, "lds"),
+                                      (abi.PRK_SEM_SCALAR, "lds"), (abi.PRK_SEM_AVX, "lds_ties"),
+                                      (abi.PRK_SEM_AVX_ST, "lds_ties"), (abi.PRK_SEM_SCALAR, "lds_ties")])
+def test_huge_walk_lds_several_windows(gpu, sem, name, monkeypatch):
+    """B. k_obj_walk_lds with 4096 < most <= 9200: a row of more than 2048
+    new edges, several hundred more about ten rows later into the long list,
+    rows of odd length (Cn.check_lds_scene); every semantics, and with exact
+    duplicate keys (ties: the order is by arrival alone)."""
+    c, _ = _huge_case(name, sem, "huge_lds", monkeypatch)
+    Cn.check_lds_scene(c)
+
+
+@pytest.mark.parametrize("most,route", [(9200, "huge_lds"), (9201, "huge_mem")])
+def test_huge_walk_lds_handover(gpu, most, route, monkeypatch):
+    """C. The last list the LDS walk takes and the first it hands to the
+    device-memory walk."""
+    c, _ = _huge_case("handover_%d" % most, abi.PRK_SEM_AVX, route, monkeypatch, other_form=most == 9200)
+    assert c["most"] == most
+
+
+@pytest.mark.parametrize("sem", [abi.PRK_SEM_AVX, abi.PRK_SEM_SCALAR])
+@pytest.mark.parametrize("ns", [8192, 8193])
+def test_huge_walk_mem_reload_boundary(gpu, ns, sem, monkeypatch):
+    """D. k_obj_walk_big (forced: PRK_OBJ_LDSWALK=0) on tied scenes whose
+    longest scan (big_insert_expire's ns, census ns: Cn.window_scans) is
+    exactly 8192 entries -- eight tiles, kept in registers -- and 8193, the
+    first that reloads.  (The list itself peaks higher, at 8259: the peak
+    row's last window scans the list before its own edges go in.  A scan
+    that inserts is odd, its old entries + 1, so the 8192 is an expiry-only
+    pass and the 8193 an inserting one.)"""
+    monkeypatch.setenv("PRK_OBJ_LDSWALK", "0")
+    name = "reload_%d" % ns
+    c, _ = _huge_case(name, sem, "huge_mem", monkeypatch, other_form=False)
+    assert c["ns"] == ns and c["most"] <= Cn.LDS_CAP
+    monkeypatch.delenv("PRK_OBJ_LDSWALK")
+    v = _huge_render(Cn.scene(name), sem)  # the other memory form
+    assert v[3].walk_routes["huge_lds"] == 1
+    o = Cn.reference(name, sem)
+    for k in range(3):
+        assert np.array_equal(v[k].view(np.uint32), o[k].view(np.uint32)), (name, sem, k)
+
+
+@pytest.mark.parametrize("sem", [abi.PRK_SEM_AVX, abi.PRK_SEM_SCALAR])
+def test_huge_walk_mem_unforced(gpu, sem, monkeypatch):
+    """D. k_obj_walk_big as the host picks it: most of 11k to 14k, scans of
+    up to 12001 entries (reloaded)."""
+    c, _ = _huge_case("big", sem, "huge_mem", monkeypatch, other_form=False)
+    assert 11000 <= c["most"] <= 14000 and c["ns"] > 8192
+
+
+@pytest.mark.parametrize("sem", [abi.PRK_SEM_AVX, abi.PRK_SEM_SCALAR])
+@pytest.mark.parametrize("name,route", [("lds", "huge_lds"), ("lds_ties", "huge_lds"), ("big", "huge_mem")])
+def test_huge_walk_bands(gpu, name, route, sem, monkeypatch):
+    """E. A row band that starts ~30 rows below the rows where thousands of
+    edges enter (multi-tile rows paired, not emitted; RowLo is row0 - 1
+    outside AVX) and ends inside the object (the sizes are clipped at row1)."""
+    c, _ = _huge_case(name, sem, route, monkeypatch, rows=Cn.BAND, other_form=route == "huge_lds")
+    Cn.check_band(c)
+
+
+@pytest.mark.parametrize("name,route,rows", [("big", "huge_mem", None), ("big", "huge_mem", Cn.BAND),
+                                             ("lds_ties", "huge_lds", None)])
+def test_huge_walk_many_workgroup_sizing(gpu, name, route, rows, monkeypatch):
+    """F. The sizes from k_maxact_huge_part / k_maxact_huge_fin (forced:
+    PRK_OBJ_HUGE_EDGES below the object's edges): 18000 edges are three
+    histogram workgroups of 8192, 8820 are two; the same route and the same
+    sizes as the census."""
+    monkeypatch.setenv("PRK_OBJ_HUGE_EDGES", "5000")
+    c, _ = _huge_case(name, abi.PRK_SEM_AVX, route, monkeypatch, rows=rows, other_form=False, wave=False,
+                      sized_huge=1)
+    assert c["edges"] > (2 * 8192 if name == "big" else 8192)
+
+
+def test_huge_walk_tall_object(gpu, monkeypatch):
+    """Tall frames, case 1: rows of 15990 to 15999 (the LDS walk packs a row
+    offset and Left into 16 bits; the host admits it below 16000 rows) with a
+    list of more than 1024."""
+    c, _ = _huge_case("tall", abi.PRK_SEM_AVX, "huge_lds", monkeypatch, other_form=False, wave=False)
+    assert 15990 <= c["rows"] <= 15999 and c["most"] > 1024
+
+
+def test_huge_walk_tall_object_past_histogram(gpu, monkeypatch):
+    """Tall frames, case 2: the same object stretched past the frame's bottom
+    (rows >= 16000: today k_obj_maxact counts nothing and the object goes to
+    one wave).  Whatever walk takes it must be exact; only the LDS walk is
+    ruled out, and the sizes are left open, so sizing such objects later
+    does not break this."""
+    c, _ = _huge_case("tall_stretched", abi.PRK_SEM_AVX, ("huge_mem", "wave"), monkeypatch, other_form=False,
+                      wave=False, sizes=False)
+    assert c["rows"] >= 16000 and c["first"] + c["rows"] == Cn.TALL_H and c["most"] > 1024
 
 
 @pytest.mark.parametrize("tpo", [1, 5, 300])
