@@ -4,7 +4,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import
 this module, and only as the checker / the timed CPU baseline.  The product
 path (cpu-renderer_amd/prk, libprk_hip.so) never imports it.
 
-PARITY UNPINNED: see the header of oracle/prk_oracle.c and DESIGN.md §3.
+Parity with the reference: tests/golden/ref/ and oracle/ref/, DESIGN.md §3.
 """
 import ctypes as C
 import os

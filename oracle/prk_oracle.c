@@ -6,16 +6,12 @@
  *   checker / the timed CPU baseline.  The product (libprk_hip.so) never
  *   links, loads or calls it.
  *
- *   PARITY UNPINNED: the reference (MacSpain/cpu-renderer, /root/reference)
- *   has no tests, no fixtures and no golden images, and it cannot be built
- *   here without writing stand-ins for its absent platform/math headers
- *   (v3, loaded_bitmap, game_render_commands, RoundR32ToS32, ...), which this
- *   round's rules forbid.  This file is a restatement written from reading
- *   projekt.cpp; every function cites the lines it follows.  SURVEY.md
- *   records that the same semantic description (its Appendix A/B) matched a
- *   shimmed build of the reference bit-exactly during the survey; that check
- *   is not reproducible under this round's rules, so it is cited, not relied
- *   on.  Pins for the absent helpers follow SURVEY §8(c)/App. C/D:
+ *   PARITY: the reference (MacSpain/cpu-renderer) has no tests, fixtures or
+ *   golden images.  This file is a restatement written from reading
+ *   projekt.cpp; every function cites the lines it follows.  It is held to
+ *   frames the reference itself drew (tests/golden/ref/, built by the recipe in
+ *   oracle/ref/, checked by tests/test_ref_parity.py; DESIGN.md §3 says under
+ *   which pins and patch).  Pins for the absent helpers follow SURVEY §8(c)/App. C/D:
  *     RoundR32ToS32(x) = (s32)roundf(x)     (half away from zero)
  *     RoundR32ToU32(x) = (u32)roundf(x)
  *     Normalize(a)     = (1/sqrtf(Inner(a,a))) * a

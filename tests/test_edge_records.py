@@ -3,7 +3,8 @@ caller's memory (prk_fill_edge_records / prk_advance_edge_records, host code
 of libprk_hip.so) against the oracle's FillEdgeTable (projekt.cpp:3894-4117)
 and its AET walk (3654-3869), word for word, list pointers included.
 
-Parity is against the restatement (oracle/prk_oracle.c): UNPINNED, DESIGN.md §3.
+Parity here is against the restatement (oracle/prk_oracle.c); tests/test_ref_parity.py
+holds both to the reference's own edge_info.
 """
 import numpy as np
 import pytest

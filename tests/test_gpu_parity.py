@@ -7,7 +7,8 @@ everywhere; `COLOR_TOL` is the contract, reported in the message.  The scalar
 Phong path's double pow is exact too: test_phong_pow.py shows x^16 never comes
 within 8 double ulps of a float rounding boundary for x in [0, 1].
 
-Oracle parity is UNPINNED: the reference cannot be built here.
+The oracle itself is pinned to frames the reference drew (tests/golden/ref/, DESIGN.md §3);
+tests/test_gpu_ref_parity.py holds the GPU to those frames directly.
 """
 import ctypes
 

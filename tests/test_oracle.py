@@ -7,7 +7,7 @@
   spans and its one-past-the-row store, strict z-test in submission order,
   back-face cull, near-plane collapse, FillEdgeTable fields.
 * Committed golden fixtures (tests/golden, regression only: parity with the
-  reference itself is unpinned).
+  reference itself is tests/test_ref_parity.py).
 """
 import glob
 import os

@@ -1,10 +1,11 @@
 """Generate tests/golden/*.npz — regression fixtures of the CPU restatement.
 
-The reference ships no tests or golden images and cannot be built here
-(DESIGN.md §3), so these fixtures are produced by oracle/prk_oracle.c and
-cross-checked by tests/pyref.py (an independent restatement) at generation
-time.  They pin the restatement against regressions and give the GPU tests a
-committed expected image; they do NOT pin parity with the reference itself.
+These fixtures are produced by oracle/prk_oracle.c and cross-checked by
+tests/pyref.py (an independent restatement) at generation time.  They pin the
+restatement against regressions and give the GPU tests a committed expected
+image.  Parity with the reference itself is pinned by tests/golden/ref/
+(tools/make_ref_golden.py), which redraws these scenes with the
+reference's own code; tests/test_ref_parity.py compares the two sets.
 
 Each fixture holds the inputs (geometry, texture, camera, lights, semantics)
 and the expected colour, z and winning-triangle maps.
