@@ -16,17 +16,42 @@
 //                 recursion (merges take Half1 first on ties, a two-entry run
 //                 keeps its order); the key (object, YMin, recursion path)
 //                 reproduces it exactly under one device radix sort.
-//   k_obj_walk    the AET walk with the reference's list operations (insertion
-//                 scan, expiry, pairing, the two crossing swaps of 3831-3853
-//                 with the P3 head/tail fix), stepping the paired edges row by
-//                 row: one thread per small object or caller edge list, one
-//                 wave per large object (k_obj_walk_wave: the list in LDS, the
-//                 insertion scan, expiry compaction, the pairs' span setup and
-//                 edge steps and both swap passes spread over the lanes).
-//                 Pass 0 counts the object's emitted spans; pass 1 writes, for
-//                 each span in submission order (object, row, pair), its lane-
-//                 init record (FillLineOptimized SpanRec 1543-1835, or DrawModel
-//                 ScSpanRec 298-412) and its pixel range.
+//   the walk      the AET walk with the reference's list operations (insertion
+//                 scan 3654-3713, expiry 3715-3749, pairing 3751-3869 with
+//                 the two crossing swaps of 3831-3853 and the P3 head/tail
+//                 fix), stepping the paired edges row by row.  Every pair
+//                 of the pass's rows takes a slot in submission order (object,
+//                 row, pair; k_obj_bound bounds each object's slots).  The
+//                 host (prk_api.hip flush_spans) picks a walk per object:
+//     thread walk          k_obj_walk: a thread per caller edge list or span,
+//                          and per small triangle object when segments are off
+//                          (PRK_OBJ_SEGMENTS=0).
+//     segments             k_obj_seg + k_obj_walk_seg: small triangle objects
+//                          (fewer than wave_tris triangles), a thread per
+//                          stretch of rows with a non-empty list.
+//     slot-list walk       k_obj_walk_wave, lcap > 0 (walk_rows over every
+//                          row): a workgroup per large object whose most
+//                          listed edges (k_obj_maxact) fit an LDS capacity
+//                          class; objects the chunked walk did not take.
+//     chunked rows         k_pr_hist .. k_pr_fix (walk_rows per chunk of rows,
+//                          all chunks at once, checked and re-walked where
+//                          needed): the same objects when every row pairs all
+//                          its entries and no key is NaN (PRK_OBJ_ROWS=0: off).
+//     LDS walk             k_obj_walk_lds: an object whose list outgrows the
+//                          slot classes and fits prk_big_lds_cap() entries, a
+//                          workgroup of 1024 with the whole list in LDS.
+//     device-memory walk   k_obj_walk_big: the same with the list in a pool
+//                          slice, up to kBigMaxM entries.
+//     replay               k_big_replay: after either huge-object walk, a
+//                          thread per pair replays both edges to the pair's row.
+//     one-wave walk        k_obj_walk_wave, lcap == 0 (walk_object_wave): what
+//                          is left (sizes unknown or past every limit,
+//                          PRK_OBJ_BIG=0), one wave with the list in a pool slice.
+//                 The thread, segment and one-wave walks set each span up
+//                 themselves (FillLineOptimized SpanRec 1543-1835, or DrawModel
+//                 ScSpanRec 298-412, and its pixel range); the others write
+//                 both edges' values at the row (PairRaw) and
+//   k_span_finish sets those spans up, a thread per slot.
 //   k_span_tiles  span -> tile bin entries: every tile's count (wave-
 //                 aggregated atomics), their scan, each span placed at its
 //                 tile's offset + arrival rank (no sort: the visibility max
@@ -39,14 +64,23 @@
 #include "prk_device.h"
 
 namespace prk {
-// Diagnostic builds (-DPRK_WPROF=1): walk_object_block accumulates its
-// phases' cycles into fp.prof (prk_debug_counters): 0 insertion, 1 expiry,
-// 2 pairing, 3 rows walked, 4 batches (insert_batch_b), 6 one-at-a-time
-// insertions, 7 the whole walk, 8 new edges.
+// Diagnostic builds (-DPRK_WPROF=1): the whole-object slot-list walk
+// (walk_rows<M, false>) accumulates its phases' cycles into fp.prof
+// (prk_debug_counters): 0 insertion, 1 expiry, 2 pairing, 3 rows walked,
+// 4 batches (insert_batch_b), 6 one-at-a-time insertions, 7 the whole walk,
+// 8 new edges.
 #ifndef PRK_WPROF
 #define PRK_WPROF 0
 #endif
 #define PRK_WT() (PRK_WPROF ? __builtin_amdgcn_s_memtime() : 0ull)
+// The slot-list walk's counters exist in diagnostic builds only (not even as
+// dead code: an unused counter array moved k_pr_chunk's register allocation).
+#if PRK_WPROF
+#define PRK_WP(...) __VA_ARGS__
+#else
+#define PRK_WP(...)
+#endif
+#define PRK_WP_PHASE(i) PRK_WP({ const unsigned long long t1_ = PRK_WT(); wp[i] += t1_ - t0; t0 = t1_; })
 
 // One object of the span path.
 //   kind 0: triangles [g0, g0 + tris) of its draw's geometry: FillEdgeTable +
@@ -1114,7 +1148,7 @@ __global__ void __launch_bounds__(kLinkThreads) k_obj_walk_seg(FrameParams fp, c
 //                          passes.  An odd last entry neither pairs nor steps.
 // ---------------------------------------------------------------------------
 constexpr int kWaveListArrays = 9;   // int32 arrays of cap + 2 entries each
-constexpr uint32_t kSlotCapLds = 1022;  // walk_object_block's largest LDS capacity (listed edges; 1024 threads)
+constexpr uint32_t kSlotCapLds = 1022;  // the slot-list walk's largest LDS capacity (listed edges; 1024 threads)
 struct WaveList {
     int32_t *idx;
     float *x, *g;
@@ -1815,13 +1849,15 @@ struct PairRaw {
     float4 l0, l1, l2, r0, r1, r2;  // X Z W U | V N0 N1 N2 | C0 C1 C2 C3, left then right edge
 };
 static_assert(sizeof(PairRaw) == 96, "six dwordx4");
+// One edge's half of a PairRaw (pair_raw_in reads it back).
+__device__ __forceinline__ void pair_raw_half(const ObjEdge &e, float4 &q0, float4 &q1, float4 &q2) {
+    q0 = make_float4(e.X, e.Z, e.W, e.U);
+    q1 = make_float4(e.V, e.N0, e.N1, e.N2);
+    q2 = make_float4(e.C0, e.C1, e.C2, e.C3);
+}
 __device__ __forceinline__ void pair_raw_out(const ObjEdge &a, const ObjEdge &b, PairRaw &o) {
-    o.l0 = make_float4(a.X, a.Z, a.W, a.U);
-    o.l1 = make_float4(a.V, a.N0, a.N1, a.N2);
-    o.l2 = make_float4(a.C0, a.C1, a.C2, a.C3);
-    o.r0 = make_float4(b.X, b.Z, b.W, b.U);
-    o.r1 = make_float4(b.V, b.N0, b.N1, b.N2);
-    o.r2 = make_float4(b.C0, b.C1, b.C2, b.C3);
+    pair_raw_half(a, o.l0, o.l1, o.l2);
+    pair_raw_half(b, o.r0, o.r1, o.r2);
 }
 __device__ __forceinline__ ObjEdge pair_raw_in(const float4 &q0, const float4 &q1, const float4 &q2) {
     ObjEdge e = ObjEdge{};
@@ -1908,102 +1944,137 @@ __global__ void k_span_finish(FrameParams fp, const PairRaw *__restrict__ raw, u
         d_[4] = w##4; d_[5] = w##5; d_[6] = w##6;                                      \
     } while (0)
 
-template <int M>
-__device__ void walk_object_block(const FrameParams &fp, const ObjDesc &od, const ObjEdge *__restrict__ E,
-                                  uint32_t n, int32_t MaxY, uint32_t base, uint32_t bound, const SlotLds &S,
-                                  BlockRed &R, uint32_t cap, PairRaw *__restrict__ raw, SpanPos *__restrict__ pos,
-                                  uint32_t *__restrict__ span_tri, uint32_t *__restrict__ err) {
+// The slot-list walk of the rows [r0, r1) of an object (r1 <= MaxY), the
+// reference's list operations 3654-3869 once for every caller.
+//   CHUNK false, the whole object (k_obj_walk_wave): from the empty list at
+//     its first row r0 = E[0].YMin over every row (re = r0, r1 = MaxY, ins0 =
+//     m0 = emitted0 = 0, no start, sidx, cmp or end).
+//   CHUNK true, a chunk of its rows (k_pr_chunk, k_pr_fix): from the list
+//     start[0, m0) at row r0 (states at r0, their sorted edge index in Next;
+//     that row's insertion and expiry done; ins0: the first sorted edge with
+//     YMin > r0), and every edge it inserts records its sorted index in Next.
+// Its spans from row re >= r0 on (the rows before: a warm-up, walked and
+// stepped but not emitted), from slot base + emitted0.  sidx: the list at re
+// (its sorted edge indices) goes to sidx[] / *s_m.  r1 < MaxY: the list after
+// r1's insertion and expiry goes to end[] / *end_m, and the return value says
+// whether its edges are cmp[0, mc) in order (cmp null: false).  Every thread
+// returns the same.  A row with more new edges than free slots (never: cap
+// >= the most listed edges) sets err bit 0 and ends the walk.
+template <int M, bool CHUNK>
+__device__ bool walk_rows(const FrameParams &fp, const ObjDesc &od, const ObjEdge *__restrict__ E, uint32_t n,
+                          int32_t MaxY, uint32_t base, uint32_t bound, const SlotLds &S, BlockRed &R, uint32_t cap,
+                          int32_t r0, int32_t re, int32_t r1, uint32_t ins0, const ObjEdge *__restrict__ start, int m0,
+                          uint32_t emitted0, uint32_t *__restrict__ sidx, uint32_t *__restrict__ s_m,
+                          const uint32_t *__restrict__ cmp, int mc, ObjEdge *__restrict__ end,
+                          uint32_t *__restrict__ end_m, PairRaw *__restrict__ raw, SpanPos *__restrict__ pos,
+                          uint32_t *__restrict__ span_tri, uint32_t *__restrict__ err) {
     constexpr bool kScalar = M != MODE_AVX;
     const int tid = threadIdx.x;
     const uint32_t NT = blockDim.x;
     const int32_t RowLo = kScalar ? fp.row0 - 1 : fp.row0;
-    unsigned long long wp[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long wt0 = PRK_WT();
-    for (uint32_t q = tid; q < cap; q += NT) S.fs[q] = (int32_t)q;
-    int top = (int)cap;  // free slots (the same value in every thread, as every uniform below)
+    PRK_WP(unsigned long long wp[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long wt0 = PRK_WT();)
+    // the start list in slots [0, m0), the free slots above (the same values
+    // in every thread, as every uniform below)
+    for (int q = tid; q < m0; q += (int)NT) {
+        S.st[q] = start[q];
+        S.idx[q] = q;
+    }
+    for (uint32_t q = tid; q + m0 < cap; q += NT) S.fs[q] = (int32_t)(q + m0);
+    int top = (int)cap - m0;
+    int m = m0;
+    uint32_t ins = ins0;
     // read-ahead window: thread t holds sorted edge wb + t
-    uint32_t wb = 0;
+    uint32_t wb = ins;
     PRK_WIN(wa);
-    PRK_WIN_LOAD(wa, E, (uint32_t)tid, n);
+    PRK_WIN_LOAD(wa, E, wb + (uint32_t)tid, n);
     PRK_WIN_WAIT();
     PRK_WIN_LAUNDER(wa);
-    uint32_t emitted = 0;
-    int m = 0;
-    uint32_t ins = 0;
+    uint32_t emitted = emitted0;
     __syncthreads();
-    for (int32_t Row = E[0].YMin; Row < MaxY; ++Row) {
-        unsigned long long t0 = PRK_WT();
-        if (PRK_WPROF) wp[3] += 1;
-        // insertion (3654-3713): the edges with YMin == Row, in sorted order,
-        // a window at a time (batches in order == one at a time)
-        for (;;) {
-            if (ins == wb + NT) {
-                wb += NT;
-                PRK_WIN_LOAD(wa, E, wb + tid, n);
-                PRK_WIN_WAIT();
-                PRK_WIN_LAUNDER(wa);
+    for (int32_t Row = r0;; ++Row) {
+        PRK_WP(unsigned long long t0 = PRK_WT();)
+        if (!CHUNK || Row != r0) {
+            if (Row >= MaxY) break;  // (the last rows: no list after them)
+            PRK_WP(wp[3] += 1;)
+            // insertion (3654-3713): the edges with YMin == Row, in sorted order,
+            // a window at a time (batches in order == one at a time)
+            for (;;) {
+                if (ins == wb + NT) {
+                    wb += NT;
+                    PRK_WIN_LOAD(wa, E, wb + tid, n);
+                    PRK_WIN_WAIT();
+                    PRK_WIN_LAUNDER(wa);
+                }
+                const float wx = wa0.x, wg = wa0.y;
+                const int32_t wymin = __float_as_int(wa4.x), wl = __float_as_int(wa4.z);
+                const int rel = tid - (int)(ins - wb);
+                const bool eqr = rel >= 0 && wymin == Row;
+                int32_t lt, k, nanc;
+                blk_sum3(R, (rel >= 0 && wymin < Row) ? 1 : 0, eqr ? 1 : 0, (eqr && (wx != wx || wg != wg)) ? 1 : 0,
+                         lt, k, nanc);
+                if (lt) {  // (never past the first row: entries below the row are skipped)
+                    ins += (uint32_t)lt;
+                    continue;
+                }
+                if (k == 0) break;
+                if (k > top) {  // (never: cap >= the most listed edges)
+                    if (tid == 0) atomicOr(err, 1u);
+                    return false;
+                }
+                if (rel >= 0 && rel < k) {  // the row's new edges take slots; their keys go to nk*
+                    const int32_t slot = S.fs[top - 1 - rel];
+                    PRK_WIN_STORE(&S.st[slot], wa);
+                    if (CHUNK) S.st[slot].Next = (int32_t)(ins + (uint32_t)rel);  // (its sorted index)
+                    S.nkx[rel] = wx;
+                    S.nkg[rel] = wg;
+                    S.nkl[rel] = wl;
+                    S.nks[rel] = slot;
+                }
+                top -= k;
+                __syncthreads();
+                PRK_WP(wp[8] += (unsigned long long)k; wp[(k <= 2 || nanc) ? 6 : 4] += 1;)
+                if (k <= 2 || nanc) {  // one at a time (any NaN key), 3654-3713
+                    for (int t = 0; t < k; ++t)
+                        insert_one_b(S, R, m, LKey{S.nkx[t], S.nkg[t], S.nkl[t]}, S.nks[t]);
+                } else {
+                    insert_batch_b(S, R, m, k);
+                }
+                ins += (uint32_t)k;
+                if (ins < wb + NT) break;  // the row's edges end inside the window
             }
-            const float wx = wa0.x, wg = wa0.y;
-            const int32_t wymin = __float_as_int(wa4.x), wl = __float_as_int(wa4.z);
-            const int rel = tid - (int)(ins - wb);
-            const bool eqr = rel >= 0 && wymin == Row;
-            int32_t lt, k, nanc;
-            blk_sum3(R, (rel >= 0 && wymin < Row) ? 1 : 0, eqr ? 1 : 0, (eqr && (wx != wx || wg != wg)) ? 1 : 0, lt,
-                     k, nanc);
-            if (lt) {  // (never past the first row: entries below the row are skipped)
-                ins += (uint32_t)lt;
-                continue;
+            PRK_WP_PHASE(0);
+            {  // expiry 3715-3749: keep entries with YMax > Row, in order; free the others' slots
+                int32_t e = 0;
+                bool keep = false;
+                if (tid < m) {
+                    e = S.idx[tid];
+                    keep = !(S.st[e].YMax <= Row);
+                }
+                const bool gone = tid < m && !keep;
+                int32_t kp, gp, kt, gt;
+                blk_excl_sum2(R, keep ? 1 : 0, gone ? 1 : 0, kp, gp, kt, gt);
+                if (keep) S.idx[kp] = e;
+                if (gone) S.fs[top + gp] = e;
+                m = kt;
+                top += gt;
+                __syncthreads();
             }
-            if (k == 0) break;
-            if (rel >= 0 && rel < k) {  // the row's new edges take slots; their keys go to nk*
-                const int32_t slot = S.fs[top - 1 - rel];
-                PRK_WIN_STORE(&S.st[slot], wa);
-                S.nkx[rel] = wx;
-                S.nkg[rel] = wg;
-                S.nkl[rel] = wl;
-                S.nks[rel] = slot;
-            }
-            top -= k;
-            __syncthreads();
-            if (PRK_WPROF) {
-                wp[8] += (unsigned long long)k;
-                wp[(k <= 2 || nanc) ? 6 : 4] += 1;
-            }
-            if (k <= 2 || nanc) {  // one at a time (any NaN key), 3654-3713
-                for (int t = 0; t < k; ++t)
-                    insert_one_b(S, R, m, LKey{S.nkx[t], S.nkg[t], S.nkl[t]}, S.nks[t]);
-            } else {
-                insert_batch_b(S, R, m, k);
-            }
-            ins += (uint32_t)k;
-            if (ins < wb + NT) break;  // the row's edges end inside the window
+            PRK_WP_PHASE(1);
         }
-        if (PRK_WPROF) { const unsigned long long t1 = PRK_WT(); wp[0] += t1 - t0; t0 = t1; }
-        {  // expiry 3715-3749: keep entries with YMax > Row, in order; free the others' slots
-            int32_t e = 0;
-            bool keep = false;
-            if (tid < m) {
-                e = S.idx[tid];
-                keep = !(S.st[e].YMax <= Row);
-            }
-            const bool gone = tid < m && !keep;
-            int32_t kp, gp, kt, gt;
-            blk_excl_sum2(R, keep ? 1 : 0, gone ? 1 : 0, kp, gp, kt, gt);
-            if (keep) S.idx[kp] = e;
-            if (gone) S.fs[top + gp] = e;
-            m = kt;
-            top += gt;
-            __syncthreads();
+        if (Row >= r1) break;
+        if (CHUNK && Row == re && sidx) {  // the list where the spans begin
+            for (int q = tid; q < m; q += (int)NT) sidx[q] = (uint32_t)S.st[S.idx[q]].Next;
+            if (tid == 0) *s_m = (uint32_t)m;
         }
-        if (PRK_WPROF) { const unsigned long long t1 = PRK_WT(); wp[1] += t1 - t0; t0 = t1; }
-        if (m == 0) {  // nothing happens on the rows before the next insertion: go there
-            if (ins >= n) break;
-            Row = max(Row, E[ins].YMin - 1);
+        if (m == 0) {  // nothing happens on the rows before the next insertion (or re, r1): go there
+            const int32_t nx = ins < n ? E[ins].YMin : INT32_MAX;
+            Row = max(Row, min(nx, Row < re ? re : r1) - 1);
             continue;
         }
         const int P = m / 2;  // pairing 3751-3869: thread k holds pair k
         const bool valid = tid < P;
-        const bool emit = Row >= RowLo;  // every pair of the pass's rows takes a slot (k_span_finish sets it up)
+        // every pair of the pass's rows takes a slot (k_span_finish sets it up)
+        const bool emit = Row >= RowLo && Row >= re;
         int32_t i0 = 0, i1 = 0;
         float x0 = 0.0f, x1 = 0.0f;
         if (valid) {
@@ -2014,19 +2085,13 @@ __device__ void walk_object_block(const FrameParams &fp, const ObjDesc &od, cons
             if (emit && j >= bound) atomicOr(err, 2u);  // (never: the bound holds every pair)
             const uint32_t at = base + j;
             ObjEdge a = S.st[i0];  // left edge: its values at the row, then its step (3811-3829)
-            if (w) {
-                raw[at].l0 = make_float4(a.X, a.Z, a.W, a.U);
-                raw[at].l1 = make_float4(a.V, a.N0, a.N1, a.N2);
-                raw[at].l2 = make_float4(a.C0, a.C1, a.C2, a.C3);
-            }
+            if (w) pair_raw_half(a, raw[at].l0, raw[at].l1, raw[at].l2);
             obj_step<M>(a);
             S.st[i0] = a;
             x0 = a.X;
             ObjEdge b = S.st[i1];  // right edge
             if (w) {
-                raw[at].r0 = make_float4(b.X, b.Z, b.W, b.U);
-                raw[at].r1 = make_float4(b.V, b.N0, b.N1, b.N2);
-                raw[at].r2 = make_float4(b.C0, b.C1, b.C2, b.C3);
+                pair_raw_half(b, raw[at].r0, raw[at].r1, raw[at].r2);
                 pos[at] = SpanPos{Row, (int32_t)od.draw, 0, SPAN_RAW};
                 span_tri[at] = od.g0;
             }
@@ -2058,12 +2123,22 @@ __device__ void walk_object_block(const FrameParams &fp, const ObjDesc &od, cons
         }
         if (emit) emitted += (uint32_t)P;
         __syncthreads();
-        if (PRK_WPROF) wp[2] += PRK_WT() - t0;
+        PRK_WP_PHASE(2);
     }
-    if (PRK_WPROF && tid == 0) {
+    PRK_WP(if (!CHUNK && tid == 0) {  // (the whole-object walk's phases, tools/wprof.py)
         wp[7] = PRK_WT() - wt0;
         for (int k = 0; k < 14; ++k) atomicAdd(fp.prof + k, wp[k]);
+    })
+    if (!CHUNK || r1 >= MaxY) return true;
+    // the list at r1: out, and against cmp
+    bool same = cmp != nullptr && m == mc;
+    for (int q = tid; q < m; q += (int)NT) {
+        const ObjEdge &e = S.st[S.idx[q]];
+        end[q] = e;
+        if (cmp && q < mc) same = same && (uint32_t)e.Next == cmp[q];
     }
+    if (tid == 0) *end_m = (uint32_t)m;
+    return blk_max(R, same ? 0 : 1) == 0;
 }
 
 // The most entries each large object's list holds at once (thread block
@@ -2230,7 +2305,7 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_maxact_huge_fin(FrameParams
 }
 
 // One workgroup per large object: lcap > 0, everything in LDS
-// (walk_object_block, lcap slots, slot_threads(lcap) threads); lcap == 0, the
+// (walk_rows over every row, lcap slots, slot_threads(lcap) threads); lcap == 0, the
 // list in the object's pool slice pool + big_off[blockIdx.x]
 // (kWaveListArrays arrays of big_cap[blockIdx.x] + 2 ints, big_cap >= its
 // edge count), walked by one wave (64 threads).
@@ -2273,7 +2348,9 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_obj_walk_wave(FrameParams f
     const int32_t MaxY = min(min(blk_max(R, mr), fp.H), fp.row1);
     SlotLds S;
     S.carve(lds_list, lcap, blockDim.x);
-    walk_object_block<M>(fp, od, E, n, MaxY, base, bound, S, R, lcap, raw, pos, span_tri, err);
+    const int32_t r0 = E[0].YMin;  // every row, from the empty list
+    (void)walk_rows<M, false>(fp, od, E, n, MaxY, base, bound, S, R, lcap, r0, r0, MaxY, 0u, nullptr, 0, 0u, nullptr,
+                              nullptr, nullptr, 0, nullptr, nullptr, raw, pos, span_tri, err);
 }
 
 // ---------------------------------------------------------------------------
@@ -3368,8 +3445,8 @@ __global__ void __launch_bounds__(256) k_big_replay(FrameParams fp, const ObjDes
 // order, which is what a batch inserted into an empty list is -- usually
 // reaches the true list.  So the object's rows are cut into chunks of
 // kPrChunk rows and every chunk is walked at once by the workgroup walk's
-// own list operations (walk_chunk = walk_object_block from a given list over
-// a given row range): chunk j > 0 from the sorted list of chunk j - 1's first
+// own list operations (walk_rows from a given list over a given row
+// range): chunk j > 0 from the sorted list of chunk j - 1's first
 // row, walking chunk j - 1's rows as a warm-up (stepping, no spans), then its
 // own rows (spans).  Exactness is checked, not assumed: chunk j's list at its
 // first row must equal the list chunk j - 1 ended with (k_pr_cmp); chunk 0
@@ -3592,183 +3669,39 @@ __global__ void __launch_bounds__(kPrStartThreads) k_pr_start(const PrObj *__res
     if (__any(bad) && (tid & 63) == 0) atomicMax(&prstat[P.o], kPrFailed);
 }
 
-// walk_object_block over the rows [r0, r1) of an object, from the list
-// start[0, m0) at row r0 (states at r0, their sorted edge index in Next; the
-// row's insertion and expiry done); its spans from row re >= r0 on (the rows
-// before: a warm-up, walked and stepped but not emitted), from slot base +
-// emitted0.  sidx: the list at re (its sorted edge indices) goes to
-// sidx[] / *s_m.  r1 < MaxY: the list after r1's insertion and expiry goes to
-// end[] / *end_m, and the return value says whether its edges are
-// cmp[0, mc) in order (cmp null: false).  Every thread returns the same.
-template <int M>
-__device__ bool walk_chunk(const FrameParams &fp, const ObjDesc &od, const ObjEdge *__restrict__ E, uint32_t n,
-                           int32_t MaxY, uint32_t base, uint32_t bound, const SlotLds &S, BlockRed &R, uint32_t cap,
-                           int32_t r0, int32_t re, int32_t r1, uint32_t ins0, const ObjEdge *__restrict__ start, int m0,
-                           uint32_t emitted0, uint32_t *__restrict__ sidx, uint32_t *__restrict__ s_m,
-                           const uint32_t *__restrict__ cmp, int mc, ObjEdge *__restrict__ end,
-                           uint32_t *__restrict__ end_m, PairRaw *__restrict__ raw, SpanPos *__restrict__ pos,
-                           uint32_t *__restrict__ span_tri, uint32_t *__restrict__ err) {
-    constexpr bool kScalar = M != MODE_AVX;
-    const int tid = threadIdx.x;
-    const uint32_t NT = blockDim.x;
-    const int32_t RowLo = kScalar ? fp.row0 - 1 : fp.row0;
-    // the start list in slots [0, m0), the free slots above
-    for (int q = tid; q < m0; q += (int)NT) {
-        S.st[q] = start[q];
-        S.idx[q] = q;
+// What k_pr_chunk and k_pr_fix set up for an object of the walk: its sorted
+// edges, its rows, its span slots [base, base + bound) and the slot list
+// carved from the workgroup's LDS.
+struct PrWalk {
+    ObjDesc od;
+    const ObjEdge *E;
+    uint32_t n;
+    PrRow pr;
+    uint32_t base, bound;
+    SlotLds S;
+    uint32_t jlo;  // its first row (from first_row) of the pass's rows: the rows before emit no span
+    // The pairs the rows before first_row + jr emit (eoff: k_pr_hist's scan): that row's first slot from base.
+    __device__ __forceinline__ uint32_t emitted0(const uint32_t *__restrict__ eoff, const PrObj &P, uint32_t jr) const {
+        return (eoff[P.row_off + max(jr, jlo)] - eoff[P.row_off + jlo]) / 2;
     }
-    for (uint32_t q = tid; q + m0 < cap; q += NT) S.fs[q] = (int32_t)(q + m0);
-    int top = (int)cap - m0;
-    int m = m0;
-    uint32_t ins = ins0;  // the first sorted edge with YMin > r0
-    uint32_t wb = ins;
-    PRK_WIN(wa);
-    PRK_WIN_LOAD(wa, E, wb + (uint32_t)tid, n);
-    PRK_WIN_WAIT();
-    PRK_WIN_LAUNDER(wa);
-    uint32_t emitted = emitted0;
-    __syncthreads();
-    for (int32_t Row = r0;; ++Row) {
-        if (Row != r0) {
-            if (Row >= MaxY) break;  // (the last chunk: no list after it)
-            // insertion (3654-3713), as walk_object_block
-            for (;;) {
-                if (ins == wb + NT) {
-                    wb += NT;
-                    PRK_WIN_LOAD(wa, E, wb + tid, n);
-                    PRK_WIN_WAIT();
-                    PRK_WIN_LAUNDER(wa);
-                }
-                const float wx = wa0.x, wg = wa0.y;
-                const int32_t wymin = __float_as_int(wa4.x), wl = __float_as_int(wa4.z);
-                const int rel = tid - (int)(ins - wb);
-                const bool eqr = rel >= 0 && wymin == Row;
-                int32_t lt, k, nanc;
-                blk_sum3(R, (rel >= 0 && wymin < Row) ? 1 : 0, eqr ? 1 : 0, (eqr && (wx != wx || wg != wg)) ? 1 : 0,
-                         lt, k, nanc);
-                if (lt) {
-                    ins += (uint32_t)lt;
-                    continue;
-                }
-                if (k == 0) break;
-                if (k > top) {  // (never: cap >= the most listed edges)
-                    if (tid == 0) atomicOr(err, 1u);
-                    return false;
-                }
-                if (rel >= 0 && rel < k) {
-                    const int32_t slot = S.fs[top - 1 - rel];
-                    PRK_WIN_STORE(&S.st[slot], wa);
-                    S.st[slot].Next = (int32_t)(ins + (uint32_t)rel);  // (its sorted index)
-                    S.nkx[rel] = wx;
-                    S.nkg[rel] = wg;
-                    S.nkl[rel] = wl;
-                    S.nks[rel] = slot;
-                }
-                top -= k;
-                __syncthreads();
-                if (k <= 2 || nanc) {
-                    for (int t = 0; t < k; ++t)
-                        insert_one_b(S, R, m, LKey{S.nkx[t], S.nkg[t], S.nkl[t]}, S.nks[t]);
-                } else {
-                    insert_batch_b(S, R, m, k);
-                }
-                ins += (uint32_t)k;
-                if (ins < wb + NT) break;
-            }
-            {  // expiry 3715-3749
-                int32_t e = 0;
-                bool keep = false;
-                if (tid < m) {
-                    e = S.idx[tid];
-                    keep = !(S.st[e].YMax <= Row);
-                }
-                const bool gone = tid < m && !keep;
-                int32_t kp, gp, kt, gt;
-                blk_excl_sum2(R, keep ? 1 : 0, gone ? 1 : 0, kp, gp, kt, gt);
-                if (keep) S.idx[kp] = e;
-                if (gone) S.fs[top + gp] = e;
-                m = kt;
-                top += gt;
-                __syncthreads();
-            }
-        }
-        if (Row >= r1) break;
-        if (Row == re && sidx) {  // the list where the spans begin
-            for (int q = tid; q < m; q += (int)NT) sidx[q] = (uint32_t)S.st[S.idx[q]].Next;
-            if (tid == 0) *s_m = (uint32_t)m;
-        }
-        if (m == 0) {  // nothing happens on the rows before the next insertion (or re, r1): go there
-            const int32_t nx = ins < n ? E[ins].YMin : INT32_MAX;
-            Row = max(Row, min(nx, Row < re ? re : r1) - 1);
-            continue;
-        }
-        const int P = m / 2;  // pairing 3751-3869, as walk_object_block
-        const bool valid = tid < P;
-        const bool emit = Row >= RowLo && Row >= re;
-        int32_t i0 = 0, i1 = 0;
-        float x0 = 0.0f, x1 = 0.0f;
-        if (valid) {
-            i0 = S.idx[2 * tid];
-            i1 = S.idx[2 * tid + 1];
-            const uint32_t j = emitted + (uint32_t)tid;
-            const bool w = emit && j < bound;
-            if (emit && j >= bound) atomicOr(err, 2u);
-            const uint32_t at = base + j;
-            ObjEdge a = S.st[i0];
-            if (w) {
-                raw[at].l0 = make_float4(a.X, a.Z, a.W, a.U);
-                raw[at].l1 = make_float4(a.V, a.N0, a.N1, a.N2);
-                raw[at].l2 = make_float4(a.C0, a.C1, a.C2, a.C3);
-            }
-            obj_step<M>(a);
-            S.st[i0] = a;
-            x0 = a.X;
-            ObjEdge b = S.st[i1];
-            if (w) {
-                raw[at].r0 = make_float4(b.X, b.Z, b.W, b.U);
-                raw[at].r1 = make_float4(b.V, b.N0, b.N1, b.N2);
-                raw[at].r2 = make_float4(b.C0, b.C1, b.C2, b.C3);
-                pos[at] = SpanPos{Row, (int32_t)od.draw, 0, SPAN_RAW};
-                span_tri[at] = od.g0;
-            }
-            obj_step<M>(b);
-            S.st[i1] = b;
-            x1 = b.X;
-            if (x0 > x1) {
-                const int32_t t = i0; i0 = i1; i1 = t;
-                const float f = x0; x0 = x1; x1 = f;
-            }
-            S.nb[tid] = i0;
-            S.bk[tid] = __float_as_int(x0);
-            S.aux[tid] = i1;
-            S.bk2[tid] = __float_as_int(x1);
-        }
-        __syncthreads();
-        if (valid) {
-            const bool sw = tid >= 1 && __int_as_float(S.bk2[tid - 1]) > x0;
-            const bool swn = tid + 1 < P && x1 > __int_as_float(S.bk[tid + 1]);
-            const int32_t nf = sw ? S.aux[tid - 1] : i0, ns = swn ? S.nb[tid + 1] : i1;
-            i0 = nf;
-            i1 = ns;
-        }
-        __syncthreads();
-        if (valid) {
-            S.idx[2 * tid] = i0;
-            S.idx[2 * tid + 1] = i1;
-        }
-        if (emit) emitted += (uint32_t)P;
-        __syncthreads();
-    }
-    if (r1 >= MaxY) return true;
-    // the list at r1: out, and against cmp
-    bool same = cmp != nullptr && m == mc;
-    for (int q = tid; q < m; q += (int)NT) {
-        const ObjEdge &e = S.st[S.idx[q]];
-        end[q] = e;
-        if (cmp && q < mc) same = same && (uint32_t)e.Next == cmp[q];
-    }
-    if (tid == 0) *end_m = (uint32_t)m;
-    return blk_max(R, same ? 0 : 1) == 0;
+};
+__device__ __forceinline__ PrWalk pr_walk(const FrameParams &fp, const ObjDesc *__restrict__ objs, const PrObj &P,
+                                          const PrRow &pr,
+                                          const uint32_t *__restrict__ escan, const uint32_t *__restrict__ total0p,
+                                          const ObjEdge *__restrict__ work,
+                                          const unsigned long long *__restrict__ soff, int32_t *lds, uint32_t cap) {
+    PrWalk W;
+    W.od = objs[P.o];
+    uint32_t e0;
+    obj_range(W.od, escan, *total0p, e0, W.n);
+    W.E = work + e0;
+    W.pr = pr;
+    const int32_t RowLo = fp.draws[W.od.draw].mode != MODE_AVX ? fp.row0 - 1 : fp.row0;
+    W.jlo = (uint32_t)min(max(0, RowLo - pr.first_row), (int32_t)P.rows);
+    W.base = (uint32_t)soff[P.o];
+    W.bound = (uint32_t)(soff[P.o + 1] - soff[P.o]);
+    W.S.carve(lds, cap, blockDim.x);
+    return W;
 }
 
 // Chunk j of the objects of one mode (pro[pi], pi in group [0, ngroup)):
@@ -3800,27 +3733,19 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_pr_chunk(FrameParams fp, co
     const PrObj P = pro[pi];
     const uint32_t j = blockIdx.x;
     if (j >= pr_chunks(P) || prstat[P.o] != kPrDone) return;  // (prstat is final here: k_pr_start ran)
-    const ObjDesc od = objs[P.o];
-    uint32_t e0, n;
-    obj_range(od, escan, *total0p, e0, n);
-    const ObjEdge *E = work + e0;
-    const PrRow pr = prrow[pi];
+    const PrWalk W = pr_walk(fp, objs, P, prrow[pi], escan, total0p, work, soff, lds_list, cap);
+    const PrRow &pr = W.pr;
     const int32_t re = pr.first_row + (int32_t)(j * kPrChunk), r1 = min(re + kPrChunk, pr.max_y);
     const uint32_t js = j && warmup ? j - 1 : j;  // the chunk whose first row it starts from
     const int32_t r0 = pr.first_row + (int32_t)(js * kPrChunk);
     const uint32_t jr0 = js * kPrChunk, jre = j * kPrChunk;
-    const int32_t RowLo = fp.draws[od.draw].mode != MODE_AVX ? fp.row0 - 1 : fp.row0;
-    const uint32_t jlo = (uint32_t)min(max(0, RowLo - pr.first_row), (int32_t)P.rows);
-    const uint32_t emitted0 = (eoff[P.row_off + max(jre, jlo)] - eoff[P.row_off + jlo]) / 2;
-    const uint32_t base = (uint32_t)soff[P.o], bound = (uint32_t)(soff[P.o + 1] - soff[P.o]);
-    SlotLds S;
-    S.carve(lds_list, cap, blockDim.x);
     const uint32_t c = P.chunk_off + j;
     const uint32_t gs = P.ent_off + js * P.most, ge = P.ent_off + j * P.most, g1 = ge + P.most;
     const bool last = r1 >= pr.max_y;
-    (void)walk_chunk<M>(fp, od, E, n, pr.max_y, base, bound, S, R, cap, r0, re, r1, fge[P.row_off + jr0 + 1],
-                        sst + gs, (int)cnt[P.row_off + jr0], emitted0, sidx + ge, s_m + c, nullptr, 0,
-                        last ? nullptr : eend + g1, eend_m + c, raw, pos, span_tri, err);
+    (void)walk_rows<M, true>(fp, W.od, W.E, W.n, pr.max_y, W.base, W.bound, W.S, R, cap, r0, re, r1,
+                             fge[P.row_off + jr0 + 1], sst + gs, (int)cnt[P.row_off + jr0], W.emitted0(eoff, P, jre),
+                             sidx + ge, s_m + c, nullptr, 0, last ? nullptr : eend + g1, eend_m + c, raw, pos,
+                             span_tri, err);
 }
 
 // match[c] = chunk c's end list (eend) is chunk c + 1's list at its first
@@ -3870,16 +3795,8 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_pr_fix(FrameParams fp, cons
     const uint32_t pi = grp[blockIdx.x];
     const PrObj P = pro[pi];
     if (prstat[P.o] != kPrDone) return;
-    const ObjDesc od = objs[P.o];
-    uint32_t e0, n;
-    obj_range(od, escan, *total0p, e0, n);
-    const ObjEdge *E = work + e0;
-    const PrRow pr = prrow[pi];
-    const int32_t RowLo = fp.draws[od.draw].mode != MODE_AVX ? fp.row0 - 1 : fp.row0;
-    const uint32_t jlo = (uint32_t)min(max(0, RowLo - pr.first_row), (int32_t)P.rows);
-    const uint32_t base = (uint32_t)soff[P.o], bound = (uint32_t)(soff[P.o + 1] - soff[P.o]);
-    SlotLds S;
-    S.carve(lds_list, cap, blockDim.x);
+    const PrWalk W = pr_walk(fp, objs, P, prrow[pi], escan, total0p, work, soff, lds_list, cap);
+    const PrRow &pr = W.pr;
     const uint32_t nch = pr_chunks(P);
     bool prev_true = true;  // chunk j walked its rows from the true list (chunk 0: from the first row)
     for (uint32_t j = 0; j < nch; ++j) {
@@ -3891,16 +3808,14 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_pr_fix(FrameParams fp, cons
         // walk it again from the true list: chunk j - 1's end (eend at its entry block)
         if (threadIdx.x == 0) atomicAdd(&err[3], 1u);  // (the pass's re-walked chunks)
         const int32_t r0 = pr.first_row + (int32_t)(j * kPrChunk), r1 = min(r0 + kPrChunk, pr.max_y);
-        const uint32_t jr0 = j * kPrChunk, jr1 = (uint32_t)(r1 - pr.first_row);
-        const uint32_t emitted0 = (eoff[P.row_off + max(jr0, jlo)] - eoff[P.row_off + jlo]) / 2;
+        const uint32_t jr0 = j * kPrChunk;
         const uint32_t g0 = P.ent_off + j * P.most, g1 = g0 + P.most;
         const bool last = r1 >= pr.max_y;
         __syncthreads();  // (the previous walk's LDS and eend writes)
-        prev_true = walk_chunk<M>(fp, od, E, n, pr.max_y, base, bound, S, R, cap, r0, r0, r1, fge[P.row_off + jr0 + 1],
-                                  eend + g0, (int)eend_m[c - 1], emitted0, nullptr, nullptr,
-                                  last ? nullptr : sidx + g1, last ? 0 : (int)s_m[c + 1],
-                                  last ? nullptr : eend + g1, eend_m + c, raw, pos, span_tri, err);
-        (void)jr1;
+        prev_true = walk_rows<M, true>(fp, W.od, W.E, W.n, pr.max_y, W.base, W.bound, W.S, R, cap, r0, r0, r1,
+                                       fge[P.row_off + jr0 + 1], eend + g0, (int)eend_m[c - 1], W.emitted0(eoff, P, jr0),
+                                       nullptr, nullptr, last ? nullptr : sidx + g1, last ? 0 : (int)s_m[c + 1],
+                                       last ? nullptr : eend + g1, eend_m + c, raw, pos, span_tri, err);
     }
 }
 

@@ -918,6 +918,20 @@ def test_whole_object_chunked_walk(gpu, sem, monkeypatch):
     assert w[3]["objects_chunked"] == 0 and w[3]["objects_walked"] == 1, w[3]
     for k in range(3):
         assert np.array_equal(g[k].view(np.uint32), w[k].view(np.uint32)), k
+    if sem == abi.PRK_SEM_SCALAR:  # the two Gouraud modes through both routes
+        for textured in (True, False):
+            sg = _sphere_scene()
+            if not textured:
+                sg.texture = None
+            gg, _ = run_both(sg, semantics=sem, phong=False, tris_per_object=sg.tri_count, threads=1,
+                             label="sphere chunked gouraud tex=%d" % textured)
+            assert gg[3]["objects_chunked"] == 1 and gg[3]["objects_walked"] == 0, gg[3]
+            monkeypatch.setenv("PRK_OBJ_ROWS", "0")
+            gw = prk.render_scene(sg, semantics=sem, phong=False, tris_per_object=sg.tri_count)
+            monkeypatch.delenv("PRK_OBJ_ROWS")
+            assert gw[3]["objects_chunked"] == 0 and gw[3]["objects_walked"] == 1, gw[3]
+            for k in range(3):
+                assert np.array_equal(gg[k].view(np.uint32), gw[k].view(np.uint32)), k
     soup = scenes.with_ties(scenes.random_soup(2800, 384, 256, radius=40, seed=9, centroid_margin=40), seed=9)
     if sem == abi.PRK_SEM_SCALAR:
         soup.texture = None
