@@ -66,6 +66,10 @@ hipError_t prk_objtri_emit(const prk::FrameParams *, const void *, const uint32_
 hipError_t prk_obj_sort_local(const void *, const uint32_t *, uint32_t, const uint32_t *, const void *, const void *,
                               void *, void *, uint32_t *, hipStream_t);
 hipError_t prk_obj_sort(void *, uint32_t *, void *, uint32_t *, uint32_t, uint32_t, void *, size_t *, hipStream_t);
+hipError_t prk_rec_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t, uint32_t,
+                        const uint32_t *, int32_t, uint32_t, void *, void *, uint32_t *, int, hipStream_t);
+hipError_t prk_rec_counts(const void *, const uint32_t *, uint32_t, const uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipStream_t);
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
@@ -320,7 +324,8 @@ struct prk_context {
             d_keys_b, d_vals_b, d_offs, d_nwin, d_wtag, d_srecs, d_work, d_ekeys, d_ekeys2, d_evals, d_ecnt, d_escan,
             d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
-            d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab;
+            d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab,
+            d_rectab, d_reccnt, d_recout;  // prk_edge_records: its tables, counts and packed records
         // the pass's host tables, packed into pinned memory for one upload
         // (stage_ev: that upload, before the staging is rewritten)
         char *h_stage = nullptr;
@@ -528,7 +533,8 @@ int prk_destroy(prk_context *c) {
                         &S.d_raw, &S.d_most, &S.d_cls, &S.d_prrow, &S.d_prcnt, &S.d_preoff, &S.d_prfge,
                         &S.d_prccur, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend, &S.d_preendm,
                         &S.d_prmatch, &S.d_prsidx, &S.d_prsm, &S.d_prstat, &S.d_segcnt, &S.d_segoff,
-                        &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab};
+                        &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_rectab, &S.d_reccnt,
+                        &S.d_recout};
         for (DevBuf *b : sb) b->release();
         if (S.h_rb) (void)hipHostFree(S.h_rb);
         if (S.stage_ev) {
@@ -2455,6 +2461,133 @@ int prk_fill_edge_count(const float *V, uint32_t vertex_count, const float P[3],
     for (uint32_t t = 0; t < vertex_count / 3; ++t) n += prk_tri_edge_count(V + 9 * (size_t)t, p0, p1, p2, T);
     *count_out = n;
     return PRK_OK;
+}
+
+// FillEdgeTable's records of a batch of objects, set up on the GPU: the span
+// path's own chain (k_objtri_count -> scan -> emit -> sort, prk_spans.hip)
+// with the record setup (k_rec_emit: all 27 fields, the sort key on the true
+// YMin) in place of the frame's, then k_rec_export packs the sorted edges as
+// prk_edge.  The scratch is the span path's (c->spans), taken only once the
+// device is idle, as prk_geometry_update takes the geometry; nothing the
+// next flush reads is kept in it from one pass to the next.  The call needs
+// no target (the frame parameters' rows only bound the span slots, which are
+// not used here), records no draw and leaves c->draws, the pending edge /
+// span input and c->stats as they are.
+int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                     uint32_t tris_per_object, const float P[3], int32_t setup, prk_edge *records,
+                     uint64_t capacity, uint32_t *counts, uint64_t *total_out) {
+    if (!c || !total_out) return PRK_ERR_ARG;
+    *total_out = 0;
+    if (geometry < 0 || geometry >= (int32_t)c->geoms.size() || tris_per_object == 0) return PRK_ERR_ARG;
+    if (setup < 0 || setup > (PRK_SETUP_PHONG | PRK_SETUP_BITMAP)) return PRK_ERR_ARG;
+    const Geometry &g = c->geoms[geometry];
+    if ((uint64_t)first_tri + tri_count > g.vertex_count / 3) return PRK_ERR_ARG;
+    if (!c->have_camera) return PRK_ERR_ARG;
+    if (tri_count == 0) return PRK_OK;
+    const uint32_t nt = tri_count, per = std::min(tris_per_object, tri_count);
+    const uint32_t nobj = (uint32_t)(((uint64_t)nt + per - 1) / per);
+    if (3ull * nt >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;  // 31-bit edge slots
+    // MergeSort key: (object, true YMin: 31 bits, recursion path)
+    auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+    const uint32_t maxn = 3 * per;  // the most edges FillEdgeTable writes for one object
+    const uint32_t pbits = bitlen(maxn) + 1, ybits = 31, obits = std::max(1u, bitlen(nobj - 1));
+    if (obits + ybits + pbits > 64) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below and read the geometry
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    prk::FrameParams fp;
+    frame_params(c, fp);
+    fp.tri_count = nt;
+    fp.ndraws = 1;
+    prk::DrawRec d{};
+    d.V = g.V; d.C = g.C; d.N = g.N; d.UV = g.UV;
+    d.geom = geometry;
+    d.geom_tri0 = first_tri;
+    d.tri_count = nt;
+    d.mode = prk::MODE_AVX;
+    d.tex = -1;
+    d.P[0] = P ? P[0] : 0.0f;
+    d.P[1] = P ? P[1] : 0.0f;
+    d.P[2] = P ? P[2] : 0.0f;
+    d.obj_tris = per;
+    const ObjRun run{0u, 0u, 0u, nobj, per, nt, 0u, 0u, 0u, 0u, 0u, 0u};
+    // the draw and the run of objects (one small upload), expanded on the device
+    constexpr size_t kRunOff = (sizeof(prk::DrawRec) + 255) & ~(size_t)255;
+    char tab[kRunOff + sizeof(ObjRun)] = {};
+    std::memcpy(tab, &d, sizeof d);
+    std::memcpy(tab + kRunOff, &run, sizeof run);
+    PRK_TRY(S.d_rectab.ensure(sizeof tab));
+    PRK_TRY(hipMemcpyAsync(S.d_rectab.p, tab, sizeof tab, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (tab is on this stack)
+    fp.draws = (const prk::DrawRec *)S.d_rectab.p;
+    fp.draw0 = d;
+    PRK_TRY(S.d_objtab.ensure((size_t)nobj * sizeof(ObjDesc)));
+    PRK_TRY(S.d_k0tab.ensure((size_t)nobj * 8));
+    void *d_objs = S.d_objtab.p;
+    uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
+    const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nobj;
+    PRK_TRY(prk_obj_tables(static_cast<char *>(S.d_rectab.p) + kRunOff, 1, nobj, kObjWaveTris, d_objs, k0tab,
+                           k0tab + nobj, s));
+    const size_t es = 3 * (size_t)nt;
+    PRK_TRY(S.d_ecnt.ensure(((size_t)nt + 1) * 4));
+    PRK_TRY(S.d_escan.ensure(((size_t)nt + 1) * 4));
+    PRK_TRY(S.d_rcnt.ensure(((size_t)nt + 1) * 8));
+    PRK_TRY(S.d_reccnt.ensure((size_t)nobj * 4));
+    PRK_TRY(S.d_err.ensure(16));
+    PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
+    uint32_t *escan = (uint32_t *)S.d_escan.p;
+    size_t tb = 0;
+    PRK_TRY(prk_objtri_count(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, (uint32_t *)S.d_ecnt.p,
+                             (unsigned long long *)S.d_rcnt.p, s));
+    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, nullptr, &tb, s));
+    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
+    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(prk_rec_counts(d_objs, d_k0obj, nobj, escan, (uint32_t *)S.d_reccnt.p, s));
+    // the total sizes the records (and decides whether the caller's buffer holds them)
+    uint32_t total = 0;
+    PRK_TRY(hipMemcpyAsync(&total, escan + nt, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    *total_out = total;
+    const bool fill = records != nullptr && capacity >= total;
+    if (fill && total) {
+        PRK_TRY(S.d_edges.ensure(es * 112));  // prk_spans.hip ObjEdge
+        PRK_TRY(S.d_ekeys.ensure(es * 8));
+        PRK_TRY(S.d_evals.ensure(es * 4));
+        const size_t out_bytes = (((size_t)total * 27 + 3) / 4) * 16;
+        PRK_TRY(S.d_recout.ensure(out_bytes));
+        // MergeSort per object: at most 64 edges by one wave each
+        // (k_obj_sort_local, into the working copy), else one radix sort
+        const bool local_sort = maxn <= 64;
+        PRK_TRY(prk_rec_emit(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, escan, setup, pbits, S.d_edges.p,
+                             S.d_ekeys.p, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
+        if (local_sort) {
+            PRK_TRY(S.d_work.ensure(es * 112));
+            PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nobj, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, nullptr,
+                                       (uint32_t *)S.d_err.p, s));
+            PRK_TRY(prk_rec_export(S.d_work.p, nullptr, total, S.d_recout.p, s));
+        } else {
+            PRK_TRY(S.d_ekeys2.ensure(es * 8));
+            PRK_TRY(S.d_ord.ensure(es * 4));
+            const uint32_t end_bit = obits + ybits + pbits;
+            PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
+                                 end_bit, nullptr, &tb, s));
+            PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
+            PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
+                                 end_bit, S.d_temp.p, &tb, s));
+            PRK_TRY(prk_rec_export(S.d_edges.p, (const uint32_t *)S.d_ord.p, total, S.d_recout.p, s));
+        }
+        uint32_t err = 0;
+        PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipMemcpyAsync(records, S.d_recout.p, (size_t)total * sizeof(prk_edge), hipMemcpyDeviceToHost, s));
+        if (counts) PRK_TRY(hipMemcpyAsync(counts, S.d_reccnt.p, (size_t)nobj * 4, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipStreamSynchronize(s));
+        if (err) return PRK_ERR_DEVICE;
+        return PRK_OK;
+    }
+    if (counts) PRK_TRY(hipMemcpy(counts, S.d_reccnt.p, (size_t)nobj * 4, hipMemcpyDeviceToHost));
+    return records && capacity < total ? PRK_ERR_ARG : PRK_OK;
 }
 
 // ConstructSphere (projekt.cpp:4123-4289): the reference's only test mesh.

@@ -59,6 +59,11 @@
 //   k_span_vis (prk_kernels.hip)  per-tile visibility over the spans with
 //                 the 64-bit key max (tag = span index in submission order).
 //   k_pix (prk_kernels.hip, span records indexed by span)  shading.
+//
+// prk_edge_records (FillEdgeTable's records handed back, no frame) runs the
+// same count / scan / sort with k_rec_emit (every edge_info field, the key on
+// the true YMin), k_rec_counts and k_rec_export (packed prk_edge), at the end
+// of this file.
 #include <atomic>
 
 #include "prk_device.h"
@@ -3904,9 +3909,256 @@ __global__ void k_span_tiles(FrameParams fp, const SpanPos *__restrict__ pos, ui
     }
 }
 
+// ---------------------------------------------------------------------------
+// FillEdgeTable's edge_info records (prk_edge_records): the same count ->
+// scan -> emit -> sort chain, with every field FillEdgeTable writes.
+// ---------------------------------------------------------------------------
+// The visible edges of one front-facing triangle as FillEdgeTable(Object,
+// Commands, PhongShading) writes them into zero-filled EdgeMemory
+// (projekt.cpp:3947-4111, the host restatement prk_edge_records.cpp:166-251),
+// all 27 fields, in the reference's operation order.  tri_edges<M> keeps only
+// what mode M's span kernel reads; a record also holds what none reads: the
+// raw colours of a Phong + Bitmap edge, the white-based lit colours of a
+// Gouraud + Bitmap edge, NormalGradient.  Which fields are written depends on
+// `setup` (PRK_SETUP_*) and the light count alone:
+//   MinColor          Phong: the vertex colour; else lit per vertex (from white
+//                     with a Bitmap), never written without lights -- then it
+//                     is 0, as is MaxColor, and 4091 / 4095 compute on zeros;
+//   MinNormal         Phong only; NormalGradient always (zeros without it);
+//   U/V/OneOverZ gradients and their top clip: Bitmap only (the minima always).
+// A missing vertex array reads as zeros.  The edges go to out[0 ..) in edge
+// order {0,1},{1,2},{2,0}, those of `mask` (tri_vis_mask) only.
+__device__ __forceinline__ void rec_tri_edges(const FrameParams &fp, const DrawRec &d, uint32_t gt, int32_t setup,
+                                              uint32_t mask, ObjEdge *out) {
+    const bool kPhong = (setup & 1) != 0, kBitmap = (setup & 2) != 0;  // PRK_SETUP_PHONG, PRK_SETUP_BITMAP
+    V3 cam[3], proj[3], nrm[3];
+    float col[3][4], uv[3][2];
+    load_positions(d, gt, fp, cam, proj);  // 3898-3910
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        nrm[k] = d.N ? V3{d.N[9 * (size_t)gt + 3 * k], d.N[9 * (size_t)gt + 3 * k + 1], d.N[9 * (size_t)gt + 3 * k + 2]}
+                     : V3{0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) col[k][c] = d.C ? d.C[12 * (size_t)gt + 4 * k + c] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) uv[k][c] = d.UV ? d.UV[6 * (size_t)gt + 2 * k + c] : 0.0f;
+    }
+    uint32_t slot = 0;
+#pragma unroll
+    for (int ei = 0; ei < 3; ++ei) {
+        const int i0 = ei, i1 = (ei + 1) % 3;     // Indices {0,1},{1,2},{2,0}
+        const bool sw = proj[i0].y > proj[i1].y;  // 3957-3966
+        const V3 MinV = sw ? proj[i1] : proj[i0], MaxV = sw ? proj[i0] : proj[i1];
+        const V3 FirstCam = sw ? cam[i1] : cam[i0], SecondCam = sw ? cam[i0] : cam[i1];
+        const V3 FirstN = sw ? nrm[i1] : nrm[i0], SecondN = sw ? nrm[i0] : nrm[i1];
+        float FirstCol[4], SecondCol[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            FirstCol[c] = sw ? col[i1][c] : col[i0][c];
+            SecondCol[c] = sw ? col[i0][c] : col[i1][c];
+        }
+        float FirstUV0 = sw ? uv[i1][0] : uv[i0][0], FirstUV1 = sw ? uv[i1][1] : uv[i0][1];
+        float SecondUV0 = sw ? uv[i0][0] : uv[i1][0], SecondUV1 = sw ? uv[i0][1] : uv[i1][1];
+        Edge E;
+        E.Vtx = 0;
+        E.YMax = round_s32(MaxV.y);  // 3988
+        float ClippedY = 0.0f, t = 0.0f;
+        if (MinV.y < 0.0f) {  // 3993-3997
+            ClippedY = -MinV.y;
+            t = (-MinV.y) / (MaxV.y - MinV.y);
+        }
+        {
+            const float r = (float)round_s32(MinV.y);
+            E.YMin = (int32_t)(0.0f > r ? 0.0f : r);  // Maximum(0, .) 3999
+        }
+        E.X = MinV.x;  // 4000-4004
+        E.Z = FirstCam.z;
+        E.U = FirstUV0 / MinV.z;
+        E.V = FirstUV1 / MinV.z;
+        E.W = 1.0f / MinV.z;
+        E.UG = E.VG = E.WG = 0.0f;
+        {  // 4006-4008
+            const float s2 = 1.0f / MaxV.z;
+            SecondUV0 *= s2; SecondUV1 *= s2;
+            const float s1 = 1.0f / MinV.z;
+            FirstUV0 *= s1; FirstUV1 *= s1;
+        }
+        float MinC[4] = {0.0f, 0.0f, 0.0f, 0.0f}, MaxC[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // 3985-3986
+        float MaxN[3] = {0.0f, 0.0f, 0.0f};
+        E.N0 = E.N1 = E.N2 = 0.0f;
+        if (kPhong) {  // 4012-4019
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { MinC[c] = FirstCol[c]; MaxC[c] = SecondCol[c]; }
+            E.N0 = FirstN.x; E.N1 = FirstN.y; E.N2 = FirstN.z;
+            MaxN[0] = SecondN.x; MaxN[1] = SecondN.y; MaxN[2] = SecondN.z;
+        } else {  // per-vertex lighting 4020-4063
+            float cmi[4], cma[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {  // Hadamard(V4(1,1,1,1), .) with a Bitmap: 1.0f * x == x
+                cmi[c] = kBitmap ? 1.0f : FirstCol[c];
+                cma[c] = kBitmap ? 1.0f : SecondCol[c];
+            }
+            for (uint32_t li = 0; li < fp.light_count; ++li) {
+                const V3 LP = V3{fp.lp[li][0], fp.lp[li][1], fp.lp[li][2]};
+                const V3 FVL = nrm_rcp(V3{LP.x - FirstCam.x, LP.y - FirstCam.y, LP.z - FirstCam.z});
+                const V3 SVL = nrm_rcp(V3{LP.x - SecondCam.x, LP.y - SecondCam.y, LP.z - SecondCam.z});
+                if (li == 0) {  // 4032-4045
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        MinC[c] = cmi[c] * fp.amb[c];
+                        MaxC[c] = cma[c] * fp.amb[c];
+                    }
+                }
+                const float FD = clamp01((FVL.x * FirstN.x + FVL.y * FirstN.y) + FVL.z * FirstN.z);  // 4047-4048
+                const float SD = clamp01((SVL.x * SecondN.x + SVL.y * SecondN.y) + SVL.z * SecondN.z);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {  // 4050-4061
+                    MinC[c] = clamp01(MinC[c] + FD * (cmi[c] * fp.li[li][c]));
+                    MaxC[c] = clamp01(MaxC[c] + SD * (cma[c] * fp.li[li][c]));
+                }
+            }
+        }
+        // 4066-4111 (an edge outside `mask` computes on and is dropped below)
+        const float YDiff = (float)E.YMax - (float)E.YMin;
+        E.G = (MaxV.x - MinV.x) / (MaxV.y - MinV.y);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) MinC[c] = (1.0f - t) * MinC[c] + t * MaxC[c];  // 4091
+        // every quotient over YDiff through one shared reciprocal (div_all):
+        // ZGradient, ColorGradient, NormalGradient, with a Bitmap U/V/(1/z) too
+        if (kBitmap) {  // 4078-4089
+            float q[11] = {SecondCam.z - FirstCam.z, MaxC[0] - MinC[0], MaxC[1] - MinC[1], MaxC[2] - MinC[2],
+                           MaxC[3] - MinC[3], MaxN[0] - E.N0, MaxN[1] - E.N1, MaxN[2] - E.N2,
+                           SecondUV0 - FirstUV0, SecondUV1 - FirstUV1, (1.0f / MaxV.z) - E.W};
+            div_all(YDiff, q);
+            E.ZG = q[0];
+            E.CG0 = q[1]; E.CG1 = q[2]; E.CG2 = q[3]; E.CG3 = q[4];
+            E.NG0 = q[5]; E.NG1 = q[6]; E.NG2 = q[7];
+            E.UG = q[8]; E.VG = q[9]; E.WG = q[10];
+            E.U += ClippedY * E.UG;
+            E.V += ClippedY * E.VG;
+            E.W += ClippedY * E.WG;
+        } else {
+            float q[8] = {SecondCam.z - FirstCam.z, MaxC[0] - MinC[0], MaxC[1] - MinC[1], MaxC[2] - MinC[2],
+                          MaxC[3] - MinC[3], MaxN[0] - E.N0, MaxN[1] - E.N1, MaxN[2] - E.N2};
+            div_all(YDiff, q);
+            E.ZG = q[0];
+            E.CG0 = q[1]; E.CG1 = q[2]; E.CG2 = q[3]; E.CG3 = q[4];
+            E.NG0 = q[5]; E.NG1 = q[6]; E.NG2 = q[7];
+        }
+        E.X += ClippedY * E.G;
+        E.Z += ClippedY * E.ZG;
+        E.C0 = MinC[0]; E.C1 = MinC[1]; E.C2 = MinC[2]; E.C3 = MinC[3];
+        E.Left = (E.YMin == round_s32(proj[i0].y)) ? 1 : 0;  // 4093
+        if ((mask >> ei) & 1u) obj_edge_store(out[slot++], E);
+    }
+}
+
+// k_objtri_emit for records: every field (rec_tri_edges), and a MergeSort key
+// (object, YMin, path) on the TRUE YMin (31 bits: Maximum(0, .) of an s32) --
+// no frame bounds a record, and the clamp of the frame path's key would leave
+// the edges that start below it in tie order.
+__global__ void k_rec_emit(FrameParams fp, const ObjDesc *__restrict__ objs, const uint32_t *__restrict__ k0obj,
+                           const uint32_t *__restrict__ k0tri0, uint32_t nk0, uint32_t ntri,
+                           const uint32_t *__restrict__ escan, int32_t setup, uint32_t pbits,
+                           ObjEdge *__restrict__ edges, unsigned long long *__restrict__ keys,
+                           uint32_t *__restrict__ vals) {
+    constexpr uint32_t kYBits = 31;
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= ntri) return;
+    const uint32_t j = obj_of_tri(k0tri0, nk0, s);
+    const ObjDesc od = objs[k0obj[j]];
+    const DrawRec &d = fp.draws[od.draw];
+    const uint32_t g = od.g0 + (s - od.tri0);
+    const uint32_t gt = d.geom_tri0 + (g - d.first_global);
+    const uint32_t mask = tri_vis_mask(fp, d, gt, 0, 0);
+    if (!mask) return;
+    const uint32_t e0 = escan[s];
+    rec_tri_edges(fp, d, gt, setup, mask, edges + e0);
+    const uint32_t ob = escan[od.tri0], n = escan[od.tri0 + od.tris] - ob;
+    const uint32_t c = (uint32_t)__popc(mask);
+    for (uint32_t k = 0; k < c; ++k) {
+        const uint64_t ymin = (uint64_t)(uint32_t)edges[e0 + k].YMin;
+        keys[e0 + k] = ((uint64_t)j << (kYBits + pbits)) | (ymin << pbits) | merge_path(e0 + k - ob, n, pbits);
+        vals[e0 + k] = e0 + k;
+    }
+}
+
+// FillEdgeTable's return value of every object: its edges in the scan.
+__global__ void k_rec_counts(const ObjDesc *__restrict__ objs, const uint32_t *__restrict__ k0obj, uint32_t nk0,
+                             const uint32_t *__restrict__ escan, uint32_t *__restrict__ counts) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nk0) return;
+    const ObjDesc od = objs[k0obj[j]];
+    counts[j] = escan[od.tri0 + od.tris] - escan[od.tri0];
+}
+
+// The sorted edges as packed prk_edge records (27 dwords, prk.h field order).
+// 27 dwords do not divide into dwordx4 per record, and a lane per record
+// would store with a 108-byte stride; instead the output is one flat dword
+// array and lane i writes dwords [4i, 4i + 4) of it -- 16 B a lane, 1 KiB
+// contiguous a wave instruction, whichever records they belong to.  Each
+// dword is gathered from its record's ObjEdge (112 B, read through the
+// cache: a wave touches ten consecutive records).  src[r] = edges[ord[r]]
+// (the radix sort's order) or, ord == nullptr, edges[r] (k_obj_sort_local
+// placed them).  `out` holds ndw dwords rounded up to four.
+__global__ void __launch_bounds__(256) k_rec_export(const ObjEdge *__restrict__ edges,
+                                                    const uint32_t *__restrict__ ord, unsigned long long ndw,
+                                                    uint4 *__restrict__ out) {
+    // prk_edge field f -> ObjEdge dword
+    constexpr uint8_t kWord[27] = {17, 0, 2, 4, 1, 3, 5, 16, 6, 8, 7, 9, 18, 20, 21, 22, 23,
+                                   24, 25, 26, 27, 10, 11, 12, 13, 14, 15};
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long q0 = 4ull * i;
+    if (q0 >= ndw) return;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(edges);
+    uint32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long q = q0 + (unsigned long long)k;
+        v[k] = 0u;
+        if (q < ndw) {
+            const uint32_t r = (uint32_t)(q / 27ull), f = (uint32_t)(q % 27ull);
+            const uint32_t src = ord ? ord[r] : r;
+            v[k] = w[(size_t)src * (sizeof(ObjEdge) / 4) + kWord[f]];
+        }
+    }
+    out[i] = make_uint4(v[0], v[1], v[2], v[3]);
+}
+
 }  // namespace prk
 
 extern "C" {
+
+// prk_edge_records: the edges of every object triangle with all their fields
+// and true-YMin MergeSort keys (as prk_objtri_emit otherwise), the objects'
+// edge counts, and the sorted edges as packed prk_edge records.
+hipError_t prk_rec_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj, const uint32_t *k0tri0,
+                        uint32_t nk0, uint32_t ntri, const uint32_t *escan, int32_t setup, uint32_t pbits,
+                        void *edges, void *keys, uint32_t *vals, int pad, hipStream_t s) {
+    if (ntri == 0) return hipSuccess;
+    if (pad) {  // (the radix sort reads every slot)
+        const hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)3 * ntri * 8, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(prk::k_rec_emit, dim3((ntri + 255) / 256), dim3(256), 0, s, *fp,
+                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, k0tri0, nk0, ntri, escan, setup, pbits,
+                       reinterpret_cast<prk::ObjEdge *>(edges), reinterpret_cast<unsigned long long *>(keys), vals);
+    return hipGetLastError();
+}
+hipError_t prk_rec_counts(const void *objs, const uint32_t *k0obj, uint32_t nk0, const uint32_t *escan,
+                          uint32_t *counts, hipStream_t s) {
+    if (nk0 == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_rec_counts, dim3((nk0 + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, nk0, escan, counts);
+    return hipGetLastError();
+}
+hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total, void *out, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    const unsigned long long ndw = 27ull * total, nthr = (ndw + 3) / 4;
+    hipLaunchKernelGGL(prk::k_rec_export, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const prk::ObjEdge *>(edges), ord, ndw, reinterpret_cast<uint4 *>(out));
+    return hipGetLastError();
+}
 
 // The pass's objects (ObjDesc) and kind-0 object tables from the host's runs.
 hipError_t prk_obj_tables(const void *runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris, void *objs,

@@ -101,6 +101,8 @@ _SIGS = {
     "prk_advance_edge_records": (C.c_int, [C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int32]),
     "prk_fill_edge_count": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(abi.PrkTransform),
                                       C.POINTER(C.c_uint32)]),
+    "prk_edge_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
+                                   C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -551,6 +553,24 @@ class Renderer:
         self._keep.append(w)
         _check("prk_draw_edges", self._L.prk_draw_edges(self._h, _ptr(w), w.shape[0], semantics, int(bool(phong)),
                                                         -1 if bitmap is None else bitmap))
+
+    def edge_records(self, geom, tri_count, first_tri=0, P=None, setup=3, tris_per_object=None):
+        """prk_edge_records: FillEdgeTable's records of consecutive objects of
+        tris_per_object triangles (None: one object), set up on the GPU under
+        set_camera's transform and lights with abi.PRK_SETUP_* bits `setup`.
+        Returns (words, counts): uint32 [total, 27] in prk_edge layout (what
+        draw_edges takes), object o's MergeSorted records at
+        words[counts[:o].sum():][:counts[o]], and uint32 [nobj]."""
+        per = max(1, tri_count) if tris_per_object is None else int(tris_per_object)
+        nobj = (tri_count + per - 1) // per if per > 0 else 0
+        words = np.empty((3 * tri_count, 27), np.uint32)  # (FillEdgeTable writes at most 3 edges a triangle)
+        counts = np.zeros(nobj, np.uint32)
+        total = C.c_uint64(0)
+        Pc = (C.c_float * 3)(*(P or (0.0, 0.0, 0.0)))
+        _check("prk_edge_records", self._L.prk_edge_records(self._h, geom, first_tri, tri_count, per, Pc, int(setup),
+                                                            _ptr(words), words.shape[0], _ptr(counts),
+                                                            C.byref(total)))
+        return words[:total.value], counts
 
     def draw_spans(self, span_words, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
         """Caller spans (the work records of DoLineRenderWork): uint32 [n, 25]

@@ -522,6 +522,33 @@ int prk_fill_edge_records(const float *vertices, const float *colors, const floa
  * first-pair swap moves the list head (P3), an emptied list skips the row. */
 int prk_advance_edge_records(void *edges, uint32_t count, size_t stride, size_t next_offset, int32_t height);
 
+/* FillEdgeTable's records (projekt.cpp:3894-4117) of consecutive objects of
+ * tris_per_object triangles (the last may be smaller), set up on the GPU
+ * under prk_set_camera's transform and lights with explicit PRK_SETUP_* bits.
+ * Object o's records, MergeSorted (2-72), are packed one after another:
+ * records[sum(counts[0..o)) ...], counts[o] = FillEdgeTable's return value.
+ * Every record is what prk_fill_edge_records leaves in zero-filled memory:
+ * a field the reference does not write for this setup is all-zero bits.
+ * records == NULL: counts and *total_out only.  Needs no render target,
+ * records no draw, touches no recorded draw; synchronous.
+ *
+ * For a caller that wants the records of many objects at once (to keep them,
+ * or to draw them later with prk_draw_edges).  PRK_ERR_ARG: a NULL context or
+ * total_out, a bad geometry handle or triangle range, tris_per_object == 0,
+ * setup outside 0..3, a call before any prk_set_camera, or a capacity (in
+ * records) below the total -- *total_out is written all the same, so the
+ * caller can size its buffer and call again.  PRK_ERR_LIMIT: the object
+ * index, the 31-bit YMin and the MergeSort path bits (bit length of
+ * 3 * tris_per_object, plus one) do not fit the 64-bit sort key.  Frames in
+ * flight finish first.  The drop-in's record mode (projekt.h) does not use
+ * this: there FillEdgeTable must leave the records in the caller's own
+ * memory before it returns and keep the caller's bytes in unwritten fields,
+ * which a batched call cannot do; and the list DrawModel* leaves
+ * (prk_advance_edge_records) is host-only. */
+int prk_edge_records(prk_context *ctx, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                     uint32_t tris_per_object, const float P[3], int32_t setup,
+                     prk_edge *records, uint64_t capacity, uint32_t *counts, uint64_t *total_out);
+
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
  * vertex count through *count_out. */
