@@ -57,7 +57,10 @@ hipError_t prk_launch_raster(const prk::FrameParams *, int, const uint32_t *, co
                              hipStream_t, hipStream_t);
 hipError_t prk_walk_select_bytes(uint32_t, size_t *);
 hipError_t prk_selftest_div_launch(uint32_t n, uint64_t seed, unsigned long long *bad, hipStream_t s);
-hipError_t prk_obj_tables(const void *, uint32_t, uint32_t, uint32_t, void *, uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_obj_tables(const void *, uint32_t, uint32_t, uint32_t, void *, uint32_t *, uint32_t *, const uint32_t *,
+                          const uint32_t *, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
+hipError_t prk_list_prep(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *,
+                         const void *, const uint32_t *, uint32_t, void *, void *, unsigned long long *, hipStream_t);
 hipError_t prk_objtri_count(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
                             uint32_t, uint32_t *, unsigned long long *, hipStream_t);
 hipError_t prk_objtri_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
@@ -73,7 +76,7 @@ hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipS
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
-                         unsigned long long *, hipStream_t);
+                         const unsigned long long *, unsigned long long *, hipStream_t);
 uint32_t prk_obj_walk_lcap(void);
 hipError_t prk_obj_walk(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, const uint32_t *, void *,
                         const unsigned long long *, void *, void *, void *, uint32_t *, const void *, uint32_t *, int,
@@ -125,6 +128,9 @@ struct ObjRun {
     uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
 };
 constexpr uint32_t kObjWaveTris = 48;        // objects of this many triangles or more
+// ... and sorted edge lists (prk_draw_edge_lists) of this many edges or more
+// are large objects: the most edges the smallest large triangle object has
+constexpr uint32_t kObjWaveEdges = 3 * kObjWaveTris;
 constexpr uint64_t kPrMaxEntries = 1ull << 23;  // the chunked walk's list entries per pass (~3 GB of scratch)
 constexpr int kWaveListArrays = 9;           // prk_spans.hip WaveList: int32 arrays of cap + 2 entries
 
@@ -226,6 +232,12 @@ struct prk_context {
     uint32_t pending_tris = 0;
     std::vector<prk_edge> pend_edges;  // prk_draw_edges input of the pending frame
     std::vector<prk_span> pend_spans;  // prk_draw_spans input of the pending frame
+    // prk_draw_edge_lists input of the pending frame: the batches' records back
+    // to back, and per list its edge count and whether it takes the sorted
+    // walks (list_walks_sorted).  A batch's DrawRec: src_kind 3, src_off /
+    // src_n its records, geom_tri0 its first list, tri_count its lists.
+    std::vector<prk_edge> pend_ledges;
+    std::vector<uint32_t> pend_lcnt, pend_lflag;
     // Per-frame scratch, nsets of them in use (2, or PRK_FRAME_SETS for small
     // bands): frame k bins (and, on span-record frames, runs k_vis) into the
     // set after frame k-1's on bin_stream while frame k-1 shades on the
@@ -324,7 +336,7 @@ struct prk_context {
             d_keys_b, d_vals_b, d_offs, d_nwin, d_wtag, d_srecs, d_work, d_ekeys, d_ekeys2, d_evals, d_ecnt, d_escan,
             d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
-            d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab,
+            d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
             d_rectab, d_reccnt, d_recout;  // prk_edge_records: its tables, counts and packed records
         // the pass's host tables, packed into pinned memory for one upload
         // (stage_ev: that upload, before the staging is rewritten)
@@ -334,7 +346,7 @@ struct prk_context {
         bool stage_busy = false;
         // host tables of the pass, kept until their asynchronous uploads ran
         std::vector<ObjRun> h_runs;
-        std::vector<uint32_t> h_big_gl, h_big_cap, h_k1src;
+        std::vector<uint32_t> h_big_gl, h_big_cap, h_k1src, h_lcnt;
         std::vector<unsigned long long> h_big_off;
         std::vector<prk::DrawRec> h_draws;
         std::vector<prk::TexRec> h_texs;
@@ -1143,7 +1155,7 @@ static int draw_src(prk_context *c, uint32_t kind, uint32_t off, uint32_t n, uin
     if (semantics == PRK_SEM_SCALAR) {
         // DrawModel on a caller's edge list (projekt.cpp:162-601); work
         // records (kind 2) are FillLineOptimized spans only
-        if (kind != 1) return PRK_ERR_UNSUPPORTED;
+        if (kind == 2) return PRK_ERR_UNSUPPORTED;
         const bool tex = texture >= 0;
         mode = phong ? (tex ? prk::MODE_SC_PHONG_TEX : prk::MODE_SC_PHONG)
                      : (tex ? prk::MODE_SC_GOURAUD_TEX : prk::MODE_SC_GOURAUD);
@@ -1178,6 +1190,43 @@ int prk_draw_edges(prk_context *c, const prk_edge *edges, uint32_t edge_count, i
     return rc;
 }
 
+// Whether a list of a batch takes the walks of a triangle object: sorted by
+// YMin (the sorted insertion cursor then inserts exactly what the reference's
+// whole-list scan inserts, in the same order), and every edge inside the
+// value range FillEdgeTable writes (0 <= YMin <= YMax, Left 0 or 1), which
+// those walks' list mirrors are sized for.  Any other list is walked as
+// prk_draw_edges walks it.
+static bool list_walks_sorted(const prk_edge *e, uint32_t n) {
+    int32_t prev = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (e[i].YMin < prev || e[i].YMax < e[i].YMin || (uint32_t)e[i].Left > 1u) return false;
+        prev = e[i].YMin;
+    }
+    return true;
+}
+
+int prk_draw_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                        int32_t semantics, int32_t phong, int32_t texture) {
+    if (!c || (!counts && list_count)) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    if (list_count == 0) return PRK_OK;
+    // the frame's batch records and lists are indexed by 31 bits (as a pass's edge slots, flush_spans)
+    if (c->pend_ledges.size() + total >= 0x7FFFFFFFull || c->pend_lcnt.size() + (uint64_t)list_count >= 0x7FFFFFFFull)
+        return PRK_ERR_LIMIT;
+    const uint32_t off = (uint32_t)c->pend_ledges.size(), l0 = (uint32_t)c->pend_lcnt.size();
+    const int rc = draw_src(c, 3, off, (uint32_t)total, list_count, semantics, phong, texture);
+    if (rc != PRK_OK) return rc;
+    c->draws.back().geom_tri0 = l0;
+    c->pend_ledges.insert(c->pend_ledges.end(), records, records + total);
+    c->pend_lcnt.insert(c->pend_lcnt.end(), counts, counts + list_count);
+    const prk_edge *e = records;
+    for (uint32_t o = 0; o < list_count; e += counts[o], ++o)
+        c->pend_lflag.push_back(list_walks_sorted(e, counts[o]) ? 1u : 0u);
+    return PRK_OK;
+}
+
 int prk_draw_spans(prk_context *c, const prk_span *spans, uint32_t count, int32_t semantics, int32_t phong,
                    int32_t texture) {
     if (!c || (!spans && count)) return PRK_ERR_ARG;
@@ -1194,6 +1243,9 @@ int prk_reset_draws(prk_context *c) {
     c->pending_tris = 0;
     c->pend_edges.clear();
     c->pend_spans.clear();
+    c->pend_ledges.clear();
+    c->pend_lcnt.clear();
+    c->pend_lflag.clear();
     return PRK_OK;
 }
 
@@ -1735,6 +1787,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     S.h_big_cap.clear();
     S.h_k1src.clear();
     uint64_t ntri = 0, nk1 = 0, pool = 0, maxn = 1, small_tris = 0, nobj64 = 0, nk064 = 0;
+    // the pass's batches (prk_draw_edge_lists) take consecutive records and
+    // lists of the frame's: [le0, le0 + nle) and [ll0, ll0 + nll); the small
+    // sorted lists' edges bound their segments
+    uint64_t nle = 0, nll = 0, small_ledges = 0;
+    uint32_t le0 = 0, ll0 = 0;
     bool thread_links = false;  // a thread-walked triangle object small enough for LDS list links
     std::vector<uint32_t> bigm[prk::MODE_COUNT], bige[prk::MODE_COUNT];  // wave-walked objects by mode, their edges
     for (uint32_t di = 0; di < draws.size(); ++di) {
@@ -1749,6 +1806,29 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
             if (!d.src_n) continue;
             S.h_runs.push_back(ObjRun{2u, di, (uint32_t)nobj64, d.src_n, 0u, 0u, d.first_global, 0u, 0u, d.src_off, 0u, 0u});
             nobj64 += d.src_n;
+        } else if (d.src_kind == 3) {
+            // one run for the batch; its sorted lists are routed like triangle
+            // objects of as many edges (k1off: the first batch edge's slot, below)
+            if (!nll) {
+                le0 = d.src_off;
+                ll0 = d.geom_tri0;
+            }
+            S.h_runs.push_back(ObjRun{3u, di, (uint32_t)nobj64, d.tri_count, 0u, 0u, d.first_global, 0u, (uint32_t)nll,
+                                      0u, 0u, 0u});
+            for (uint32_t j = 0; j < d.tri_count; ++j) {
+                const uint32_t n = c->pend_lcnt[d.geom_tri0 + j];
+                if (!c->pend_lflag[d.geom_tri0 + j]) continue;
+                if (n >= kObjWaveEdges) {
+                    bigm[d.mode].push_back((uint32_t)(nobj64 + j));
+                    bige[d.mode].push_back(n);
+                } else {
+                    small_ledges += n;
+                    thread_links = thread_links || (n && n <= prk_obj_link_cap());
+                }
+            }
+            nobj64 += d.tri_count;
+            nll += d.tri_count;
+            nle += d.src_n;
         } else {
             const uint32_t per = std::max<uint32_t>(1u, d.obj_tris);
             const uint32_t cnt = (uint32_t)(((uint64_t)d.tri_count + per - 1) / per);
@@ -1786,7 +1866,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
             big_edges.push_back(bige[mo][i]);
         }
     // edge slots (3 per triangle + the caller edges) are indexed by 31 bits
-    if (3 * ntri + nk1 >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    if (3 * ntri + nk1 + nle >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    for (ObjRun &r : S.h_runs)  // the batch edges' slots follow the prk_draw_edges lists'
+        if (r.kind == 3) r.k1off = (uint32_t)nk1;
+    S.h_lcnt.assign(c->pend_lcnt.begin() + ll0, c->pend_lcnt.begin() + ll0 + nll);
+    S.h_lcnt.push_back(0u);  // (the scan's total)
     const uint32_t nobj = (uint32_t)nobj64, nk0 = (uint32_t)nk064;
     const uint32_t nt = (uint32_t)ntri, nbig_all = (uint32_t)S.h_big_gl.size();
     // MergeSort key: (object, min(YMin, H), recursion path) in one radix sort
@@ -1801,7 +1885,8 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     // (the scratch below is reused frame to frame: stream order on s covers it)
     // The pass's host tables go up in one copy from pinned staging (a pageable
     // hipMemcpyAsync per table held the host for each).
-    enum { T_DRAWS, T_TEXS, T_OBJS, T_K0OBJ, T_K0TRI0, T_BIG, T_BIG_OFF, T_BIG_CAP, T_K1SRC, T_EDGES, T_SPANS, T_N };  // (T_OBJS: the runs)
+    enum { T_DRAWS, T_TEXS, T_OBJS, T_K0OBJ, T_K0TRI0, T_BIG, T_BIG_OFF, T_BIG_CAP, T_K1SRC, T_EDGES, T_SPANS,
+           T_LCNT, T_LFLAG, T_LEDGES, T_N };  // (T_OBJS: the runs)
     struct Part {
         const void *src;
         size_t bytes, off;
@@ -1815,7 +1900,10 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                     {nullptr, 0, 0},
                     {S.h_k1src.data(), S.h_k1src.size() * 4, 0},
                     {c->pend_edges.data(), c->pend_edges.size() * sizeof(prk_edge), 0},
-                    {c->pend_spans.data(), c->pend_spans.size() * sizeof(prk_span), 0}};
+                    {c->pend_spans.data(), c->pend_spans.size() * sizeof(prk_span), 0},
+                    {S.h_lcnt.data(), nll ? S.h_lcnt.size() * 4 : 0, 0},
+                    {c->pend_lflag.data() + ll0, (size_t)nll * 4, 0},
+                    {c->pend_ledges.data() + le0, (size_t)nle * sizeof(prk_edge), 0}};
     size_t stage_bytes = 0;
     for (Part &pt : parts) {
         pt.off = stage_bytes;
@@ -1854,7 +1942,23 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     void *d_objs = S.d_objtab.p;
     uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
     const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nk0;
-    PRK_TRY(prk_obj_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0, s));
+    // the batch lists' first edges: the scan of their counts
+    const uint32_t nlist = (uint32_t)nll, nledge = (uint32_t)nle;
+    uint32_t *lscan = nullptr, *lobj = nullptr;
+    if (nlist) {
+        size_t lb = 0;
+        PRK_TRY(S.d_lscan.ensure(((size_t)nlist + 1) * 4));
+        PRK_TRY(S.d_lobj.ensure((size_t)nlist * 4));
+        PRK_TRY(S.d_lrows.ensure((size_t)nlist * 8));
+        lscan = (uint32_t *)S.d_lscan.p;
+        lobj = (uint32_t *)S.d_lobj.p;
+        PRK_TRY(prk_scan_u32((const uint32_t *)dev(T_LCNT), lscan, nlist + 1, nullptr, &lb, s));
+        PRK_TRY(S.d_temp.ensure(std::max<size_t>(lb, 16)));
+        PRK_TRY(prk_scan_u32((const uint32_t *)dev(T_LCNT), lscan, nlist + 1, S.d_temp.p, &lb, s));
+    }
+    PRK_TRY(prk_obj_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0,
+                           (const uint32_t *)dev(T_LCNT), (const uint32_t *)dev(T_LFLAG), lscan, kObjWaveEdges, lobj,
+                           s));
     const uint32_t *d_big = (const uint32_t *)dev(T_BIG);
     const uint32_t *d_k1src = (const uint32_t *)dev(T_K1SRC);
     uint32_t modes = 0;  // the pass's span kinds: bit per Mode
@@ -1909,34 +2013,39 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt, end_bit, S.d_temp.p,
                              &tb, s));
     }
-    // Span slots: each object's bound, exclusive-scanned into its first slot.
     PRK_TRY(S.d_bound.ensure(((size_t)nobj + 1) * 8));
     PRK_TRY(S.d_oslot.ensure(((size_t)nobj + 1) * 8));
     unsigned long long *oslot = (unsigned long long *)S.d_oslot.p;
-    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, d_edges_in, (unsigned long long *)S.d_bound.p, s));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, nullptr, &tb, s));
-    PRK_TRY(temp(tb));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, S.d_temp.p, &tb, s));
-    // The walk's working copy, and each large object's most active edges
-    // (read back with the slot total: they size its walk's workgroup).
-    const uint32_t nwork = 3 * nt + (uint32_t)nk1;
+    // The walk's working copy (the triangle edges, the prk_draw_edges lists,
+    // the batch lists), and each large object's most active edges (read back
+    // with the slot total: they size its walk's workgroup).
+    const uint32_t nwork = 3 * nt + (uint32_t)nk1 + nledge;
     PRK_TRY(S.d_work.ensure(std::max<size_t>(nwork, 1) * 112));
     // The small triangle objects' segments (prk_spans.hip k_obj_seg, below):
     // a thread per stretch of rows with a non-empty list (PRK_OBJ_SEGMENTS=0:
     // a thread per object).
-    const uint64_t max_segs = 3 * small_tris;
+    const uint64_t max_segs = 3 * small_tris + small_ledges;  // (a segment has an edge at least)
     bool segmented = false;
     {
         const char *env = std::getenv("PRK_OBJ_SEGMENTS");
         segmented = max_segs && max_segs < 0x7FFFFFFFull && !(env && env[0] == '0');
     }
-    if (segmented) PRK_TRY(S.d_wy.ensure((size_t)std::max<uint64_t>(3 * nt, 1) * 8));
+    if (segmented) PRK_TRY(S.d_wy.ensure((size_t)std::max<uint32_t>(nwork, 1) * 8));
     if (local_sort)
         PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nk0, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p,
                                    segmented ? S.d_wy.p : nullptr, (uint32_t *)S.d_err.p, s));
     if (!local_sort || nk1)
         PRK_TRY(prk_obj_gather(S.d_edges.p, local_sort ? nullptr : ord, total0p, d_edges_in, d_k1src, (uint32_t)nk1,
-                               S.d_work.p, nwork, segmented ? S.d_wy.p : nullptr, s));
+                               S.d_work.p, 3 * nt + (uint32_t)nk1, segmented ? S.d_wy.p : nullptr, s));
+    // the batch lists' records into it, with their lists' row sums; then the
+    // span slots: each object's bound, exclusive-scanned into its first slot
+    PRK_TRY(prk_list_prep(&fp, dev(T_LEDGES), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1, S.d_work.p,
+                          segmented ? S.d_wy.p : nullptr, (unsigned long long *)S.d_lrows.p, s));
+    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, d_edges_in, (const unsigned long long *)S.d_lrows.p,
+                          (unsigned long long *)S.d_bound.p, s));
+    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, nullptr, &tb, s));
+    PRK_TRY(temp(tb));
+    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, S.d_temp.p, &tb, s));
     // per large object: most, rows, entries (12, k_obj_maxact) | big (4) |
     // off (8) | cap (4) | the chunked walk's table (32, prk_spans.hip PrObj)
     // and groups (4)
@@ -2343,7 +2452,13 @@ int prk_flush(prk_context *c, void *stream) {
     c->pending_tris = 0;
     struct Clear {  // the frame's edge / span input goes with its draws
         prk_context *c;
-        ~Clear() { c->pend_edges.clear(); c->pend_spans.clear(); }
+        ~Clear() {
+            c->pend_edges.clear();
+            c->pend_spans.clear();
+            c->pend_ledges.clear();
+            c->pend_lcnt.clear();
+            c->pend_lflag.clear();
+        }
     } clear_src{c};
     if (dr.empty()) return c->clear_pending ? fill_pending_clear(c, s) : PRK_OK;
     auto span_path = [](const prk::DrawRec &d) { return d.obj_tris > 1 || d.src_kind != 0; };
@@ -2529,7 +2644,7 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
     uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
     const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nobj;
     PRK_TRY(prk_obj_tables(static_cast<char *>(S.d_rectab.p) + kRunOff, 1, nobj, kObjWaveTris, d_objs, k0tab,
-                           k0tab + nobj, s));
+                           k0tab + nobj, nullptr, nullptr, nullptr, 0u, nullptr, s));
     const size_t es = 3 * (size_t)nt;
     PRK_TRY(S.d_ecnt.ensure(((size_t)nt + 1) * 4));
     PRK_TRY(S.d_escan.ensure(((size_t)nt + 1) * 4));

@@ -29,6 +29,14 @@
 //     segments             k_obj_seg + k_obj_walk_seg: small triangle objects
 //                          (fewer than wave_tris triangles), a thread per
 //                          stretch of rows with a non-empty list.
+//                 A prk_draw_edge_lists batch is a run of lists (k_obj_tables
+//                 expands it; k_list_prep converts its records into the
+//                 working copy and sums each list's rows for k_obj_bound).
+//                 Its lists sorted by YMin are objects of kind 3 and routed
+//                 as triangle objects are: below wave_edges edges to the
+//                 segments (or the thread walk, with LDS links), from there
+//                 on to k_obj_maxact and one of the walks below.  Its other
+//                 lists are caller edge lists of the thread walk.
 //     slot-list walk       k_obj_walk_wave, lcap > 0 (walk_rows over every
 //                          row): a workgroup per large object whose most
 //                          listed edges (k_obj_maxact) fit an LDS capacity
@@ -63,7 +71,8 @@
 // prk_edge_records (FillEdgeTable's records handed back, no frame) runs the
 // same count / scan / sort with k_rec_emit (every edge_info field, the key on
 // the true YMin), k_rec_counts and k_rec_export (packed prk_edge), at the end
-// of this file.
+// of this file; k_list_prep, k_rec_export's reverse for prk_draw_edge_lists,
+// follows them.
 #include <atomic>
 
 #include "prk_device.h"
@@ -94,7 +103,13 @@ namespace prk {
 //           edge input), drawn as DrawModelOptimized* draws it: no sort, the
 //           insertion scan over every edge each row (3654-3713);
 //   kind 2: one caller-given span (span input src): line_render_work /
-//           buffer_line_render_work's pair of one row (2336-2348).
+//           buffer_line_render_work's pair of one row (2336-2348);
+//   kind 3: a list of a prk_draw_edge_lists batch that is sorted by YMin (and
+//           within FillEdgeTable's value range, prk_api.hip): its nsrc edges
+//           are in the working copy as given (k_list_prep) and walked with
+//           the sorted insertion cursor by every walk a kind-0 object takes.
+//           A batch's other lists are kind 1.  Either way src is kListSrc
+//           and tri0 the list's index among the pass's batch lists (lrows).
 // g0 is the winner id (pass-local) of what it draws.
 struct ObjDesc {
     uint32_t draw;
@@ -102,22 +117,32 @@ struct ObjDesc {
     uint32_t tris;
     uint32_t tri0;      // kind 0: its first triangle among the pass's object triangles
     uint32_t kind, src, nsrc;
-    uint32_t k1off;     // kind 1: its first edge slot after the pass's triangle edges;
-                        // bit 31 (kObjWave): walked by one wave (k_obj_walk_wave)
+    uint32_t k1off;     // kind 1, 3: its first edge slot after the pass's triangle edges;
+                        // bit 31 (kObjWave): a large object (k_obj_maxact, then its walk)
 };
 constexpr uint32_t kObjWave = 0x80000000u;
+constexpr uint32_t kListSrc = 0xFFFFFFFFu;  // ObjDesc::src of a batch's list
+// Kinds whose edges are sorted by YMin: every walk but the whole-list scan.
+__device__ __forceinline__ bool obj_sorted(const ObjDesc &od) { return od.kind == 0 || od.kind == 3; }
 // An object's status in the parallel-rows walk (k_pr_*): 0 not taken,
 // walked by rows, or failed its check (the workgroup walk takes it).
 constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 
 // A run of objects as the host lists them (prk_api.hip ObjRun): a draw of
 // kind 0 is `count` objects of `per` triangles (the last one shorter), kind 2
-// one object per span, kind 1 one object; k_obj_tables expands them.
+// one object per span, kind 1 one object; k_obj_tables expands them.  A
+// prk_draw_edge_lists batch is one run of kind 3, `count` lists from the
+// pass's batch list k0base on: list l has lcnt[l] edges from edge slot
+// k1off + lscan[l] on (lscan: the exclusive scan of lcnt), is sorted iff
+// lflag[l], and is a large object from wave_edges edges on when sorted;
+// lobj[l] = its object.
 struct ObjRun {
     uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
 };
 __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris,
-                             ObjDesc *__restrict__ objs, uint32_t *__restrict__ k0obj, uint32_t *__restrict__ k0tri0) {
+                             ObjDesc *__restrict__ objs, uint32_t *__restrict__ k0obj, uint32_t *__restrict__ k0tri0,
+                             const uint32_t *__restrict__ lcnt, const uint32_t *__restrict__ lflag,
+                             const uint32_t *__restrict__ lscan, uint32_t wave_edges, uint32_t *__restrict__ lobj) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= nobj) return;
     uint32_t lo = 0, hi = nruns;  // the last run with obj0 <= o
@@ -132,6 +157,12 @@ __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, ui
         objs[o] = ObjDesc{R.draw, R.first_global, 0u, 0u, 1u, R.src_off, R.src_n, R.k1off};
     } else if (R.kind == 2) {
         objs[o] = ObjDesc{R.draw, R.first_global + j, 0u, 0u, 2u, R.src_off + j, 1u, 0u};
+    } else if (R.kind == 3) {
+        const uint32_t l = R.k0base + j, n = lcnt[l];
+        const bool sorted = lflag[l] != 0;
+        objs[o] = ObjDesc{R.draw, R.first_global + j, 0u, l, sorted ? 3u : 1u, kListSrc, n,
+                          (R.k1off + lscan[l]) | (sorted && n >= wave_edges ? kObjWave : 0u)};
+        lobj[l] = o;
     } else {
         const uint32_t t = j * R.per, n = min(R.per, R.tri_count - t);
         objs[o] = ObjDesc{R.draw, R.first_global + t, n, R.tri0 + t, 0u, 0u, 0u, n >= wave_tris ? kObjWave : 0u};
@@ -504,10 +535,11 @@ __global__ void k_objtri_emit(FrameParams fp, const ObjDesc *__restrict__ objs, 
 // Span slots of every object: the most spans its walk can emit — a span
 // pairs two entries active on its row, an entry is active on the rows
 // [YMin, YMax) of its edge walked — so half its edges' active rows (kind 0:
-// from the per-triangle counts; kind 1: its caller edges; kind 2: one).
+// from the per-triangle counts; kind 1: its caller edges; kind 2: one; a
+// batch's list, kind 1 or 3: from k_list_prep's sum of its edges' rows).
 __global__ void k_obj_bound(FrameParams fp, const ObjDesc *__restrict__ objs, uint32_t nobj,
                             const unsigned long long *__restrict__ rscan, const EdgeIn *__restrict__ edges_in,
-                            unsigned long long *__restrict__ bound) {
+                            const unsigned long long *__restrict__ lrows, unsigned long long *__restrict__ bound) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o > nobj) return;
     if (o == nobj) {
@@ -518,6 +550,8 @@ __global__ void k_obj_bound(FrameParams fp, const ObjDesc *__restrict__ objs, ui
     unsigned long long b = 1;
     if (od.kind == 0) {
         b = (rscan[od.tri0 + od.tris] - rscan[od.tri0]) / 2;
+    } else if (od.kind == 3 || (od.kind == 1 && od.src == kListSrc)) {
+        b = lrows[od.tri0] / 2;
     } else if (od.kind == 1) {
         const DrawRec &d = fp.draws[od.draw];
         const int32_t lo = draw_row_lo(fp, d), hi = draw_row_hi(fp);
@@ -735,7 +769,7 @@ __global__ void __launch_bounds__(256) k_obj_sort_local(const ObjDesc *__restric
 }
 
 // The AET walk of one object by one thread (small objects, caller edge
-// lists): E = its n edges, sorted (kind 0) or as given (kind 1).  Its spans
+// lists): E = its n edges, sorted (kind 0, 3) or as given (kind 1).  Its spans
 // go to slots [base, base + bound) in emission order.
 template <int M, class LK>
 __device__ void walk_object(const FrameParams &fp, const ObjDesc &od, const DrawRec &d, ObjEdge *__restrict__ E,
@@ -941,7 +975,7 @@ __global__ void __launch_bounds__(kLinkThreads, 1) k_obj_walk(FrameParams fp, co
     if (o >= nobj) return;
     const ObjDesc od = objs[o];
     if (od.kind != 2 && (od.k1off & kObjWave)) return;  // k_obj_walk_wave's
-    if (od.kind == 0 && segmented) return;             // k_obj_walk_seg's
+    if (obj_sorted(od) && segmented) return;           // k_obj_walk_seg's
     const DrawRec &d = fp.draws[od.draw];
     const bool st = (d.flags & DRAW_ST) != 0;
     const uint32_t base = (uint32_t)soff[o], bound = (uint32_t)(soff[o + 1] - soff[o]);
@@ -959,8 +993,9 @@ __global__ void __launch_bounds__(kLinkThreads, 1) k_obj_walk(FrameParams fp, co
     ObjEdge *E = work + e0;
     __shared__ typename std::conditional<LINKS, LinkLds, char>::type lds_;
     LinkLds &lds = *reinterpret_cast<LinkLds *>(&lds_);
-    // (triangle edges only: their Left is 0 / 1, a caller's edge_info.Left any b32)
-    bool in_lds = LINKS && od.kind == 0 && n > 0 && n <= (uint32_t)kLinkCap;
+    // (triangle edges and a batch's sorted lists only: their Left is 0 / 1, another
+    // caller's edge_info.Left any b32)
+    bool in_lds = LINKS && obj_sorted(od) && n > 0 && n <= (uint32_t)kLinkCap;
     const int32_t row0 = n ? E[0].YMin : 0;  // (sorted: the smallest YMin)
     if (in_lds) {
         int32_t hi = row0;
@@ -1032,7 +1067,7 @@ __global__ void k_obj_seg(FrameParams fp, const ObjDesc *__restrict__ objs, uint
     }
     const ObjDesc od = objs[o];
     uint32_t k = 0;
-    if (od.kind == 0 && !(od.k1off & kObjWave)) {
+    if (obj_sorted(od) && !(od.k1off & kObjWave)) {
         uint32_t e0, n;
         obj_range(od, escan, *total0p, e0, n);
         const int2 *Y = wy + e0;
@@ -2166,7 +2201,9 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_obj_maxact(FrameParams fp, 
     __shared__ BlockRed R;
     __shared__ unsigned long long ents;
     const ObjDesc od = objs[big[blockIdx.x]];
-    if (huge_min && od.kind == 0 && 3ull * od.tris >= huge_min) return;  // (k_maxact_huge_*)
+    // (k_maxact_huge_*: by the edges the host counts, 3 a triangle or the list's)
+    const unsigned long long host_edges = od.kind == 0 ? 3ull * od.tris : (unsigned long long)od.nsrc;
+    if (huge_min && obj_sorted(od) && host_edges >= huge_min) return;
     uint32_t e0, n;
     obj_range(od, escan, *total0p, e0, n);
     const ObjEdge *E = work + e0;
@@ -4125,6 +4162,103 @@ __global__ void __launch_bounds__(256) k_rec_export(const ObjEdge *__restrict__ 
     out[i] = make_uint4(v[0], v[1], v[2], v[3]);
 }
 
+// ---------------------------------------------------------------------------
+// prk_draw_edge_lists: the batch lists' packed prk_edge records into the
+// walk's working copy -- k_rec_export in reverse -- with each list's slot
+// bound.  A workgroup takes kPrepEdges consecutive edges of the pass's batch
+// lists (all runs together: `in` is their records back to back).  Their
+// 27 * kPrepEdges dwords are a 16-byte-aligned stretch of the flat input,
+// read in 16-byte pieces into LDS; then lane t of pass k stores dwordx4
+// number t + k * 256 of the workgroup's ObjEdge output (edge (t + 256 k) / 7,
+// quad (t + 256 k) % 7: 4 KiB contiguous a pass), each dword picked from its
+// record in LDS (obj_edge_in's field map; Next = -1), and a lane per edge
+// adds the edge's rows max(0, min(YMax, hi) - max(YMin, lo)) to its list's sum
+// (lrows, zeroed by the launcher; the halving is k_obj_bound's, once per
+// list): a wave sums the lanes of one list and its first lane adds the sum,
+// one 64-bit integer atomic per list and wave, so the sum is exact.
+//   in     the records, readable up to a multiple of 16 bytes
+//   lscan  nlist + 1 values: the lists' first edges, the last = nedge
+//   lobj   each list's object (k_obj_tables): its draw gives lo (draw_row_lo)
+//   ebase  the first batch edge's slot after the triangle edges (*total0p)
+//   wy     null, or (YMin, YMax) per working-copy slot for k_obj_seg
+// ---------------------------------------------------------------------------
+constexpr int kPrepEdges = 256;
+struct PrepMap {
+    uint8_t f[28];  // ObjEdge dword -> prk_edge field (27: none, the link)
+};
+constexpr PrepMap prep_map() {
+    // prk_edge field f -> ObjEdge dword (k_rec_export's kWord)
+    constexpr uint8_t kWord[27] = {17, 0, 2, 4, 1, 3, 5, 16, 6, 8, 7, 9, 18, 20, 21, 22, 23,
+                                   24, 25, 26, 27, 10, 11, 12, 13, 14, 15};
+    PrepMap m{};
+    for (int d = 0; d < 28; ++d) m.f[d] = 27;
+    for (int f = 0; f < 27; ++f) m.f[kWord[f]] = (uint8_t)f;
+    return m;
+}
+__global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const uint4 *__restrict__ in, uint32_t nedge,
+                                                          const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                          const uint32_t *__restrict__ lobj,
+                                                          const ObjDesc *__restrict__ objs,
+                                                          const uint32_t *__restrict__ total0p, uint32_t ebase,
+                                                          ObjEdge *__restrict__ work, int2 *__restrict__ wy,
+                                                          unsigned long long *__restrict__ lrows) {
+    static constexpr PrepMap kMap = prep_map();
+    static_assert(kMap.f[19] == 27 && kMap.f[16] == 7 && kMap.f[17] == 0, "ObjEdge: Next, YMin, YMax");
+    constexpr uint32_t kPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
+    static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
+    __shared__ uint4 rec4[kPieces];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;  // (< nedge: the grid)
+    const uint32_t ne = min((uint32_t)kPrepEdges, nedge - e_first);
+    const uint32_t np = (27u * ne + 3u) / 4u;
+    const uint4 *src = in + (size_t)blockIdx.x * kPieces;
+    for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
+    __syncthreads();
+    const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4);
+    const size_t slot0 = (size_t)*total0p + ebase + e_first;
+    float4 *dst = reinterpret_cast<float4 *>(work + slot0);
+    for (uint32_t j = tid; j < 7u * ne; j += (uint32_t)kPrepEdges) {
+        const uint32_t e = j / 7u, q = j - 7u * e;
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // (q is not a constant: the map is read from a small table)
+            const uint32_t f = kMap.f[4 * q + k];
+            v[k] = f < 27u ? rec[27u * e + f] : 0xFFFFFFFFu;
+        }
+        dst[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                             __uint_as_float(v[3]));
+    }
+    // the edge's rows into its list's sum
+    const bool have = tid < ne;
+    uint32_t l = 0;
+    unsigned long long r = 0;
+    if (have) {
+        const uint32_t e = e_first + tid;
+        uint32_t lo = 0, hi = nlist;  // the last list with lscan[l] <= e (an empty list is never the last)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (lscan[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        l = lo;
+        const int32_t ymin = (int32_t)rec[27u * tid + 7u], ymax = (int32_t)rec[27u * tid];
+        if (wy) wy[slot0 + tid] = make_int2(ymin, ymax);
+        const DrawRec &d = fp.draws[objs[lobj[l]].draw];
+        r = (unsigned long long)max(0, min(ymax, draw_row_hi(fp)) - max(ymin, draw_row_lo(fp, d)));
+    }
+    unsigned long long todo = __ballot(have);
+    while (todo) {  // (wave-uniform: one turn per list the wave's edges belong to)
+        const int lead = __ffsll((long long)todo) - 1;
+        const uint32_t ll = (uint32_t)__builtin_amdgcn_readlane((int)l, lead);
+        const bool mine = have && l == ll;
+        unsigned long long sum = mine ? r : 0ull;
+        for (int off = 32; off; off >>= 1) sum += __shfl_xor(sum, off);
+        if ((int)(tid & 63u) == lead && sum) atomicAdd(&lrows[ll], sum);
+        todo &= ~__ballot(mine);
+    }
+}
+
 }  // namespace prk
 
 extern "C" {
@@ -4161,12 +4295,29 @@ hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total
 }
 
 // The pass's objects (ObjDesc) and kind-0 object tables from the host's runs.
+// (lcnt, lflag, lscan, lobj: the batch lists' tables, k_obj_tables; null
+// without runs of kind 3)
 hipError_t prk_obj_tables(const void *runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris, void *objs,
-                          uint32_t *k0obj, uint32_t *k0tri0, hipStream_t s) {
+                          uint32_t *k0obj, uint32_t *k0tri0, const uint32_t *lcnt, const uint32_t *lflag,
+                          const uint32_t *lscan, uint32_t wave_edges, uint32_t *lobj, hipStream_t s) {
     if (nobj == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_obj_tables, dim3((nobj + 255) / 256), dim3(256), 0, s,
                        reinterpret_cast<const prk::ObjRun *>(runs), nruns, nobj, wave_tris,
-                       reinterpret_cast<prk::ObjDesc *>(objs), k0obj, k0tri0);
+                       reinterpret_cast<prk::ObjDesc *>(objs), k0obj, k0tri0, lcnt, lflag, lscan, wave_edges, lobj);
+    return hipGetLastError();
+}
+// The batch lists' records into the working copy, and each list's row sum
+// (k_list_prep; lrows: nlist values, zeroed here).
+hipError_t prk_list_prep(const prk::FrameParams *fp, const void *records, uint32_t nedge, const uint32_t *lscan,
+                         uint32_t nlist, const uint32_t *lobj, const void *objs, const uint32_t *total0p,
+                         uint32_t ebase, void *work, void *wy, unsigned long long *lrows, hipStream_t s) {
+    if (nlist == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(lrows, 0, (size_t)nlist * 8, s);
+    if (e != hipSuccess || nedge == 0) return e;
+    hipLaunchKernelGGL(prk::k_list_prep, dim3((nedge + prk::kPrepEdges - 1) / prk::kPrepEdges),
+                       dim3(prk::kPrepEdges), 0, s, *fp, reinterpret_cast<const uint4 *>(records), nedge, lscan, nlist,
+                       lobj, reinterpret_cast<const prk::ObjDesc *>(objs), total0p, ebase,
+                       reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy), lrows);
     return hipGetLastError();
 }
 // FillEdgeTable of the pass's object triangles: per-triangle edge and
@@ -4222,10 +4373,11 @@ hipError_t prk_obj_sort_local(const void *objs, const uint32_t *k0obj, uint32_t 
 // Span slots per object (nobj + 1 values, the last 0; exclusive-scanned by
 // the caller into each object's first slot).
 hipError_t prk_obj_bound(const prk::FrameParams *fp, const void *objs, uint32_t nobj, const unsigned long long *rscan,
-                         const void *edges_in, unsigned long long *bound, hipStream_t s) {
+                         const void *edges_in, const unsigned long long *lrows, unsigned long long *bound,
+                         hipStream_t s) {
     hipLaunchKernelGGL(prk::k_obj_bound, dim3((nobj + 1 + 255) / 256), dim3(256), 0, s, *fp,
                        reinterpret_cast<const prk::ObjDesc *>(objs), nobj, rscan,
-                       reinterpret_cast<const prk::EdgeIn *>(edges_in), bound);
+                       reinterpret_cast<const prk::EdgeIn *>(edges_in), lrows, bound);
     return hipGetLastError();
 }
 // The LDS capacity of the workgroup walk on the current device (listed edges;

@@ -80,6 +80,8 @@ _SIGS = {
                                          C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "prk_draw_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]),
     "prk_draw_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]),
+    "prk_draw_edge_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32,
+                                      C.c_int32]),
     "prk_flush": (C.c_int, [C.c_void_p, C.c_void_p]),
     "prk_reset_draws": (C.c_int, [C.c_void_p]),
     "prk_synchronize": (C.c_int, [C.c_void_p]),
@@ -571,6 +573,21 @@ class Renderer:
                                                             _ptr(words), words.shape[0], _ptr(counts),
                                                             C.byref(total)))
         return words[:total.value], counts
+
+    def draw_edge_lists(self, words, counts, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
+        """prk_draw_edge_lists: a batch of edge_info lists in one call, the two
+        arrays edge_records returns (uint32 [total, 27] in prk_edge layout,
+        uint32 [nobj]).  List o is drawn as draw_edges(words of list o) draws
+        it and takes winner id base + o, empty or not; lists sorted by YMin
+        run through the walks of triangle objects of their size."""
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1, 27)
+        n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if int(n.sum(dtype=np.uint64)) != w.shape[0]:
+            raise ValueError("draw_edge_lists: counts sum to %d, %d records given" % (int(n.sum(dtype=np.uint64)),
+                                                                                   w.shape[0]))
+        _check("prk_draw_edge_lists", self._L.prk_draw_edge_lists(self._h, _ptr(w), _ptr(n), n.shape[0], semantics,
+                                                                  int(bool(phong)),
+                                                                  -1 if bitmap is None else bitmap))
 
     def draw_spans(self, span_words, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
         """Caller spans (the work records of DoLineRenderWork): uint32 [n, 25]

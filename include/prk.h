@@ -357,6 +357,38 @@ typedef struct prk_edge {
 } prk_edge;
 int prk_draw_edges(prk_context *ctx, const prk_edge *edges, uint32_t edge_count, int32_t semantics, int32_t phong,
                    int32_t texture);
+/* A batch of such lists in one call, in the packed layout prk_edge_records
+ * produces: list o is records[sum(counts[0..o)) ...], counts[o] entries long.
+ * Each list is drawn exactly as one prk_draw_edges call of it would draw it,
+ * the lists in order, one after another, at this point of the frame's
+ * submission order; the records are copied at the call.  Semantics, phong and
+ * texture are checked as prk_draw_edges checks them.
+ *
+ * Winner ids: list o takes id base + o of the frame's numbering, base being
+ * the id the next draw would have had.  EVERY list takes one id, empty or
+ * not, so ids map to list indices -- unlike prk_draw_edges, which takes no id
+ * for an empty list (a loop of prk_draw_edges calls over the same lists
+ * numbers the lists after an empty one differently).
+ *
+ * A list whose YMin is non-decreasing (what FillEdgeTable's MergeSort and
+ * prk_edge_records leave) and whose edges lie in FillEdgeTable's value range
+ * (0 <= YMin <= YMax, Left 0 or 1) is walked as a triangle object of as many
+ * edges is: the sorted insertion cursor inserts on every row exactly the
+ * edges the reference's whole-list scan (3654-3713) inserts, in the same
+ * order, so the frame is the same, and long lists take the parallel walks
+ * (144 edges or more: the large-object walks, counted by
+ * prk_debug_walk_routes and prk_stats.objects_chunked / objects_walked).
+ * Any other list is walked as prk_draw_edges walks it, by one thread that
+ * scans the whole list on every row.
+ *
+ * PRK_ERR_ARG: a NULL context, NULL counts with list_count > 0, NULL records
+ * with a non-zero total, a bad semantics or texture, ids past the frame's
+ * numbering.  PRK_ERR_UNSUPPORTED: as prk_draw_edges.  PRK_ERR_LIMIT: the
+ * frame's batch records or lists pass 31 bits (prk_flush returns it when a
+ * pass's edge slots do).  list_count == 0: PRK_OK, nothing recorded.  On any
+ * error nothing is recorded. */
+int prk_draw_edge_lists(prk_context *ctx, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                        int32_t semantics, int32_t phong, int32_t texture);
 
 /* One span end as line_render_work carries it by value (projekt.h:65-74) or
  * thread_edge_info holds it (39-63): what FillLineOptimized /
@@ -533,7 +565,9 @@ int prk_advance_edge_records(void *edges, uint32_t count, size_t stride, size_t 
  * records no draw, touches no recorded draw; synchronous.
  *
  * For a caller that wants the records of many objects at once (to keep them,
- * or to draw them later with prk_draw_edges).  PRK_ERR_ARG: a NULL context or
+ * or to draw them later: all at once with prk_draw_edge_lists, which takes
+ * records and counts as they are, or one list at a time with
+ * prk_draw_edges).  PRK_ERR_ARG: a NULL context or
  * total_out, a bad geometry handle or triangle range, tris_per_object == 0,
  * setup outside 0..3, a call before any prk_set_camera, or a capacity (in
  * records) below the total -- *total_out is written all the same, so the
