@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <functional>
 #include <atomic>
 #include <string>
 #include <cmath>
@@ -73,6 +74,8 @@ hipError_t prk_rec_emit(const prk::FrameParams *, const void *, const uint32_t *
                         const uint32_t *, int32_t, uint32_t, void *, void *, uint32_t *, int, hipStream_t);
 hipError_t prk_rec_counts(const void *, const uint32_t *, uint32_t, const uint32_t *, uint32_t *, hipStream_t);
 hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipStream_t);
+hipError_t prk_adv_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, hipStream_t);
+hipError_t prk_adv_next(const void *, uint32_t, int32_t *, hipStream_t);
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
@@ -2703,6 +2706,93 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
     }
     if (counts) PRK_TRY(hipMemcpy(counts, S.d_reccnt.p, (size_t)nobj * 4, hipMemcpyDeviceToHost));
     return records && capacity < total ? PRK_ERR_ARG : PRK_OK;
+}
+
+// The lists DrawModel* leaves (prk_advance_edge_records' result) for a batch
+// of sorted lists, walked on the GPU: k_adv_import -> k_adv_walk (one thread
+// per list) -> k_rec_export + k_adv_next (prk_spans.hip).  Every refusal is
+// decided on the host, in the one pass over the records that checks the
+// sorted rule (list_walks_sorted) and sizes each list's walk -- a list is one
+// thread's, so a list over kAdvMaxSteps is refused before anything is
+// launched.  The scratch is the span path's, taken as prk_edge_records takes
+// it; the packed records go in and come out through one buffer (the import
+// has read it before the export writes it).
+//
+// kAdvMaxSteps: one thread walks 1.6 M edge-rows a second (DESIGN §4.4.3,
+// one pair a row and 128 pairs a row alike), so the 2^24 edge-rows first
+// meant would hold the GPU for 10 s; halved until a list at the cap stays
+// under two seconds: 2^21, 1.3 s.
+constexpr uint64_t kAdvMaxSteps = 1ull << 21;
+// A list's walk in list steps: its edge-rows, the sum over its edges of
+// max(0, min(YMax, height) - YMin) (k_list_prep's lrows; the removal scan and
+// the pairing visit every listed edge once a row), plus its insertion scans:
+// an inserted edge is compared with at most every edge still linked, those
+// inserted before it whose YMax is not below its YMin (an edge leaves the
+// list on row YMax, after that row's insertions).  The count of all earlier
+// edges bounds that for short lists; a list that bound would refuse is swept
+// with a heap of the linked edges' YMax.  Returns at once past `cap`.
+static uint64_t list_walk_steps(const prk_edge *e, uint32_t n, int32_t height, uint64_t cap,
+                                std::vector<int32_t> &heap) {
+    uint64_t steps = 0;
+    for (uint32_t i = 0; i < n; ++i) steps += (uint64_t)std::max(0, std::min(e[i].YMax, height) - e[i].YMin);
+    const uint64_t all = (uint64_t)n * (n ? n - 1 : 0) / 2;
+    if (steps > cap || steps + all <= cap) return steps + all;
+    heap.clear();
+    for (uint32_t i = 0; i < n && e[i].YMin < height && steps <= cap; ++i) {  // (the walk ends at `height`)
+        while (!heap.empty() && heap.front() < e[i].YMin) {
+            std::pop_heap(heap.begin(), heap.end(), std::greater<int32_t>());
+            heap.pop_back();
+        }
+        steps += heap.size();
+        heap.push_back(e[i].YMax);
+        std::push_heap(heap.begin(), heap.end(), std::greater<int32_t>());
+    }
+    return steps;
+}
+int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                           int32_t height, prk_edge *records_out, int32_t *next_out) {
+    if (!c || (!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if ((!records || !records_out) && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) return PRK_OK;
+    std::vector<uint32_t> lscan((size_t)list_count + 1);
+    std::vector<int32_t> heap;
+    bool too_long = false;
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            lscan[o] = at;
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap) > kAdvMaxSteps;
+        }
+        lscan[list_count] = at;
+    }
+    if (too_long) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const uint32_t n = (uint32_t)total;
+    const size_t rec_bytes = (size_t)n * sizeof(prk_edge);
+    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
+    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
+    PRK_TRY(S.d_escan.ensure(lscan.size() * 4));
+    if (next_out) PRK_TRY(S.d_evals.ensure((size_t)n * 4));
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, rec_bytes, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_escan.p, lscan.data(), lscan.size() * 4, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (lscan is this call's; records may be records_out)
+    PRK_TRY(prk_adv_walk(S.d_recout.p, n, (const uint32_t *)S.d_escan.p, list_count, height, S.d_work.p, s));
+    PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, S.d_recout.p, s));
+    if (next_out) PRK_TRY(prk_adv_next(S.d_work.p, n, (int32_t *)S.d_evals.p, s));
+    PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernels ran
+    PRK_TRY(hipMemcpyAsync(records_out, S.d_recout.p, rec_bytes, hipMemcpyDeviceToHost, s));
+    if (next_out) PRK_TRY(hipMemcpyAsync(next_out, S.d_evals.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    return PRK_OK;
 }
 
 // ConstructSphere (projekt.cpp:4123-4289): the reference's only test mesh.

@@ -72,7 +72,9 @@
 // same count / scan / sort with k_rec_emit (every edge_info field, the key on
 // the true YMin), k_rec_counts and k_rec_export (packed prk_edge), at the end
 // of this file; k_list_prep, k_rec_export's reverse for prk_draw_edge_lists,
-// follows them.
+// follows them, and then prk_advance_edge_lists' kernels (the list DrawModel*
+// leaves, no frame): k_adv_import (k_list_prep's import), k_adv_walk (a
+// thread per list, every field stepped), k_adv_next (the links).
 #include <atomic>
 
 #include "prk_device.h"
@@ -4195,28 +4197,25 @@ constexpr PrepMap prep_map() {
     for (int f = 0; f < 27; ++f) m.f[kWord[f]] = (uint8_t)f;
     return m;
 }
-__global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const uint4 *__restrict__ in, uint32_t nedge,
-                                                          const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                          const uint32_t *__restrict__ lobj,
-                                                          const ObjDesc *__restrict__ objs,
-                                                          const uint32_t *__restrict__ total0p, uint32_t ebase,
-                                                          ObjEdge *__restrict__ work, int2 *__restrict__ wy,
-                                                          unsigned long long *__restrict__ lrows) {
+// A workgroup's records into LDS and on into the working copy: edges
+// [e_first, e_first + ne) of the flat input as ObjEdges at dst[0 .. ne)
+// (shared by k_list_prep and k_adv_import; ends in a barrier, so the callers
+// read `rec4` after it).  Returns ne.
+constexpr uint32_t kPrepPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
+static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
+__device__ __forceinline__ uint32_t prep_records(const uint4 *__restrict__ in, uint32_t nedge, uint4 *rec4,
+                                                 ObjEdge *__restrict__ dst_edges) {
     static constexpr PrepMap kMap = prep_map();
     static_assert(kMap.f[19] == 27 && kMap.f[16] == 7 && kMap.f[17] == 0, "ObjEdge: Next, YMin, YMax");
-    constexpr uint32_t kPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
-    static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
-    __shared__ uint4 rec4[kPieces];
     const uint32_t tid = threadIdx.x;
     const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;  // (< nedge: the grid)
     const uint32_t ne = min((uint32_t)kPrepEdges, nedge - e_first);
     const uint32_t np = (27u * ne + 3u) / 4u;
-    const uint4 *src = in + (size_t)blockIdx.x * kPieces;
+    const uint4 *src = in + (size_t)blockIdx.x * kPrepPieces;
     for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
     __syncthreads();
     const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4);
-    const size_t slot0 = (size_t)*total0p + ebase + e_first;
-    float4 *dst = reinterpret_cast<float4 *>(work + slot0);
+    float4 *dst = reinterpret_cast<float4 *>(dst_edges);
     for (uint32_t j = tid; j < 7u * ne; j += (uint32_t)kPrepEdges) {
         const uint32_t e = j / 7u, q = j - 7u * e;
         uint32_t v[4];
@@ -4229,6 +4228,21 @@ __global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const 
         dst[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
                              __uint_as_float(v[3]));
     }
+    return ne;
+}
+__global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const uint4 *__restrict__ in, uint32_t nedge,
+                                                          const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                          const uint32_t *__restrict__ lobj,
+                                                          const ObjDesc *__restrict__ objs,
+                                                          const uint32_t *__restrict__ total0p, uint32_t ebase,
+                                                          ObjEdge *__restrict__ work, int2 *__restrict__ wy,
+                                                          unsigned long long *__restrict__ lrows) {
+    __shared__ uint4 rec4[kPrepPieces];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;
+    const size_t slot0 = (size_t)*total0p + ebase + e_first;
+    const uint32_t ne = prep_records(in, nedge, rec4, work + slot0);
+    const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4);
     // the edge's rows into its list's sum
     const bool have = tid < ne;
     uint32_t l = 0;
@@ -4257,6 +4271,180 @@ __global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const 
         if ((int)(tid & 63u) == lead && sum) atomicAdd(&lrows[ll], sum);
         todo &= ~__ballot(mine);
     }
+}
+
+// ---------------------------------------------------------------------------
+// prk_advance_edge_lists: the list DrawModel* leaves in the caller's
+// edge_info array (3654-3869), for a batch of sorted lists and no frame:
+// k_adv_import (k_list_prep's import alone: list o's records at slots
+// lscan[o] ..) -> k_adv_walk (a thread per list) -> k_rec_export of the
+// working copy and k_adv_next of its links.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPrepEdges) k_adv_import(const uint4 *__restrict__ in, uint32_t nedge,
+                                                           ObjEdge *__restrict__ work) {
+    __shared__ uint4 rec4[kPrepPieces];
+    prep_records(in, nedge, rec4, work + (size_t)blockIdx.x * kPrepEdges);
+}
+
+// The whole edge step (3811-3829): every field, whatever the draw's mode
+// reads (obj_step<M> steps only those) -- here the stepped record is the
+// result.  The record's quads that hold no stepped field (row range, Left and
+// link; the colour gradient) are not written back.
+__device__ __forceinline__ void adv_step(ObjEdge *p) {
+    PRK_ER(w);
+    PRK_ER_LOAD(w, p);
+    ObjEdge E = PRK_ER_EDGE(w);
+    E.X += E.G;
+    E.Z += E.ZG;
+    E.C0 += E.CG0; E.C1 += E.CG1; E.C2 += E.CG2; E.C3 += E.CG3;
+    float x = E.N0 + E.NG0, y = E.N1 + E.NG1, z = E.N2 + E.NG2;
+    normalize_rcp(x, y, z);
+    E.N0 = x; E.N1 = y; E.N2 = z;
+    E.U += E.UG;
+    E.V += E.VG;
+    E.W += E.WG;
+    PRK_ER_FROM(w, E);
+    float4 *d = reinterpret_cast<float4 *>(p);
+    d[0] = w0; d[1] = w1; d[2] = w2; d[3] = w3; d[5] = w5;
+}
+
+// walk_object's sorted branch without the frame: the same insertion cursor,
+// expiry, 3722-3749 removal, pairing with both swaps (P3) and empty-list row
+// skip, no span, every field stepped (adv_step), over the rows
+// [YMin[0], min(max YMax, height)) -- prk_advance_edge_records' rows, no band
+// or target clip.  Under the sorted rule (prk.h) the cursor inserts on every
+// row the edges the reference's whole-list scan inserts, in the same order.
+// The list is walked whole: an edge that expires on the row later edges are
+// inserted on is still linked when they are, and its final Next depends on
+// them (k_obj_seg's split would lose that word).  The records are stepped in
+// place; the links are LK's (GLinks: the records' own Next).
+template <class LK>
+__device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK lk) {
+    const int32_t FirstRow = lk.ymin(0);
+    int32_t MaxRow = lk.ymax(0);
+    for (uint32_t i = 1; i < n; ++i) MaxRow = max(MaxRow, lk.ymax((int)i));
+    const int32_t MaxY = min(MaxRow, height);
+    for (uint32_t i = 0; i < n; ++i) lk.set_next((int)i, -1);  // 4094
+    int32_t Head = -1, Tail = -1;
+    uint32_t ins = 0;        // next sorted edge to insert
+    int32_t nym = FirstRow;  // its YMin (INT32_MAX past the end)
+    for (int32_t Row = FirstRow; Row < MaxY; ++Row) {
+        while (ins < n && nym < Row) nym = ++ins < n ? lk.ymin((int)ins) : INT32_MAX;
+        const uint32_t i0 = ins;
+        while (ins < n && nym == Row) nym = ++ins < n ? lk.ymin((int)ins) : INT32_MAX;
+        for (uint32_t ii = i0; ii < ins; ++ii) {  // insertion 3654-3713
+            const int32_t c = (int32_t)ii;
+            if (Head >= 0) {
+                if (lk.before(c, Head)) {
+                    lk.set_next(c, Head);
+                    Head = c;
+                } else {
+                    int32_t Cmp = Head, Prev = Head;
+                    while (Cmp != Tail) {
+                        Cmp = lk.next(Cmp);
+                        if (lk.before(c, Cmp)) {
+                            lk.set_next(c, Cmp);
+                            lk.set_next(Prev, c);
+                            Cmp = Tail;
+                        } else {
+                            Prev = Cmp;
+                        }
+                    }
+                    if (Prev == Cmp) {
+                        lk.set_next(Tail, c);
+                        Tail = c;
+                    }
+                }
+            } else {
+                Head = c;
+                Tail = c;
+            }
+        }
+        while (Head >= 0 && lk.ymax(Head) <= Row) {  // expiry 3715-3720
+            const int32_t Rm = Head;
+            Head = lk.next(Head);
+            lk.set_next(Rm, -1);
+        }
+        if (Head < 0) {  // pin: the row is skipped, and so are the rows before the next insertion
+            Tail = -1;
+            if (ins >= n) break;
+            Row = max(Row, nym - 1);
+            continue;
+        }
+        {
+            int32_t Prev = Head, Chk = Head;  // 3722-3749
+            while (Chk != Tail) {
+                Chk = lk.next(Chk);
+                if (lk.ymax(Chk) <= Row) {
+                    if (Chk == Tail) {
+                        Tail = Prev;
+                        lk.set_next(Tail, -1);
+                        Chk = Tail;
+                    } else {
+                        lk.set_next(Prev, lk.next(Chk));
+                        Chk = Prev;
+                    }
+                }
+                Prev = Chk;
+            }
+        }
+        int32_t PrevCur = -1, PrevNext = -1;  // pairing 3751-3869
+        int32_t Cur = Head, Next = lk.next(Cur);
+        while (Next >= 0) {
+            adv_step(&E[Cur]);  // 3811-3829
+            adv_step(&E[Next]);
+            lk.stepped(Cur);
+            lk.stepped(Next);
+            if (lk.x(Cur) > lk.x(Next)) {  // 3831-3841
+                lk.set_next(Cur, lk.next(Next));
+                lk.set_next(Next, Cur);
+                if (PrevNext >= 0) lk.set_next(PrevNext, Next);
+                else Head = Next;              // P3
+                if (Tail == Next) Tail = Cur;  // P3
+                Cur = Next;
+                Next = lk.next(Cur);
+            }
+            if (PrevNext >= 0) {  // 3843-3853
+                if (lk.x(PrevNext) > lk.x(Cur)) {
+                    lk.set_next(PrevNext, lk.next(Cur));
+                    lk.set_next(Cur, PrevNext);
+                    lk.set_next(PrevCur, Cur);
+                    PrevNext = Cur;
+                    Cur = lk.next(PrevNext);
+                }
+            }
+            PrevCur = Cur;
+            PrevNext = Next;
+            if (lk.next(Next) >= 0) {
+                Cur = lk.next(Next);
+                Next = lk.next(Cur);
+            } else {
+                Next = -1;
+            }
+        }
+    }
+}
+
+// One thread per list; list o: lscan[o + 1] - lscan[o] edges at work +
+// lscan[o].  The list fields are the records' own (GLinks): k_obj_walk's LDS
+// mirrors of short lists were measured here too and left out (DESIGN
+// §4.4.3).  A list of fewer than two edges pairs nothing: it stays as
+// imported, every Next -1.
+__global__ void __launch_bounds__(kLinkThreads) k_adv_walk(ObjEdge *__restrict__ work,
+                                                           const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                           int32_t height) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= nlist) return;
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    if (n < 2) return;
+    adv_walk_list(work + e0, n, height, GLinks{work + e0});
+}
+
+// Each edge's Next, an index within its own list or -1, as one flat array.
+__global__ void __launch_bounds__(256) k_adv_next(const ObjEdge *__restrict__ work, uint32_t total,
+                                                  int32_t *__restrict__ next_out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) next_out[i] = work[i].Next;
 }
 
 }  // namespace prk
@@ -4291,6 +4479,29 @@ hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total
     const unsigned long long ndw = 27ull * total, nthr = (ndw + 3) / 4;
     hipLaunchKernelGGL(prk::k_rec_export, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const prk::ObjEdge *>(edges), ord, ndw, reinterpret_cast<uint4 *>(out));
+    return hipGetLastError();
+}
+
+// prk_advance_edge_lists: `total` packed records (readable up to a multiple
+// of 16 bytes) of nlist lists (lscan: nlist + 1 first edges) into the working
+// copy, walked over `height` rows there; prk_rec_export(work, nullptr, ...)
+// packs the result, prk_adv_next its links.
+hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
+                        void *work, hipStream_t s) {
+    if (total == 0 || nlist == 0) return hipSuccess;
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
+                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(prk::k_adv_walk, dim3((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads),
+                       dim3(prk::kLinkThreads), 0, s, w, lscan, nlist, height);
+    return hipGetLastError();
+}
+hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_adv_next, dim3((total + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const prk::ObjEdge *>(work), total, next_out);
     return hipGetLastError();
 }
 

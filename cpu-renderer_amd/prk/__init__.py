@@ -105,6 +105,8 @@ _SIGS = {
                                       C.POINTER(C.c_uint32)]),
     "prk_edge_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                    C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "prk_advance_edge_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p,
+                                         C.c_void_p]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -588,6 +590,23 @@ class Renderer:
         _check("prk_draw_edge_lists", self._L.prk_draw_edge_lists(self._h, _ptr(w), _ptr(n), n.shape[0], semantics,
                                                                   int(bool(phong)),
                                                                   -1 if bitmap is None else bitmap))
+
+    def advance_edge_lists(self, words, counts, height):
+        """prk_advance_edge_lists: what DrawModel* leaves in every list of a
+        batch over a frame of `height` rows, walked on the GPU -- the two
+        arrays edge_records returns in, (words_out uint32 [total, 27],
+        next int32 [total]: each record's Next as an index within its own
+        list, -1 for NULL) out.  Lists sorted by YMin only (prk.h)."""
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1, 27)
+        n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if int(n.sum(dtype=np.uint64)) != w.shape[0]:
+            raise ValueError("advance_edge_lists: counts sum to %d, %d records given" % (int(n.sum(dtype=np.uint64)),
+                                                                                      w.shape[0]))
+        out = np.empty_like(w)
+        nxt = np.empty(w.shape[0], np.int32)
+        _check("prk_advance_edge_lists", self._L.prk_advance_edge_lists(self._h, _ptr(w), _ptr(n), n.shape[0],
+                                                                        int(height), _ptr(out), _ptr(nxt)))
+        return out, nxt
 
     def draw_spans(self, span_words, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
         """Caller spans (the work records of DoLineRenderWork): uint32 [n, 25]

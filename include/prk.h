@@ -577,11 +577,50 @@ int prk_advance_edge_records(void *edges, uint32_t count, size_t stride, size_t 
  * flight finish first.  The drop-in's record mode (projekt.h) does not use
  * this: there FillEdgeTable must leave the records in the caller's own
  * memory before it returns and keep the caller's bytes in unwritten fields,
- * which a batched call cannot do; and the list DrawModel* leaves
- * (prk_advance_edge_records) is host-only. */
+ * which a batched call cannot do.  The lists DrawModel* leaves come from
+ * prk_advance_edge_lists (below) for such a batch; the record mode still
+ * uses the host call prk_advance_edge_records there, since DrawModel* must
+ * leave its list in the caller's memory at its return, with real addresses. */
 int prk_edge_records(prk_context *ctx, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
                      uint32_t tris_per_object, const float P[3], int32_t setup,
                      prk_edge *records, uint64_t capacity, uint32_t *counts, uint64_t *total_out);
+
+/* What DrawModel* leaves in the lists of a batch (projekt.cpp:3654-3869),
+ * walked on the GPU: records / counts in the packed layout of
+ * prk_edge_records and prk_draw_edge_lists, all pointers host memory.  List
+ * o's part of records_out (the same layout; may be `records` itself: in
+ * place) and of next_out (one word per record, or NULL) is what
+ * prk_advance_edge_records(mem, counts[o], 120, 112, height) leaves in an
+ * edge_info array `mem` made of list o with every Next NULL (what
+ * FillEdgeTable leaves, 4094): the 27 fields word for word, and next_out[i]
+ * = the Next of record i as an index within its own list, -1 for NULL.  One
+ * allowance: where the host's word is a NaN the word here is a NaN too, of
+ * any sign and payload (Normalize of a zero normal is inf * 0: x86's default
+ * NaN has the sign bit set, gfx950's has not).  Such NaNs sit in normals and
+ * colours only, never in what orders the list; every word that is not a NaN
+ * on the host is equal.
+ *
+ * Only lists inside prk_draw_edge_lists' sorted rule are taken (YMin
+ * non-decreasing, 0 <= YMin <= YMax, Left 0 or 1: what FillEdgeTable's
+ * MergeSort and prk_edge_records leave): there the sorted insertion cursor
+ * inserts what the reference's whole-list scan inserts, in its order.  Any
+ * other list goes to prk_advance_edge_records.  One GPU thread walks a list,
+ * over at most `height` rows.
+ *
+ * Synchronous; needs no render target, records no draw, touches no recorded
+ * draw and no prk_stats; frames in flight finish first.  PRK_ERR_ARG: a NULL
+ * context, NULL counts with list_count > 0, NULL records or records_out with
+ * a non-zero total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside the
+ * sorted rule.  PRK_ERR_LIMIT: the total passes 31 bits, height > 65536, or
+ * a list's walk is too long for one thread: its edge-rows, the sum over its
+ * edges of max(0, min(YMax, height) - YMin), plus its insertion scans, for
+ * every edge the edges still linked when it is inserted (the earlier ones
+ * whose YMax is not below its YMin), pass 2^21 steps.  The cap keeps a call
+ * from holding the GPU for seconds (a thread walks 1.6 M edge-rows a second);
+ * it is no tuned number.  list_count == 0 or a zero total: PRK_OK.  On any
+ * error nothing is written to records_out or next_out. */
+int prk_advance_edge_lists(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
+                           uint32_t list_count, int32_t height, prk_edge *records_out, int32_t *next_out);
 
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
