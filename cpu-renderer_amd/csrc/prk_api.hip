@@ -76,6 +76,10 @@ hipError_t prk_rec_counts(const void *, const uint32_t *, uint32_t, const uint32
 hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipStream_t);
 hipError_t prk_adv_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, hipStream_t);
 hipError_t prk_adv_next(const void *, uint32_t, int32_t *, hipStream_t);
+hipError_t prk_span_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, const uint32_t *, void *,
+                         int32_t *, uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_span_pack(const void *, const int32_t *, const uint32_t *, const uint32_t *, uint32_t, uint32_t, void *,
+                         hipStream_t);
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
@@ -340,7 +344,8 @@ struct prk_context {
             d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
             d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
-            d_rectab, d_reccnt, d_recout;  // prk_edge_records: its tables, counts and packed records
+            d_rectab, d_reccnt, d_recout,  // prk_edge_records: its tables, counts and packed records
+            d_spanout;                     // prk_span_records: its packed spans
         // the pass's host tables, packed into pinned memory for one upload
         // (stage_ev: that upload, before the staging is rewritten)
         char *h_stage = nullptr;
@@ -549,7 +554,7 @@ int prk_destroy(prk_context *c) {
                         &S.d_prccur, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend, &S.d_preendm,
                         &S.d_prmatch, &S.d_prsidx, &S.d_prsm, &S.d_prstat, &S.d_segcnt, &S.d_segoff,
                         &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_rectab, &S.d_reccnt,
-                        &S.d_recout};
+                        &S.d_recout, &S.d_spanout};
         for (DevBuf *b : sb) b->release();
         if (S.h_rb) (void)hipHostFree(S.h_rb);
         if (S.stage_ev) {
@@ -2731,10 +2736,13 @@ constexpr uint64_t kAdvMaxSteps = 1ull << 21;
 // list on row YMax, after that row's insertions).  The count of all earlier
 // edges bounds that for short lists; a list that bound would refuse is swept
 // with a heap of the linked edges' YMax.  Returns at once past `cap`.
+// (edge_rows: the first term alone, which bounds the list's pairs --
+// prk_span_records' slots -- at half of it.)
 static uint64_t list_walk_steps(const prk_edge *e, uint32_t n, int32_t height, uint64_t cap,
-                                std::vector<int32_t> &heap) {
+                                std::vector<int32_t> &heap, uint64_t *edge_rows = nullptr) {
     uint64_t steps = 0;
     for (uint32_t i = 0; i < n; ++i) steps += (uint64_t)std::max(0, std::min(e[i].YMax, height) - e[i].YMin);
+    if (edge_rows) *edge_rows = steps;
     const uint64_t all = (uint64_t)n * (n ? n - 1 : 0) / 2;
     if (steps > cap || steps + all <= cap) return steps + all;
     heap.clear();
@@ -2791,6 +2799,101 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernels ran
     PRK_TRY(hipMemcpyAsync(records_out, S.d_recout.p, rec_bytes, hipMemcpyDeviceToHost, s));
     if (next_out) PRK_TRY(hipMemcpyAsync(next_out, S.d_evals.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    return PRK_OK;
+}
+
+// The work records DrawModelOptimized(RenderQueue) queues for every list of
+// such a batch (3756-3809: both edges of every pair as they stand on the row,
+// and the row), from prk_advance_edge_lists' walk with the emission hook:
+// k_adv_import -> k_span_walk (one thread per list: pairs into the list's
+// slots, its count) -> scan of the counts -> k_span_pack (prk_spans.hip).
+// The refusals and the one host pass are prk_advance_edge_lists'; the pass
+// also sizes each list's slots, floor(edge-rows / 2): a pair uses up one row
+// of each of two listed edges (each listed on rows [YMin, min(YMax, height))
+// at most, and in one pair a row), so no walk passes that.  spans == NULL:
+// the counting walk, no slots.
+int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                     int32_t height, prk_span *spans, uint64_t capacity, uint32_t *span_counts,
+                     uint64_t *total_out) {
+    if (!c || !total_out) return PRK_ERR_ARG;
+    *total_out = 0;
+    if ((!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) {
+        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    // lscan, then sbase: each list's first edge and first slot
+    const size_t nl1 = (size_t)list_count + 1;
+    std::vector<uint32_t> tab(2 * nl1);
+    uint32_t *lscan = tab.data(), *sbase = tab.data() + nl1;
+    std::vector<int32_t> heap;
+    bool too_long = false;
+    uint64_t nslot = 0;
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            lscan[o] = at;
+            sbase[o] = (uint32_t)nslot;
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            uint64_t edge_rows = 0;
+            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap, &edge_rows) > kAdvMaxSteps;
+            nslot += edge_rows / 2;
+            too_long = too_long || nslot >= 0x7FFFFFFFull;
+        }
+        lscan[list_count] = at;
+        sbase[list_count] = (uint32_t)nslot;
+    }
+    if (too_long) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const uint32_t n = (uint32_t)total;
+    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
+    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
+    PRK_TRY(S.d_escan.ensure(tab.size() * 4));
+    PRK_TRY(S.d_scnt.ensure(nl1 * 4));
+    PRK_TRY(S.d_soff.ensure(nl1 * 4));
+    PRK_TRY(S.d_err.ensure(16));
+    if (spans) {
+        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));  // prk_spans.hip PairRaw
+        PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)nslot * 4, 16)));    // the slots' rows
+    }
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1;
+    uint32_t *d_cnt = (uint32_t *)S.d_scnt.p, *d_cscan = (uint32_t *)S.d_soff.p;
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scan reads list_count + 1 counts)
+    PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
+    PRK_TRY(prk_span_walk(S.d_recout.p, n, d_lscan, list_count, height, S.d_work.p, d_sbase,
+                          spans ? S.d_raw.p : nullptr, spans ? (int32_t *)S.d_pos.p : nullptr, d_cnt,
+                          (uint32_t *)S.d_err.p, s));
+    size_t tb = 0;
+    PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, nullptr, &tb, s));
+    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
+    PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, S.d_temp.p, &tb, s));
+    uint32_t nspan = 0, err = 0;
+    PRK_TRY(hipMemcpyAsync(&nspan, d_cscan + list_count, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    if (err) return PRK_ERR_DEVICE;  // a walk passed its slot bound
+    *total_out = nspan;
+    if (span_counts) PRK_TRY(hipMemcpy(span_counts, d_cnt, (size_t)list_count * 4, hipMemcpyDeviceToHost));
+    if (!spans) return PRK_OK;
+    if (capacity < nspan) return PRK_ERR_ARG;
+    if (nspan == 0) return PRK_OK;
+    PRK_TRY(S.d_spanout.ensure((((size_t)nspan * 25 + 3) / 4) * 16));
+    PRK_TRY(prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, S.d_spanout.p, s));
+    PRK_TRY(hipStreamSynchronize(s));  // nothing is written to `spans` unless the kernel ran
+    PRK_TRY(hipMemcpyAsync(spans, S.d_spanout.p, (size_t)nspan * sizeof(prk_span), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     return PRK_OK;
 }

@@ -74,7 +74,9 @@
 // of this file; k_list_prep, k_rec_export's reverse for prk_draw_edge_lists,
 // follows them, and then prk_advance_edge_lists' kernels (the list DrawModel*
 // leaves, no frame): k_adv_import (k_list_prep's import), k_adv_walk (a
-// thread per list, every field stepped), k_adv_next (the links).
+// thread per list, every field stepped), k_adv_next (the links); last,
+// prk_span_records' (the spans that walk queues): k_span_walk (the same walk
+// with the emission hook) and k_span_pack (packed prk_span).
 #include <atomic>
 
 #include "prk_device.h"
@@ -4290,10 +4292,21 @@ __global__ void __launch_bounds__(kPrepEdges) k_adv_import(const uint4 *__restri
 // reads (obj_step<M> steps only those) -- here the stepped record is the
 // result.  The record's quads that hold no stepped field (row range, Left and
 // link; the colour gradient) are not written back.
-__device__ __forceinline__ void adv_step(ObjEdge *p) {
+//
+// EM is the walk's emission hook: em.half(right, E) sees the record as it
+// stands on the row, before the step -- one end of the line_render_work
+// DrawModelOptimized(RenderQueue) queues for the pair (3756-3809).  AdvNoEmit
+// (prk_advance_edge_lists) compiles to nothing.
+struct AdvNoEmit {
+    __device__ __forceinline__ void half(bool, const ObjEdge &) const {}
+    __device__ __forceinline__ void pair(int32_t) {}
+};
+template <class EM>
+__device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
     PRK_ER(w);
     PRK_ER_LOAD(w, p);
     ObjEdge E = PRK_ER_EDGE(w);
+    em.half(right, E);
     E.X += E.G;
     E.Z += E.ZG;
     E.C0 += E.CG0; E.C1 += E.CG1; E.C2 += E.CG2; E.C3 += E.CG3;
@@ -4317,9 +4330,11 @@ __device__ __forceinline__ void adv_step(ObjEdge *p) {
 // The list is walked whole: an edge that expires on the row later edges are
 // inserted on is still linked when they are, and its final Next depends on
 // them (k_obj_seg's split would lose that word).  The records are stepped in
-// place; the links are LK's (GLinks: the records' own Next).
-template <class LK>
-__device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK lk) {
+// place; the links are LK's (GLinks: the records' own Next).  Every pair goes
+// to the emission hook before it is stepped: its two ends (adv_step), then
+// em.pair(Row).
+template <class LK, class EM>
+__device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK lk, EM &em) {
     const int32_t FirstRow = lk.ymin(0);
     int32_t MaxRow = lk.ymax(0);
     for (uint32_t i = 1; i < n; ++i) MaxRow = max(MaxRow, lk.ymax((int)i));
@@ -4391,8 +4406,9 @@ __device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK l
         int32_t PrevCur = -1, PrevNext = -1;  // pairing 3751-3869
         int32_t Cur = Head, Next = lk.next(Cur);
         while (Next >= 0) {
-            adv_step(&E[Cur]);  // 3811-3829
-            adv_step(&E[Next]);
+            adv_step(&E[Cur], em, false);  // 3811-3829
+            adv_step(&E[Next], em, true);
+            em.pair(Row);
             lk.stepped(Cur);
             lk.stepped(Next);
             if (lk.x(Cur) > lk.x(Next)) {  // 3831-3841
@@ -4437,7 +4453,8 @@ __global__ void __launch_bounds__(kLinkThreads) k_adv_walk(ObjEdge *__restrict__
     if (o >= nlist) return;
     const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
     if (n < 2) return;
-    adv_walk_list(work + e0, n, height, GLinks{work + e0});
+    AdvNoEmit em;
+    adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
 }
 
 // Each edge's Next, an index within its own list or -1, as one flat array.
@@ -4445,6 +4462,121 @@ __global__ void __launch_bounds__(256) k_adv_next(const ObjEdge *__restrict__ wo
                                                   int32_t *__restrict__ next_out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < total) next_out[i] = work[i].Next;
+}
+
+// ---------------------------------------------------------------------------
+// prk_span_records: the line_render_work records DrawModelOptimized
+// (RenderQueue) queues for a list (3756-3809), for the same batches and by
+// the same walk: k_adv_import -> k_span_walk (k_adv_walk with the emission
+// hook: a thread per list, each pair's PairRaw and row into the list's slot
+// range, the list's count) -> prk_scan_u32 of the counts -> k_span_pack (the
+// used slots as packed prk_span).
+// ---------------------------------------------------------------------------
+// The hook: pair k of the list at slot at0 + k, both edges as they stand on
+// the row (six dwordx4 stores) and the row.  STORE = false counts only: no
+// slots, the emission compiled out.  A pair past the list's range is counted
+// and not stored (the host's bound rules it out; k_span_walk reports it).
+template <bool STORE>
+struct AdvSpanEmit {
+    PairRaw *raw;
+    int32_t *row;
+    uint32_t at, end;
+    __device__ __forceinline__ void half(bool right, const ObjEdge &E) const {
+        if constexpr (STORE) {
+            if (at < end) {
+                float4 *q = reinterpret_cast<float4 *>(raw + at) + (right ? 3 : 0);
+                pair_raw_half(E, q[0], q[1], q[2]);
+            }
+        }
+    }
+    __device__ __forceinline__ void pair(int32_t Row) {
+        if constexpr (STORE) {
+            if (at < end) row[at] = Row;
+        }
+        ++at;
+    }
+};
+
+// sbase: nlist + 1 values, list o's slots [sbase[o], sbase[o + 1]) --
+// floor(edge-rows / 2) of them: a pair uses up one row of each of two listed
+// edges.  cnt[o]: the list's pairs.  err: set when a list passed its range.
+template <bool STORE>
+__global__ void __launch_bounds__(kLinkThreads) k_span_walk(ObjEdge *__restrict__ work,
+                                                            const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                            int32_t height, const uint32_t *__restrict__ sbase,
+                                                            PairRaw *__restrict__ raw, int32_t *__restrict__ row,
+                                                            uint32_t *__restrict__ cnt, uint32_t *__restrict__ err) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= nlist) return;
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    uint32_t pairs = 0;
+    if (n >= 2) {
+        const uint32_t s0 = STORE ? sbase[o] : 0u, s1 = STORE ? sbase[o + 1] : 0xFFFFFFFFu;
+        AdvSpanEmit<STORE> em{raw, row, s0, s1};
+        adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
+        pairs = em.at - s0;
+        if (STORE && em.at > s1) {
+            pairs = s1 - s0;
+            atomicOr(err, 1u);
+        }
+    }
+    cnt[o] = pairs;
+}
+
+// The used slots as packed prk_span records (25 dwords: Left, Right, Row;
+// an end is XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3], prk.h).
+// A workgroup takes kPackSpans consecutive packed spans; their 25 * kPackSpans
+// dwords are a 16-byte-aligned stretch of the flat output.  Lane t finds span
+// k's list by a binary search of the scanned counts (cscan: nlist + 1 values,
+// the last = total; the list is the last o with cscan[o] <= k, never an empty
+// one), reads its slot sbase[o] + k - cscan[o] (six dwordx4 and the row) and
+// puts the 25 dwords in prk_span's order into LDS at dword 25 t: the stride is
+// odd, so the 32 lanes of a ds_write_b32 group fall on 32 different banks.
+// Then lane t of pass j stores dwordx4 t + 256 j of the stretch from LDS
+// (ds_read_b128 of consecutive 16-byte slots, 1 KiB contiguous a wave
+// instruction).  `out` holds 25 * total dwords rounded up to four; the last
+// piece's spare dwords are zero.
+constexpr int kPackSpans = 256;
+constexpr uint32_t kPackPieces = 25u * kPackSpans / 4u;
+static_assert(25 * kPackSpans % 4 == 0, "a workgroup's spans start on a 16-byte boundary");
+__global__ void __launch_bounds__(kPackSpans) k_span_pack(const PairRaw *__restrict__ raw,
+                                                          const int32_t *__restrict__ row,
+                                                          const uint32_t *__restrict__ sbase,
+                                                          const uint32_t *__restrict__ cscan, uint32_t nlist,
+                                                          uint32_t total, uint4 *__restrict__ out) {
+    __shared__ uint4 st4[kPackPieces];
+    float *st = reinterpret_cast<float *>(st4);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< total: the grid)
+    const uint32_t ns = min((uint32_t)kPackSpans, total - k0);
+    const uint32_t k = k0 + tid;
+    if (tid < ns) {
+        uint32_t lo = 0, hi = nlist;  // cscan[lo] <= k < cscan[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (cscan[mid] <= k) lo = mid;
+            else hi = mid;
+        }
+        const size_t slot = (size_t)sbase[lo] + (k - cscan[lo]);
+        const PairRaw r = raw[slot];
+        float *d = st + 25u * tid;
+        const float4 q[6] = {r.l0, r.l1, r.l2, r.r0, r.r1, r.r2};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float4 a = q[3 * h], b = q[3 * h + 1], c = q[3 * h + 2];
+            float *e = d + 12 * h;
+            e[0] = a.x; e[1] = a.y; e[2] = a.z; e[3] = a.w; e[4] = b.x;  // X Z W U V
+            e[5] = c.x; e[6] = c.y; e[7] = c.z; e[8] = c.w;              // MinColor
+            e[9] = b.y; e[10] = b.z; e[11] = b.w;                        // MinNormal
+        }
+        d[24] = __int_as_float(row[slot]);
+    } else if (tid < ns + 1u) {
+        st[25u * ns] = st[25u * ns + 1u] = st[25u * ns + 2u] = 0.0f;  // (the last piece's spare dwords; < 25 * 256)
+    }
+    __syncthreads();
+    const uint32_t np = (25u * ns + 3u) / 4u;
+    uint4 *dst = out + (size_t)blockIdx.x * kPackPieces;
+    for (uint32_t p = tid; p < np; p += (uint32_t)kPackSpans) dst[p] = st4[p];
 }
 
 }  // namespace prk
@@ -4496,6 +4628,38 @@ hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lsc
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prk::k_adv_walk, dim3((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads),
                        dim3(prk::kLinkThreads), 0, s, w, lscan, nlist, height);
+    return hipGetLastError();
+}
+// prk_span_records: prk_adv_walk's import, then the walk with the emission:
+// list o's pairs into PairRaw slots [sbase[o], sbase[o + 1]) and their rows,
+// its count into cnt[o]; err |= 1 should a list pass its slots.  raw ==
+// nullptr: the counts alone (no slots are read or written).
+hipError_t prk_span_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
+                         void *work, const uint32_t *sbase, void *raw, int32_t *row, uint32_t *cnt, uint32_t *err,
+                         hipStream_t s) {
+    if (total == 0 || nlist == 0) return hipSuccess;
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
+                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
+    if (raw)
+        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, lscan, nlist, height, sbase,
+                           reinterpret_cast<prk::PairRaw *>(raw), row, cnt, err);
+    else
+        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, lscan, nlist, height, sbase,
+                           (prk::PairRaw *)nullptr, (int32_t *)nullptr, cnt, err);
+    return hipGetLastError();
+}
+// The `total` spans the walk left (cscan: the scanned counts, nlist + 1) as
+// packed prk_span; `out` holds 25 * total dwords rounded up to four.
+hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sbase, const uint32_t *cscan,
+                         uint32_t nlist, uint32_t total, void *out, hipStream_t s) {
+    if (total == 0 || nlist == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_span_pack, dim3((total + prk::kPackSpans - 1) / prk::kPackSpans),
+                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const prk::PairRaw *>(raw), row, sbase, cscan,
+                       nlist, total, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }
 hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {

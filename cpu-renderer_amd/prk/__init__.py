@@ -107,6 +107,8 @@ _SIGS = {
                                    C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "prk_advance_edge_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p,
                                          C.c_void_p]),
+    "prk_span_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.POINTER(C.c_uint64)]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -607,6 +609,26 @@ class Renderer:
         _check("prk_advance_edge_lists", self._L.prk_advance_edge_lists(self._h, _ptr(w), _ptr(n), n.shape[0],
                                                                         int(height), _ptr(out), _ptr(nxt)))
         return out, nxt
+
+    def span_records(self, words, counts, height):
+        """prk_span_records: the spans DrawModelOptimized(RenderQueue) queues
+        for every list of a batch over a frame of `height` rows, walked on
+        the GPU (two calls: size, then fill) -- (span_words uint32
+        [total, 25] in prk_span layout, list o's at sum(span_counts[:o]),
+        span_counts uint32 [nlist]).  Lists sorted by YMin only (prk.h)."""
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1, 27)
+        n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if int(n.sum(dtype=np.uint64)) != w.shape[0]:
+            raise ValueError("span_records: counts sum to %d, %d records given" % (int(n.sum(dtype=np.uint64)),
+                                                                                w.shape[0]))
+        sc = np.zeros(n.shape[0], np.uint32)
+        total = C.c_uint64(0)
+        _check("prk_span_records", self._L.prk_span_records(self._h, _ptr(w), _ptr(n), n.shape[0], int(height), None,
+                                                            0, _ptr(sc), C.byref(total)))
+        spans = np.empty((total.value, 25), np.uint32)
+        _check("prk_span_records", self._L.prk_span_records(self._h, _ptr(w), _ptr(n), n.shape[0], int(height),
+                                                            _ptr(spans), total.value, _ptr(sc), C.byref(total)))
+        return spans, sc
 
     def draw_spans(self, span_words, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
         """Caller spans (the work records of DoLineRenderWork): uint32 [n, 25]

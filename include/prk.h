@@ -404,7 +404,8 @@ typedef struct prk_span {
 } prk_span;
 /* Draw caller-built spans (the work records DoLineRenderWork /
  * DoBufferLineRenderWork run, 2336-2348), in order, each with
- * FillLineOptimized's span body.  Each span counts as one triangle id. */
+ * FillLineOptimized's span body.  Each span counts as one triangle id.
+ * prk_span_records (below) returns the spans of batches of edge lists. */
 int prk_draw_spans(prk_context *ctx, const prk_span *spans, uint32_t count, int32_t semantics, int32_t phong,
                    int32_t texture);
 
@@ -618,9 +619,55 @@ int prk_edge_records(prk_context *ctx, int32_t geometry, uint32_t first_tri, uin
  * whose YMax is not below its YMin), pass 2^21 steps.  The cap keeps a call
  * from holding the GPU for seconds (a thread walks 1.6 M edge-rows a second);
  * it is no tuned number.  list_count == 0 or a zero total: PRK_OK.  On any
- * error nothing is written to records_out or next_out. */
+ * error nothing is written to records_out or next_out.  The spans the same
+ * walk queues on its way: prk_span_records (below). */
 int prk_advance_edge_lists(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
                            uint32_t list_count, int32_t height, prk_edge *records_out, int32_t *next_out);
+
+/* The work records DrawModelOptimized(RenderQueue, ...) queues for the lists
+ * of a batch (projekt.cpp:3756-3809), from the same walk on the GPU: records
+ * / counts as for prk_advance_edge_lists, all pointers host memory.  For
+ * every pair the walk meets on every row it emits one prk_span before it
+ * steps the pair (3811-3829): Left is CurrentEdgeInList, Right is
+ * NextEdgeInList as they stand on that row (XMin, ZMin, OneOverZMin, UMin,
+ * VMin, MinColor, MinNormal), Row is RowIndex -- what prk_draw_spans and the
+ * drop-in's DoLineRenderWork take.  List o's spans are packed at
+ * spans[span_counts[0] + ... + span_counts[o - 1]] in queue order: rows
+ * ascending, the pairs of a row in list order; a row with one listed edge
+ * emits nothing, an odd list leaves its last edge unpaired.  span_counts
+ * (list_count words, or NULL) gets every list's number of spans, *total_out
+ * their sum.  Span k of list o is, word for word, the k-th work record a
+ * walk of 3654-3869 over list o with every Next NULL queues; the walk's rows
+ * and rules are prk_advance_edge_lists' ([YMin[0], min(max YMax, height)), no
+ * band or target clip), and so is the one allowance: where the expected
+ * MinColor or MinNormal word is a NaN the word here is a NaN of any sign and
+ * payload.  Every other word, Row included, is equal.
+ *
+ * Calling pattern, as prk_edge_records: spans == NULL sizes -- span_counts
+ * and *total_out are written by a counting walk that takes no span memory;
+ * with spans and a `capacity` (in spans) below the total the call returns
+ * PRK_ERR_ARG with span_counts and *total_out written and `spans` untouched.
+ *
+ * Only lists inside the sorted rule are taken, and one GPU thread walks a
+ * list: ConstructSphere as one list is slower here than a host walk would
+ * be, as it is for prk_advance_edge_lists (serving long lists from the
+ * parallel slot walks needs those walks to step every field).
+ *
+ * Synchronous; needs no render target, records no draw, touches no recorded
+ * draw and no prk_stats; frames in flight finish first.  PRK_ERR_ARG: a NULL
+ * context or total_out, NULL counts with list_count > 0, NULL records with a
+ * non-zero record total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside
+ * the sorted rule.  PRK_ERR_LIMIT: the record total or list_count passes 31
+ * bits, height > 65536, a list's walk passes prk_advance_edge_lists' 2^21
+ * steps, or the batch's span slots pass 31 bits (a list gets half its
+ * edge-rows, the sum over its edges of max(0, min(YMax, height) - YMin): a
+ * span uses up one row of each of two edges).  list_count == 0 or no
+ * records: PRK_OK, *total_out = 0, span_counts zero.  On any error but the
+ * short capacity nothing is written to spans or span_counts. */
+int prk_span_records(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
+                     uint32_t list_count, int32_t height,
+                     prk_span *spans, uint64_t capacity,
+                     uint32_t *span_counts, uint64_t *total_out);
 
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
