@@ -492,3 +492,71 @@ def with_ties(scene, frac=0.5, seed=0):
     return Scene(scene.width, scene.height, Vd[o].reshape(-1, 3).copy(), C[o].reshape(-1, 4).copy(),
                  N[o].reshape(-1, 3).astype(np.float32).copy(), UV[o].reshape(-1, 2).copy(), scene.transform,
                  scene.lights, scene.ambient, scene.texture, scene.P, scene.name + "+ties", dict(scene.meta))
+
+
+# ---- texture addressing (tests/texcases.py names the cases; tools/make_ref_golden.py draws some) ----
+PAD_FILL = 0xFF00FF00  # what the pad columns of a padded texture hold: one colour, not random data
+# the first row of a 33000-row texture whose 16-bit low half is negative, as a v
+TALL_V = 0.9931
+
+
+def padded_texture(w, h, pitch_texels, seed, pad_fill=PAD_FILL, filt=abi.PRK_FILTER_NEAREST):
+    """Texture of shape (h + 1, pitch_texels): random body, pad columns
+    of the body rows = pad_fill, guard row zero."""
+    assert pitch_texels >= w
+    rng = np.random.default_rng(seed)
+    t = np.zeros((h + 1, pitch_texels), np.uint32)
+    t[:h, :w] = rng.integers(0, 2**32, size=(h, w), dtype=np.uint64).astype(np.uint32)
+    t[:h, w:] = np.uint32(pad_fill)
+    return Texture(t, w, h, filt)
+
+
+def addressing_uvs(n_tris, recipe, seed):
+    """float32 [3 * n_tris, 2] by a recipe: ("uniform", lo, hi), ("edges01",), ("far",) or
+    ("tall",) (the cases of tests/texcases.py)."""
+    rng = np.random.default_rng(seed)
+    kind = recipe[0]
+    if kind == "uniform":
+        return rng.uniform(recipe[1], recipe[2], (3 * n_tris, 2)).astype(np.float32)
+    uv = rng.uniform(0.0, 1.0, (n_tris, 3, 2))
+    if kind == "edges01":
+        # a third of the vertices get an exact 0.0 or 1.0 in u, in v or in both ...
+        pick = rng.random((n_tris, 3, 2)) < 1.0 / 3.0
+        uv[pick] = rng.integers(0, 2, int(pick.sum())).astype(np.float64)
+        # ... and whole triangles sit on u == 1, v == 1, u == 0, v == 0 and the (1, 1) corner:
+        # their pixels, not only their vertices, fetch from the pad column / the guard row
+        k = np.arange(n_tris)
+        uv[k % 8 == 0, :, 0] = 1.0
+        uv[k % 8 == 1, :, 1] = 1.0
+        uv[k % 8 == 2, :, 0] = 0.0
+        uv[k % 8 == 3, :, 1] = 0.0
+        uv[k % 16 == 4] = 1.0
+    elif kind == "far":
+        # triangles far outside: |uv| of 3e4 (an offset past the texture) and 3e9
+        # (the float -> int32 conversion gives INT32_MIN), constant over the
+        # triangle or changing sign across it; the rest stay in [0, 1)
+        k = np.arange(n_tris)
+        for m, val in ((0, 3e4), (1, -3e4), (2, 3e9), (3, -3e9)):
+            uv[k % 10 == m] = val
+        uv[k % 10 == 4, 0] = -3e4
+        uv[k % 10 == 4, 1:] = 3e4
+        uv[k % 10 == 5, 0] = 3e9
+        uv[k % 10 == 5, 1:] = -3e9
+        uv[k % 10 == 6, :, 0] = 3e9   # u far outside, v inside
+        uv[k % 10 == 7, :, 1] = -3e4  # v far outside, u inside
+    elif kind == "tall":
+        # every third triangle lies wholly in the rows from 32768 on
+        k = np.arange(n_tris)
+        top = k % 3 == 0
+        uv[top, :, 1] = rng.uniform(TALL_V, 0.99995, (int(top.sum()), 3))
+    else:
+        raise ValueError(kind)
+    return uv.reshape(-1, 2).astype(np.float32)
+
+
+def retexture(scene, w, h, pitch_texels, recipe, seed, pad_fill=PAD_FILL, filt=abi.PRK_FILTER_NEAREST):
+    """`scene` (a random_soup) with a texture of padded_texture and uvs of
+    addressing_uvs in place of its own."""
+    scene.texture = padded_texture(w, h, pitch_texels, seed + 1, pad_fill, filt)
+    scene.uvs = addressing_uvs(scene.tri_count, recipe, seed + 2)
+    return scene

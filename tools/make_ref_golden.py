@@ -181,6 +181,23 @@ def cases():
     c["queue_no_lights"] = (nolight, QUEUE, True, 1, False)
     c["scalar_no_lights"] = (_untextured(scenes.random_soup(150, 128, 96, radius=14, seed=77, lights=[],
                                                             ambient=scenes.AMBIENT_TWO)), SCALAR, False, 1, False)
+    # texture shapes (every texture above is square): Width != Height, 24 x 40, through each entry point, and
+    # for the queue path uv of exactly 0 and 1 over whole triangles (its mask keeps u == 1 and v == 1: the next
+    # row's first texel and the guard row).  The scene of tests/texcases.py's case of that name (edges01 there
+    # has pad columns; the driver's Pitch is 4 * Width).  DrawModel masks nothing, so its uvs stay inside the
+    # texture as in scalar_phongtex_soup.
+    def tex(recipe, seed):
+        s = scenes.random_soup(200, 128, 96, radius=12.0, seed=seed, tex_size=8, lights=scenes.LIGHTS_TWO,
+                               ambient=scenes.AMBIENT_TWO)
+        return scenes.retexture(s, 24, 40, 24, recipe, seed)
+    for tag, entry in (("queue", QUEUE), ("single", SINGLE)):
+        c["%s_nonsquare" % tag] = (tex(("uniform", 0.0, 1.0), 81), entry, True, 1, False)
+    # (of the seeds 82 to 99 with uvs in [0.35, 0.65], 93 is the one with no pixel read outside the texture)
+    c["scalar_nonsquare"] = (inner_uvs(tex(("uniform", 0.0, 1.0), 93), 0.35, 0.65), SCALAR, True, 1, False)
+    # (without pad columns the (1, 1) corner lies one texel past the guard row: those vertices go to (1, 0))
+    e01 = tex(("edges01",), 85)
+    e01.uvs[(e01.uvs[:, 0] == 1) & (e01.uvs[:, 1] == 1), 1] = 0
+    c["queue_edges01"] = (e01, QUEUE, True, 1, False)
     return c
 
 
