@@ -80,6 +80,12 @@ hipError_t prk_span_walk(const void *, uint32_t, const uint32_t *, uint32_t, int
                          int32_t *, uint32_t *, uint32_t *, hipStream_t);
 hipError_t prk_span_pack(const void *, const int32_t *, const uint32_t *, const uint32_t *, uint32_t, uint32_t, void *,
                          hipStream_t);
+hipError_t prk_row_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, const uint32_t *,
+                        const uint32_t *, void *, void *, uint32_t *, uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_row_pack(const void *, const void *, const uint32_t *, const uint32_t *, const uint32_t *,
+                        const uint32_t *, uint32_t, uint32_t, uint32_t, void *, void *, hipStream_t);
+hipError_t prk_rows_counts(const void *, uint32_t, uint32_t *, hipStream_t);
+hipError_t prk_rows_unpack(const void *, const uint32_t *, uint32_t, const void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
@@ -345,7 +351,11 @@ struct prk_context {
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
             d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
             d_rectab, d_reccnt, d_recout,  // prk_edge_records: its tables, counts and packed records
-            d_spanout;                     // prk_span_records: its packed spans
+            d_spanout,                     // prk_span_records: its packed spans
+            d_rowslot, d_rowcnt, d_rowscan, d_rowout;  // prk_row_records: its row slots, counts, scan, packed rows
+        // prk_draw_rows' own buffers (frames in flight use the ones above): the
+        // caller's rows and pairs, the EdgeCounts and their scan, the spans
+        DevBuf d_dr_rows, d_dr_pairs, d_dr_cnt, d_dr_scan, d_dr_temp, d_dr_out;
         // the pass's host tables, packed into pinned memory for one upload
         // (stage_ev: that upload, before the staging is rewritten)
         char *h_stage = nullptr;
@@ -554,7 +564,8 @@ int prk_destroy(prk_context *c) {
                         &S.d_prccur, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend, &S.d_preendm,
                         &S.d_prmatch, &S.d_prsidx, &S.d_prsm, &S.d_prstat, &S.d_segcnt, &S.d_segoff,
                         &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_rectab, &S.d_reccnt,
-                        &S.d_recout, &S.d_spanout};
+                        &S.d_recout, &S.d_spanout, &S.d_rowslot, &S.d_rowcnt, &S.d_rowscan, &S.d_rowout,
+                        &S.d_dr_rows, &S.d_dr_pairs, &S.d_dr_cnt, &S.d_dr_scan, &S.d_dr_temp, &S.d_dr_out};
         for (DevBuf *b : sb) b->release();
         if (S.h_rb) (void)hipHostFree(S.h_rb);
         if (S.stage_ev) {
@@ -1242,6 +1253,63 @@ int prk_draw_spans(prk_context *c, const prk_span *spans, uint32_t count, int32_
     const uint32_t off = (uint32_t)c->pend_spans.size();
     const int rc = draw_src(c, 2, off, count, count, semantics, phong, texture);
     if (rc == PRK_OK) c->pend_spans.insert(c->pend_spans.end(), spans, spans + count);
+    return rc;
+}
+
+// Row work records (prk_row_records' output, or a caller's own) as a draw of
+// their pairs: the rows and pairs go up as they are, k_rows_unpack
+// (prk_spans.hip) turns every pair into the prk_span of its row on the device
+// -- no host loop over the pairs, only the one over the rows that checks the
+// arguments -- and the spans come back into the pending frame's span input,
+// where the draw is prk_draw_spans' from then on.  The buffers are this
+// call's own: frames in flight keep the span scratch.
+static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_row_pair *pairs,
+                         uint32_t npair, prk_span *out) {
+    PRK_TRY(hipSetDevice(c->device));
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const size_t out_bytes = (((size_t)npair * 25 + 3) / 4) * 16;
+    PRK_TRY(S.d_dr_rows.ensure((size_t)nrow * sizeof(prk_row)));
+    PRK_TRY(S.d_dr_pairs.ensure((size_t)npair * sizeof(prk_row_pair)));
+    PRK_TRY(S.d_dr_cnt.ensure(((size_t)nrow + 1) * 4));
+    PRK_TRY(S.d_dr_scan.ensure(((size_t)nrow + 1) * 4));
+    PRK_TRY(S.d_dr_out.ensure(out_bytes));
+    PRK_TRY(hipMemcpyAsync(S.d_dr_rows.p, rows, (size_t)nrow * sizeof(prk_row), hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_dr_pairs.p, pairs, (size_t)npair * sizeof(prk_row_pair), hipMemcpyHostToDevice, s));
+    PRK_TRY(prk_rows_counts(S.d_dr_rows.p, nrow, (uint32_t *)S.d_dr_cnt.p, s));
+    size_t tb = 0;
+    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, nullptr, &tb, s));
+    PRK_TRY(S.d_dr_temp.ensure(std::max<size_t>(tb, 16)));
+    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, S.d_dr_temp.p, &tb, s));
+    PRK_TRY(prk_rows_unpack(S.d_dr_rows.p, (const uint32_t *)S.d_dr_scan.p, nrow, S.d_dr_pairs.p, npair,
+                            S.d_dr_out.p, s));
+    PRK_TRY(hipMemcpyAsync(out, S.d_dr_out.p, (size_t)npair * sizeof(prk_span), hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (the caller's arrays are copied at the call)
+    return PRK_OK;
+}
+
+int prk_draw_rows(prk_context *c, const prk_row *rows, uint64_t row_count, const prk_row_pair *pairs,
+                  uint64_t pair_count, int32_t semantics, int32_t phong, int32_t texture) {
+    if (!c || (!rows && row_count) || (!pairs && pair_count)) return PRK_ERR_ARG;
+    uint64_t sum = 0;
+    for (uint64_t r = 0; r < row_count; ++r) {
+        if (rows[r].RowIndex < 0) return PRK_ERR_ARG;
+        sum += rows[r].EdgeCount;
+    }
+    if (sum != pair_count) return PRK_ERR_ARG;
+    if (row_count == 0 || pair_count == 0) return PRK_OK;
+    // the frame's span input is indexed by 31 bits, as the other caller records
+    if (row_count >= 0x7FFFFFFFull || c->pend_spans.size() + pair_count >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    const uint32_t off = (uint32_t)c->pend_spans.size(), n = (uint32_t)pair_count;
+    int rc = draw_src(c, 2, off, n, n, semantics, phong, texture);
+    if (rc != PRK_OK) return rc;
+    c->pend_spans.resize((size_t)off + n);
+    rc = rows_to_spans(c, rows, (uint32_t)row_count, pairs, n, c->pend_spans.data() + off);
+    if (rc != PRK_OK) {  // nothing is recorded
+        c->pend_spans.resize(off);
+        c->draws.pop_back();
+        c->pending_tris -= n;
+    }
     return rc;
 }
 
@@ -2894,6 +2962,124 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
     PRK_TRY(prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, S.d_spanout.p, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to `spans` unless the kernel ran
     PRK_TRY(hipMemcpyAsync(spans, S.d_spanout.p, (size_t)nspan * sizeof(prk_span), hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    return PRK_OK;
+}
+
+// The row work records DrawModelOptimizedLines queues for every list of such
+// a batch (3509-3609: one buffer_line_render_work a row the walk reaches,
+// RowIndex, EdgeCount and that many thread_edge_info pairs), from the same
+// walk with the row hook: k_adv_import -> k_row_walk (one thread per list:
+// pairs into the list's pair slots, a row record a row into its row slots, its
+// two counts) -> two scans -> k_row_pack (prk_spans.hip).  The refusals and
+// the one host pass are prk_span_records'; the pass also sizes each list's row
+// slots, the rows of its walk.  What the pass cannot know -- a row with more
+// than 1000 pairs, the reference's ThreadEdges[1000] -- the walk flags, and
+// the flag is read before anything is written.  rows == pairs == NULL: the
+// counting walk, no slots.
+int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                    int32_t height, prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs,
+                    uint64_t pair_capacity, uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
+    if (!c || !row_total_out || !pair_total_out) return PRK_ERR_ARG;
+    if ((!counts && list_count) || height < 0 || (rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) {
+        *row_total_out = *pair_total_out = 0;
+        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    // lscan, sbase, rbase: each list's first edge, first pair slot and first row slot
+    const size_t nl1 = (size_t)list_count + 1;
+    std::vector<uint32_t> tab(3 * nl1);
+    uint32_t *lscan = tab.data(), *sbase = lscan + nl1, *rbase = sbase + nl1;
+    std::vector<int32_t> heap;
+    bool too_long = false;
+    uint64_t nslot = 0, nrslot = 0;
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            lscan[o] = at;
+            sbase[o] = (uint32_t)nslot;
+            rbase[o] = (uint32_t)nrslot;
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            uint64_t edge_rows = 0;
+            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap, &edge_rows) > kAdvMaxSteps;
+            nslot += edge_rows / 2;
+            if (counts[o]) {  // the walk's rows: [YMin[0], min(max YMax, height))
+                int32_t ymax = e[0].YMax;
+                for (uint32_t i = 1; i < counts[o]; ++i) ymax = std::max(ymax, e[i].YMax);
+                nrslot += (uint64_t)std::max(0, std::min(ymax, height) - e[0].YMin);
+            }
+            too_long = too_long || nslot >= 0x7FFFFFFFull || nrslot >= 0x7FFFFFFFull;
+        }
+        lscan[list_count] = at;
+        sbase[list_count] = (uint32_t)nslot;
+        rbase[list_count] = (uint32_t)nrslot;
+    }
+    if (too_long) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const uint32_t n = (uint32_t)total;
+    const bool fill = rows != nullptr;
+    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
+    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
+    PRK_TRY(S.d_escan.ensure(tab.size() * 4));
+    PRK_TRY(S.d_scnt.ensure(nl1 * 4));
+    PRK_TRY(S.d_soff.ensure(nl1 * 4));
+    PRK_TRY(S.d_rowcnt.ensure(nl1 * 4));
+    PRK_TRY(S.d_rowscan.ensure(nl1 * 4));
+    PRK_TRY(S.d_err.ensure(16));
+    if (fill) {
+        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));     // prk_spans.hip PairRaw
+        PRK_TRY(S.d_rowslot.ensure(std::max<size_t>((size_t)nrslot * 8, 16)));  // {row, pairs}
+    }
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1, *d_rbase = d_sbase + nl1;
+    uint32_t *d_pcnt = (uint32_t *)S.d_scnt.p, *d_pscan = (uint32_t *)S.d_soff.p;
+    uint32_t *d_rcnt = (uint32_t *)S.d_rowcnt.p, *d_rscan = (uint32_t *)S.d_rowscan.p;
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scans read list_count + 1 counts)
+    PRK_TRY(hipMemsetAsync(S.d_rowcnt.p, 0, nl1 * 4, s));
+    PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
+    PRK_TRY(prk_row_walk(S.d_recout.p, n, d_lscan, list_count, height, S.d_work.p, d_sbase, d_rbase,
+                         fill ? S.d_raw.p : nullptr, fill ? S.d_rowslot.p : nullptr, d_pcnt, d_rcnt,
+                         (uint32_t *)S.d_err.p, s));
+    size_t tb = 0;
+    PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, nullptr, &tb, s));
+    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
+    PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(prk_scan_u32(d_rcnt, d_rscan, list_count + 1, S.d_temp.p, &tb, s));
+    uint32_t npair = 0, nrow = 0, err = 0;
+    PRK_TRY(hipMemcpyAsync(&npair, d_pscan + list_count, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipMemcpyAsync(&nrow, d_rscan + list_count, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    if (err & 1u) return PRK_ERR_DEVICE;       // a walk passed a slot bound
+    if (err & 2u) return PRK_ERR_UNSUPPORTED;  // a row of more than 1000 pairs
+    const bool is_short = fill && (row_capacity < nrow || pair_capacity < npair);
+    if (fill && !is_short && (npair || nrow)) {
+        PRK_TRY(S.d_spanout.ensure(std::max<size_t>((size_t)npair * sizeof(prk_row_pair), 16)));
+        PRK_TRY(S.d_rowout.ensure(std::max<size_t>((size_t)nrow * sizeof(prk_row), 16)));
+        PRK_TRY(prk_row_pack(S.d_raw.p, S.d_rowslot.p, d_sbase, d_rbase, d_pscan, d_rscan, list_count, npair, nrow,
+                             S.d_spanout.p, S.d_rowout.p, s));
+        PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernel ran
+    }
+    *row_total_out = nrow;
+    *pair_total_out = npair;
+    if (row_counts) PRK_TRY(hipMemcpy(row_counts, d_rcnt, (size_t)list_count * 4, hipMemcpyDeviceToHost));
+    if (!fill) return PRK_OK;
+    if (is_short) return PRK_ERR_ARG;
+    if (nrow) PRK_TRY(hipMemcpyAsync(rows, S.d_rowout.p, (size_t)nrow * sizeof(prk_row), hipMemcpyDeviceToHost, s));
+    if (npair)
+        PRK_TRY(hipMemcpyAsync(pairs, S.d_spanout.p, (size_t)npair * sizeof(prk_row_pair), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     return PRK_OK;
 }

@@ -74,9 +74,12 @@
 // of this file; k_list_prep, k_rec_export's reverse for prk_draw_edge_lists,
 // follows them, and then prk_advance_edge_lists' kernels (the list DrawModel*
 // leaves, no frame): k_adv_import (k_list_prep's import), k_adv_walk (a
-// thread per list, every field stepped), k_adv_next (the links); last,
+// thread per list, every field stepped), k_adv_next (the links); then
 // prk_span_records' (the spans that walk queues): k_span_walk (the same walk
-// with the emission hook) and k_span_pack (packed prk_span).
+// with the emission hook) and k_span_pack (packed prk_span); last,
+// prk_row_records' (DrawModelOptimizedLines' row work): k_row_walk (the walk
+// with the row hook too), k_row_pack (packed prk_row / prk_row_pair), and
+// prk_draw_rows' k_rows_unpack (such records back into packed prk_span).
 #include <atomic>
 
 #include "prk_device.h"
@@ -4296,10 +4299,13 @@ __global__ void __launch_bounds__(kPrepEdges) k_adv_import(const uint4 *__restri
 // EM is the walk's emission hook: em.half(right, E) sees the record as it
 // stands on the row, before the step -- one end of the line_render_work
 // DrawModelOptimized(RenderQueue) queues for the pair (3756-3809).  AdvNoEmit
-// (prk_advance_edge_lists) compiles to nothing.
+// (prk_advance_edge_lists) compiles to nothing.  em.row(Row) ends every row
+// the walk does not skip, paired or not: DrawModelOptimizedLines queues one
+// buffer_line_render_work there (3604-3609); only AdvRowEmit listens.
 struct AdvNoEmit {
     __device__ __forceinline__ void half(bool, const ObjEdge &) const {}
     __device__ __forceinline__ void pair(int32_t) {}
+    __device__ __forceinline__ void row(int32_t) {}
 };
 template <class EM>
 __device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
@@ -4332,7 +4338,7 @@ __device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
 // them (k_obj_seg's split would lose that word).  The records are stepped in
 // place; the links are LK's (GLinks: the records' own Next).  Every pair goes
 // to the emission hook before it is stepped: its two ends (adv_step), then
-// em.pair(Row).
+// em.pair(Row); em.row(Row) once the row's pairs are through.
 template <class LK, class EM>
 __device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK lk, EM &em) {
     const int32_t FirstRow = lk.ymin(0);
@@ -4438,6 +4444,7 @@ __device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK l
                 Next = -1;
             }
         }
+        em.row(Row);
     }
 }
 
@@ -4479,7 +4486,7 @@ __global__ void __launch_bounds__(256) k_adv_next(const ObjEdge *__restrict__ wo
 template <bool STORE>
 struct AdvSpanEmit {
     PairRaw *raw;
-    int32_t *row;
+    int32_t *prow;  // the pairs' rows
     uint32_t at, end;
     __device__ __forceinline__ void half(bool right, const ObjEdge &E) const {
         if constexpr (STORE) {
@@ -4491,10 +4498,11 @@ struct AdvSpanEmit {
     }
     __device__ __forceinline__ void pair(int32_t Row) {
         if constexpr (STORE) {
-            if (at < end) row[at] = Row;
+            if (at < end) prow[at] = Row;
         }
         ++at;
     }
+    __device__ __forceinline__ void row(int32_t) {}
 };
 
 // sbase: nlist + 1 values, list o's slots [sbase[o], sbase[o + 1]) --
@@ -4579,6 +4587,222 @@ __global__ void __launch_bounds__(kPackSpans) k_span_pack(const PairRaw *__restr
     for (uint32_t p = tid; p < np; p += (uint32_t)kPackSpans) dst[p] = st4[p];
 }
 
+// ---------------------------------------------------------------------------
+// prk_row_records: the buffer_line_render_work records DrawModelOptimizedLines
+// queues for a list (3509-3609: one a row, RowIndex, EdgeCount and EdgeCount
+// thread_edge_info pairs), by the same walk once more: k_adv_import ->
+// k_row_walk (the pairs as k_span_walk leaves them, and a {row, pairs} record
+// at the end of every row the walk does not skip) -> prk_scan_u32 of the row
+// counts and of the pair counts -> k_row_pack (packed prk_row, packed
+// prk_row_pair).  prk_draw_rows' k_rows_unpack turns such records back into
+// prk_draw_spans' input.
+// ---------------------------------------------------------------------------
+// The reference's ThreadEdges[1000] (3403): a row with more pairs writes past it.
+constexpr uint32_t kRowMaxPairs = 1000u;
+// The hook: the halves as AdvSpanEmit's (pair k of the list at slot at0 + k;
+// the row is not stored with the pair), and row(): {Row, pairs since the last
+// row()} into the list's next row slot.  FILL = false counts only: no slot is
+// addressed.  A pair or a row past the list's range is counted and not stored
+// (the host's bounds rule both out; k_row_walk reports it).  over: a row
+// passed kRowMaxPairs.
+template <bool FILL>
+struct AdvRowEmit {
+    PairRaw *raw;
+    int2 *rows;
+    uint32_t at, end;    // pair slots
+    uint32_t rat, rend;  // row slots
+    uint32_t at_row;     // `at` at the last row()
+    uint32_t over;
+    __device__ __forceinline__ void half(bool right, const ObjEdge &E) const {
+        if constexpr (FILL) {
+            if (at < end) {
+                float4 *q = reinterpret_cast<float4 *>(raw + at) + (right ? 3 : 0);
+                pair_raw_half(E, q[0], q[1], q[2]);
+            }
+        }
+    }
+    __device__ __forceinline__ void pair(int32_t) { ++at; }
+    __device__ __forceinline__ void row(int32_t Row) {
+        const uint32_t k = at - at_row;
+        if constexpr (FILL) {
+            if (rat < rend) rows[rat] = make_int2(Row, (int32_t)k);
+        }
+        ++rat;
+        at_row = at;
+        if (k > kRowMaxPairs) over = 1u;
+    }
+};
+
+// sbase / rbase: nlist + 1 values each, list o's pair slots [sbase[o],
+// sbase[o + 1]) (floor(edge-rows / 2), as k_span_walk's) and row slots
+// [rbase[o], rbase[o + 1]) (the rows of its walk, max(0, min(max YMax, height)
+// - YMin[0])).  pcnt[o], rcnt[o]: the list's pairs and rows.  err bit 0: a
+// list passed a range; bit 1: a row passed kRowMaxPairs pairs.  A one-edge
+// list is walked too: its rows pair nothing and are queued all the same.
+template <bool FILL>
+__global__ void __launch_bounds__(kLinkThreads) k_row_walk(ObjEdge *__restrict__ work,
+                                                           const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                           int32_t height, const uint32_t *__restrict__ sbase,
+                                                           const uint32_t *__restrict__ rbase,
+                                                           PairRaw *__restrict__ raw, int2 *__restrict__ rows,
+                                                           uint32_t *__restrict__ pcnt, uint32_t *__restrict__ rcnt,
+                                                           uint32_t *__restrict__ err) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= nlist) return;
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    uint32_t pairs = 0, nrow = 0;
+    if (n >= 1) {
+        const uint32_t s0 = FILL ? sbase[o] : 0u, s1 = FILL ? sbase[o + 1] : 0xFFFFFFFFu;
+        const uint32_t r0 = FILL ? rbase[o] : 0u, r1 = FILL ? rbase[o + 1] : 0xFFFFFFFFu;
+        AdvRowEmit<FILL> em{raw, rows, s0, s1, r0, r1, s0, 0u};
+        adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
+        pairs = em.at - s0;
+        nrow = em.rat - r0;
+        uint32_t bits = em.over ? 2u : 0u;
+        if (FILL && (em.at > s1 || em.rat > r1)) {
+            pairs = min(pairs, s1 - s0);
+            nrow = min(nrow, r1 - r0);
+            bits |= 1u;
+        }
+        if (bits) atomicOr(err, bits);
+    }
+    pcnt[o] = pairs;
+    rcnt[o] = nrow;
+}
+
+// The used slots as packed records.  Workgroups [0, npb) pack the pairs,
+// kPackSpans consecutive packed pairs each: lane t finds pair k's list as
+// k_span_pack does (pscan: the scanned pair counts), reads its slot (six
+// dwordx4) and puts the 24 dwords in prk_row_pair's interleaved order into LDS
+// at dword kPairStride t.  24 t would put lanes 0, 4, 8, .. of a ds_write_b32
+// group on one bank (24 t mod 32 takes four values); 25 is odd, so the 32
+// lanes fall on 32 banks.  Then lane t of pass j stores dwordx4 t + 256 j of
+// the workgroup's 24 KiB stretch of the output (1 KiB contiguous a wave
+// instruction, every store 16-byte aligned: 96 bytes are six dwordx4), read
+// from LDS as four dwords -- the odd stride leaves no 16-byte alignment for
+// one ds_read_b128.  The workgroups after them copy the rows, one 8-byte
+// record a lane, from list slots to packed position (rscan: the scanned row
+// counts).
+constexpr uint32_t kPairStride = 25u;
+__global__ void __launch_bounds__(kPackSpans) k_row_pack(const PairRaw *__restrict__ raw,
+                                                         const int2 *__restrict__ rows,
+                                                         const uint32_t *__restrict__ sbase,
+                                                         const uint32_t *__restrict__ rbase,
+                                                         const uint32_t *__restrict__ pscan,
+                                                         const uint32_t *__restrict__ rscan, uint32_t nlist,
+                                                         uint32_t npair, uint32_t nrow, uint32_t npb,
+                                                         uint4 *__restrict__ pairs_out, int2 *__restrict__ rows_out) {
+    __shared__ float st[kPairStride * kPackSpans];
+    const uint32_t tid = threadIdx.x;
+    if (blockIdx.x >= npb) {  // (workgroup-uniform)
+        const uint32_t k = (blockIdx.x - npb) * (uint32_t)kPackSpans + tid;
+        if (k >= nrow) return;
+        uint32_t lo = 0, hi = nlist;  // rscan[lo] <= k < rscan[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (rscan[mid] <= k) lo = mid;
+            else hi = mid;
+        }
+        rows_out[k] = rows[(size_t)rbase[lo] + (k - rscan[lo])];
+        return;
+    }
+    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< npair: npb)
+    const uint32_t ns = min((uint32_t)kPackSpans, npair - k0);
+    const uint32_t k = k0 + tid;
+    if (tid < ns) {
+        uint32_t lo = 0, hi = nlist;  // pscan[lo] <= k < pscan[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (pscan[mid] <= k) lo = mid;
+            else hi = mid;
+        }
+        const PairRaw r = raw[(size_t)sbase[lo] + (k - pscan[lo])];
+        float *d = st + kPairStride * tid;
+        d[0] = r.l0.x; d[1] = r.r0.x;  // XMin
+        d[2] = r.l0.y; d[3] = r.r0.y;  // ZMin
+        d[4] = r.l0.z; d[5] = r.r0.z;  // OneOverZMin
+        d[6] = r.l0.w; d[7] = r.r0.w;  // UMin
+        d[8] = r.l1.x; d[9] = r.r1.x;  // VMin
+        d[10] = r.l2.x; d[11] = r.l2.y; d[12] = r.l2.z; d[13] = r.l2.w;  // LeftMinColor
+        d[14] = r.r2.x; d[15] = r.r2.y; d[16] = r.r2.z; d[17] = r.r2.w;  // RightMinColor
+        d[18] = r.l1.y; d[19] = r.l1.z; d[20] = r.l1.w;                  // LeftMinNormal
+        d[21] = r.r1.y; d[22] = r.r1.z; d[23] = r.r1.w;                  // RightMinNormal
+    }
+    __syncthreads();
+    uint4 *dst = pairs_out + (size_t)k0 * 6u;
+    for (uint32_t p = tid; p < 6u * ns; p += (uint32_t)kPackSpans) {
+        const uint32_t t = p / 6u, q = p - 6u * t;
+        const float *sp = st + kPairStride * t + 4u * q;
+        dst[p] = make_uint4(__float_as_uint(sp[0]), __float_as_uint(sp[1]), __float_as_uint(sp[2]),
+                            __float_as_uint(sp[3]));
+    }
+}
+
+// prk_draw_rows: packed rows and pairs back into prk_draw_spans' records
+// (packed prk_span, 25 dwords).  rows: the caller's prk_row records; rscan:
+// their scanned EdgeCounts (nrow + 1 values, the last = npair).  A workgroup
+// takes kPackSpans consecutive pairs: their 24 KiB come in as dwordx4 (lane t
+// of pass j loads piece t + 256 j) and go to LDS at dword kPairStride * pair +
+// word; lane t then reads pair t's 24 dwords (the odd stride: 32 banks for a
+// group's 32 lanes), finds the pair's row -- the last row r with rscan[r] <=
+// k, never one with EdgeCount 0 -- and writes the span's 25 dwords in prk_span's
+// order over them: dwords [25 t, 25 t + 25) are lane t's alone, in and out.
+// The stretch leaves as k_span_pack's does (`out`: 25 * npair dwords rounded
+// up to four, the spare dwords zero).
+__global__ void __launch_bounds__(kPackSpans) k_rows_unpack(const int2 *__restrict__ rows,
+                                                            const uint32_t *__restrict__ rscan, uint32_t nrow,
+                                                            const uint4 *__restrict__ pairs, uint32_t npair,
+                                                            uint4 *__restrict__ out) {
+    static_assert(kPairStride == 25u, "a pair's LDS stretch holds its span");
+    __shared__ uint4 st4[kPackPieces];
+    float *st = reinterpret_cast<float *>(st4);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< npair: the grid)
+    const uint32_t ns = min((uint32_t)kPackSpans, npair - k0);
+    const uint4 *src = pairs + (size_t)k0 * 6u;
+    for (uint32_t p = tid; p < 6u * ns; p += (uint32_t)kPackSpans) {
+        const uint32_t t = p / 6u, q = p - 6u * t;
+        const uint4 v = src[p];
+        float *sp = st + kPairStride * t + 4u * q;
+        sp[0] = __uint_as_float(v.x); sp[1] = __uint_as_float(v.y);
+        sp[2] = __uint_as_float(v.z); sp[3] = __uint_as_float(v.w);
+    }
+    __syncthreads();
+    if (tid < ns) {
+        const uint32_t k = k0 + tid;
+        uint32_t lo = 0, hi = nrow;  // rscan[lo] <= k < rscan[hi]
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (rscan[mid] <= k) lo = mid;
+            else hi = mid;
+        }
+        float *d = st + kPairStride * tid;
+        float w[24];
+#pragma unroll
+        for (int i = 0; i < 24; ++i) w[i] = d[i];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float *e = d + 12 * h;
+            e[0] = w[0 + h]; e[1] = w[2 + h]; e[2] = w[4 + h]; e[3] = w[6 + h]; e[4] = w[8 + h];  // X Z W U V
+            e[5] = w[10 + 4 * h]; e[6] = w[11 + 4 * h]; e[7] = w[12 + 4 * h]; e[8] = w[13 + 4 * h];  // MinColor
+            e[9] = w[18 + 3 * h]; e[10] = w[19 + 3 * h]; e[11] = w[20 + 3 * h];                      // MinNormal
+        }
+        d[24] = __int_as_float(rows[lo].x);
+    } else if (tid < ns + 1u) {
+        st[25u * ns] = st[25u * ns + 1u] = st[25u * ns + 2u] = 0.0f;  // (the last piece's spare dwords; < 25 * 256)
+    }
+    __syncthreads();
+    const uint32_t np = (25u * ns + 3u) / 4u;
+    uint4 *dst = out + (size_t)blockIdx.x * kPackPieces;
+    for (uint32_t p = tid; p < np; p += (uint32_t)kPackSpans) dst[p] = st4[p];
+}
+// The rows' EdgeCounts as one array for the scan (cnt[nrow] = 0: its total).
+__global__ void __launch_bounds__(256) k_rows_counts(const int2 *__restrict__ rows, uint32_t nrow,
+                                                     uint32_t *__restrict__ cnt) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= nrow) cnt[i] = i < nrow ? (uint32_t)rows[i].y : 0u;
+}
+
 }  // namespace prk
 
 extern "C" {
@@ -4660,6 +4884,59 @@ hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sb
     hipLaunchKernelGGL(prk::k_span_pack, dim3((total + prk::kPackSpans - 1) / prk::kPackSpans),
                        dim3(prk::kPackSpans), 0, s, reinterpret_cast<const prk::PairRaw *>(raw), row, sbase, cscan,
                        nlist, total, reinterpret_cast<uint4 *>(out));
+    return hipGetLastError();
+}
+// prk_row_records: the import, then the walk with the row emission: list o's
+// pairs into PairRaw slots [sbase[o], sbase[o + 1]), its row records into row
+// slots [rbase[o], rbase[o + 1]), its counts into pcnt[o] / rcnt[o]; err |= 1
+// should a list pass its slots, |= 2 when a row holds more than 1000 pairs.
+// raw == nullptr: the counts and err alone (no slots are read or written).
+hipError_t prk_row_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
+                        void *work, const uint32_t *sbase, const uint32_t *rbase, void *raw, void *rows,
+                        uint32_t *pcnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) {
+    if (total == 0 || nlist == 0) return hipSuccess;
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
+                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
+    if (raw)
+        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, lscan, nlist, height, sbase, rbase,
+                           reinterpret_cast<prk::PairRaw *>(raw), reinterpret_cast<int2 *>(rows), pcnt, rcnt, err);
+    else
+        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, lscan, nlist, height, sbase, rbase,
+                           (prk::PairRaw *)nullptr, (int2 *)nullptr, pcnt, rcnt, err);
+    return hipGetLastError();
+}
+// The npair pairs and nrow rows the walk left (pscan, rscan: the scanned
+// counts, nlist + 1 each) as packed prk_row_pair and prk_row.
+hipError_t prk_row_pack(const void *raw, const void *rows, const uint32_t *sbase, const uint32_t *rbase,
+                        const uint32_t *pscan, const uint32_t *rscan, uint32_t nlist, uint32_t npair, uint32_t nrow,
+                        void *pairs_out, void *rows_out, hipStream_t s) {
+    if (nlist == 0 || (npair == 0 && nrow == 0)) return hipSuccess;
+    const uint32_t npb = (npair + prk::kPackSpans - 1) / prk::kPackSpans;
+    const uint32_t nrb = (nrow + prk::kPackSpans - 1) / prk::kPackSpans;
+    hipLaunchKernelGGL(prk::k_row_pack, dim3(npb + nrb), dim3(prk::kPackSpans), 0, s,
+                       reinterpret_cast<const prk::PairRaw *>(raw), reinterpret_cast<const int2 *>(rows), sbase, rbase,
+                       pscan, rscan, nlist, npair, nrow, npb, reinterpret_cast<uint4 *>(pairs_out),
+                       reinterpret_cast<int2 *>(rows_out));
+    return hipGetLastError();
+}
+// prk_draw_rows: the rows' EdgeCounts (nrow + 1 words, the last 0) for the
+// scan, and npair packed pairs as packed prk_span (`out`: 25 * npair dwords
+// rounded up to four), each on its row's RowIndex.
+hipError_t prk_rows_counts(const void *rows, uint32_t nrow, uint32_t *cnt, hipStream_t s) {
+    hipLaunchKernelGGL(prk::k_rows_counts, dim3(nrow / 256 + 1), dim3(256), 0, s,
+                       reinterpret_cast<const int2 *>(rows), nrow, cnt);
+    return hipGetLastError();
+}
+hipError_t prk_rows_unpack(const void *rows, const uint32_t *rscan, uint32_t nrow, const void *pairs, uint32_t npair,
+                           void *out, hipStream_t s) {
+    if (nrow == 0 || npair == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_rows_unpack, dim3((npair + prk::kPackSpans - 1) / prk::kPackSpans),
+                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const int2 *>(rows), rscan, nrow,
+                       reinterpret_cast<const uint4 *>(pairs), npair, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }
 hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {

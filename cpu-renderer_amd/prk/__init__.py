@@ -109,6 +109,10 @@ _SIGS = {
                                          C.c_void_p]),
     "prk_span_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
                                    C.c_void_p, C.POINTER(C.c_uint64)]),
+    "prk_row_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
+                                  C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "prk_draw_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32,
+                                C.c_int32]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -637,6 +641,37 @@ class Renderer:
         self._keep.append(w)
         _check("prk_draw_spans", self._L.prk_draw_spans(self._h, _ptr(w), w.shape[0], semantics, int(bool(phong)),
                                                         -1 if bitmap is None else bitmap))
+
+    def row_records(self, words, counts, height):
+        """prk_row_records: the row work DrawModelOptimizedLines queues for
+        every list of a batch over a frame of `height` rows, walked on the
+        GPU (two calls: size, then fill) -- (rows int32 [k, 2]: RowIndex and
+        EdgeCount, list o's at sum(row_counts[:o]); pairs uint32 [m, 24] in
+        prk_row_pair layout, row r's at sum(rows[:r, 1]); row_counts uint32
+        [nlist]).  Lists sorted by YMin only (prk.h)."""
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1, 27)
+        n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if int(n.sum(dtype=np.uint64)) != w.shape[0]:
+            raise ValueError("row_records: counts sum to %d, %d records given" % (int(n.sum(dtype=np.uint64)),
+                                                                               w.shape[0]))
+        rc = np.zeros(n.shape[0], np.uint32)
+        nrow, npair = C.c_uint64(0), C.c_uint64(0)
+        _check("prk_row_records", self._L.prk_row_records(self._h, _ptr(w), _ptr(n), n.shape[0], int(height), None,
+                                                          0, None, 0, _ptr(rc), C.byref(nrow), C.byref(npair)))
+        rows = np.empty((nrow.value, 2), np.int32)
+        pairs = np.empty((npair.value, 24), np.uint32)
+        _check("prk_row_records", self._L.prk_row_records(self._h, _ptr(w), _ptr(n), n.shape[0], int(height),
+                                                          _ptr(rows), nrow.value, _ptr(pairs), npair.value,
+                                                          _ptr(rc), C.byref(nrow), C.byref(npair)))
+        return rows, pairs, rc
+
+    def draw_rows(self, rows, pairs, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
+        """prk_draw_rows: row work records (the arrays row_records returns)
+        drawn as draw_spans draws their pairs, one winner id a pair."""
+        r = np.ascontiguousarray(rows, np.int32).reshape(-1, 2)
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 24)
+        _check("prk_draw_rows", self._L.prk_draw_rows(self._h, _ptr(r), r.shape[0], _ptr(p), p.shape[0], semantics,
+                                                      int(bool(phong)), -1 if bitmap is None else bitmap))
 
     def complete_all_work(self, stream=None):
         """Platform.CompleteAllWork: run every recorded draw (asynchronous)."""

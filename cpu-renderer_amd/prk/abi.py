@@ -66,6 +66,26 @@ class PrkStats(C.Structure):
                 ("object_chunks", C.c_uint32), ("object_chunks_rewalked", C.c_uint32)]
 
 
+class PrkRowPair(C.Structure):
+    """prk_row_pair: thread_edge_info, left and right interleaved (24 words)."""
+    _fields_ = [("LeftXMin", C.c_float), ("RightXMin", C.c_float), ("LeftZMin", C.c_float), ("RightZMin", C.c_float),
+                ("LeftOneOverZMin", C.c_float), ("RightOneOverZMin", C.c_float),
+                ("LeftUMin", C.c_float), ("RightUMin", C.c_float), ("LeftVMin", C.c_float), ("RightVMin", C.c_float),
+                ("LeftMinColor", C.c_float * 4), ("RightMinColor", C.c_float * 4),
+                ("LeftMinNormal", C.c_float * 3), ("RightMinNormal", C.c_float * 3)]
+
+
+class PrkRow(C.Structure):
+    """prk_row: buffer_line_render_work's RowIndex and EdgeCount (pairs)."""
+    _fields_ = [("RowIndex", C.c_int32), ("EdgeCount", C.c_uint32)]
+
+
+# prk_row_pair word w holds prk_span word ROW_PAIR_SPAN_WORD[w] (an end is
+# XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3]; Right at +12)
+ROW_PAIR_SPAN_WORD = ([h * 12 + k for k in range(5) for h in (0, 1)] + [5, 6, 7, 8] + [17, 18, 19, 20] +
+                      [9, 10, 11] + [21, 22, 23])
+
+
 def make_transform(D, F, M2P, cx, cy):
     t = PrkTransform()
     t.DistanceAboveTarget = D

@@ -669,6 +669,80 @@ int prk_span_records(prk_context *ctx, const prk_edge *records, const uint32_t *
                      prk_span *spans, uint64_t capacity,
                      uint32_t *span_counts, uint64_t *total_out);
 
+/* thread_edge_info, field for field (projekt.h:39-63): 24 words, 96 bytes */
+typedef struct prk_row_pair {
+    float LeftXMin, RightXMin, LeftZMin, RightZMin, LeftOneOverZMin, RightOneOverZMin,
+          LeftUMin, RightUMin, LeftVMin, RightVMin;
+    float LeftMinColor[4], RightMinColor[4], LeftMinNormal[3], RightMinNormal[3];
+} prk_row_pair;
+/* buffer_line_render_work's RowIndex / EdgeCount (EdgeCount counts PAIRS, 3521) */
+typedef struct prk_row { int32_t RowIndex; uint32_t EdgeCount; } prk_row;
+
+/* The row work records DrawModelOptimizedLines queues for the lists of a batch
+ * (projekt.cpp:3362-3613: one buffer_line_render_work a row, followed by its
+ * EdgeCount thread_edge_info pairs), from the same walk on the GPU: records /
+ * counts / height are the packed batch of prk_advance_edge_lists, all
+ * pointers host memory; the walk's rows, the sorted rule and the 2^21-step
+ * cap are that call's.  For list o RowIndex runs over [YMin[0], min(max YMax,
+ * height)), ascending, and every row the walk reaches emits one prk_row whose
+ * EdgeCount is the number of pairs the walk meets on it -- 0 for a row with
+ * one listed edge (a one-edge list emits nothing else; 3509-3516, 3604-3609).
+ * A row on which the list is empty after the head expiry (3467-3472, where
+ * the reference dereferences NULL) emits no record: a row of the range is
+ * emitted if and only if some edge of the list has YMin <= RowIndex < YMax.
+ * Pair k of a row has Left* = CurrentEdgeInList and Right* = NextEdgeInList
+ * as they stand before the pair's step (3523-3542 precede 3546-3564),
+ * whatever their X order.  List o's rows are packed at rows[row_counts[0] +
+ * ... + row_counts[o - 1]]; `pairs` holds every pair of the batch in queue
+ * order (lists in order, rows ascending, a row's pairs in list order), so row
+ * r's pairs start at the sum of EdgeCount over the batch's earlier rows.
+ * Pair k of the batch holds the 24 values of span k of prk_span_records on
+ * the same input, re-ordered, and the allowance is that call's: where the
+ * expected MinColor or MinNormal word is a NaN the word here is a NaN of any
+ * sign and payload.  Every other word, RowIndex and EdgeCount included, is
+ * equal.  row_counts (list_count words, or NULL) gets every list's number of
+ * rows, *row_total_out their sum, *pair_total_out the batch's pairs.
+ *
+ * Calling pattern: rows == NULL and pairs == NULL size -- row_counts and both
+ * totals are written by a counting walk that takes no row or pair memory;
+ * with both arrays and either capacity (in records) below its total the call
+ * returns PRK_ERR_ARG with row_counts and the totals written and both arrays
+ * untouched.  One array NULL and the other not: PRK_ERR_ARG.
+ *
+ * Synchronous; needs no render target, records no draw, touches no recorded
+ * draw and no prk_stats; frames in flight finish first.  PRK_ERR_ARG: a NULL
+ * context or total pointer, NULL counts with list_count > 0, NULL records
+ * with a non-zero record total, height < 0.  PRK_ERR_UNSUPPORTED: a list
+ * outside the sorted rule, or a row with more than 1000 pairs (the reference
+ * writes past its ThreadEdges[1000], 3403) -- the walk itself finds such a
+ * row, so the counting call refuses it too.  PRK_ERR_LIMIT: whatever
+ * prk_span_records refuses, or the batch's row slots pass 31 bits (a list
+ * gets max(0, min(max YMax, height) - YMin[0])).  list_count == 0 or no
+ * records: PRK_OK, both totals 0, row_counts zero.  On any error but the
+ * short capacity nothing is written to any output. */
+int prk_row_records(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
+                    uint32_t list_count, int32_t height,
+                    prk_row *rows, uint64_t row_capacity,
+                    prk_row_pair *pairs, uint64_t pair_capacity,
+                    uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out);
+
+/* Draw row work records (what DoBufferLineRenderWork runs, 2341-2348): the
+ * pairs in order, each with FillLineOptimized's span body on its row's
+ * RowIndex (FillLinesOptimized, 629-1490, has the same block math) -- exactly
+ * what prk_draw_spans draws for the same pairs regrouped as prk_spans, frame
+ * and winner ids: one id per pair, a row with EdgeCount == 0 takes none.  Row
+ * r's pairs are pairs[sum of EdgeCount over rows before r ..].  The records
+ * are copied at the call (the GPU regroups them; the call waits for that).
+ * Semantics, phong and texture as prk_draw_spans: PRK_SEM_SCALAR is
+ * PRK_ERR_UNSUPPORTED.  PRK_ERR_ARG: the EdgeCounts do not sum to pair_count,
+ * an array is NULL with a non-zero count, a RowIndex is negative.
+ * PRK_ERR_LIMIT: row_count or the frame's spans pass 31 bits.  row_count == 0
+ * or pair_count == 0: PRK_OK, nothing recorded.  On any error nothing is
+ * recorded. */
+int prk_draw_rows(prk_context *ctx, const prk_row *rows, uint64_t row_count,
+                  const prk_row_pair *pairs, uint64_t pair_count,
+                  int32_t semantics, int32_t phong, int32_t texture);
+
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
  * vertex count through *count_out. */
