@@ -74,14 +74,20 @@ hipError_t prk_rec_emit(const prk::FrameParams *, const void *, const uint32_t *
                         const uint32_t *, int32_t, uint32_t, void *, void *, uint32_t *, int, hipStream_t);
 hipError_t prk_rec_counts(const void *, const uint32_t *, uint32_t, const uint32_t *, uint32_t *, hipStream_t);
 hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipStream_t);
-hipError_t prk_adv_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, hipStream_t);
+hipError_t prk_adv_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
+                        hipStream_t);
+uint32_t prk_adv_wg_lcap(void);
+hipError_t prk_adv_walk_wg(int, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
+                           const uint32_t *, const uint32_t *, void *, int32_t *, void *, uint32_t *, uint32_t *,
+                           uint32_t *, hipStream_t);
 hipError_t prk_adv_next(const void *, uint32_t, int32_t *, hipStream_t);
-hipError_t prk_span_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, const uint32_t *, void *,
-                         int32_t *, uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_span_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
+                         const uint32_t *, void *, int32_t *, uint32_t *, uint32_t *, hipStream_t);
 hipError_t prk_span_pack(const void *, const int32_t *, const uint32_t *, const uint32_t *, uint32_t, uint32_t, void *,
                          hipStream_t);
-hipError_t prk_row_walk(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, const uint32_t *,
-                        const uint32_t *, void *, void *, uint32_t *, uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_row_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
+                        const uint32_t *, const uint32_t *, void *, void *, uint32_t *, uint32_t *, uint32_t *,
+                        hipStream_t);
 hipError_t prk_row_pack(const void *, const void *, const uint32_t *, const uint32_t *, const uint32_t *,
                         const uint32_t *, uint32_t, uint32_t, uint32_t, void *, void *, hipStream_t);
 hipError_t prk_rows_counts(const void *, uint32_t, uint32_t *, hipStream_t);
@@ -376,6 +382,9 @@ struct prk_context {
         // first large object's (most, rows, entries) as read back
         uint32_t walk_routes[9] = {};
         int32_t walk_sizes[3] = {};
+        // debug (prk_debug_list_routes): the most recent record call's lists
+        // on the thread walk, then in each slot class of the workgroup walk
+        uint32_t list_routes[6] = {};
     } spans;
 };
 
@@ -1391,6 +1400,12 @@ int prk_debug_walk_routes(prk_context *c, uint32_t *out, int32_t n) {
     RESOLVE_COUNT(c);
     const prk_context::SpanScratch &S = c->spans;
     for (int i = 0; i < n; ++i) out[i] = i < 9 ? S.walk_routes[i] : (uint32_t)S.walk_sizes[i - 9];
+    return PRK_OK;
+}
+
+int prk_debug_list_routes(prk_context *c, uint32_t *out, int32_t n) {
+    if (!c || !out || n < 0 || n > 6) return PRK_ERR_ARG;
+    for (int i = 0; i < n; ++i) out[i] = c->spans.list_routes[i];
     return PRK_OK;
 }
 
@@ -2783,13 +2798,14 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
 
 // The lists DrawModel* leaves (prk_advance_edge_records' result) for a batch
 // of sorted lists, walked on the GPU: k_adv_import -> k_adv_walk (one thread
-// per list) -> k_rec_export + k_adv_next (prk_spans.hip).  Every refusal is
-// decided on the host, in the one pass over the records that checks the
-// sorted rule (list_walks_sorted) and sizes each list's walk -- a list is one
-// thread's, so a list over kAdvMaxSteps is refused before anything is
-// launched.  The scratch is the span path's, taken as prk_edge_records takes
-// it; the packed records go in and come out through one buffer (the import
-// has read it before the export writes it).
+// per list) and k_adv_walk_wg (one workgroup per long list, ListRouter below)
+// -> k_rec_export + k_adv_next (prk_spans.hip).  Every refusal is decided on
+// the host, in the one pass over the records that checks the sorted rule
+// (list_walks_sorted), sizes each list's walk and routes it -- a list over
+// kAdvMaxSteps is refused before anything is launched.  The scratch is the
+// span path's, taken as prk_edge_records takes it; the packed records go in
+// and come out through one buffer (the import has read it before the export
+// writes it).
 //
 // kAdvMaxSteps: one thread walks 1.6 M edge-rows a second (DESIGN §4.4.3,
 // one pair a row and 128 pairs a row alike), so the 2^24 edge-rows first
@@ -2825,6 +2841,116 @@ static uint64_t list_walk_steps(const prk_edge *e, uint32_t n, int32_t height, u
     }
     return steps;
 }
+// The most edges of a sorted list linked at once: list_walk_steps' sweep (the
+// edges in YMin order, a heap of the linked edges' YMax), an edge counted from
+// its YMin row through its YMax row -- it is still linked while that row's
+// insertions happen.  Only edges with YMin < height are ever inserted.
+// Returns at once past `stop`.
+static uint32_t list_most_listed(const prk_edge *e, uint32_t n, int32_t height, uint32_t stop,
+                                 std::vector<int32_t> &heap) {
+    size_t most = 0;
+    heap.clear();
+    for (uint32_t i = 0; i < n && e[i].YMin < height && most <= stop; ++i) {
+        while (!heap.empty() && heap.front() < e[i].YMin) {
+            std::pop_heap(heap.begin(), heap.end(), std::greater<int32_t>());
+            heap.pop_back();
+        }
+        heap.push_back(e[i].YMax);
+        std::push_heap(heap.begin(), heap.end(), std::greater<int32_t>());
+        most = std::max(most, heap.size());
+    }
+    return (uint32_t)std::min<size_t>(most, 0xFFFFFFFFu);
+}
+// Which walk each list of a record call takes.  A thread
+// (k_adv_walk, k_span_walk, k_row_walk) walks a list unless its thread-walk
+// cost, list_walk_steps, reaches kAdvWgMinSteps and its most linked edges fit
+// the workgroup walk's largest slot class: then a workgroup walks it
+// (k_*_walk_wg), in the smallest class that holds them.  A routed list has no
+// insertion scan -- a row's new edges are inserted as one batch -- so only the
+// edge-row term of kAdvMaxSteps applies to it; that term applies to every
+// list.  The route does not depend on how many lists take it: 61,440 equal
+// lists at the threshold are still faster as workgroups.
+// kAdvWgMinSteps: the sweep of tools/time_advance_lists.py
+// (profiles/advance_edge_lists.json, "wg_sweep"; DESIGN §4.4.6 names the
+// rows).  PRK_ADV_WG_MIN_STEPS=n in the environment, read per call, replaces
+// it: 0 routes every list that fits, a huge value none.
+// A call without a candidate does what it did before there was a route: the
+// device is not asked for its slot classes, no route word is made or
+// uploaded, and the thread kernels get a null route.
+constexpr uint64_t kAdvWgMinSteps = 3432;  // (the sweep's square_48x48: 48 * 48 + 48 * 47 / 2)
+constexpr uint32_t kAdvWgCaps[5] = {62, 126, 254, 510, 1022};
+struct ListRouter {
+    struct Cand {
+        uint32_t o, cls;
+    };
+    int device;
+    uint64_t min_steps = kAdvWgMinSteps;
+    bool asked = false;
+    uint32_t lcap = 0;  // the largest class the device grants
+    std::vector<int32_t> heap;
+    std::vector<Cand> cand;
+    std::vector<uint32_t> words;  // finish(): a route word per list (+ 1), then the routed lists by class
+    uint32_t ncls[5] = {};
+    explicit ListRouter(int dev) : device(dev) {
+        if (const char *env = std::getenv("PRK_ADV_WG_MIN_STEPS")) {
+            char *end = nullptr;
+            const unsigned long long v = std::strtoull(env, &end, 10);
+            if (end != env) min_steps = v;
+        }
+    }
+    // One list of the pass; false: over the cap.
+    bool take(const prk_edge *e, uint32_t n, int32_t height, uint32_t o, uint64_t *edge_rows_out) {
+        uint64_t edge_rows = 0;
+        const uint64_t cost = list_walk_steps(e, n, height, kAdvMaxSteps, heap, &edge_rows);
+        if (edge_rows_out) *edge_rows_out = edge_rows;
+        if (n && cost >= min_steps && edge_rows <= kAdvMaxSteps) {
+            if (!asked) {  // (the first list past the threshold: the device's slot classes)
+                asked = true;
+                if (hipSetDevice(device) == hipSuccess) lcap = std::min(prk_adv_wg_lcap(), kAdvWgCaps[4]);
+            }
+            if (lcap) {
+                const uint32_t most = list_most_listed(e, n, height, lcap, heap);
+                for (uint32_t ci = 0; ci < 5; ++ci)
+                    if (most <= kAdvWgCaps[ci] && kAdvWgCaps[ci] <= lcap) {
+                        cand.push_back(Cand{o, ci});
+                        return true;
+                    }
+            }
+        }
+        return cost <= kAdvMaxSteps;
+    }
+    // After the pass: the routed lists' words.
+    void finish(uint32_t list_count) {
+        if (cand.empty()) return;
+        const size_t nl1 = (size_t)list_count + 1;
+        words.assign(nl1 + cand.size(), 0u);
+        for (const Cand &k : cand) {
+            words[k.o] = k.cls + 1;
+            ++ncls[k.cls];
+        }
+        uint32_t at[5], sum = 0;
+        for (int ci = 0; ci < 5; sum += ncls[ci], ++ci) at[ci] = sum;
+        for (const Cand &k : cand) words[nl1 + at[k.cls]++] = k.o;
+    }
+    size_t routed() const { return cand.size(); }
+    void note(prk_context *c, uint32_t list_count) const {
+        c->spans.list_routes[0] = list_count - (uint32_t)cand.size();
+        for (int ci = 0; ci < 5; ++ci) c->spans.list_routes[1 + ci] = ncls[ci];
+    }
+    // The workgroup kernels, a launch per occupied class (d_lists: the words after the route words).
+    hipError_t launch(int kind, const uint32_t *d_lists, const uint32_t *lscan, int32_t height, void *work,
+                      const uint32_t *sbase, const uint32_t *rbase, void *raw, int32_t *prow, void *rows,
+                      uint32_t *cnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) const {
+        if (cand.empty()) return hipSuccess;
+        for (int ci = 0; ci < 5; ++ci) {
+            const hipError_t e = prk_adv_walk_wg(kind, kAdvWgCaps[ci], d_lists, ncls[ci], lscan, height, work, sbase,
+                                                 rbase, raw, prow, rows, cnt, rcnt, err, s);
+            if (e != hipSuccess) return e;
+            d_lists += ncls[ci];
+        }
+        return hipSuccess;
+    }
+};
 int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
                            int32_t height, prk_edge *records_out, int32_t *next_out) {
     if (!c || (!counts && list_count) || height < 0) return PRK_ERR_ARG;
@@ -2833,8 +2959,10 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
     if ((!records || !records_out) && total) return PRK_ERR_ARG;
     if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
     if (list_count == 0 || total == 0) return PRK_OK;
-    std::vector<uint32_t> lscan((size_t)list_count + 1);
-    std::vector<int32_t> heap;
+    const size_t nl1 = (size_t)list_count + 1;
+    std::vector<uint32_t> tab(nl1);
+    uint32_t *lscan = tab.data();
+    ListRouter router(c->device);
     bool too_long = false;
     {
         const prk_edge *e = records;
@@ -2842,29 +2970,45 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
         for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
             lscan[o] = at;
             if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap) > kAdvMaxSteps;
+            too_long = !router.take(e, counts[o], height, o, nullptr) || too_long;
         }
         lscan[list_count] = at;
     }
     if (too_long) return PRK_ERR_LIMIT;
+    router.finish(list_count);
+    const bool wg = router.routed() != 0;  // (else: the call as it was before there was a route)
     RESOLVE_COUNT(c);
     PRK_TRY(hipSetDevice(c->device));
     PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    router.note(c, list_count);
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
     const uint32_t n = (uint32_t)total;
     const size_t rec_bytes = (size_t)n * sizeof(prk_edge);
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
     PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure(lscan.size() * 4));
+    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
+    if (wg) PRK_TRY(S.d_err.ensure(16));
     if (next_out) PRK_TRY(S.d_evals.ensure((size_t)n * 4));
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_route = wg ? d_lscan + tab.size() : nullptr,
+                   *d_lists = wg ? d_route + nl1 : nullptr;
     PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, rec_bytes, hipMemcpyHostToDevice, s));
-    PRK_TRY(hipMemcpyAsync(S.d_escan.p, lscan.data(), lscan.size() * 4, hipMemcpyHostToDevice, s));
-    PRK_TRY(hipStreamSynchronize(s));  // (lscan is this call's; records may be records_out)
-    PRK_TRY(prk_adv_walk(S.d_recout.p, n, (const uint32_t *)S.d_escan.p, list_count, height, S.d_work.p, s));
+    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    if (wg) {
+        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
+                               hipMemcpyHostToDevice, s));
+        PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
+    }
+    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's; records may be records_out)
+    PRK_TRY(prk_adv_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, s));
+    PRK_TRY(router.launch(0, d_lists, d_lscan, height, S.d_work.p, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, (uint32_t *)S.d_err.p, s));
     PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, S.d_recout.p, s));
     if (next_out) PRK_TRY(prk_adv_next(S.d_work.p, n, (int32_t *)S.d_evals.p, s));
+    uint32_t err = 0;
+    if (wg) PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernels ran
+    if (err) return PRK_ERR_DEVICE;    // a workgroup walk ran out of slots
     PRK_TRY(hipMemcpyAsync(records_out, S.d_recout.p, rec_bytes, hipMemcpyDeviceToHost, s));
     if (next_out) PRK_TRY(hipMemcpyAsync(next_out, S.d_evals.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
@@ -2875,7 +3019,8 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
 // such a batch (3756-3809: both edges of every pair as they stand on the row,
 // and the row), from prk_advance_edge_lists' walk with the emission hook:
 // k_adv_import -> k_span_walk (one thread per list: pairs into the list's
-// slots, its count) -> scan of the counts -> k_span_pack (prk_spans.hip).
+// slots, its count) and k_span_walk_wg (a workgroup per routed list, the same
+// slots and count) -> scan of the counts -> k_span_pack (prk_spans.hip).
 // The refusals and the one host pass are prk_advance_edge_lists'; the pass
 // also sizes each list's slots, floor(edge-rows / 2): a pair uses up one row
 // of each of two listed edges (each listed on rows [YMin, min(YMax, height))
@@ -2899,7 +3044,7 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
     const size_t nl1 = (size_t)list_count + 1;
     std::vector<uint32_t> tab(2 * nl1);
     uint32_t *lscan = tab.data(), *sbase = tab.data() + nl1;
-    std::vector<int32_t> heap;
+    ListRouter router(c->device);
     bool too_long = false;
     uint64_t nslot = 0;
     {
@@ -2910,7 +3055,7 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
             sbase[o] = (uint32_t)nslot;
             if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
             uint64_t edge_rows = 0;
-            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap, &edge_rows) > kAdvMaxSteps;
+            too_long = !router.take(e, counts[o], height, o, &edge_rows) || too_long;
             nslot += edge_rows / 2;
             too_long = too_long || nslot >= 0x7FFFFFFFull;
         }
@@ -2918,15 +3063,18 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
         sbase[list_count] = (uint32_t)nslot;
     }
     if (too_long) return PRK_ERR_LIMIT;
+    router.finish(list_count);
+    const bool wg = router.routed() != 0;
     RESOLVE_COUNT(c);
     PRK_TRY(hipSetDevice(c->device));
     PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    router.note(c, list_count);
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
     const uint32_t n = (uint32_t)total;
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
     PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure(tab.size() * 4));
+    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
     PRK_TRY(S.d_scnt.ensure(nl1 * 4));
     PRK_TRY(S.d_soff.ensure(nl1 * 4));
     PRK_TRY(S.d_err.ensure(16));
@@ -2934,16 +3082,22 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
         PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));  // prk_spans.hip PairRaw
         PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)nslot * 4, 16)));    // the slots' rows
     }
-    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1;
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1,
+                   *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
     uint32_t *d_cnt = (uint32_t *)S.d_scnt.p, *d_cscan = (uint32_t *)S.d_soff.p;
     PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    if (wg)
+        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
+                               hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scan reads list_count + 1 counts)
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
     PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
-    PRK_TRY(prk_span_walk(S.d_recout.p, n, d_lscan, list_count, height, S.d_work.p, d_sbase,
+    PRK_TRY(prk_span_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, d_sbase,
                           spans ? S.d_raw.p : nullptr, spans ? (int32_t *)S.d_pos.p : nullptr, d_cnt,
                           (uint32_t *)S.d_err.p, s));
+    PRK_TRY(router.launch(1, d_lists, d_lscan, height, S.d_work.p, d_sbase, nullptr, spans ? S.d_raw.p : nullptr,
+                          spans ? (int32_t *)S.d_pos.p : nullptr, nullptr, d_cnt, nullptr, (uint32_t *)S.d_err.p, s));
     size_t tb = 0;
     PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, nullptr, &tb, s));
     PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
@@ -2971,9 +3125,10 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
 // RowIndex, EdgeCount and that many thread_edge_info pairs), from the same
 // walk with the row hook: k_adv_import -> k_row_walk (one thread per list:
 // pairs into the list's pair slots, a row record a row into its row slots, its
-// two counts) -> two scans -> k_row_pack (prk_spans.hip).  The refusals and
-// the one host pass are prk_span_records'; the pass also sizes each list's row
-// slots, the rows of its walk.  What the pass cannot know -- a row with more
+// two counts) and k_row_walk_wg (a workgroup per routed list) -> two scans ->
+// k_row_pack (prk_spans.hip).  The refusals and the one host pass are
+// prk_span_records'; the pass also sizes each list's row slots, the rows of
+// its walk.  What the pass cannot know -- a row with more
 // than 1000 pairs, the reference's ThreadEdges[1000] -- the walk flags, and
 // the flag is read before anything is written.  rows == pairs == NULL: the
 // counting walk, no slots.
@@ -2995,7 +3150,7 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
     const size_t nl1 = (size_t)list_count + 1;
     std::vector<uint32_t> tab(3 * nl1);
     uint32_t *lscan = tab.data(), *sbase = lscan + nl1, *rbase = sbase + nl1;
-    std::vector<int32_t> heap;
+    ListRouter router(c->device);
     bool too_long = false;
     uint64_t nslot = 0, nrslot = 0;
     {
@@ -3007,7 +3162,7 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
             rbase[o] = (uint32_t)nrslot;
             if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
             uint64_t edge_rows = 0;
-            too_long = too_long || list_walk_steps(e, counts[o], height, kAdvMaxSteps, heap, &edge_rows) > kAdvMaxSteps;
+            too_long = !router.take(e, counts[o], height, o, &edge_rows) || too_long;
             nslot += edge_rows / 2;
             if (counts[o]) {  // the walk's rows: [YMin[0], min(max YMax, height))
                 int32_t ymax = e[0].YMax;
@@ -3021,6 +3176,8 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
         rbase[list_count] = (uint32_t)nrslot;
     }
     if (too_long) return PRK_ERR_LIMIT;
+    router.finish(list_count);
+    const bool wg = router.routed() != 0;
     RESOLVE_COUNT(c);
     PRK_TRY(hipSetDevice(c->device));
     PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
@@ -3028,9 +3185,10 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
     prk_context::SpanScratch &S = c->spans;
     const uint32_t n = (uint32_t)total;
     const bool fill = rows != nullptr;
+    router.note(c, list_count);
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
     PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure(tab.size() * 4));
+    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
     PRK_TRY(S.d_scnt.ensure(nl1 * 4));
     PRK_TRY(S.d_soff.ensure(nl1 * 4));
     PRK_TRY(S.d_rowcnt.ensure(nl1 * 4));
@@ -3040,18 +3198,24 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
         PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));     // prk_spans.hip PairRaw
         PRK_TRY(S.d_rowslot.ensure(std::max<size_t>((size_t)nrslot * 8, 16)));  // {row, pairs}
     }
-    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1, *d_rbase = d_sbase + nl1;
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1, *d_rbase = d_sbase + nl1,
+                   *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
     uint32_t *d_pcnt = (uint32_t *)S.d_scnt.p, *d_pscan = (uint32_t *)S.d_soff.p;
     uint32_t *d_rcnt = (uint32_t *)S.d_rowcnt.p, *d_rscan = (uint32_t *)S.d_rowscan.p;
     PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    if (wg)
+        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
+                               hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scans read list_count + 1 counts)
     PRK_TRY(hipMemsetAsync(S.d_rowcnt.p, 0, nl1 * 4, s));
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
     PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
-    PRK_TRY(prk_row_walk(S.d_recout.p, n, d_lscan, list_count, height, S.d_work.p, d_sbase, d_rbase,
+    PRK_TRY(prk_row_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, d_sbase, d_rbase,
                          fill ? S.d_raw.p : nullptr, fill ? S.d_rowslot.p : nullptr, d_pcnt, d_rcnt,
                          (uint32_t *)S.d_err.p, s));
+    PRK_TRY(router.launch(2, d_lists, d_lscan, height, S.d_work.p, d_sbase, d_rbase, fill ? S.d_raw.p : nullptr,
+                          nullptr, fill ? S.d_rowslot.p : nullptr, d_pcnt, d_rcnt, (uint32_t *)S.d_err.p, s));
     size_t tb = 0;
     PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, nullptr, &tb, s));
     PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));

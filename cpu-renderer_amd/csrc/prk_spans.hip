@@ -4307,12 +4307,9 @@ struct AdvNoEmit {
     __device__ __forceinline__ void pair(int32_t) {}
     __device__ __forceinline__ void row(int32_t) {}
 };
-template <class EM>
-__device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
-    PRK_ER(w);
-    PRK_ER_LOAD(w, p);
-    ObjEdge E = PRK_ER_EDGE(w);
-    em.half(right, E);
+// (the arithmetic alone: the thread walk steps the record in device memory,
+// the workgroup walk its LDS state -- one text, so one result)
+__device__ __forceinline__ void adv_step_fields(ObjEdge &E) {
     E.X += E.G;
     E.Z += E.ZG;
     E.C0 += E.CG0; E.C1 += E.CG1; E.C2 += E.CG2; E.C3 += E.CG3;
@@ -4322,6 +4319,14 @@ __device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
     E.U += E.UG;
     E.V += E.VG;
     E.W += E.WG;
+}
+template <class EM>
+__device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
+    PRK_ER(w);
+    PRK_ER_LOAD(w, p);
+    ObjEdge E = PRK_ER_EDGE(w);
+    em.half(right, E);
+    adv_step_fields(E);
     PRK_ER_FROM(w, E);
     float4 *d = reinterpret_cast<float4 *>(p);
     d[0] = w0; d[1] = w1; d[2] = w2; d[3] = w3; d[5] = w5;
@@ -4455,9 +4460,9 @@ __device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK l
 // imported, every Next -1.
 __global__ void __launch_bounds__(kLinkThreads) k_adv_walk(ObjEdge *__restrict__ work,
                                                            const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                           int32_t height) {
+                                                           const uint32_t *__restrict__ route, int32_t height) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist) return;
+    if (o >= nlist || (route && route[o])) return;  // (routed: a workgroup walks it, k_adv_walk_wg)
     const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
     if (n < 2) return;
     AdvNoEmit em;
@@ -4511,11 +4516,12 @@ struct AdvSpanEmit {
 template <bool STORE>
 __global__ void __launch_bounds__(kLinkThreads) k_span_walk(ObjEdge *__restrict__ work,
                                                             const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                            int32_t height, const uint32_t *__restrict__ sbase,
+                                                            const uint32_t *__restrict__ route, int32_t height,
+                                                            const uint32_t *__restrict__ sbase,
                                                             PairRaw *__restrict__ raw, int32_t *__restrict__ row,
                                                             uint32_t *__restrict__ cnt, uint32_t *__restrict__ err) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist) return;
+    if (o >= nlist || (route && route[o])) return;  // (routed: k_span_walk_wg walks and counts it)
     const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
     uint32_t pairs = 0;
     if (n >= 2) {
@@ -4642,13 +4648,14 @@ struct AdvRowEmit {
 template <bool FILL>
 __global__ void __launch_bounds__(kLinkThreads) k_row_walk(ObjEdge *__restrict__ work,
                                                            const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                           int32_t height, const uint32_t *__restrict__ sbase,
+                                                           const uint32_t *__restrict__ route, int32_t height,
+                                                           const uint32_t *__restrict__ sbase,
                                                            const uint32_t *__restrict__ rbase,
                                                            PairRaw *__restrict__ raw, int2 *__restrict__ rows,
                                                            uint32_t *__restrict__ pcnt, uint32_t *__restrict__ rcnt,
                                                            uint32_t *__restrict__ err) {
     const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist) return;
+    if (o >= nlist || (route && route[o])) return;  // (routed: k_row_walk_wg walks and counts it)
     const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
     uint32_t pairs = 0, nrow = 0;
     if (n >= 1) {
@@ -4803,6 +4810,319 @@ __global__ void __launch_bounds__(256) k_rows_counts(const int2 *__restrict__ ro
     if (i <= nrow) cnt[i] = i < nrow ? (uint32_t)rows[i].y : 0u;
 }
 
+// ---------------------------------------------------------------------------
+// Long lists of the three record calls: one workgroup walks one list, the
+// slot-list walk (walk_rows<M, false>'s row loop: read-ahead window,
+// insert_one_b / insert_batch_b, the expiry compaction, the m == 0 row skip,
+// a pair per thread and both swaps) without a frame -- adv_walk_list's rows
+// [YMin[0], min(max YMax, height)), no band or target clip, every field
+// stepped on the LDS state (adv_step_fields) and the thread walk's emission
+// contract: an edge is seen as it stands on the row, before its step.
+//
+// The records' result.  A slot keeps its edge's sorted index in Next (as
+// walk_rows' CHUNK mode does).  An entry's stepped state goes back to
+// work[sorted index] -- the five quads adv_step stores, and its final Next --
+// when it expires, and for the survivors after the last row.  The ordered
+// array gives the reference's Next: on a row, after its insertions and before
+// the removal, an expiring entry in the leading run of expiring entries gets
+// -1 (the head expiry, 3715-3720); any other expiring entry keeps its
+// successor's sorted index, whether that one expires too or not (3722-3749
+// never writes the removed edge's own pointer); the last entry has -1.  After
+// the last walked row every entry still listed gets its successor's sorted
+// index, the last -1.  Edges never inserted stay as imported (Next -1).
+//
+// The hooks (every member holds the same value in every thread):
+//   half(k, right, E, Row)  thread k, pair k of the row: one end before its step
+//   row(Row, P, lead)       a row that is not skipped, P pairs (0 when one
+//                           edge is listed); lead: the one thread that stores
+// ---------------------------------------------------------------------------
+struct WgNoEmit {
+    __device__ __forceinline__ void half(int, bool, const ObjEdge &, int32_t) const {}
+    __device__ __forceinline__ void row(int32_t, uint32_t, bool) {}
+};
+// Pair k of a row at slot at + k (k_span_pack's layout); the row with it.
+template <bool STORE>
+struct WgSpanEmit {
+    PairRaw *raw;
+    int32_t *prow;
+    uint32_t at, end;
+    __device__ __forceinline__ void half(int k, bool right, const ObjEdge &E, int32_t Row) const {
+        if constexpr (STORE) {
+            const uint32_t j = at + (uint32_t)k;
+            if (j < end) {
+                float4 *q = reinterpret_cast<float4 *>(raw + j) + (right ? 3 : 0);
+                pair_raw_half(E, q[0], q[1], q[2]);
+                if (!right) prow[j] = Row;
+            }
+        }
+    }
+    __device__ __forceinline__ void row(int32_t, uint32_t P, bool) { at += P; }
+};
+// The same pair slots (k_row_pack's layout) and {Row, P} into the next row slot.
+template <bool FILL>
+struct WgRowEmit {
+    PairRaw *raw;
+    int2 *rows;
+    uint32_t at, end;    // pair slots
+    uint32_t rat, rend;  // row slots
+    uint32_t over;
+    __device__ __forceinline__ void half(int k, bool right, const ObjEdge &E, int32_t) const {
+        if constexpr (FILL) {
+            const uint32_t j = at + (uint32_t)k;
+            if (j < end) {
+                float4 *q = reinterpret_cast<float4 *>(raw + j) + (right ? 3 : 0);
+                pair_raw_half(E, q[0], q[1], q[2]);
+            }
+        }
+    }
+    __device__ __forceinline__ void row(int32_t Row, uint32_t P, bool lead) {
+        if constexpr (FILL) {
+            if (lead && rat < rend) rows[rat] = make_int2(Row, (int32_t)P);
+        }
+        ++rat;
+        at += P;
+        // (kept with the hook's contract; out of reach while the largest class
+        // holds 1022 edges, 511 pairs: the 1000-pair rule is the thread walk's to test)
+        if (P > kRowMaxPairs) over = 1u;
+    }
+};
+
+// An entry's state back into its record: the quads adv_step stores, and Next.
+__device__ __forceinline__ void adv_write_back(ObjEdge *__restrict__ dst, const ObjEdge &st, int32_t next) {
+    const float4 *q = reinterpret_cast<const float4 *>(&st);
+    float4 *d = reinterpret_cast<float4 *>(dst);
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3]; d[5] = q[5];
+    dst->Next = next;
+}
+
+// E: the list's n >= 1 records (sorted, as imported); cap: the slot class
+// (>= the most edges listed at once: the host's sweep); blockDim.x ==
+// slot_threads(cap).  Every barrier is reached by the whole workgroup: the
+// loop bounds and the branches around them are values every thread holds
+// alike (Row, MaxY, m, ins, wb, top, k, lt, nanc, P).  A row with more new
+// edges than free slots (never) sets err bit 0 and ends the walk for every
+// thread at once; false then.
+template <class EM>
+__device__ bool adv_walk_rows(ObjEdge *__restrict__ E, uint32_t n, int32_t height, const SlotLds &S, BlockRed &R,
+                              uint32_t cap, EM &em, uint32_t *__restrict__ err) {
+    const int tid = threadIdx.x;
+    const uint32_t NT = blockDim.x;
+    int32_t mr = INT32_MIN;
+    for (uint32_t i = tid; i < n; i += NT) mr = max(mr, E[i].YMax);
+    const int32_t MaxY = min(blk_max(R, mr), height);
+    const int32_t FirstRow = E[0].YMin;
+    for (uint32_t q = tid; q < cap; q += NT) S.fs[q] = (int32_t)q;
+    int top = (int)cap;
+    int m = 0;
+    uint32_t ins = 0;
+    // read-ahead window: thread t holds sorted edge wb + t
+    uint32_t wb = 0;
+    PRK_WIN(wa);
+    PRK_WIN_LOAD(wa, E, wb + (uint32_t)tid, n);
+    PRK_WIN_WAIT();
+    PRK_WIN_LAUNDER(wa);
+    __syncthreads();
+    for (int32_t Row = FirstRow; Row < MaxY; ++Row) {
+        // insertion (3654-3713): the edges with YMin == Row, in sorted order,
+        // a window at a time (batches in order == one at a time)
+        for (;;) {
+            if (ins == wb + NT) {
+                wb += NT;
+                PRK_WIN_LOAD(wa, E, wb + tid, n);
+                PRK_WIN_WAIT();
+                PRK_WIN_LAUNDER(wa);
+            }
+            const float wx = wa0.x, wg = wa0.y;
+            const int32_t wymin = __float_as_int(wa4.x), wl = __float_as_int(wa4.z);
+            const int rel = tid - (int)(ins - wb);
+            const bool eqr = rel >= 0 && wymin == Row;
+            int32_t lt, k, nanc;
+            blk_sum3(R, (rel >= 0 && wymin < Row) ? 1 : 0, eqr ? 1 : 0, (eqr && (wx != wx || wg != wg)) ? 1 : 0, lt,
+                     k, nanc);
+            if (lt) {  // (never: the list is sorted and the walk starts on its first row)
+                ins += (uint32_t)lt;
+                continue;
+            }
+            if (k == 0) break;
+            if (k > top) {  // (never: cap >= the most listed edges)
+                if (tid == 0) atomicOr(err, 1u);
+                return false;
+            }
+            if (rel >= 0 && rel < k) {  // the row's new edges take slots; their keys go to nk*
+                const int32_t slot = S.fs[top - 1 - rel];
+                PRK_WIN_STORE(&S.st[slot], wa);
+                S.st[slot].Next = (int32_t)(ins + (uint32_t)rel);  // (its sorted index)
+                S.nkx[rel] = wx;
+                S.nkg[rel] = wg;
+                S.nkl[rel] = wl;
+                S.nks[rel] = slot;
+            }
+            top -= k;
+            __syncthreads();
+            if (k <= 2 || nanc) {  // one at a time (any NaN key), 3654-3713
+                for (int t = 0; t < k; ++t) insert_one_b(S, R, m, LKey{S.nkx[t], S.nkg[t], S.nkl[t]}, S.nks[t]);
+            } else {
+                insert_batch_b(S, R, m, k);
+            }
+            ins += (uint32_t)k;
+            if (ins < wb + NT) break;  // the row's edges end inside the window
+        }
+        {  // expiry 3715-3749: keep entries with YMax > Row, in order; the others' records and slots
+            int32_t e = 0, se = -1;
+            bool keep = false;
+            if (tid < m) {
+                e = S.idx[tid];
+                keep = !(S.st[e].YMax <= Row);
+                if (tid + 1 < m) se = S.idx[tid + 1];  // (its successor before the removal)
+            }
+            const bool gone = tid < m && !keep;
+            int32_t kp, gp, kt, gt;
+            blk_excl_sum2(R, keep ? 1 : 0, gone ? 1 : 0, kp, gp, kt, gt);
+            if (gone) {  // kp == 0: nothing before it stays, the head expiry
+                const int32_t nx = (kp == 0 || se < 0) ? -1 : S.st[se].Next;
+                adv_write_back(&E[S.st[e].Next], S.st[e], nx);
+                S.fs[top + gp] = e;
+            }
+            if (keep) S.idx[kp] = e;
+            m = kt;
+            top += gt;
+            __syncthreads();
+        }
+        if (m == 0) {  // nothing happens on the rows before the next insertion: go there
+            const int32_t nx = ins < n ? E[ins].YMin : INT32_MAX;
+            Row = max(Row, min(nx, MaxY) - 1);
+            continue;
+        }
+        const int P = m / 2;  // pairing 3751-3869: thread k holds pair k
+        const bool valid = tid < P;
+        int32_t i0 = 0, i1 = 0;
+        float x0 = 0.0f, x1 = 0.0f;
+        if (valid) {
+            i0 = S.idx[2 * tid];
+            i1 = S.idx[2 * tid + 1];
+            ObjEdge a = S.st[i0];  // left edge: its values at the row, then its step (3811-3829)
+            em.half(tid, false, a, Row);
+            adv_step_fields(a);
+            S.st[i0] = a;
+            x0 = a.X;
+            ObjEdge b = S.st[i1];  // right edge
+            em.half(tid, true, b, Row);
+            adv_step_fields(b);
+            S.st[i1] = b;
+            x1 = b.X;
+            if (x0 > x1) {  // 3831-3841
+                const int32_t t = i0; i0 = i1; i1 = t;
+                const float f = x0; x0 = x1; x1 = f;
+            }
+            // pair k's entries after its first swap, for its neighbours
+            S.nb[tid] = i0;
+            S.bk[tid] = __float_as_int(x0);
+            S.aux[tid] = i1;
+            S.bk2[tid] = __float_as_int(x1);
+        }
+        __syncthreads();
+        if (valid) {  // 3843-3853: pair k's first entry against pair k-1's second
+            const bool sw = tid >= 1 && __int_as_float(S.bk2[tid - 1]) > x0;
+            const bool swn = tid + 1 < P && x1 > __int_as_float(S.bk[tid + 1]);  // pair k+1's swap takes my second
+            const int32_t nf = sw ? S.aux[tid - 1] : i0, ns = swn ? S.nb[tid + 1] : i1;
+            i0 = nf;
+            i1 = ns;
+        }
+        __syncthreads();
+        if (valid) {
+            S.idx[2 * tid] = i0;
+            S.idx[2 * tid + 1] = i1;
+        }
+        em.row(Row, (uint32_t)P, tid == 0);
+        __syncthreads();
+    }
+    // the list after the last walked row
+    if (tid < m) {
+        const int32_t e = S.idx[tid];
+        const int32_t nx = tid + 1 < m ? S.st[S.idx[tid + 1]].Next : -1;
+        adv_write_back(&E[S.st[e].Next], S.st[e], nx);
+    }
+    return true;
+}
+
+// lists: the indices of the lists of one slot class (`lcap` entries), one
+// workgroup of slot_threads(lcap) threads each; dynamic LDS slot_lds_bytes(lcap).
+__global__ void __launch_bounds__(kSlotMaxThreads) k_adv_walk_wg(ObjEdge *__restrict__ work,
+                                                                 const uint32_t *__restrict__ lscan,
+                                                                 const uint32_t *__restrict__ lists, uint32_t lcap,
+                                                                 int32_t height, uint32_t *__restrict__ err) {
+    extern __shared__ int32_t lds_list[];
+    __shared__ BlockRed R;
+    const uint32_t o = lists[blockIdx.x];
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    if (n == 0) return;  // (the whole workgroup; the host routes no empty list)
+    SlotLds S;
+    S.carve(lds_list, lcap, blockDim.x);
+    WgNoEmit em;
+    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
+}
+template <bool STORE>
+__global__ void __launch_bounds__(kSlotMaxThreads) k_span_walk_wg(ObjEdge *__restrict__ work,
+                                                                  const uint32_t *__restrict__ lscan,
+                                                                  const uint32_t *__restrict__ lists, uint32_t lcap,
+                                                                  int32_t height, const uint32_t *__restrict__ sbase,
+                                                                  PairRaw *__restrict__ raw, int32_t *__restrict__ row,
+                                                                  uint32_t *__restrict__ cnt,
+                                                                  uint32_t *__restrict__ err) {
+    extern __shared__ int32_t lds_list[];
+    __shared__ BlockRed R;
+    const uint32_t o = lists[blockIdx.x];
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    if (n == 0) return;
+    SlotLds S;
+    S.carve(lds_list, lcap, blockDim.x);
+    const uint32_t s0 = STORE ? sbase[o] : 0u, s1 = STORE ? sbase[o + 1] : 0xFFFFFFFFu;
+    WgSpanEmit<STORE> em{raw, row, s0, s1};
+    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
+    if (threadIdx.x == 0) {
+        uint32_t pairs = em.at - s0;
+        if (STORE && em.at > s1) {
+            pairs = s1 - s0;
+            atomicOr(err, 1u);
+        }
+        cnt[o] = pairs;
+    }
+}
+template <bool FILL>
+__global__ void __launch_bounds__(kSlotMaxThreads) k_row_walk_wg(ObjEdge *__restrict__ work,
+                                                                 const uint32_t *__restrict__ lscan,
+                                                                 const uint32_t *__restrict__ lists, uint32_t lcap,
+                                                                 int32_t height, const uint32_t *__restrict__ sbase,
+                                                                 const uint32_t *__restrict__ rbase,
+                                                                 PairRaw *__restrict__ raw, int2 *__restrict__ rows,
+                                                                 uint32_t *__restrict__ pcnt,
+                                                                 uint32_t *__restrict__ rcnt,
+                                                                 uint32_t *__restrict__ err) {
+    extern __shared__ int32_t lds_list[];
+    __shared__ BlockRed R;
+    const uint32_t o = lists[blockIdx.x];
+    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
+    if (n == 0) return;
+    SlotLds S;
+    S.carve(lds_list, lcap, blockDim.x);
+    const uint32_t s0 = FILL ? sbase[o] : 0u, s1 = FILL ? sbase[o + 1] : 0xFFFFFFFFu;
+    const uint32_t r0 = FILL ? rbase[o] : 0u, r1 = FILL ? rbase[o + 1] : 0xFFFFFFFFu;
+    WgRowEmit<FILL> em{raw, rows, s0, s1, r0, r1, 0u};
+    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
+    if (threadIdx.x == 0) {
+        uint32_t pairs = em.at - s0, nrow = em.rat - r0;
+        uint32_t bits = em.over ? 2u : 0u;
+        if (FILL && (em.at > s1 || em.rat > r1)) {
+            pairs = min(pairs, s1 - s0);
+            nrow = min(nrow, r1 - r0);
+            bits |= 1u;
+        }
+        if (bits) atomicOr(err, bits);
+        pcnt[o] = pairs;
+        rcnt[o] = nrow;
+    }
+}
+
 }  // namespace prk
 
 extern "C" {
@@ -4842,8 +5162,8 @@ hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total
 // of 16 bytes) of nlist lists (lscan: nlist + 1 first edges) into the working
 // copy, walked over `height` rows there; prk_rec_export(work, nullptr, ...)
 // packs the result, prk_adv_next its links.
-hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
-                        void *work, hipStream_t s) {
+hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
+                        const uint32_t *route, int32_t height, void *work, hipStream_t s) {
     if (total == 0 || nlist == 0) return hipSuccess;
     prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
     hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
@@ -4851,16 +5171,16 @@ hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lsc
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prk::k_adv_walk, dim3((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads),
-                       dim3(prk::kLinkThreads), 0, s, w, lscan, nlist, height);
+                       dim3(prk::kLinkThreads), 0, s, w, lscan, nlist, route, height);
     return hipGetLastError();
 }
 // prk_span_records: prk_adv_walk's import, then the walk with the emission:
 // list o's pairs into PairRaw slots [sbase[o], sbase[o + 1]) and their rows,
 // its count into cnt[o]; err |= 1 should a list pass its slots.  raw ==
 // nullptr: the counts alone (no slots are read or written).
-hipError_t prk_span_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
-                         void *work, const uint32_t *sbase, void *raw, int32_t *row, uint32_t *cnt, uint32_t *err,
-                         hipStream_t s) {
+hipError_t prk_span_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
+                         const uint32_t *route, int32_t height, void *work, const uint32_t *sbase, void *raw,
+                         int32_t *row, uint32_t *cnt, uint32_t *err, hipStream_t s) {
     if (total == 0 || nlist == 0) return hipSuccess;
     prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
     hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
@@ -4869,10 +5189,10 @@ hipError_t prk_span_walk(const void *records, uint32_t total, const uint32_t *ls
     if (e != hipSuccess) return e;
     const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
     if (raw)
-        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, lscan, nlist, height, sbase,
+        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, lscan, nlist, route, height, sbase,
                            reinterpret_cast<prk::PairRaw *>(raw), row, cnt, err);
     else
-        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, lscan, nlist, height, sbase,
+        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, lscan, nlist, route, height, sbase,
                            (prk::PairRaw *)nullptr, (int32_t *)nullptr, cnt, err);
     return hipGetLastError();
 }
@@ -4891,9 +5211,10 @@ hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sb
 // slots [rbase[o], rbase[o + 1]), its counts into pcnt[o] / rcnt[o]; err |= 1
 // should a list pass its slots, |= 2 when a row holds more than 1000 pairs.
 // raw == nullptr: the counts and err alone (no slots are read or written).
-hipError_t prk_row_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist, int32_t height,
-                        void *work, const uint32_t *sbase, const uint32_t *rbase, void *raw, void *rows,
-                        uint32_t *pcnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) {
+hipError_t prk_row_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
+                        const uint32_t *route, int32_t height, void *work, const uint32_t *sbase,
+                        const uint32_t *rbase, void *raw, void *rows, uint32_t *pcnt, uint32_t *rcnt, uint32_t *err,
+                        hipStream_t s) {
     if (total == 0 || nlist == 0) return hipSuccess;
     prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
     hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
@@ -4902,10 +5223,10 @@ hipError_t prk_row_walk(const void *records, uint32_t total, const uint32_t *lsc
     if (e != hipSuccess) return e;
     const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
     if (raw)
-        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, lscan, nlist, height, sbase, rbase,
+        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, lscan, nlist, route, height, sbase, rbase,
                            reinterpret_cast<prk::PairRaw *>(raw), reinterpret_cast<int2 *>(rows), pcnt, rcnt, err);
     else
-        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, lscan, nlist, height, sbase, rbase,
+        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, lscan, nlist, route, height, sbase, rbase,
                            (prk::PairRaw *)nullptr, (int2 *)nullptr, pcnt, rcnt, err);
     return hipGetLastError();
 }
@@ -4943,6 +5264,76 @@ hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hip
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_adv_next, dim3((total + 255) / 256), dim3(256), 0, s,
                        reinterpret_cast<const prk::ObjEdge *>(work), total, next_out);
+    return hipGetLastError();
+}
+
+// The record calls' workgroup walk (k_adv_walk_wg, k_span_walk_wg,
+// k_row_walk_wg).  prk_adv_wg_lcap: the largest slot class the current device
+// grants them as dynamic LDS (1022, 510 or 254; 0: none, every list stays on
+// the thread walk).  `route` words: 0 the thread walk, c + 1 slot class c.
+uint32_t prk_adv_wg_lcap(void) {
+    static std::atomic<int> cap[64];  // per device: 0 unknown, else cap + 1
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    int c = cap[dev].load();
+    if (c == 0) {
+        c = 1;
+        const void *fn[5] = {reinterpret_cast<const void *>(&prk::k_adv_walk_wg),
+                             reinterpret_cast<const void *>(&prk::k_span_walk_wg<true>),
+                             reinterpret_cast<const void *>(&prk::k_span_walk_wg<false>),
+                             reinterpret_cast<const void *>(&prk::k_row_walk_wg<true>),
+                             reinterpret_cast<const void *>(&prk::k_row_walk_wg<false>)};
+        for (uint32_t k = prk::kSlotCapLds; k >= 254; k = (k + 2) / 2 - 2) {
+            const size_t bytes = prk::slot_lds_bytes(k);
+            bool ok = true;
+            for (int q = 0; q < 5 && ok; ++q)
+                ok = hipFuncSetAttribute(fn[q], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+            if (ok) {
+                c = (int)k + 1;
+                break;
+            }
+            (void)hipGetLastError();
+        }
+        cap[dev].store(c);
+    }
+    return (uint32_t)(c - 1);
+}
+// The nl lists lists[0, nl) of slot class lcap, a workgroup each, after the
+// call's import (prk_adv_walk / prk_span_walk / prk_row_walk, whose thread
+// kernels skip them).  kind 0: prk_advance_edge_lists; 1: prk_span_records
+// (cnt: the lists' pairs); 2: prk_row_records (cnt, rcnt: pairs and rows).
+// raw == nullptr: the counting variants.  err as the thread kernels'.
+hipError_t prk_adv_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint32_t nl, const uint32_t *lscan,
+                           int32_t height, void *work, const uint32_t *sbase, const uint32_t *rbase, void *raw,
+                           int32_t *prow, void *rows, uint32_t *cnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) {
+    if (nl == 0) return hipSuccess;
+    if (lcap == 0 || lcap > prk_adv_wg_lcap()) return hipErrorInvalidValue;
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    const dim3 grid(nl), block(prk::slot_threads(lcap));
+    const size_t bytes = prk::slot_lds_bytes(lcap);
+    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(raw);
+    switch (kind) {
+        case 0:
+            hipLaunchKernelGGL(prk::k_adv_walk_wg, grid, block, bytes, s, w, lscan, lists, lcap, height, err);
+            break;
+        case 1:
+            if (raw)
+                hipLaunchKernelGGL(prk::k_span_walk_wg<true>, grid, block, bytes, s, w, lscan, lists, lcap, height,
+                                   sbase, pr, prow, cnt, err);
+            else
+                hipLaunchKernelGGL(prk::k_span_walk_wg<false>, grid, block, bytes, s, w, lscan, lists, lcap, height,
+                                   sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, cnt, err);
+            break;
+        case 2:
+            if (raw)
+                hipLaunchKernelGGL(prk::k_row_walk_wg<true>, grid, block, bytes, s, w, lscan, lists, lcap, height,
+                                   sbase, rbase, pr, reinterpret_cast<int2 *>(rows), cnt, rcnt, err);
+            else
+                hipLaunchKernelGGL(prk::k_row_walk_wg<false>, grid, block, bytes, s, w, lscan, lists, lcap, height,
+                                   sbase, rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, cnt, rcnt, err);
+            break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

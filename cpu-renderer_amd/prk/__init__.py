@@ -93,6 +93,7 @@ _SIGS = {
     "prk_download_winners": (C.c_int, [C.c_void_p, C.c_void_p]),
     "prk_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
     "prk_debug_walk_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]),
+    "prk_debug_list_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]),
     "prk_set_tile": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "prk_construct_sphere": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_uint32)]),
@@ -710,6 +711,15 @@ class Renderer:
         sizes = [v - (1 << 32) if v >> 31 else v for v in out[9:12]]  # (int32_t bits)
         return dict(slots=tuple(out[0:5]), huge_lds=out[5], huge_mem=out[6], wave=out[7], sized_huge=out[8],
                     most=sizes[0], rows=sizes[1], ents=sizes[2])
+
+    def list_routes(self):
+        """Which walk the lists of the last advance_edge_lists / span_records
+        / row_records call took (prk_debug_list_routes): thread (one GPU
+        thread a list, empty lists among them) and slots (a workgroup a list,
+        per LDS slot class of 62 / 126 / 254 / 510 / 1022 entries)."""
+        out = (C.c_uint32 * 6)()
+        _check("prk_debug_list_routes", self._L.prk_debug_list_routes(self._h, out, 6))
+        return dict(thread=out[0], slots=tuple(out[1:6]))
 
     def stats(self):
         s = abi.PrkStats()

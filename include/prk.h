@@ -455,6 +455,13 @@ int prk_debug_counters(prk_context *ctx, uint64_t *out, int32_t n);
  * object's most active edges, rows and list entries as read back (int32_t
  * bits; INT32_MAX: past the histogram).  n <= 12 words are written. */
 int prk_debug_walk_routes(prk_context *ctx, uint32_t *out, int32_t n);
+/* Debug/test: which walk the lists of the most recent prk_advance_edge_lists,
+ * prk_span_records or prk_row_records call were given, from the host's
+ * bookkeeping (no kernel reports in).  out[0]: lists walked by one GPU thread
+ * each (empty lists among them); out[1..5]: lists walked by a workgroup each,
+ * in the slot classes of 62 / 126 / 254 / 510 / 1022 entries.  A refused call
+ * leaves the words of the call before it.  n <= 6 words are written. */
+int prk_debug_list_routes(prk_context *ctx, uint32_t *out, int32_t n);
 
 /* Test: the raster kernels divide several values by one divisor through a
  * shared reciprocal; this checks n hashed (x, d) draws and
@@ -605,22 +612,29 @@ int prk_edge_records(prk_context *ctx, int32_t geometry, uint32_t first_tri, uin
  * non-decreasing, 0 <= YMin <= YMax, Left 0 or 1: what FillEdgeTable's
  * MergeSort and prk_edge_records leave): there the sorted insertion cursor
  * inserts what the reference's whole-list scan inserts, in its order.  Any
- * other list goes to prk_advance_edge_records.  One GPU thread walks a list,
- * over at most `height` rows.
+ * other list goes to prk_advance_edge_records.  A list is walked over at
+ * most `height` rows, by one GPU thread -- or, when that thread's walk would
+ * be long (its steps, below, reach a measured threshold; PRK_ADV_WG_MIN_STEPS
+ * in the environment replaces it) and the list never links
+ * more than 1022 edges at once, by one workgroup with the list in LDS: a mesh
+ * passed as ONE list.  A batch may mix both; the results are the same words
+ * (prk_debug_list_routes tells which walk a call's lists took).
  *
  * Synchronous; needs no render target, records no draw, touches no recorded
  * draw and no prk_stats; frames in flight finish first.  PRK_ERR_ARG: a NULL
- * context, NULL counts with list_count > 0, NULL records or records_out with
- * a non-zero total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside the
- * sorted rule.  PRK_ERR_LIMIT: the total passes 31 bits, height > 65536, or
- * a list's walk is too long for one thread: its edge-rows, the sum over its
- * edges of max(0, min(YMax, height) - YMin), plus its insertion scans, for
- * every edge the edges still linked when it is inserted (the earlier ones
- * whose YMax is not below its YMin), pass 2^21 steps.  The cap keeps a call
- * from holding the GPU for seconds (a thread walks 1.6 M edge-rows a second);
- * it is no tuned number.  list_count == 0 or a zero total: PRK_OK.  On any
- * error nothing is written to records_out or next_out.  The spans the same
- * walk queues on its way: prk_span_records (below). */
+ * context, NULL counts with list_count > 0, NULL records or records_out with a
+ * non-zero total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside the sorted
+ * rule.  PRK_ERR_LIMIT: the total passes 31 bits, height > 65536, or a list's
+ * walk is too long: its edge-rows, the sum over its edges of max(0, min(YMax,
+ * height) - YMin), pass 2^21 -- or, for a list one thread walks (in particular
+ * every list that links more than 1022 edges at once), its edge-rows plus its
+ * insertion scans, for every edge the edges still linked when it is inserted
+ * (the earlier ones whose YMax is not below its YMin), pass 2^21 steps; the
+ * workgroup walk inserts a row's edges as one batch and has no such scan.  The
+ * cap keeps a call from holding the GPU for seconds (a thread walks 1.6 M
+ * edge-rows a second); it is no tuned number.  list_count == 0 or a zero
+ * total: PRK_OK.  On any error nothing is written to records_out or next_out.  The
+ * spans the same walk queues on its way: prk_span_records (below). */
 int prk_advance_edge_lists(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
                            uint32_t list_count, int32_t height, prk_edge *records_out, int32_t *next_out);
 
@@ -648,22 +662,22 @@ int prk_advance_edge_lists(prk_context *ctx, const prk_edge *records, const uint
  * with spans and a `capacity` (in spans) below the total the call returns
  * PRK_ERR_ARG with span_counts and *total_out written and `spans` untouched.
  *
- * Only lists inside the sorted rule are taken, and one GPU thread walks a
- * list: ConstructSphere as one list is slower here than a host walk would
- * be, as it is for prk_advance_edge_lists (serving long lists from the
- * parallel slot walks needs those walks to step every field).
+ * Only lists inside the sorted rule are taken.  A thread or a workgroup
+ * walks a list, as in prk_advance_edge_lists: ConstructSphere as one list is
+ * a workgroup's (DESIGN §4.4.6 has its times beside a host walk's).
  *
  * Synchronous; needs no render target, records no draw, touches no recorded
  * draw and no prk_stats; frames in flight finish first.  PRK_ERR_ARG: a NULL
  * context or total_out, NULL counts with list_count > 0, NULL records with a
- * non-zero record total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside
- * the sorted rule.  PRK_ERR_LIMIT: the record total or list_count passes 31
- * bits, height > 65536, a list's walk passes prk_advance_edge_lists' 2^21
- * steps, or the batch's span slots pass 31 bits (a list gets half its
- * edge-rows, the sum over its edges of max(0, min(YMax, height) - YMin): a
- * span uses up one row of each of two edges).  list_count == 0 or no
- * records: PRK_OK, *total_out = 0, span_counts zero.  On any error but the
- * short capacity nothing is written to spans or span_counts. */
+ * non-zero record total, height < 0.  PRK_ERR_UNSUPPORTED: a list outside the
+ * sorted rule.  PRK_ERR_LIMIT: the record total or list_count passes 31 bits,
+ * height > 65536, a list's walk passes prk_advance_edge_lists' 2^21 cap (its
+ * edge-rows; with its insertion scans where a thread walks it), or the batch's
+ * span slots pass 31 bits (a list gets half its edge-rows, the sum over its
+ * edges of max(0, min(YMax, height) - YMin): a span uses up one row of each of
+ * two edges).  list_count == 0 or no records: PRK_OK, *total_out = 0,
+ * span_counts zero.  On any error but the short capacity nothing is written to
+ * spans or span_counts. */
 int prk_span_records(prk_context *ctx, const prk_edge *records, const uint32_t *counts,
                      uint32_t list_count, int32_t height,
                      prk_span *spans, uint64_t capacity,
@@ -681,27 +695,28 @@ typedef struct prk_row { int32_t RowIndex; uint32_t EdgeCount; } prk_row;
 /* The row work records DrawModelOptimizedLines queues for the lists of a batch
  * (projekt.cpp:3362-3613: one buffer_line_render_work a row, followed by its
  * EdgeCount thread_edge_info pairs), from the same walk on the GPU: records /
- * counts / height are the packed batch of prk_advance_edge_lists, all
- * pointers host memory; the walk's rows, the sorted rule and the 2^21-step
- * cap are that call's.  For list o RowIndex runs over [YMin[0], min(max YMax,
- * height)), ascending, and every row the walk reaches emits one prk_row whose
- * EdgeCount is the number of pairs the walk meets on it -- 0 for a row with
- * one listed edge (a one-edge list emits nothing else; 3509-3516, 3604-3609).
- * A row on which the list is empty after the head expiry (3467-3472, where
- * the reference dereferences NULL) emits no record: a row of the range is
- * emitted if and only if some edge of the list has YMin <= RowIndex < YMax.
- * Pair k of a row has Left* = CurrentEdgeInList and Right* = NextEdgeInList
- * as they stand before the pair's step (3523-3542 precede 3546-3564),
- * whatever their X order.  List o's rows are packed at rows[row_counts[0] +
- * ... + row_counts[o - 1]]; `pairs` holds every pair of the batch in queue
- * order (lists in order, rows ascending, a row's pairs in list order), so row
- * r's pairs start at the sum of EdgeCount over the batch's earlier rows.
- * Pair k of the batch holds the 24 values of span k of prk_span_records on
- * the same input, re-ordered, and the allowance is that call's: where the
- * expected MinColor or MinNormal word is a NaN the word here is a NaN of any
- * sign and payload.  Every other word, RowIndex and EdgeCount included, is
- * equal.  row_counts (list_count words, or NULL) gets every list's number of
- * rows, *row_total_out their sum, *pair_total_out the batch's pairs.
+ * counts / height are the packed batch of prk_advance_edge_lists, all pointers
+ * host memory; the walk's rows, the sorted rule, the choice between a thread
+ * and a workgroup per list and the 2^21 cap are that call's.  For list o
+ * RowIndex runs over [YMin[0], min(max YMax, height)), ascending, and every
+ * row the walk reaches emits one prk_row whose EdgeCount is the number of
+ * pairs the walk meets on it -- 0 for a row with one listed edge (a one-edge
+ * list emits nothing else; 3509-3516, 3604-3609).  A row on which the list is
+ * empty after the head expiry (3467-3472, where the reference dereferences
+ * NULL) emits no record: a row of the range is emitted if and only if some
+ * edge of the list has YMin <= RowIndex < YMax.  Pair k of a row has Left* =
+ * CurrentEdgeInList and Right* = NextEdgeInList as they stand before the
+ * pair's step (3523-3542 precede 3546-3564), whatever their X order.  List o's
+ * rows are packed at rows[row_counts[0] + ... + row_counts[o - 1]]; `pairs`
+ * holds every pair of the batch in queue order (lists in order, rows
+ * ascending, a row's pairs in list order), so row r's pairs start at the sum
+ * of EdgeCount over the batch's earlier rows.  Pair k of the batch holds the
+ * 24 values of span k of prk_span_records on the same input, re-ordered, and
+ * the allowance is that call's: where the expected MinColor or MinNormal word
+ * is a NaN the word here is a NaN of any sign and payload.  Every other word,
+ * RowIndex and EdgeCount included, is equal. row_counts (list_count words, or
+ * NULL) gets every list's number of rows, *row_total_out their sum,
+ * *pair_total_out the batch's pairs.
  *
  * Calling pattern: rows == NULL and pairs == NULL size -- row_counts and both
  * totals are written by a counting walk that takes no row or pair memory;
