@@ -58,6 +58,7 @@ hipError_t prk_launch_raster(const prk::FrameParams *, int, const uint32_t *, co
                              hipStream_t, hipStream_t);
 hipError_t prk_walk_select_bytes(uint32_t, size_t *);
 hipError_t prk_selftest_div_launch(uint32_t n, uint64_t seed, unsigned long long *bad, hipStream_t s);
+hipError_t prk_selftest_ops_launch(int32_t op, uint32_t n, const uint32_t *in, uint32_t *out, hipStream_t s);
 hipError_t prk_obj_tables(const void *, uint32_t, uint32_t, uint32_t, void *, uint32_t *, uint32_t *, const uint32_t *,
                           const uint32_t *, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
 hipError_t prk_list_prep(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *,
@@ -470,19 +471,59 @@ int prk_device_count(int *out) {
 
 // Self-test of the shared-divisor quotients against the compiler's division
 // (prk.h).  Runs on `device`, synchronously.
-int prk_selftest_div(int32_t device, uint32_t n, uint64_t seed, uint64_t *mismatches) {
+int prk_selftest_div_paths(int32_t device, uint32_t n, uint64_t seed, uint64_t *mismatches, uint32_t fast_waves[2]) {
     if (!mismatches || device < 0) return PRK_ERR_ARG;
     PRK_TRY(hipSetDevice(device));
     unsigned long long *d = nullptr;
-    PRK_TRY(hipMalloc(&d, sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, sizeof(unsigned long long));
+    PRK_TRY(hipMalloc(&d, 3 * sizeof(unsigned long long)));
+    hipError_t e = hipMemset(d, 0, 3 * sizeof(unsigned long long));
     if (e == hipSuccess) e = prk_selftest_div_launch(n, seed, d, nullptr);
-    unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
+    unsigned long long h[3] = {0, 0, 0};
+    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return status_of(e);
-    *mismatches = h;
+    *mismatches = h[0];
+    if (fast_waves) {
+        fast_waves[0] = (uint32_t)h[1];
+        fast_waves[1] = (uint32_t)h[2];
+    }
     return PRK_OK;
+}
+int prk_selftest_div(int32_t device, uint32_t n, uint64_t seed, uint64_t *mismatches) {
+    return prk_selftest_div_paths(device, n, seed, mismatches, nullptr);
+}
+
+// One device primitive on the caller's words (prk.h).  Runs on `device`,
+// synchronously; the kernel reads and writes whole 4 x n buffers, so an input
+// the op does not read is zeros.
+int prk_selftest_ops(int32_t device, int32_t op, uint32_t n, const uint32_t *a, const uint32_t *b,
+                     const uint32_t *c, const uint32_t *d, uint32_t *out0, uint32_t *out1, uint32_t *out2,
+                     uint32_t *fast) {
+    static const uint8_t kInputs[PRK_OP_COUNT] = {2, 2, 4, 4, 4, 4, 4, 2, 1, 1, 3, 3, 1,
+                                                  1, 1, 1, 2, 2, 1, 2, 1, 1, 2, 1, 3, 3};
+    if (device < 0 || op < 0 || op >= PRK_OP_COUNT || n > (1u << 24) || !out0) return PRK_ERR_ARG;
+    const uint32_t *in[4] = {a, b, c, d};
+    for (int k = 0; k < kInputs[op]; ++k)
+        if (!in[k]) return PRK_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    if (n == 0) return PRK_OK;
+    PRK_TRY(hipSetDevice(device));
+    const size_t bytes = (size_t)n * sizeof(uint32_t);
+    uint32_t *din = nullptr, *dout = nullptr;
+    PRK_TRY(hipMalloc(&din, 4 * bytes));
+    hipError_t e = hipMalloc(&dout, 4 * bytes);
+    if (e == hipSuccess) e = hipMemset(din, 0, 4 * bytes);
+    for (int k = 0; k < kInputs[op] && e == hipSuccess; ++k)
+        e = hipMemcpy(din + (size_t)k * n, in[k], bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = prk_selftest_ops_launch(op, n, din, dout, nullptr);
+    uint32_t *outs[4] = {out0, out1, out2, fast};
+    for (int k = 0; k < 4 && e == hipSuccess; ++k)
+        if (outs[k]) e = hipMemcpy(outs[k], dout + (size_t)k * n, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(din);
+    if (dout) (void)hipFree(dout);
+    return status_of(e);
 }
 
 int prk_create(int device, prk_context **out) {

@@ -266,8 +266,11 @@ __device__ __forceinline__ void normalize_rcp(float &x, float &y, float &z) {
 // per quotient.  div_all takes that path when every lane of the wave is in
 // range (a wave-uniform branch, so the quotients stay one straight-line,
 // interleaved block) and the plain divisions otherwise: every quotient is the
-// correctly rounded x / d, bit for bit (prk_selftest_div,
-// tests/test_gpu_parity.py::test_shared_divisor_exact).
+// correctly rounded x / d, bit for bit: tests/test_gpu_arith.py holds both
+// paths to IEEE quotients computed on the host (prk_selftest_ops, with whole
+// waves inside the range, waves with one lane outside it, and operands at the
+// very bounds), and test_shared_divisor_exact to the compiler's own x / d over
+// 2^24 hashed draws (prk_selftest_div_paths, half of whose waves take this path).
 #ifndef PRK_SHARED_DIV
 #define PRK_SHARED_DIV 1
 #endif
@@ -289,9 +292,10 @@ __device__ __forceinline__ float div_fast(const DivBy &s, float x) {
     const float f4 = __builtin_fmaf(s.nd, m1, x);
     return __builtin_fmaf(f4, s.r, m1);
 }
-// x[k] / d for every k.
+// x[k] / d for every k.  True when the wave took the shared reciprocal (the
+// raster kernels ignore it; prk_selftest_ops reports it).
 template <int K>
-__device__ __forceinline__ void div_all(float d, float (&x)[K]) {
+__device__ __forceinline__ bool div_all(float d, float (&x)[K]) {
     if (PRK_SHARED_DIV) {
         // NaN / inf / large numerators fail the sum, zero and tiny ones the min
         float sum = fabsf(x[0]), mn = fabsf(x[0]);
@@ -306,11 +310,12 @@ __device__ __forceinline__ void div_all(float d, float (&x)[K]) {
             const DivBy s = div_by(d);
 #pragma unroll
             for (int k = 0; k < K; ++k) x[k] = div_fast(s, x[k]);
-            return;
+            return true;
         }
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) x[k] = x[k] / d;
+    return false;
 }
 
 // d / F (the focal length divide of UnprojectVertex); F is uniform, so its
@@ -326,7 +331,8 @@ __device__ __forceinline__ float div_focal(const FrameParams &fp, float d) {
 // sqrt (denormals on) is v_sqrt_f32 plus a one-ulp correction from the two
 // neighbours' residuals, wrapped in a 2^32 pre-scale for x < 2^-96 and a
 // zero / +inf pass-through; in this range both wrappers are identities, so
-// this is the same value bit for bit (prk_selftest_div checks it).
+// this is the same value bit for bit (tests/test_gpu_arith.py: against the
+// host's IEEE sqrt, and prk_selftest_div_paths against the compiler's sqrtf).
 __device__ __forceinline__ float sqrt_mid(float x) {
     const float s = __builtin_amdgcn_sqrtf(x);
     const float dn = __int_as_float(__float_as_int(s) - 1), up = __int_as_float(__float_as_int(s) + 1);
@@ -344,7 +350,8 @@ __device__ __forceinline__ float sqrt_mid(float x) {
 #ifndef PRK_FAST_NORM
 #define PRK_FAST_NORM 1
 #endif
-__device__ __forceinline__ void normalize_div(float &x, float &y, float &z) {
+// True when the wave took the fast path (as div_all).
+__device__ __forceinline__ bool normalize_div(float &x, float &y, float &z) {
     const float d = (x * x + y * y) + z * z;
     if (PRK_SHARED_DIV && PRK_FAST_NORM) {
         const float mn = fminf(fminf(fabsf(x), fabsf(y)), fabsf(z));
@@ -354,7 +361,7 @@ __device__ __forceinline__ void normalize_div(float &x, float &y, float &z) {
             x = div_fast(s, x);
             y = div_fast(s, y);
             z = div_fast(s, z);
-            return;
+            return true;
         }
     }
     const float len = sqrtf(d);
@@ -363,6 +370,7 @@ __device__ __forceinline__ void normalize_div(float &x, float &y, float &z) {
     x = q[0];
     y = q[1];
     z = q[2];
+    return false;
 }
 
 // _mm_mullo_epi16/_mm_mulhi_epi16 pitch multiply (projekt.cpp:1916-1920).

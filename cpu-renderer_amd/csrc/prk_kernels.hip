@@ -23,6 +23,7 @@
 //            a pixel and shades only their winning fragments.
 
 #include "prk_device.h"
+#include "../../include/prk.h"  // PRK_OP_* (k_selftest_ops)
 
 // Diagnostic builds only (tools/diag): 1 = skip the shading sweep, 2 = skip
 // work items, 4 = skip the AET rows (setup only), 8 = skip the shading sweep's
@@ -1828,10 +1829,16 @@ PRK_INST(MODE_SC_PHONG, true)
 #undef PRK_INST
 
 // Self-test of the shared-divisor quotients (prk_device.h DivBy): thread i
-// draws (x, d) from a hash of (seed, i) — random signs, mantissas and
-// exponents in [-64, 64) (both inside and outside the fast range), every 16th
-// x zero — and counts quotients and normalisations that differ in any bit
-// from the compiler's own x / d.
+// draws (x, d) from a hash of (seed, i) and counts quotients and
+// normalisations that differ in any bit from the compiler's own x / d.  The
+// class of a draw goes by the wave (i >> 6), because div_all and
+// normalize_div choose their path per wave.  Even waves: random signs,
+// mantissas and exponents in [-64, 64) (inside and outside the fast range),
+// every 16th x and every 32nd third component zero, so these waves take the
+// plain divisions.  Odd waves: every lane inside the fast range (|d| in
+// [2^-32, 2^32), |x| in [2^-64, 2^32), components in [2^-12, 2^28)) and no
+// zero, so they take the shared reciprocal.  bad[1] / bad[2] count the waves
+// whose quotient / normalisation took it.
 __device__ __forceinline__ uint32_t st_hash(uint64_t v) {
     v ^= v >> 33; v *= 0xff51afd7ed558ccdull; v ^= v >> 33; v *= 0xc4ceb9fe1a85ec53ull; v ^= v >> 33;
     return (uint32_t)v;
@@ -1843,20 +1850,31 @@ __device__ __forceinline__ float st_float(uint32_t h, uint32_t e) {
 __global__ void k_selftest_div(uint32_t n, uint64_t seed, unsigned long long *bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const bool in_range = ((i >> 6) & 1u) != 0u;
     const uint64_t k = seed * 0x9E3779B97F4A7C15ull + 4ull * i;
     const uint32_t h0 = st_hash(k), h1 = st_hash(k + 1), h2 = st_hash(k + 2), h3 = st_hash(k + 3);
-    const float x = (i & 15u) == 7u ? ((h0 & 1u) ? -0.0f : 0.0f) : st_float(h0, h2);
-    const float d = st_float(h1, h2 >> 8);
+    float x, d;
+    if (in_range) {
+        x = st_float(h0, (h2 & 127u) % 96u);          // exponents [-64, 32)
+        d = st_float(h1, 32u + ((h2 >> 8) & 63u));    // exponents [-32, 32)
+    } else {
+        x = (i & 15u) == 7u ? ((h0 & 1u) ? -0.0f : 0.0f) : st_float(h0, h2);
+        d = st_float(h1, h2 >> 8);
+    }
     const volatile float dv = d;  // the plain quotient sees an opaque divisor
     float q1[1] = {x};
-    div_all(d, q1);
+    const bool fq = div_all(d, q1);
     const float q0 = x / dv;
     unsigned long long b = __float_as_uint(q0) != __float_as_uint(q1[0]) ? 1ull : 0ull;
-    // normalisation of a vector of three draws (exponents within +-24)
-    const float a0 = st_float(h0, 52u + (h3 & 47u)), a1 = st_float(h1, 52u + ((h3 >> 8) & 47u));
-    const float a2 = (i & 31u) == 3u ? 0.0f : st_float(h2, 52u + ((h3 >> 16) & 47u));
+    // normalisation of a vector of three draws (even waves: exponents in
+    // [-12, 4) and [20, 36); odd waves [-12, 28): a squared length below 2^58)
+    const uint32_t e0 = in_range ? (h3 & 63u) % 40u : (h3 & 47u);
+    const uint32_t e1 = in_range ? ((h3 >> 8) & 63u) % 40u : ((h3 >> 8) & 47u);
+    const uint32_t e2 = in_range ? ((h3 >> 16) & 63u) % 40u : ((h3 >> 16) & 47u);
+    const float a0 = st_float(h0, 52u + e0), a1 = st_float(h1, 52u + e1);
+    const float a2 = (!in_range && (i & 31u) == 3u) ? 0.0f : st_float(h2, 52u + e2);
     float n0 = a0, n1 = a1, n2 = a2;
-    normalize_div(n0, n1, n2);
+    const bool fn = normalize_div(n0, n1, n2);
     const volatile float lv = sqrtf((a0 * a0 + a1 * a1) + a2 * a2);
     const float len = lv;
     if (__float_as_uint(n0) != __float_as_uint(a0 / len) || __float_as_uint(n1) != __float_as_uint(a1 / len) ||
@@ -1869,6 +1887,110 @@ __global__ void k_selftest_div(uint32_t n, uint64_t seed, unsigned long long *ba
     const float sx = sv;
     if (__float_as_uint(sqrt_mid(sx)) != __float_as_uint(sqrtf(sv))) b += 1ull << 32;
     if (b) atomicAdd(bad, b);
+    if ((i & 63u) == 0u) {
+        if (fq) atomicAdd(bad + 1, 1ull);
+        if (fn) atomicAdd(bad + 2, 1ull);
+    }
+}
+
+// prk_selftest_ops (prk.h): element i of the caller's words through one
+// primitive of prk_device.h.  The words are read through volatile pointers,
+// so no operand is known at compile time; the op is uniform.
+template <int K>
+__device__ __forceinline__ void st_div_all(float a, float b, float c, float d, uint32_t (&o)[3], uint32_t &fast) {
+    const float num[3] = {a, b, c};
+    float q[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) q[k] = num[k % 3];
+    fast = div_all(d, q) ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        if (k < 3) o[k] = __float_as_uint(q[k]);
+        else if (__float_as_uint(q[k]) != o[k % 3]) fast |= 2u;
+    }
+}
+__global__ void k_selftest_ops(int32_t op, uint32_t n, const uint32_t *pa, const uint32_t *pb, const uint32_t *pc,
+                               const uint32_t *pd, uint32_t *out /* 4 x n: out0, out1, out2, fast */) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t wa = ((const volatile uint32_t *)pa)[i], wb = ((const volatile uint32_t *)pb)[i];
+    const uint32_t wc = ((const volatile uint32_t *)pc)[i], wd = ((const volatile uint32_t *)pd)[i];
+    const float a = __uint_as_float(wa), b = __uint_as_float(wb), c = __uint_as_float(wc), d = __uint_as_float(wd);
+    uint32_t o[3] = {0u, 0u, 0u}, fast = 0u;
+    switch (op) {
+    case PRK_OP_DIV: o[0] = __float_as_uint(a / b); break;
+    case PRK_OP_DIV_ALL1: {
+        float q[1] = {a};
+        fast = div_all(b, q) ? 1u : 0u;
+        o[0] = __float_as_uint(q[0]);
+        break;
+    }
+    case PRK_OP_DIV_ALL3: st_div_all<3>(a, b, c, d, o, fast); break;
+    case PRK_OP_DIV_ALL4: st_div_all<4>(a, b, c, d, o, fast); break;
+    case PRK_OP_DIV_ALL5: st_div_all<5>(a, b, c, d, o, fast); break;
+    case PRK_OP_DIV_ALL7: st_div_all<7>(a, b, c, d, o, fast); break;
+    case PRK_OP_DIV_ALL8: st_div_all<8>(a, b, c, d, o, fast); break;
+    case PRK_OP_DIV_FOCAL: {
+        FrameParams fp;
+        fp.sh.f_pow2 = 0;
+        fp.sh.F = b;
+        fp.sh.InvF = 0.0f;
+        o[0] = __float_as_uint(div_focal(fp, a));
+        break;
+    }
+    case PRK_OP_SQRT: o[0] = __float_as_uint(sqrtf(a)); break;
+    case PRK_OP_SQRT_MID: o[0] = __float_as_uint(sqrt_mid(a)); break;
+    case PRK_OP_NORMALIZE_DIV:
+    case PRK_OP_NORMALIZE_RCP: {
+        float x = a, y = b, z = c;
+        if (op == PRK_OP_NORMALIZE_DIV) fast = normalize_div(x, y, z) ? 1u : 0u;
+        else normalize_rcp(x, y, z);
+        o[0] = __float_as_uint(x); o[1] = __float_as_uint(y); o[2] = __float_as_uint(z);
+        break;
+    }
+    case PRK_OP_CVTT_S32: o[0] = (uint32_t)cvtt_s32(a); break;
+    case PRK_OP_ROUND_S32: o[0] = (uint32_t)round_s32(a); break;
+    case PRK_OP_ROUND_U32: o[0] = round_u32(a); break;
+    case PRK_OP_CVT_RNE_S32: o[0] = (uint32_t)cvt_rne_s32(a); break;
+    case PRK_OP_MINPS: o[0] = __float_as_uint(minps(a, b)); break;
+    case PRK_OP_MAXPS: o[0] = __float_as_uint(maxps(a, b)); break;
+    case PRK_OP_CLAMP01: o[0] = __float_as_uint(clamp01(a)); break;
+    case PRK_OP_MUL16_TRICK: o[0] = (uint32_t)mul16_trick((int32_t)wa, (int32_t)wb); break;
+    case PRK_OP_U8_UNIT: o[0] = __float_as_uint(u8_unit(wa)); break;
+    case PRK_OP_ZKEY:
+        o[0] = zkey(a);
+        o[1] = __float_as_uint(zkey_z(o[0]));
+        break;
+    case PRK_OP_PAIR_TAG:
+    case PRK_OP_TAG_PAIR: {
+        const uint32_t low = op == PRK_OP_PAIR_TAG ? pair_tag(wa, wb != 0u) : wa;
+        uint32_t j = 0u;
+        const bool is_pair = tag_pair(low, j);
+        const int at = op == PRK_OP_PAIR_TAG ? 1 : 0;
+        if (at) o[0] = low;
+        o[at] = is_pair ? j : 0u;
+        o[at + 1] = is_pair ? 1u : 0u;
+        break;
+    }
+    case PRK_OP_SPAN_ENDS:
+    case PRK_OP_SPAN_OFFSET: {
+        int32_t MinX = 0, MaxX = 0, XDiff = 0;
+        float XOffset = 0.0f;
+        const bool drawn = span_ends(a, b, (int32_t)(wc & 0x7FFFFFFFu), (wc >> 31) != 0u, MinX, MaxX, XDiff, XOffset);
+        if (op == PRK_OP_SPAN_ENDS) {
+            o[0] = drawn ? (uint32_t)MinX : 0u; o[1] = drawn ? (uint32_t)MaxX : 0u; o[2] = drawn ? (uint32_t)XDiff : 0u;
+        } else {
+            o[0] = __float_as_uint(XOffset);
+            o[1] = drawn ? 1u : 0u;
+        }
+        break;
+    }
+    default: break;
+    }
+    out[i] = o[0];
+    out[(size_t)n + i] = o[1];
+    out[2 * (size_t)n + i] = o[2];
+    out[3 * (size_t)n + i] = fast;
 }
 
 }  // namespace prk
@@ -1878,11 +2000,21 @@ __global__ void k_selftest_div(uint32_t n, uint64_t seed, unsigned long long *ba
 // ---------------------------------------------------------------------------
 extern "C" {
 
-// Shared-divisor self-test: *bad = quotient mismatches | normalisation
-// mismatches << 32 over n draws (device memory).
+// Shared-divisor self-test: bad[0] = quotient mismatches | normalisation
+// mismatches << 32 over n draws, bad[1], bad[2] = waves on the quotient's /
+// the normalisation's fast path (device memory, zeroed by the caller).
 hipError_t prk_selftest_div_launch(uint32_t n, uint64_t seed, unsigned long long *bad, hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_selftest_div, dim3((n + 255) / 256), dim3(256), 0, s, n, seed, bad);
+    return hipGetLastError();
+}
+
+// prk_selftest_ops: in = 4 x n words (a, b, c, d), out = 4 x n words (out0,
+// out1, out2, fast), device memory.
+hipError_t prk_selftest_ops_launch(int32_t op, uint32_t n, const uint32_t *in, uint32_t *out, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_selftest_ops, dim3((n + 255) / 256), dim3(256), 0, s, op, n, in, in + n,
+                       in + 2 * (size_t)n, in + 3 * (size_t)n, out);
     return hipGetLastError();
 }
 

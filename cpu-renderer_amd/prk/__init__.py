@@ -120,6 +120,10 @@ _SIGS = {
     "prk_get_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
     "prk_band_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "prk_selftest_div": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "prk_selftest_div_paths": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint32)]),
+    "prk_selftest_ops": (C.c_int, [C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "prk_comm_available": (C.c_int, []),
     "prk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "prk_comm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -256,6 +260,28 @@ def selftest_div(n=1 << 22, seed=1, device=0):
     out = C.c_uint64()
     _check("prk_selftest_div", lib().prk_selftest_div(device, n, seed, C.byref(out)))
     return out.value & 0xFFFFFFFF, out.value >> 32
+
+
+def selftest_div_paths(n=1 << 22, seed=1, device=0):
+    """prk_selftest_div_paths: selftest_div's two counts, and how many 64-lane
+    waves took the quotient's and the normalisation's shared-reciprocal path."""
+    out = C.c_uint64()
+    fast = (C.c_uint32 * 2)()
+    _check("prk_selftest_div_paths", lib().prk_selftest_div_paths(device, n, seed, C.byref(out), fast))
+    return out.value & 0xFFFFFFFF, out.value >> 32, int(fast[0]), int(fast[1])
+
+
+def selftest_ops(op, a, b=None, c=None, d=None, device=0):
+    """prk_selftest_ops: device primitive `op` (abi.PRK_OP_*) on uint32 word
+    arrays of one length.  Returns (out0, out1, out2, fast) as uint32 arrays;
+    element i is thread i of the launch, so 64 consecutive elements share a wave."""
+    ins = [None if x is None else np.ascontiguousarray(x, np.uint32) for x in (a, b, c, d)]
+    n = ins[0].shape[0]
+    assert all(x is None or x.shape == (n,) for x in ins)
+    outs = [np.zeros(n, np.uint32) for _ in range(4)]
+    _check("prk_selftest_ops", lib().prk_selftest_ops(device, int(op), n, *[_ptr(x) for x in ins],
+                                                       *[_ptr(x) for x in outs]))
+    return tuple(outs)
 
 
 def band_rows(height, rank, nranks):

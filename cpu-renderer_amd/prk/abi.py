@@ -30,6 +30,13 @@ PRK_SETUP_BITMAP = 2
 PRK_FILTER_NEAREST = 0   # the reference's sampling (projekt.cpp:1881-2032)
 PRK_FILTER_BILINEAR = 1  # extension (AVX semantics)
 
+# prk_selftest_ops: one device primitive of csrc/prk_device.h each
+(PRK_OP_DIV, PRK_OP_DIV_ALL1, PRK_OP_DIV_ALL3, PRK_OP_DIV_ALL4, PRK_OP_DIV_ALL5, PRK_OP_DIV_ALL7, PRK_OP_DIV_ALL8,
+ PRK_OP_DIV_FOCAL, PRK_OP_SQRT, PRK_OP_SQRT_MID, PRK_OP_NORMALIZE_DIV, PRK_OP_NORMALIZE_RCP, PRK_OP_CVTT_S32,
+ PRK_OP_ROUND_S32, PRK_OP_ROUND_U32, PRK_OP_CVT_RNE_S32, PRK_OP_MINPS, PRK_OP_MAXPS, PRK_OP_CLAMP01,
+ PRK_OP_MUL16_TRICK, PRK_OP_U8_UNIT, PRK_OP_ZKEY, PRK_OP_PAIR_TAG, PRK_OP_TAG_PAIR, PRK_OP_SPAN_ENDS,
+ PRK_OP_SPAN_OFFSET, PRK_OP_COUNT) = range(27)
+
 STATUS_NAMES = {
     PRK_OK: "PRK_OK", PRK_ERR_ARG: "PRK_ERR_ARG", PRK_ERR_UNSUPPORTED: "PRK_ERR_UNSUPPORTED",
     PRK_ERR_DEVICE: "PRK_ERR_DEVICE", PRK_ERR_NOMEM: "PRK_ERR_NOMEM",

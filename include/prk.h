@@ -468,6 +468,57 @@ int prk_debug_list_routes(prk_context *ctx, uint32_t *out, int32_t n);
  * normalisations on `device` against the compiler's own division, bit for
  * bit.  *mismatches = quotient mismatches | normalisation mismatches << 32. */
 int prk_selftest_div(int32_t device, uint32_t n, uint64_t seed, uint64_t *mismatches);
+/* The same, and how many 64-lane waves took the shared-reciprocal path:
+ * fast_waves[0] of the quotient, fast_waves[1] of the normalisation.  Odd
+ * waves draw every lane inside the fast range with non-zero numerators, so
+ * half of the waves take it by construction; even waves mix lanes, zeros and
+ * out-of-range exponents.  prk_selftest_div is this call without the counts. */
+int prk_selftest_div_paths(int32_t device, uint32_t n, uint64_t seed, uint64_t *mismatches, uint32_t fast_waves[2]);
+
+/* Test: one arithmetic primitive of the kernels (csrc/prk_device.h) on the
+ * caller's words.  Element i is computed by thread i of a 1-D launch of 256
+ * threads a block, so elements 64k .. 64k+63 share a wave.  Every value
+ * travels as a raw 32-bit word (float bits, or an integer).  a, b, c, d: host
+ * inputs of n words; PRK_ERR_ARG when one the op reads is NULL, the others
+ * are ignored.  out0..out2: host outputs of n words, out0 required, the
+ * others may be NULL (words an op does not produce are 0).  fast: n words or
+ * NULL: for DIV_ALL* and NORMALIZE_DIV bit 0 is set when the element's wave
+ * took the shared-reciprocal path, as reported by the function itself; 0 for
+ * every other op.  n <= 2^24.  A NaN result may differ from x86's in sign and
+ * payload.  tests/test_gpu_arith.py holds each op to a host reference written
+ * from the definitions (tests/arithref.py). */
+enum {
+    PRK_OP_DIV = 0,            /* out0 = a / b */
+    PRK_OP_DIV_ALL1 = 1,       /* div_all<1>: out0 = a / b */
+    PRK_OP_DIV_ALL3 = 2,       /* div_all<K>, K = 3, 4, 5, 7, 8 (every size the raster kernels use): the */
+    PRK_OP_DIV_ALL4 = 3,       /* numerators a, b, c, a, b, ... over the divisor d; out0..2 = a / d, b / d, */
+    PRK_OP_DIV_ALL5 = 4,       /* c / d; bit 1 of fast is set when a later quotient of the same numerator */
+    PRK_OP_DIV_ALL7 = 5,       /* differs from them in any bit */
+    PRK_OP_DIV_ALL8 = 6,
+    PRK_OP_DIV_FOCAL = 7,      /* out0 = div_focal of a by the focal length b (its not-a-power-of-two branch) */
+    PRK_OP_SQRT = 8,           /* out0 = sqrtf(a) */
+    PRK_OP_SQRT_MID = 9,       /* out0 = sqrt_mid(a) */
+    PRK_OP_NORMALIZE_DIV = 10, /* out0..2 = normalize_div(a, b, c) */
+    PRK_OP_NORMALIZE_RCP = 11, /* out0..2 = normalize_rcp(a, b, c) */
+    PRK_OP_CVTT_S32 = 12,      /* out0 = cvtt_s32(a) */
+    PRK_OP_ROUND_S32 = 13,
+    PRK_OP_ROUND_U32 = 14,
+    PRK_OP_CVT_RNE_S32 = 15,
+    PRK_OP_MINPS = 16,         /* out0 = minps(a, b) */
+    PRK_OP_MAXPS = 17,
+    PRK_OP_CLAMP01 = 18,       /* out0 = clamp01(a) */
+    PRK_OP_MUL16_TRICK = 19,   /* out0 = mul16_trick(a, b) */
+    PRK_OP_U8_UNIT = 20,       /* out0 = u8_unit(a), a in [0, 255] */
+    PRK_OP_ZKEY = 21,          /* out0 = zkey(a), out1 = zkey_z(out0) */
+    PRK_OP_PAIR_TAG = 22,      /* out0 = pair_tag(a, b != 0); out1, out2 = tag_pair(out0): j (0 when false), result */
+    PRK_OP_TAG_PAIR = 23,      /* out0, out1 = tag_pair(a): j (0 when false), result */
+    PRK_OP_SPAN_ENDS = 24,     /* span_ends(LX = a, RX = b, W = c & 0x7FFFFFFF, st = c >> 31): MinX, MaxX, XDiff */
+    PRK_OP_SPAN_OFFSET = 25,   /* the same call: out0 = XOffset, out1 = its result (false: MinX.. are 0 above) */
+    PRK_OP_COUNT = 26
+};
+int prk_selftest_ops(int32_t device, int32_t op, uint32_t n, const uint32_t *a, const uint32_t *b,
+                     const uint32_t *c, const uint32_t *d, uint32_t *out0, uint32_t *out1, uint32_t *out2,
+                     uint32_t *fast);
 
 /* The bound target (any pointer may be NULL) and the context's device and
  * own stream (a hipStream_t; prk_flush(ctx, NULL) runs on it). */

@@ -101,9 +101,15 @@ def test_span_path_sort_and_scan(gpu, n, bits):
 def test_shared_divisor_exact(gpu, seed):
     """The kernels' shared-reciprocal quotients (prk_device.h DivBy) equal the
     compiler's IEEE x / d bit for bit: 2^24 hashed draws with exponents on
-    both sides of the fast range, signed zeros, and normalisations."""
-    nq, nn = prk.selftest_div(n=1 << 24, seed=seed)
+    both sides of the fast range, signed zeros, and normalisations.  Half of
+    the waves (the odd ones) are drawn wholly inside the fast range and must
+    take the shared reciprocal: before prk_selftest_div_paths drew by the
+    wave, every wave held a zero numerator and none ever did."""
+    n = 1 << 24
+    nq, nn, fast_q, fast_n = prk.selftest_div_paths(n=n, seed=seed)
     assert (nq, nn) == (0, 0)
+    assert fast_q >= n // 64 // 4 and fast_n >= n // 64 // 4, (fast_q, fast_n)
+    assert prk.selftest_div(n=1 << 16, seed=seed) == (0, 0)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -140,6 +146,18 @@ def test_scalar_modes(gpu, phong, textured):
                            lights=scenes.LIGHTS_TWO, ambient=scenes.AMBIENT_TWO)
     run_both(s, semantics=abi.PRK_SEM_SCALAR, phong=phong,
              label="scalar phong=%d tex=%d" % (phong, textured))
+
+
+@pytest.mark.parametrize("tpo", [1, 8])
+@pytest.mark.parametrize("setup", [0, abi.PRK_SETUP_PHONG])
+def test_scalar_unclamped_colours(gpu, setup, tpo):
+    """The colour pack on unclamped values (DrawModel non-Phong, projekt.cpp:515
+    "no clamp"): vertex colours in [-2, 3], NaN, +-inf, beyond 2^31 and 2^63;
+    vertex-lit and interpolated unlit, per triangle and as objects of 8
+    (tests/test_oracle.py holds the oracle to pyref on the same scene)."""
+    import arithref
+    run_both(arithref.unclamped_colour_scene(), semantics=abi.PRK_SEM_SCALAR, phong=False, setup=setup,
+             tris_per_object=tpo, label="unclamped colours setup=%d tpo=%d" % (setup, tpo))
 
 
 def test_scalar_big_triangles(gpu):

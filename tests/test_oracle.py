@@ -381,3 +381,22 @@ def test_span_list_draw_equals_per_triangle_spans():
         row += 1
     got = O.render_spans(s, np.stack(spans))
     assert (got[1].view(np.uint32) == ref[1].view(np.uint32)).all() and (got[0] == ref[0]).all()
+
+
+@pytest.mark.parametrize("setup", [0, abi.PRK_SETUP_PHONG])
+def test_two_restatements_agree_unclamped_colours(setup):
+    """DrawModel's non-Phong colour store has no clamp (projekt.cpp:515,
+    520-523): RoundR32ToU32(F * 255) of vertex colours in [-2, 3], NaN, +-inf
+    and beyond 2^31 and 2^63 -- vertex-lit (setup 0, where the lighting's
+    clamps see them first) and interpolated unlit (PRK_SETUP_PHONG, where they
+    reach the pack raw).  pyref draws per triangle only; the oracle's objects
+    of 8 are what tests/test_gpu_parity.py holds the GPU to, and must differ
+    from the per-triangle frame only where a pixel's winner does."""
+    import arithref
+    s = arithref.unclamped_colour_scene()
+    o = O.render(s, semantics=abi.PRK_SEM_SCALAR, phong=False, setup=setup)
+    assert same(o, pyref.render(s, abi.PRK_SEM_SCALAR, False, setup=setup))
+    c = o[0][o[2] >= 0]
+    assert c.size > 1000 and np.unique(c).size > 500  # the frame is covered, with many colours
+    o8 = O.render(s, semantics=abi.PRK_SEM_SCALAR, phong=False, setup=setup, tris_per_object=8)
+    assert (o8[2] >= 0).sum() > 1000
