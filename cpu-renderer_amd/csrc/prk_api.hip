@@ -63,6 +63,12 @@ hipError_t prk_obj_tables(const void *, uint32_t, uint32_t, uint32_t, void *, ui
                           const uint32_t *, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
 hipError_t prk_list_prep(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *,
                          const void *, const uint32_t *, uint32_t, void *, void *, unsigned long long *, hipStream_t);
+hipError_t prk_list_prep_segs(const prk::FrameParams *, const void *, uint32_t, uint32_t, const uint32_t *, uint32_t,
+                              const uint32_t *, const void *, const uint32_t *, uint32_t, void *, void *,
+                              unsigned long long *, hipStream_t);
+hipError_t prk_list_tables(const void *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, const void *, uint32_t,
+                           uint32_t *, uint32_t *, hipStream_t);
+hipError_t prk_list_rule(const void *, uint32_t, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
 hipError_t prk_objtri_count(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
                             uint32_t, uint32_t *, unsigned long long *, hipStream_t);
 hipError_t prk_objtri_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
@@ -147,6 +153,16 @@ struct ObjDesc {
 struct ObjRun {
     uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
 };
+// prk_spans.hip's segments of a pass's batch edges and list-table sources
+// (passes that draw from record handles).
+struct PrepSeg {
+    uint64_t src;  // (the device address of its first record)
+    uint32_t e0, n, blk0, pad;
+};
+struct ListSrc {
+    const uint32_t *cnt, *flag;
+};
+constexpr uint32_t kPrepEdges = 256;         // prk_spans.hip: edges a workgroup of k_list_prep* takes
 constexpr uint32_t kObjWaveTris = 48;        // objects of this many triangles or more
 // ... and sorted edge lists (prk_draw_edge_lists) of this many edges or more
 // are large objects: the most edges the smallest large triangle object has
@@ -210,6 +226,19 @@ struct Texture {
     int32_t filter = 0;  // PRK_FILTER_*
 };
 
+// A record batch (prk_records_*): lists in prk_edge_records' packed layout,
+// kept in device memory.  The host keeps each list's edge count and whether
+// it takes the sorted walks (flush_spans routes by them) -- no records.
+struct Records {
+    void *rec = nullptr;      // the packed records, readable up to a multiple of 16 bytes
+    uint32_t *tab = nullptr;  // device: the counts (lists + 1 words, the last 0), then the sorted flags
+    std::vector<uint32_t> cnt, flag;
+    uint64_t total = 0;
+    bool live = false;
+    const uint32_t *d_cnt() const { return tab; }
+    const uint32_t *d_flag() const { return tab + cnt.size() + 1; }
+};
+
 int status_of(hipError_t e) {
     if (e == hipSuccess) return PRK_OK;
     static const bool trace = std::getenv("PRK_TRACE_HIP") != nullptr;  // diagnostics: name the HIP error
@@ -248,6 +277,10 @@ struct prk_context {
     // resources
     std::vector<Geometry> geoms;
     std::vector<Texture> texs;
+    // record batches by handle (a destroyed one keeps its slot, dead).  A
+    // prk_draw_records DrawRec: src_kind 4, geom the handle, geom_tri0 /
+    // tri_count its lists, src_off / src_n their records within the handle.
+    std::vector<Records> recs;
     std::vector<prk::DrawRec> draws;
     uint32_t pending_tris = 0;
     std::vector<prk_edge> pend_edges;  // prk_draw_edges input of the pending frame
@@ -357,6 +390,7 @@ struct prk_context {
             d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
             d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
+            d_ltab,  // a pass with handle draws: its lists' counts and flags (k_list_tables)
             d_rectab, d_reccnt, d_recout,  // prk_edge_records: its tables, counts and packed records
             d_spanout,                     // prk_span_records: its packed spans
             d_rowslot, d_rowcnt, d_rowscan, d_rowout;  // prk_row_records: its row slots, counts, scan, packed rows
@@ -371,7 +405,10 @@ struct prk_context {
         bool stage_busy = false;
         // host tables of the pass, kept until their asynchronous uploads ran
         std::vector<ObjRun> h_runs;
-        std::vector<uint32_t> h_big_gl, h_big_cap, h_k1src, h_lcnt;
+        std::vector<uint32_t> h_big_gl, h_big_cap, h_k1src, h_lcnt, h_lflag;
+        std::vector<PrepSeg> h_segs;     // a pass with handle draws: its batch edges' segments
+        std::vector<ListSrc> h_lsrc;     // ... and the handles its runs take their list tables from
+        size_t last_stage_bytes = 0;     // debug (prk_debug_stage_bytes): the last pass's staging upload
         std::vector<unsigned long long> h_big_off;
         std::vector<prk::DrawRec> h_draws;
         std::vector<prk::TexRec> h_texs;
@@ -586,6 +623,10 @@ int prk_destroy(prk_context *c) {
             (void)hipFree((void *)g.UV);
         }
     for (auto &t : c->texs) (void)hipFree(t.mem);
+    for (auto &r : c->recs) {
+        (void)hipFree(r.rec);
+        (void)hipFree(r.tab);
+    }
     if (c->owns_target) {
         (void)hipFree(c->color);
         (void)hipFree(c->zbuf);
@@ -613,7 +654,8 @@ int prk_destroy(prk_context *c) {
                         &S.d_raw, &S.d_most, &S.d_cls, &S.d_prrow, &S.d_prcnt, &S.d_preoff, &S.d_prfge,
                         &S.d_prccur, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend, &S.d_preendm,
                         &S.d_prmatch, &S.d_prsidx, &S.d_prsm, &S.d_prstat, &S.d_segcnt, &S.d_segoff,
-                        &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_rectab, &S.d_reccnt,
+                        &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_lscan, &S.d_lobj, &S.d_lrows,
+                        &S.d_ltab, &S.d_rectab, &S.d_reccnt,
                         &S.d_recout, &S.d_spanout, &S.d_rowslot, &S.d_rowcnt, &S.d_rowscan, &S.d_rowout,
                         &S.d_dr_rows, &S.d_dr_pairs, &S.d_dr_cnt, &S.d_dr_scan, &S.d_dr_temp, &S.d_dr_out};
         for (DevBuf *b : sb) b->release();
@@ -1920,10 +1962,29 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     S.h_k1src.clear();
     uint64_t ntri = 0, nk1 = 0, pool = 0, maxn = 1, small_tris = 0, nobj64 = 0, nk064 = 0;
     // the pass's batches (prk_draw_edge_lists) take consecutive records and
-    // lists of the frame's: [le0, le0 + nle) and [ll0, ll0 + nll); the small
-    // sorted lists' edges bound their segments
-    uint64_t nle = 0, nll = 0, small_ledges = 0;
+    // lists of the frame's: [le0, le0 + nhe) and [ll0, ll0 + nhl); the small
+    // sorted lists' edges bound their segments.  With the handle draws'
+    // (prk_draw_records) the pass has nle batch edges and nll batch lists, in
+    // submission order; only a pass with handle draws lists the segments of
+    // its batch edges (h_segs; a staged segment's src: its record among the
+    // staged ones, until the staging has its address).
+    uint64_t nle = 0, nll = 0, nhe = 0, nhl = 0, small_ledges = 0;
     uint32_t le0 = 0, ll0 = 0;
+    bool handles = false;
+    for (const prk::DrawRec &d : draws) handles = handles || d.src_kind == 4;
+    S.h_segs.clear();
+    S.h_lsrc.clear();
+    std::vector<uint8_t> seg_staged;
+    auto add_seg = [&](uint64_t src, bool staged, uint32_t n) {
+        if (!handles || !n) return;
+        if (!S.h_segs.empty() && seg_staged.back() == (staged ? 1 : 0) &&
+            S.h_segs.back().src + sizeof(prk_edge) * (uint64_t)S.h_segs.back().n == src) {
+            S.h_segs.back().n += n;  // (the records go on where the previous segment's end)
+            return;
+        }
+        S.h_segs.push_back(PrepSeg{src, (uint32_t)nle, n, 0u, 0u});
+        seg_staged.push_back(staged ? 1 : 0);
+    };
     bool thread_links = false;  // a thread-walked triangle object small enough for LDS list links
     std::vector<uint32_t> bigm[prk::MODE_COUNT], bige[prk::MODE_COUNT];  // wave-walked objects by mode, their edges
     for (uint32_t di = 0; di < draws.size(); ++di) {
@@ -1938,18 +1999,39 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
             if (!d.src_n) continue;
             S.h_runs.push_back(ObjRun{2u, di, (uint32_t)nobj64, d.src_n, 0u, 0u, d.first_global, 0u, 0u, d.src_off, 0u, 0u});
             nobj64 += d.src_n;
-        } else if (d.src_kind == 3) {
+        } else if (d.src_kind == 3 || d.src_kind == 4) {
             // one run for the batch; its sorted lists are routed like triangle
-            // objects of as many edges (k1off: the first batch edge's slot, below)
-            if (!nll) {
-                le0 = d.src_off;
-                ll0 = d.geom_tri0;
+            // objects of as many edges (k1off: the first batch edge's slot, below).
+            // The run's list tables: `per` on in the staged ones (tri0 0), or
+            // in those of handle source tri0 - 1 (k_list_tables).
+            const uint32_t *lcnt, *lflag;
+            uint32_t src = 0, at;
+            if (d.src_kind == 3) {
+                if (!nhl) {
+                    le0 = d.src_off;
+                    ll0 = d.geom_tri0;
+                }
+                lcnt = c->pend_lcnt.data() + d.geom_tri0;
+                lflag = c->pend_lflag.data() + d.geom_tri0;
+                at = (uint32_t)nhl;
+                add_seg(sizeof(prk_edge) * nhe, true, d.src_n);
+                nhl += d.tri_count;
+                nhe += d.src_n;
+            } else {
+                const Records &R = c->recs[d.geom];
+                lcnt = R.cnt.data() + d.geom_tri0;
+                lflag = R.flag.data() + d.geom_tri0;
+                at = d.geom_tri0;
+                for (src = 0; src < S.h_lsrc.size() && S.h_lsrc[src].cnt != R.d_cnt(); ++src) {}
+                if (src == S.h_lsrc.size()) S.h_lsrc.push_back(ListSrc{R.d_cnt(), R.d_flag()});
+                ++src;
+                add_seg(reinterpret_cast<uintptr_t>(R.rec) + sizeof(prk_edge) * (uint64_t)d.src_off, false, d.src_n);
             }
-            S.h_runs.push_back(ObjRun{3u, di, (uint32_t)nobj64, d.tri_count, 0u, 0u, d.first_global, 0u, (uint32_t)nll,
-                                      0u, 0u, 0u});
+            S.h_runs.push_back(ObjRun{3u, di, (uint32_t)nobj64, d.tri_count, handles ? at : 0u, 0u, d.first_global,
+                                      src, (uint32_t)nll, 0u, 0u, 0u});
             for (uint32_t j = 0; j < d.tri_count; ++j) {
-                const uint32_t n = c->pend_lcnt[d.geom_tri0 + j];
-                if (!c->pend_lflag[d.geom_tri0 + j]) continue;
+                const uint32_t n = lcnt[j];
+                if (!lflag[j]) continue;
                 if (n >= kObjWaveEdges) {
                     bigm[d.mode].push_back((uint32_t)(nobj64 + j));
                     bige[d.mode].push_back(n);
@@ -2001,8 +2083,13 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     if (3 * ntri + nk1 + nle >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
     for (ObjRun &r : S.h_runs)  // the batch edges' slots follow the prk_draw_edges lists'
         if (r.kind == 3) r.k1off = (uint32_t)nk1;
-    S.h_lcnt.assign(c->pend_lcnt.begin() + ll0, c->pend_lcnt.begin() + ll0 + nll);
+    S.h_lcnt.assign(c->pend_lcnt.begin() + ll0, c->pend_lcnt.begin() + ll0 + nhl);
     S.h_lcnt.push_back(0u);  // (the scan's total)
+    uint32_t nsegblk = 0;
+    for (PrepSeg &sg : S.h_segs) {
+        sg.blk0 = nsegblk;
+        nsegblk += (sg.n + kPrepEdges - 1) / kPrepEdges;
+    }
     const uint32_t nobj = (uint32_t)nobj64, nk0 = (uint32_t)nk064;
     const uint32_t nt = (uint32_t)ntri, nbig_all = (uint32_t)S.h_big_gl.size();
     // MergeSort key: (object, min(YMin, H), recursion path) in one radix sort
@@ -2018,7 +2105,7 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     // The pass's host tables go up in one copy from pinned staging (a pageable
     // hipMemcpyAsync per table held the host for each).
     enum { T_DRAWS, T_TEXS, T_OBJS, T_K0OBJ, T_K0TRI0, T_BIG, T_BIG_OFF, T_BIG_CAP, T_K1SRC, T_EDGES, T_SPANS,
-           T_LCNT, T_LFLAG, T_LEDGES, T_N };  // (T_OBJS: the runs)
+           T_LCNT, T_LFLAG, T_LEDGES, T_LSEG, T_LSRC, T_N };  // (T_OBJS: the runs)
     struct Part {
         const void *src;
         size_t bytes, off;
@@ -2033,15 +2120,18 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                     {S.h_k1src.data(), S.h_k1src.size() * 4, 0},
                     {c->pend_edges.data(), c->pend_edges.size() * sizeof(prk_edge), 0},
                     {c->pend_spans.data(), c->pend_spans.size() * sizeof(prk_span), 0},
-                    {S.h_lcnt.data(), nll ? S.h_lcnt.size() * 4 : 0, 0},
-                    {c->pend_lflag.data() + ll0, (size_t)nll * 4, 0},
-                    {c->pend_ledges.data() + le0, (size_t)nle * sizeof(prk_edge), 0}};
+                    {S.h_lcnt.data(), nhl ? S.h_lcnt.size() * 4 : 0, 0},
+                    {c->pend_lflag.data() + ll0, (size_t)nhl * 4, 0},
+                    {c->pend_ledges.data() + le0, (size_t)nhe * sizeof(prk_edge), 0},
+                    {S.h_segs.data(), S.h_segs.size() * sizeof(PrepSeg), 0},
+                    {S.h_lsrc.data(), S.h_lsrc.size() * sizeof(ListSrc), 0}};
     size_t stage_bytes = 0;
     for (Part &pt : parts) {
         pt.off = stage_bytes;
         stage_bytes = (stage_bytes + pt.bytes + 255) & ~(size_t)255;
     }
     stage_bytes = std::max<size_t>(stage_bytes, 256);
+    S.last_stage_bytes = stage_bytes;
     if (!S.stage_ev) PRK_TRY(hipEventCreateWithFlags(&S.stage_ev, hipEventDisableTiming));
     if (S.stage_busy) {  // the previous pass's upload still reads the staging
         PRK_TRY(hipEventSynchronize(S.stage_ev));
@@ -2055,9 +2145,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         PRK_TRY(hipHostMalloc((void **)&S.h_stage, want, hipHostMallocDefault));
         S.stage_cap = want;
     }
+    PRK_TRY(S.d_stage.ensure(stage_bytes));
+    for (size_t i = 0; i < S.h_segs.size(); ++i)  // the staged segments' records, where the staging puts them
+        if (seg_staged[i]) S.h_segs[i].src += reinterpret_cast<uintptr_t>(S.d_stage.p) + parts[T_LEDGES].off;
     for (const Part &pt : parts)
         if (pt.bytes && pt.src) std::memcpy(S.h_stage + pt.off, pt.src, pt.bytes);
-    PRK_TRY(S.d_stage.ensure(stage_bytes));
     PRK_TRY(hipMemcpyAsync(S.d_stage.p, S.h_stage, stage_bytes, hipMemcpyHostToDevice, s));
     PRK_TRY(hipEventRecord(S.stage_ev, s));
     S.stage_busy = true;
@@ -2077,6 +2169,7 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     // the batch lists' first edges: the scan of their counts
     const uint32_t nlist = (uint32_t)nll, nledge = (uint32_t)nle;
     uint32_t *lscan = nullptr, *lobj = nullptr;
+    const uint32_t *d_lcnt = (const uint32_t *)dev(T_LCNT), *d_lflag = (const uint32_t *)dev(T_LFLAG);
     if (nlist) {
         size_t lb = 0;
         PRK_TRY(S.d_lscan.ensure(((size_t)nlist + 1) * 4));
@@ -2084,13 +2177,20 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         PRK_TRY(S.d_lrows.ensure((size_t)nlist * 8));
         lscan = (uint32_t *)S.d_lscan.p;
         lobj = (uint32_t *)S.d_lobj.p;
-        PRK_TRY(prk_scan_u32((const uint32_t *)dev(T_LCNT), lscan, nlist + 1, nullptr, &lb, s));
+        if (handles) {  // the lists' tables from their sources, on the device
+            PRK_TRY(S.d_ltab.ensure((2 * (size_t)nlist + 1) * 4));
+            uint32_t *lt = (uint32_t *)S.d_ltab.p;
+            PRK_TRY(prk_list_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, (const uint32_t *)dev(T_LCNT),
+                                    (const uint32_t *)dev(T_LFLAG), dev(T_LSRC), nlist, lt, lt + nlist + 1, s));
+            d_lcnt = lt;
+            d_lflag = lt + nlist + 1;
+        }
+        PRK_TRY(prk_scan_u32(d_lcnt, lscan, nlist + 1, nullptr, &lb, s));
         PRK_TRY(S.d_temp.ensure(std::max<size_t>(lb, 16)));
-        PRK_TRY(prk_scan_u32((const uint32_t *)dev(T_LCNT), lscan, nlist + 1, S.d_temp.p, &lb, s));
+        PRK_TRY(prk_scan_u32(d_lcnt, lscan, nlist + 1, S.d_temp.p, &lb, s));
     }
     PRK_TRY(prk_obj_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0,
-                           (const uint32_t *)dev(T_LCNT), (const uint32_t *)dev(T_LFLAG), lscan, kObjWaveEdges, lobj,
-                           s));
+                           d_lcnt, d_lflag, lscan, kObjWaveEdges, lobj, s));
     const uint32_t *d_big = (const uint32_t *)dev(T_BIG);
     const uint32_t *d_k1src = (const uint32_t *)dev(T_K1SRC);
     uint32_t modes = 0;  // the pass's span kinds: bit per Mode
@@ -2171,8 +2271,13 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                                S.d_work.p, 3 * nt + (uint32_t)nk1, segmented ? S.d_wy.p : nullptr, s));
     // the batch lists' records into it, with their lists' row sums; then the
     // span slots: each object's bound, exclusive-scanned into its first slot
-    PRK_TRY(prk_list_prep(&fp, dev(T_LEDGES), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1, S.d_work.p,
-                          segmented ? S.d_wy.p : nullptr, (unsigned long long *)S.d_lrows.p, s));
+    if (handles)
+        PRK_TRY(prk_list_prep_segs(&fp, dev(T_LSEG), (uint32_t)S.h_segs.size(), nsegblk, lscan, nlist, lobj, d_objs,
+                                   total0p, (uint32_t)nk1, S.d_work.p, segmented ? S.d_wy.p : nullptr,
+                                   (unsigned long long *)S.d_lrows.p, s));
+    else
+        PRK_TRY(prk_list_prep(&fp, dev(T_LEDGES), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1,
+                              S.d_work.p, segmented ? S.d_wy.p : nullptr, (unsigned long long *)S.d_lrows.p, s));
     PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, d_edges_in, (const unsigned long long *)S.d_lrows.p,
                           (unsigned long long *)S.d_bound.p, s));
     PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, nullptr, &tb, s));
@@ -2720,9 +2825,14 @@ int prk_fill_edge_count(const float *V, uint32_t vertex_count, const float P[3],
 // no target (the frame parameters' rows only bound the span slots, which are
 // not used here), records no draw and leaves c->draws, the pending edge /
 // span input and c->stats as they are.
-int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
-                     uint32_t tris_per_object, const float P[3], int32_t setup, prk_edge *records,
-                     uint64_t capacity, uint32_t *counts, uint64_t *total_out) {
+// keep (prk_records_from_geometry): k_rec_export writes into a buffer of the
+// call's own, handed over in *keep, instead of the scratch -- nothing is
+// downloaded (records, capacity, counts: null; the objects' counts stay in
+// d_reccnt, *nobj_out of them).
+static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                            uint32_t tris_per_object, const float P[3], int32_t setup, prk_edge *records,
+                            uint64_t capacity, uint32_t *counts, uint64_t *total_out, void **keep,
+                            uint32_t *nobj_out) {
     if (!c || !total_out) return PRK_ERR_ARG;
     *total_out = 0;
     if (geometry < 0 || geometry >= (int32_t)c->geoms.size() || tris_per_object == 0) return PRK_ERR_ARG;
@@ -2730,10 +2840,12 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
     const Geometry &g = c->geoms[geometry];
     if ((uint64_t)first_tri + tri_count > g.vertex_count / 3) return PRK_ERR_ARG;
     if (!c->have_camera) return PRK_ERR_ARG;
+    if (nobj_out) *nobj_out = 0;
     if (tri_count == 0) return PRK_OK;
     const uint32_t nt = tri_count, per = std::min(tris_per_object, tri_count);
     const uint32_t nobj = (uint32_t)(((uint64_t)nt + per - 1) / per);
     if (3ull * nt >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;  // 31-bit edge slots
+    if (nobj_out) *nobj_out = nobj;
     // MergeSort key: (object, true YMin: 31 bits, recursion path)
     auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
     const uint32_t maxn = 3 * per;  // the most edges FillEdgeTable writes for one object
@@ -2797,13 +2909,20 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
     PRK_TRY(hipMemcpyAsync(&total, escan + nt, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     *total_out = total;
-    const bool fill = records != nullptr && capacity >= total;
+    const bool fill = keep || (records != nullptr && capacity >= total);
     if (fill && total) {
         PRK_TRY(S.d_edges.ensure(es * 112));  // prk_spans.hip ObjEdge
         PRK_TRY(S.d_ekeys.ensure(es * 8));
         PRK_TRY(S.d_evals.ensure(es * 4));
         const size_t out_bytes = (((size_t)total * 27 + 3) / 4) * 16;
-        PRK_TRY(S.d_recout.ensure(out_bytes));
+        void *d_out = nullptr;
+        if (keep) {
+            PRK_TRY(hipMalloc(&d_out, out_bytes));
+            *keep = d_out;  // (the caller's from here on, whatever follows)
+        } else {
+            PRK_TRY(S.d_recout.ensure(out_bytes));
+            d_out = S.d_recout.p;
+        }
         // MergeSort per object: at most 64 edges by one wave each
         // (k_obj_sort_local, into the working copy), else one radix sort
         const bool local_sort = maxn <= 64;
@@ -2813,7 +2932,7 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
             PRK_TRY(S.d_work.ensure(es * 112));
             PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nobj, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, nullptr,
                                        (uint32_t *)S.d_err.p, s));
-            PRK_TRY(prk_rec_export(S.d_work.p, nullptr, total, S.d_recout.p, s));
+            PRK_TRY(prk_rec_export(S.d_work.p, nullptr, total, d_out, s));
         } else {
             PRK_TRY(S.d_ekeys2.ensure(es * 8));
             PRK_TRY(S.d_ord.ensure(es * 4));
@@ -2823,11 +2942,12 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
             PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
             PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
                                  end_bit, S.d_temp.p, &tb, s));
-            PRK_TRY(prk_rec_export(S.d_edges.p, (const uint32_t *)S.d_ord.p, total, S.d_recout.p, s));
+            PRK_TRY(prk_rec_export(S.d_edges.p, (const uint32_t *)S.d_ord.p, total, d_out, s));
         }
         uint32_t err = 0;
         PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
-        PRK_TRY(hipMemcpyAsync(records, S.d_recout.p, (size_t)total * sizeof(prk_edge), hipMemcpyDeviceToHost, s));
+        if (!keep)
+            PRK_TRY(hipMemcpyAsync(records, d_out, (size_t)total * sizeof(prk_edge), hipMemcpyDeviceToHost, s));
         if (counts) PRK_TRY(hipMemcpyAsync(counts, S.d_reccnt.p, (size_t)nobj * 4, hipMemcpyDeviceToHost, s));
         PRK_TRY(hipStreamSynchronize(s));
         if (err) return PRK_ERR_DEVICE;
@@ -2835,6 +2955,178 @@ int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint3
     }
     if (counts) PRK_TRY(hipMemcpy(counts, S.d_reccnt.p, (size_t)nobj * 4, hipMemcpyDeviceToHost));
     return records && capacity < total ? PRK_ERR_ARG : PRK_OK;
+}
+
+int prk_edge_records(prk_context *c, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                     uint32_t tris_per_object, const float P[3], int32_t setup, prk_edge *records,
+                     uint64_t capacity, uint32_t *counts, uint64_t *total_out) {
+    return edge_records_run(c, geometry, first_tri, tri_count, tris_per_object, P, setup, records, capacity, counts,
+                            total_out, nullptr, nullptr);
+}
+
+// ---- record handles (prk.h) -------------------------------
+static Records *records_of(prk_context *c, int32_t handle) {
+    if (!c || handle < 0 || (size_t)handle >= c->recs.size() || !c->recs[handle].live) return nullptr;
+    return &c->recs[handle];
+}
+static void records_free(Records &R) {
+    (void)hipFree(R.rec);
+    (void)hipFree(R.tab);
+    R = Records{};
+}
+// The rest of a handle whose records (R.rec, `total` of them) and counts
+// (R.tab[0 .. nlist)) are on the device: the sorted rule of every list
+// (k_list_rule over the scan of the counts), and the host's copies of the
+// counts and flags -- the one readback of the handle's life.  The device is
+// idle (the scratch is the span path's).
+static int records_finish(prk_context *c, Records &R, uint32_t nlist, uint64_t total) {
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    R.total = total;
+    R.cnt.assign(nlist, 0u);
+    R.flag.assign(nlist, 0u);
+    if (nlist) {
+        uint32_t *d_cnt = R.tab, *d_flag = R.tab + nlist + 1;
+        size_t tb = 0;
+        PRK_TRY(hipMemsetAsync(d_cnt + nlist, 0, 4, s));  // (the scan's total)
+        PRK_TRY(S.d_lscan.ensure(((size_t)nlist + 1) * 4));
+        uint32_t *lscan = (uint32_t *)S.d_lscan.p;
+        PRK_TRY(prk_scan_u32(d_cnt, lscan, nlist + 1, nullptr, &tb, s));
+        PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
+        PRK_TRY(prk_scan_u32(d_cnt, lscan, nlist + 1, S.d_temp.p, &tb, s));
+        PRK_TRY(prk_list_rule(R.rec, (uint32_t)total, lscan, nlist, d_flag, s));
+        PRK_TRY(hipMemcpyAsync(R.cnt.data(), d_cnt, (size_t)nlist * 4, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipMemcpyAsync(R.flag.data(), d_flag, (size_t)nlist * 4, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipStreamSynchronize(s));
+    }
+    R.live = true;
+    return PRK_OK;
+}
+static int records_tab_alloc(Records &R, uint32_t nlist) {
+    PRK_TRY(hipMalloc((void **)&R.tab, (2 * (size_t)nlist + 1) * 4));
+    return PRK_OK;
+}
+
+int prk_records_from_geometry(prk_context *c, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                              uint32_t tris_per_object, const float P[3], int32_t setup, int32_t *handle_out,
+                              uint32_t *list_count_out, uint64_t *total_out) {
+    if (!c || !handle_out) return PRK_ERR_ARG;
+    *handle_out = -1;
+    if (list_count_out) *list_count_out = 0;
+    uint64_t total = 0;
+    if (total_out) *total_out = 0;
+    if (c->recs.size() >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    Records R;
+    uint32_t nlist = 0;
+    int rc = edge_records_run(c, geometry, first_tri, tri_count, tris_per_object, P, setup, nullptr, 0, nullptr,
+                              &total, &R.rec, &nlist);
+    if (rc == PRK_OK) rc = status_of(hipSetDevice(c->device));
+    if (rc == PRK_OK) rc = records_tab_alloc(R, nlist);
+    if (rc == PRK_OK && nlist)
+        rc = status_of(hipMemcpyAsync(R.tab, c->spans.d_reccnt.p, (size_t)nlist * 4, hipMemcpyDeviceToDevice,
+                                      c->own_stream));
+    if (rc == PRK_OK) rc = records_finish(c, R, nlist, total);
+    if (rc != PRK_OK) {
+        records_free(R);
+        return rc;
+    }
+    *handle_out = (int32_t)c->recs.size();
+    c->recs.push_back(std::move(R));
+    if (list_count_out) *list_count_out = nlist;
+    if (total_out) *total_out = total;
+    return PRK_OK;
+}
+
+int prk_records_upload(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                       int32_t *handle_out) {
+    if (!c || !handle_out || (!counts && list_count)) return PRK_ERR_ARG;
+    *handle_out = -1;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    // a handle's records and lists are indexed by 31 bits, as a pass's
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || c->recs.size() >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch records_finish takes
+    Records R;
+    int rc = records_tab_alloc(R, list_count);
+    if (rc == PRK_OK && total) {
+        rc = status_of(hipMalloc(&R.rec, (((size_t)total * 27 + 3) / 4) * 16));
+        if (rc == PRK_OK)  // the one copy of the caller's records
+            rc = status_of(hipMemcpy(R.rec, records, (size_t)total * sizeof(prk_edge), hipMemcpyHostToDevice));
+    }
+    if (rc == PRK_OK && list_count)
+        rc = status_of(hipMemcpy(R.tab, counts, (size_t)list_count * 4, hipMemcpyHostToDevice));
+    if (rc == PRK_OK) rc = records_finish(c, R, list_count, total);
+    if (rc != PRK_OK) {
+        records_free(R);
+        return rc;
+    }
+    *handle_out = (int32_t)c->recs.size();
+    c->recs.push_back(std::move(R));
+    return PRK_OK;
+}
+
+int prk_records_info(prk_context *c, int32_t handle, uint32_t *list_count_out, uint64_t *total_out) {
+    const Records *R = records_of(c, handle);
+    if (!R) return PRK_ERR_ARG;
+    if (list_count_out) *list_count_out = (uint32_t)R->cnt.size();
+    if (total_out) *total_out = R->total;
+    return PRK_OK;
+}
+
+int prk_records_lists(prk_context *c, int32_t handle, uint32_t *counts, uint32_t *sorted_flags) {
+    const Records *R = records_of(c, handle);
+    if (!R) return PRK_ERR_ARG;
+    if (counts && !R->cnt.empty()) std::memcpy(counts, R->cnt.data(), R->cnt.size() * 4);
+    if (sorted_flags && !R->flag.empty()) std::memcpy(sorted_flags, R->flag.data(), R->flag.size() * 4);
+    return PRK_OK;
+}
+
+int prk_records_download(prk_context *c, int32_t handle, prk_edge *records, uint64_t capacity) {
+    const Records *R = records_of(c, handle);
+    if (!R || capacity < R->total || (!records && R->total)) return PRK_ERR_ARG;
+    if (!R->total) return PRK_OK;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipMemcpy(records, R->rec, (size_t)R->total * sizeof(prk_edge), hipMemcpyDeviceToHost));
+    return PRK_OK;
+}
+
+int prk_records_destroy(prk_context *c, int32_t handle) {
+    Records *R = records_of(c, handle);
+    if (!R) return PRK_ERR_ARG;
+    for (const prk::DrawRec &d : c->draws)  // a recorded draw reads it at the flush (prk_reset_draws releases it)
+        if (d.src_kind == 4 && d.geom == handle) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight read it
+    records_free(*R);
+    return PRK_OK;
+}
+
+// One draw of lists [first_list, first_list + list_count) of a handle: what
+// prk_draw_edge_lists records for the same lists, minus the copies -- the
+// flush reads the records where they are (flush_spans, src_kind 4).
+int prk_draw_records(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t semantics,
+                     int32_t phong, int32_t texture) {
+    const Records *R = records_of(c, handle);
+    if (!R || (uint64_t)first_list + list_count > R->cnt.size()) return PRK_ERR_ARG;
+    if (list_count == 0) return PRK_OK;
+    uint64_t r0 = 0, n = 0;
+    for (uint32_t o = 0; o < first_list; ++o) r0 += R->cnt[o];
+    for (uint32_t o = 0; o < list_count; ++o) n += R->cnt[first_list + o];
+    const int rc = draw_src(c, 4, (uint32_t)r0, (uint32_t)n, list_count, semantics, phong, texture);
+    if (rc != PRK_OK) return rc;
+    c->draws.back().geom_tri0 = first_list;
+    c->draws.back().geom = handle;
+    return PRK_OK;
+}
+
+int prk_debug_stage_bytes(prk_context *c, uint64_t *bytes_out) {
+    if (!c || !bytes_out) return PRK_ERR_ARG;
+    *bytes_out = c->spans.last_stage_bytes;
+    return PRK_OK;
 }
 
 // The lists DrawModel* leaves (prk_advance_edge_records' result) for a batch

@@ -142,7 +142,10 @@ constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 // pass's batch list k0base on: list l has lcnt[l] edges from edge slot
 // k1off + lscan[l] on (lscan: the exclusive scan of lcnt), is sorted iff
 // lflag[l], and is a large object from wave_edges edges on when sorted;
-// lobj[l] = its object.
+// lobj[l] = its object.  A prk_draw_records draw is a run of kind 3 too; in a
+// pass that has one, a kind-3 run also names where its lists' counts and
+// flags come from (tri0: 0 the staged tables, k the pass's k-th handle) and
+// its first list there (per), for k_list_tables to gather lcnt / lflag.
 struct ObjRun {
     uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
 };
@@ -4202,24 +4205,12 @@ constexpr PrepMap prep_map() {
     for (int f = 0; f < 27; ++f) m.f[kWord[f]] = (uint8_t)f;
     return m;
 }
-// A workgroup's records into LDS and on into the working copy: edges
-// [e_first, e_first + ne) of the flat input as ObjEdges at dst[0 .. ne)
-// (shared by k_list_prep and k_adv_import; ends in a barrier, so the callers
-// read `rec4` after it).  Returns ne.
-constexpr uint32_t kPrepPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
-static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
-__device__ __forceinline__ uint32_t prep_records(const uint4 *__restrict__ in, uint32_t nedge, uint4 *rec4,
-                                                 ObjEdge *__restrict__ dst_edges) {
+// The ne records at `rec` (LDS, 27 dwords each) as ObjEdges at dst_edges[0 .. ne):
+// lane t of pass k stores dwordx4 number t + 256 k.
+__device__ __forceinline__ void prep_convert(const uint32_t *rec, uint32_t ne, ObjEdge *__restrict__ dst_edges) {
     static constexpr PrepMap kMap = prep_map();
     static_assert(kMap.f[19] == 27 && kMap.f[16] == 7 && kMap.f[17] == 0, "ObjEdge: Next, YMin, YMax");
     const uint32_t tid = threadIdx.x;
-    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;  // (< nedge: the grid)
-    const uint32_t ne = min((uint32_t)kPrepEdges, nedge - e_first);
-    const uint32_t np = (27u * ne + 3u) / 4u;
-    const uint4 *src = in + (size_t)blockIdx.x * kPrepPieces;
-    for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
-    __syncthreads();
-    const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4);
     float4 *dst = reinterpret_cast<float4 *>(dst_edges);
     for (uint32_t j = tid; j < 7u * ne; j += (uint32_t)kPrepEdges) {
         const uint32_t e = j / 7u, q = j - 7u * e;
@@ -4233,22 +4224,33 @@ __device__ __forceinline__ uint32_t prep_records(const uint4 *__restrict__ in, u
         dst[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
                              __uint_as_float(v[3]));
     }
+}
+// A workgroup's records into LDS and on into the working copy: edges
+// [e_first, e_first + ne) of the flat input as ObjEdges at dst[0 .. ne)
+// (shared by k_list_prep and k_adv_import; ends in a barrier, so the callers
+// read `rec4` after it).  Returns ne.
+constexpr uint32_t kPrepPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
+static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
+__device__ __forceinline__ uint32_t prep_records(const uint4 *__restrict__ in, uint32_t nedge, uint4 *rec4,
+                                                 ObjEdge *__restrict__ dst_edges) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;  // (< nedge: the grid)
+    const uint32_t ne = min((uint32_t)kPrepEdges, nedge - e_first);
+    const uint32_t np = (27u * ne + 3u) / 4u;
+    const uint4 *src = in + (size_t)blockIdx.x * kPrepPieces;
+    for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
+    __syncthreads();
+    prep_convert(reinterpret_cast<const uint32_t *>(rec4), ne, dst_edges);
     return ne;
 }
-__global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const uint4 *__restrict__ in, uint32_t nedge,
-                                                          const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                          const uint32_t *__restrict__ lobj,
-                                                          const ObjDesc *__restrict__ objs,
-                                                          const uint32_t *__restrict__ total0p, uint32_t ebase,
-                                                          ObjEdge *__restrict__ work, int2 *__restrict__ wy,
-                                                          unsigned long long *__restrict__ lrows) {
-    __shared__ uint4 rec4[kPrepPieces];
+// The rows of a workgroup's ne edges into their lists' sums (lrows): lane t
+// has the record at rec + 27 t (LDS), the pass's batch edge e_first + t, the
+// working-copy slot slot0 + t.
+__device__ __forceinline__ void prep_rows(const FrameParams &fp, const uint32_t *rec, uint32_t ne, uint32_t e_first,
+                                          size_t slot0, const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                          const uint32_t *__restrict__ lobj, const ObjDesc *__restrict__ objs,
+                                          int2 *__restrict__ wy, unsigned long long *__restrict__ lrows) {
     const uint32_t tid = threadIdx.x;
-    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;
-    const size_t slot0 = (size_t)*total0p + ebase + e_first;
-    const uint32_t ne = prep_records(in, nedge, rec4, work + slot0);
-    const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4);
-    // the edge's rows into its list's sum
     const bool have = tid < ne;
     uint32_t l = 0;
     unsigned long long r = 0;
@@ -4275,6 +4277,136 @@ __global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const 
         for (int off = 32; off; off >>= 1) sum += __shfl_xor(sum, off);
         if ((int)(tid & 63u) == lead && sum) atomicAdd(&lrows[ll], sum);
         todo &= ~__ballot(mine);
+    }
+}
+__global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const uint4 *__restrict__ in, uint32_t nedge,
+                                                          const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                          const uint32_t *__restrict__ lobj,
+                                                          const ObjDesc *__restrict__ objs,
+                                                          const uint32_t *__restrict__ total0p, uint32_t ebase,
+                                                          ObjEdge *__restrict__ work, int2 *__restrict__ wy,
+                                                          unsigned long long *__restrict__ lrows) {
+    __shared__ uint4 rec4[kPrepPieces];
+    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;
+    const size_t slot0 = (size_t)*total0p + ebase + e_first;
+    const uint32_t ne = prep_records(in, nedge, rec4, work + slot0);
+    prep_rows(fp, reinterpret_cast<const uint32_t *>(rec4), ne, e_first, slot0, lscan, nlist, lobj, objs, wy, lrows);
+}
+
+// ---------------------------------------------------------------------------
+// Record handles (prk_records_*, prk_draw_records): batches of lists whose
+// packed records stay in device memory.  A pass that draws from a handle
+// takes its batch lists' records from several places -- the staged records
+// of the prk_draw_edge_lists batches, and sub-ranges of handles, which start
+// at byte 108 r0 of the handle's buffer for any record r0 -- so the pass's
+// batch edges are cut into segments (PrepSeg: consecutive batch edges whose
+// records are consecutive in memory), and k_list_prep_segs is k_list_prep
+// with a workgroup per kPrepEdges edges of a segment.  The import keeps the
+// 16-byte loads: a workgroup reads the aligned stretch that encloses its
+// records (up to three dwords before the first and after the last: every
+// source starts on a 256-byte boundary and is readable to a multiple of 16
+// bytes) and the records are addressed in LDS from the dword they start at.
+// The LDS reads are single dwords 27 apart, as in k_list_prep, so the shift
+// changes no lane's bank relative to the others.
+//   k_list_tables  the pass's list counts and sorted flags, gathered from the
+//                  staged tables (source 0) and the handles' device tables:
+//                  a run of kind 3 names its source in tri0 and its first
+//                  list there in per
+//   k_list_rule    prk_api.hip's list_walks_sorted for every list of a handle
+// ---------------------------------------------------------------------------
+struct PrepSeg {
+    const uint32_t *src;  // its first record
+    uint32_t e0, n;       // its first edge among the pass's batch edges, its edges
+    uint32_t blk0, pad;   // its first workgroup
+};
+struct ListSrc {
+    const uint32_t *cnt, *flag;
+};
+__global__ void __launch_bounds__(kPrepEdges) k_list_prep_segs(FrameParams fp, const PrepSeg *__restrict__ segs,
+                                                               uint32_t nseg, const uint32_t *__restrict__ lscan,
+                                                               uint32_t nlist, const uint32_t *__restrict__ lobj,
+                                                               const ObjDesc *__restrict__ objs,
+                                                               const uint32_t *__restrict__ total0p, uint32_t ebase,
+                                                               ObjEdge *__restrict__ work, int2 *__restrict__ wy,
+                                                               unsigned long long *__restrict__ lrows) {
+    __shared__ uint4 rec4[kPrepPieces + 1];
+    const uint32_t tid = threadIdx.x;
+    uint32_t lo = 0, hi = nseg;  // the last segment with blk0 <= this workgroup
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (segs[mid].blk0 <= blockIdx.x) lo = mid;
+        else hi = mid;
+    }
+    const PrepSeg sg = segs[lo];
+    const uint32_t s_first = (blockIdx.x - sg.blk0) * (uint32_t)kPrepEdges;  // (< sg.n: the grid)
+    const uint32_t ne = min((uint32_t)kPrepEdges, sg.n - s_first);
+    const uint32_t *first = sg.src + (size_t)27u * s_first;
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(first) >> 2) & 3u;
+    const uint4 *src = reinterpret_cast<const uint4 *>(first - shift);
+    const uint32_t np = (shift + 27u * ne + 3u) / 4u;  // (<= kPrepPieces + 1)
+    for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
+    __syncthreads();
+    const uint32_t *rec = reinterpret_cast<const uint32_t *>(rec4) + shift;
+    const uint32_t e_first = sg.e0 + s_first;
+    const size_t slot0 = (size_t)*total0p + ebase + e_first;
+    prep_convert(rec, ne, work + slot0);
+    prep_rows(fp, rec, ne, e_first, slot0, lscan, nlist, lobj, objs, wy, lrows);
+}
+__global__ void k_list_tables(const ObjRun *__restrict__ runs, uint32_t nruns, uint32_t nobj,
+                              const uint32_t *__restrict__ cnt0, const uint32_t *__restrict__ flag0,
+                              const ListSrc *__restrict__ srcs, uint32_t nlist, uint32_t *__restrict__ lcnt,
+                              uint32_t *__restrict__ lflag) {
+    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o == 0) lcnt[nlist] = 0u;  // (the scan's total)
+    if (o >= nobj) return;
+    uint32_t lo = 0, hi = nruns;  // the last run with obj0 <= o
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (runs[mid].obj0 <= o) lo = mid;
+        else hi = mid;
+    }
+    const ObjRun R = runs[lo];
+    if (R.kind != 3) return;
+    const uint32_t j = o - R.obj0, at = R.per + j;
+    const uint32_t *cnt = cnt0, *flag = flag0;
+    if (R.tri0) {
+        const ListSrc S = srcs[R.tri0 - 1];
+        cnt = S.cnt;
+        flag = S.flag;
+    }
+    lcnt[R.k0base + j] = cnt[at];
+    lflag[R.k0base + j] = flag[at];
+}
+// A lane per record of the flat packed array: words 0 (YMax), 7 (YMin) and 12
+// (Left) of its record and YMin of the record before it -- 0 for the first
+// record of a list, whatever the previous list ends with.  lflag[l] (1 from
+// the launcher) is cleared by one atomic per wave and list with a violation,
+// so a list's flag does not depend on how the lists fall across waves.
+__global__ void __launch_bounds__(256) k_list_rule(const uint32_t *__restrict__ rec, uint32_t nedge,
+                                                   const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                   uint32_t *__restrict__ lflag) {
+    const uint32_t tid = threadIdx.x, e = blockIdx.x * 256u + tid;
+    bool bad = false;
+    uint32_t l = 0;
+    if (e < nedge) {
+        uint32_t lo = 0, hi = nlist;  // the last list with lscan[l] <= e (an empty list is never the last)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (lscan[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        l = lo;
+        const uint32_t *r = rec + (size_t)27u * e;
+        const int32_t ymax = (int32_t)r[0], ymin = (int32_t)r[7];
+        const int32_t prev = e > lscan[l] ? (int32_t)(r - 27)[7] : 0;
+        bad = ymin < prev || ymax < ymin || r[12] > 1u;
+    }
+    unsigned long long todo = __ballot(bad);
+    while (todo) {  // (wave-uniform: one turn per list of the wave with a violation)
+        const int lead = __ffsll((long long)todo) - 1;
+        const uint32_t ll = (uint32_t)__builtin_amdgcn_readlane((int)l, lead);
+        if ((int)(tid & 63u) == lead) atomicAnd(&lflag[ll], 0u);
+        todo &= ~__ballot(bad && l == ll);
     }
 }
 
@@ -5361,6 +5493,42 @@ hipError_t prk_list_prep(const prk::FrameParams *fp, const void *records, uint32
                        dim3(prk::kPrepEdges), 0, s, *fp, reinterpret_cast<const uint4 *>(records), nedge, lscan, nlist,
                        lobj, reinterpret_cast<const prk::ObjDesc *>(objs), total0p, ebase,
                        reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy), lrows);
+    return hipGetLastError();
+}
+// k_list_prep for a pass that draws from record handles: `segs` (PrepSeg, nseg
+// of them, nblk workgroups in all) instead of one flat input.
+hipError_t prk_list_prep_segs(const prk::FrameParams *fp, const void *segs, uint32_t nseg, uint32_t nblk,
+                              const uint32_t *lscan, uint32_t nlist, const uint32_t *lobj, const void *objs,
+                              const uint32_t *total0p, uint32_t ebase, void *work, void *wy,
+                              unsigned long long *lrows, hipStream_t s) {
+    if (nlist == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(lrows, 0, (size_t)nlist * 8, s);
+    if (e != hipSuccess || nseg == 0 || nblk == 0) return e;
+    hipLaunchKernelGGL(prk::k_list_prep_segs, dim3(nblk), dim3(prk::kPrepEdges), 0, s, *fp,
+                       reinterpret_cast<const prk::PrepSeg *>(segs), nseg, lscan, nlist, lobj,
+                       reinterpret_cast<const prk::ObjDesc *>(objs), total0p, ebase,
+                       reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy), lrows);
+    return hipGetLastError();
+}
+// The pass's list counts (nlist + 1, the last 0) and sorted flags from the
+// staged tables and the handles' (k_list_tables).
+hipError_t prk_list_tables(const void *runs, uint32_t nruns, uint32_t nobj, const uint32_t *cnt0,
+                           const uint32_t *flag0, const void *srcs, uint32_t nlist, uint32_t *lcnt, uint32_t *lflag,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(prk::k_list_tables, dim3(((nobj ? nobj : 1u) + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const prk::ObjRun *>(runs), nruns, nobj, cnt0, flag0,
+                       reinterpret_cast<const prk::ListSrc *>(srcs), nlist, lcnt, lflag);
+    return hipGetLastError();
+}
+// The sorted rule of every list of `nedge` packed records (k_list_rule);
+// lflag: nlist words, set to 1 here.
+hipError_t prk_list_rule(const void *records, uint32_t nedge, const uint32_t *lscan, uint32_t nlist, uint32_t *lflag,
+                         hipStream_t s) {
+    if (nlist == 0) return hipSuccess;
+    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lflag), 1, nlist, s);
+    if (e != hipSuccess || nedge == 0) return e;
+    hipLaunchKernelGGL(prk::k_list_rule, dim3((nedge + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const uint32_t *>(records), nedge, lscan, nlist, lflag);
     return hipGetLastError();
 }
 // FillEdgeTable of the pass's object triangles: per-triangle edge and

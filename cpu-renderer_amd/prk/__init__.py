@@ -106,6 +106,16 @@ _SIGS = {
                                       C.POINTER(C.c_uint32)]),
     "prk_edge_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float),
                                    C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "prk_records_from_geometry": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "prk_records_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]),
+    "prk_records_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "prk_records_lists": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "prk_records_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64]),
+    "prk_records_destroy": (C.c_int, [C.c_void_p, C.c_int32]),
+    "prk_draw_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32]),
+    "prk_debug_stage_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "prk_advance_edge_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p,
                                          C.c_void_p]),
     "prk_span_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
@@ -383,6 +393,45 @@ def _finalizing():
     return sys.is_finalizing()
 
 
+class Records:
+    """A record handle (prk_records_*): lists in edge_records' packed layout
+    kept in device memory by the Renderer that made it, drawn with
+    Renderer.draw_records any number of times."""
+
+    def __init__(self, renderer, handle):
+        self._r, self.handle = renderer, handle
+        n, t = C.c_uint32(0), C.c_uint64(0)
+        _check("prk_records_info", renderer._L.prk_records_info(renderer._h, handle, C.byref(n), C.byref(t)))
+        self.list_count, self.total = n.value, t.value
+
+    def _lists(self, which):
+        out = np.zeros(self.list_count, np.uint32)
+        args = (_ptr(out), None) if which == 0 else (None, _ptr(out))
+        _check("prk_records_lists", self._r._L.prk_records_lists(self._r._h, self.handle, *args))
+        return out
+
+    def counts(self):
+        """uint32 [list_count]: each list's records."""
+        return self._lists(0)
+
+    def sorted_flags(self):
+        """uint32 [list_count]: 1 for a list inside draw_edge_lists' sorted
+        rule (computed on the device when the handle was made)."""
+        return self._lists(1)
+
+    def download(self):
+        """uint32 [total, 27]: the packed records (edge_records' words)."""
+        w = np.empty((self.total, 27), np.uint32)
+        _check("prk_records_download", self._r._L.prk_records_download(self._r._h, self.handle, _ptr(w), self.total))
+        return w
+
+    def close(self):
+        """prk_records_destroy (the Renderer's close frees what is left)."""
+        if self.handle is not None and getattr(self._r, "_h", None):
+            _check("prk_records_destroy", self._r._L.prk_records_destroy(self._r._h, self.handle))
+        self.handle = None
+
+
 class Renderer:
     """One GPU context: render target, camera/lights, resident geometry and
     textures, and the list of recorded draws of the current frame."""
@@ -623,6 +672,43 @@ class Renderer:
         _check("prk_draw_edge_lists", self._L.prk_draw_edge_lists(self._h, _ptr(w), _ptr(n), n.shape[0], semantics,
                                                                   int(bool(phong)),
                                                                   -1 if bitmap is None else bitmap))
+
+    def records_from_geometry(self, geom, tri_count, first_tri=0, P=None, setup=3, tris_per_object=None):
+        """prk_records_from_geometry: edge_records' records of the same
+        arguments, kept on the device -> Records."""
+        per = max(1, tri_count) if tris_per_object is None else int(tris_per_object)
+        Pc = (C.c_float * 3)(*(P or (0.0, 0.0, 0.0)))
+        h = C.c_int32(-1)
+        _check("prk_records_from_geometry", self._L.prk_records_from_geometry(
+            self._h, geom, first_tri, tri_count, per, Pc, int(setup), C.byref(h), None, None))
+        return Records(self, h.value)
+
+    def records_upload(self, words, counts):
+        """prk_records_upload: the two arrays draw_edge_lists takes, copied to
+        the device once -> Records."""
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1, 27)
+        n = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if int(n.sum(dtype=np.uint64)) != w.shape[0]:
+            raise ValueError("records_upload: counts sum to %d, %d records given" % (int(n.sum(dtype=np.uint64)),
+                                                                                  w.shape[0]))
+        h = C.c_int32(-1)
+        _check("prk_records_upload", self._L.prk_records_upload(self._h, _ptr(w), _ptr(n), n.shape[0], C.byref(h)))
+        return Records(self, h.value)
+
+    def draw_records(self, rec, first_list=0, list_count=None, semantics=abi.PRK_SEM_AVX, bitmap=None, phong=True):
+        """prk_draw_records: lists [first_list, first_list + list_count) of a
+        Records (None: to its last list), drawn as draw_edge_lists draws the
+        same lists from host arrays -- from where they are on the device."""
+        n = rec.list_count - first_list if list_count is None else list_count
+        _check("prk_draw_records", self._L.prk_draw_records(self._h, rec.handle, first_list, n, semantics,
+                                                            int(bool(phong)), -1 if bitmap is None else bitmap))
+
+    def stage_bytes(self):
+        """prk_debug_stage_bytes: the bytes the last whole-object pass copied
+        from the host in its staging upload."""
+        out = C.c_uint64(0)
+        _check("prk_debug_stage_bytes", self._L.prk_debug_stage_bytes(self._h, C.byref(out)))
+        return out.value
 
     def advance_edge_lists(self, words, counts, height):
         """prk_advance_edge_lists: what DrawModel* leaves in every list of a

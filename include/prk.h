@@ -644,6 +644,69 @@ int prk_edge_records(prk_context *ctx, int32_t geometry, uint32_t first_tri, uin
                      uint32_t tris_per_object, const float P[3], int32_t setup,
                      prk_edge *records, uint64_t capacity, uint32_t *counts, uint64_t *total_out);
 
+/* Record handles: a batch of lists in prk_edge_records' packed layout that
+ * stays in device memory -- the reference's EdgeMemory of a static mesh:
+ * FillEdgeTable once, DrawModel* from the records every frame.  The context
+ * owns the batch and names it by a handle >= 0, as geometries and textures;
+ * the host keeps each list's edge count and whether it is inside
+ * prk_draw_edge_lists' sorted rule (8 bytes a list, computed on the device
+ * when the handle is made), and no copy of the records.  A handle belongs to
+ * its context (each band context makes its own).
+ *
+ * prk_records_from_geometry: prk_edge_records' records of the same arguments,
+ * written into the handle's buffer instead of the caller's -- no record
+ * crosses to the host.  Arguments and errors are prk_edge_records' (minus
+ * records / capacity / counts); *list_count_out = the objects, *total_out =
+ * the records (either may be NULL).  Synchronous; needs no target, records no
+ * draw, touches no recorded draw and no prk_stats; frames in flight finish
+ * first.  tri_count == 0 makes a handle of no lists.
+ *
+ * prk_records_upload: the same for a caller's own lists (records / counts as
+ * prk_draw_edge_lists takes them), copied once at the call; the host does not
+ * read the records.  PRK_ERR_ARG: NULL counts with list_count > 0, NULL
+ * records with a non-zero total.  PRK_ERR_LIMIT: records or lists pass 31 bits.
+ *
+ * prk_records_info / prk_records_lists: the handle's lists and records; each
+ * list's count and sorted-rule flag (1: inside the rule), list_count words
+ * each, either pointer may be NULL.  Host bookkeeping: no device work.
+ *
+ * prk_records_download: the packed records, word for word what
+ * prk_edge_records returns for the arguments the handle was made from (or
+ * what was uploaded).  PRK_ERR_ARG: capacity (in records) below the total.
+ *
+ * prk_records_destroy: frames in flight finish first (as prk_geometry_update
+ * waits).  PRK_ERR_ARG while a recorded, unflushed draw names the handle
+ * (prk_reset_draws releases it), and for a bad or destroyed handle.
+ * prk_destroy frees every handle. */
+int prk_records_from_geometry(prk_context *ctx, int32_t geometry, uint32_t first_tri, uint32_t tri_count,
+                              uint32_t tris_per_object, const float P[3], int32_t setup, int32_t *handle_out,
+                              uint32_t *list_count_out, uint64_t *total_out);
+int prk_records_upload(prk_context *ctx, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                       int32_t *handle_out);
+int prk_records_info(prk_context *ctx, int32_t handle, uint32_t *list_count_out, uint64_t *total_out);
+int prk_records_lists(prk_context *ctx, int32_t handle, uint32_t *counts, uint32_t *sorted_flags);
+int prk_records_download(prk_context *ctx, int32_t handle, prk_edge *records, uint64_t capacity);
+int prk_records_destroy(prk_context *ctx, int32_t handle);
+/* One draw of lists [first_list, first_list + list_count) of a handle, at
+ * this point of the frame's submission order: the frame, the winner ids
+ * (base + o, one per list, empty or not), the semantics / phong / texture
+ * checks and the routing (the sorted rule, the 144-edge threshold, the
+ * parallel walks) are exactly prk_draw_edge_lists' for the same lists passed
+ * from host memory -- but nothing is copied: the flush reads the records where
+ * they are, and its staging holds the pass's tables only.  A handle may be
+ * drawn any number of times, in one frame or across frames, mixed with every
+ * other kind of draw.  PRK_ERR_ARG: a bad handle, a range past the handle's
+ * lists, and prk_draw_edge_lists' cases.  PRK_ERR_UNSUPPORTED: as
+ * prk_draw_edges.  list_count == 0: PRK_OK, nothing recorded.  On any error
+ * nothing is recorded. */
+int prk_draw_records(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
+                     int32_t semantics, int32_t phong, int32_t texture);
+/* Debug/test: the bytes the most recent whole-object pass (any flush with a
+ * whole-object, edge, span or record draw) copied from the host in its one
+ * staging upload: the pass's tables, and the records of its prk_draw_edges /
+ * prk_draw_edge_lists / prk_draw_spans draws -- none for prk_draw_records. */
+int prk_debug_stage_bytes(prk_context *ctx, uint64_t *bytes_out);
+
 /* What DrawModel* leaves in the lists of a batch (projekt.cpp:3654-3869),
  * walked on the GPU: records / counts in the packed layout of
  * prk_edge_records and prk_draw_edge_lists, all pointers host memory.  List
