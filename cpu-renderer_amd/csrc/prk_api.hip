@@ -69,6 +69,8 @@ hipError_t prk_list_prep_segs(const prk::FrameParams *, const void *, uint32_t, 
 hipError_t prk_list_tables(const void *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, const void *, uint32_t,
                            uint32_t *, uint32_t *, hipStream_t);
 hipError_t prk_list_rule(const void *, uint32_t, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
+hipError_t prk_list_stats(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, hipStream_t);
+hipError_t prk_list_most(const void *, const uint32_t *, const uint32_t *, uint32_t, int32_t, uint32_t *, hipStream_t);
 hipError_t prk_objtri_count(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
                             uint32_t, uint32_t *, unsigned long long *, hipStream_t);
 hipError_t prk_objtri_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
@@ -393,7 +395,8 @@ struct prk_context {
             d_ltab,  // a pass with handle draws: its lists' counts and flags (k_list_tables)
             d_rectab, d_reccnt, d_recout,  // prk_edge_records: its tables, counts and packed records
             d_spanout,                     // prk_span_records: its packed spans
-            d_rowslot, d_rowcnt, d_rowscan, d_rowout;  // prk_row_records: its row slots, counts, scan, packed rows
+            d_rowslot, d_rowcnt, d_rowscan, d_rowout,  // prk_row_records: its row slots, counts, scan, packed rows
+            d_lstat;  // the record walks of a handle: its lists' statistics, the candidates and their most linked
         // prk_draw_rows' own buffers (frames in flight use the ones above): the
         // caller's rows and pairs, the EdgeCounts and their scan, the spans
         DevBuf d_dr_rows, d_dr_pairs, d_dr_cnt, d_dr_scan, d_dr_temp, d_dr_out;
@@ -657,7 +660,7 @@ int prk_destroy(prk_context *c) {
                         &S.d_segs, &S.d_wy, &S.d_mhuge, &S.d_objtab, &S.d_k0tab, &S.d_lscan, &S.d_lobj, &S.d_lrows,
                         &S.d_ltab, &S.d_rectab, &S.d_reccnt,
                         &S.d_recout, &S.d_spanout, &S.d_rowslot, &S.d_rowcnt, &S.d_rowscan, &S.d_rowout,
-                        &S.d_dr_rows, &S.d_dr_pairs, &S.d_dr_cnt, &S.d_dr_scan, &S.d_dr_temp, &S.d_dr_out};
+                        &S.d_lstat, &S.d_dr_rows, &S.d_dr_pairs, &S.d_dr_cnt, &S.d_dr_scan, &S.d_dr_temp, &S.d_dr_out};
         for (DevBuf *b : sb) b->release();
         if (S.h_rb) (void)hipHostFree(S.h_rb);
         if (S.stage_ev) {
@@ -3231,26 +3234,36 @@ struct ListRouter {
             if (end != env) min_steps = v;
         }
     }
-    // One list of the pass; false: over the cap.
+    // The decisions about one list of n edges, from three numbers: its
+    // thread-walk cost and edge-rows (list_walk_steps) and, where candidate()
+    // says it is wanted, its most linked edges (list_most_listed, exact up
+    // to lcap).  The host-input calls take them from the caller's records
+    // (take), the handle calls from k_list_stats and k_list_most.
+    bool candidate(uint32_t n, uint64_t cost, uint64_t edge_rows) {
+        if (!(n && cost >= min_steps && edge_rows <= kAdvMaxSteps)) return false;
+        if (!asked) {  // (the first list past the threshold: the device's slot classes)
+            asked = true;
+            if (hipSetDevice(device) == hipSuccess) lcap = std::min(prk_adv_wg_lcap(), kAdvWgCaps[4]);
+        }
+        return lcap != 0;
+    }
+    // false: over the cap.
+    bool route(uint32_t n, uint64_t cost, uint64_t edge_rows, uint32_t most, uint32_t o) {
+        if (candidate(n, cost, edge_rows))
+            for (uint32_t ci = 0; ci < 5; ++ci)
+                if (most <= kAdvWgCaps[ci] && kAdvWgCaps[ci] <= lcap) {
+                    cand.push_back(Cand{o, ci});
+                    return true;
+                }
+        return cost <= kAdvMaxSteps;
+    }
+    // One list of a host pass; false: over the cap.
     bool take(const prk_edge *e, uint32_t n, int32_t height, uint32_t o, uint64_t *edge_rows_out) {
         uint64_t edge_rows = 0;
         const uint64_t cost = list_walk_steps(e, n, height, kAdvMaxSteps, heap, &edge_rows);
         if (edge_rows_out) *edge_rows_out = edge_rows;
-        if (n && cost >= min_steps && edge_rows <= kAdvMaxSteps) {
-            if (!asked) {  // (the first list past the threshold: the device's slot classes)
-                asked = true;
-                if (hipSetDevice(device) == hipSuccess) lcap = std::min(prk_adv_wg_lcap(), kAdvWgCaps[4]);
-            }
-            if (lcap) {
-                const uint32_t most = list_most_listed(e, n, height, lcap, heap);
-                for (uint32_t ci = 0; ci < 5; ++ci)
-                    if (most <= kAdvWgCaps[ci] && kAdvWgCaps[ci] <= lcap) {
-                        cand.push_back(Cand{o, ci});
-                        return true;
-                    }
-            }
-        }
-        return cost <= kAdvMaxSteps;
+        const uint32_t most = candidate(n, cost, edge_rows) ? list_most_listed(e, n, height, lcap, heap) : 0u;
+        return route(n, cost, edge_rows, most, o);
     }
     // After the pass: the routed lists' words.
     void finish(uint32_t list_count) {
@@ -3284,30 +3297,52 @@ struct ListRouter {
         return hipSuccess;
     }
 };
-int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
-                           int32_t height, prk_edge *records_out, int32_t *next_out) {
-    if (!c || (!counts && list_count) || height < 0) return PRK_ERR_ARG;
-    uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if ((!records || !records_out) && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
-    if (list_count == 0 || total == 0) return PRK_OK;
-    const size_t nl1 = (size_t)list_count + 1;
-    std::vector<uint32_t> tab(nl1);
-    uint32_t *lscan = tab.data();
-    ListRouter router(c->device);
+// The host side of a record call's pass over its lists: each list's first
+// edge (lscan), its first pair slot (sbase: prk_span_records, prk_row_records)
+// and first row slot (rbase: prk_row_records) -- `tables` of them, nl1 words
+// each -- its route, and whether anything is over a limit.  The host-input
+// calls fill it from the caller's records, the handle calls from the device's
+// statistics (records_plan); the rest of a call (advance_run, spans_run,
+// rows_run) does not know which.
+struct WalkPlan {
+    const uint32_t list_count;
+    const size_t nl1;
+    const int tables;
+    std::vector<uint32_t> tab;
+    ListRouter router;
+    uint64_t nslot = 0, nrslot = 0;
+    uint32_t n = 0;  // the lists' edges
     bool too_long = false;
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            lscan[o] = at;
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            too_long = !router.take(e, counts[o], height, o, nullptr) || too_long;
-        }
-        lscan[list_count] = at;
+    WalkPlan(int device, uint32_t lists, int ntab)
+        : list_count(lists), nl1((size_t)lists + 1), tables(ntab), tab((size_t)ntab * nl1), router(device) {}
+    // list o (or the end of the last: o == list_count) begins at edge `at`
+    void open(uint32_t o, uint32_t at) {
+        tab[o] = at;
+        if (tables > 1) tab[nl1 + o] = (uint32_t)nslot;
+        if (tables > 2) tab[2 * nl1 + o] = (uint32_t)nrslot;
+        if (o == list_count) n = at;
     }
-    if (too_long) return PRK_ERR_LIMIT;
+    // ... was routed (fits: not over the cap) and takes floor(edge-rows / 2)
+    // pair slots and a row slot for each of the `rows` rows of its walk
+    void close(bool fits, uint64_t edge_rows, uint64_t rows) {
+        too_long = !fits || too_long;
+        if (tables > 1) nslot += edge_rows / 2;
+        if (tables > 2) nrslot += rows;
+        too_long = too_long || nslot >= 0x7FFFFFFFull || nrslot >= 0x7FFFFFFFull;
+    }
+};
+// prk_advance_edge_lists after its pass, for records in host memory or on the
+// device (kind).  records_out, next_out: null, or host memory.  keep: null,
+// or a handle in the making, which gets a buffer of its own that k_rec_export
+// writes the advanced records into (prk_records_advance); the host outputs
+// are then left to the caller, which copies them once the handle stands.
+static int advance_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
+                       prk_edge *records_out, int32_t *next_out, Records *keep) {
+    if (plan.too_long) return PRK_ERR_LIMIT;
+    ListRouter &router = plan.router;
+    const std::vector<uint32_t> &tab = plan.tab;
+    const uint32_t list_count = plan.list_count;
+    const size_t nl1 = plan.nl1;
     router.finish(list_count);
     const bool wg = router.routed() != 0;  // (else: the call as it was before there was a route)
     RESOLVE_COUNT(c);
@@ -3316,16 +3351,21 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
     router.note(c, list_count);
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const uint32_t n = (uint32_t)total;
+    const uint32_t n = plan.n;
     const size_t rec_bytes = (size_t)n * sizeof(prk_edge);
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
     PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
     PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
     if (wg) PRK_TRY(S.d_err.ensure(16));
     if (next_out) PRK_TRY(S.d_evals.ensure((size_t)n * 4));
+    void *d_out = S.d_recout.p;
+    if (keep) {
+        PRK_TRY(hipMalloc(&keep->rec, (((size_t)n * 27 + 3) / 4) * 16));  // (the caller frees it, whatever follows)
+        d_out = keep->rec;
+    }
     const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_route = wg ? d_lscan + tab.size() : nullptr,
                    *d_lists = wg ? d_route + nl1 : nullptr;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, rec_bytes, hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, rec_bytes, kind, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
     if (wg) {
         PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
@@ -3336,16 +3376,38 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
     PRK_TRY(prk_adv_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, s));
     PRK_TRY(router.launch(0, d_lists, d_lscan, height, S.d_work.p, nullptr, nullptr, nullptr, nullptr, nullptr,
                           nullptr, nullptr, (uint32_t *)S.d_err.p, s));
-    PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, S.d_recout.p, s));
+    if (records_out || keep) PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, d_out, s));
     if (next_out) PRK_TRY(prk_adv_next(S.d_work.p, n, (int32_t *)S.d_evals.p, s));
     uint32_t err = 0;
     if (wg) PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernels ran
     if (err) return PRK_ERR_DEVICE;    // a workgroup walk ran out of slots
-    PRK_TRY(hipMemcpyAsync(records_out, S.d_recout.p, rec_bytes, hipMemcpyDeviceToHost, s));
+    if (keep) return PRK_OK;           // (the caller copies, from keep->rec and d_evals, once the handle stands)
+    if (records_out) PRK_TRY(hipMemcpyAsync(records_out, d_out, rec_bytes, hipMemcpyDeviceToHost, s));
     if (next_out) PRK_TRY(hipMemcpyAsync(next_out, S.d_evals.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     return PRK_OK;
+}
+int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                           int32_t height, prk_edge *records_out, int32_t *next_out) {
+    if (!c || (!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if ((!records || !records_out) && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) return PRK_OK;
+    WalkPlan plan(c->device, list_count, 1);
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            plan.open(o, at);
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            plan.close(plan.router.take(e, counts[o], height, o, nullptr), 0, 0);
+        }
+        plan.open(list_count, at);
+    }
+    return advance_run(c, plan, records, hipMemcpyHostToDevice, height, records_out, next_out, nullptr);
 }
 
 // The work records DrawModelOptimized(RenderQueue) queues for every list of
@@ -3359,43 +3421,16 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
 // of each of two listed edges (each listed on rows [YMin, min(YMax, height))
 // at most, and in one pair a row), so no walk passes that.  spans == NULL:
 // the counting walk, no slots.
-int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
-                     int32_t height, prk_span *spans, uint64_t capacity, uint32_t *span_counts,
-                     uint64_t *total_out) {
-    if (!c || !total_out) return PRK_ERR_ARG;
-    *total_out = 0;
-    if ((!counts && list_count) || height < 0) return PRK_ERR_ARG;
-    uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if (!records && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
-    if (list_count == 0 || total == 0) {
-        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
-        return PRK_OK;
-    }
-    // lscan, then sbase: each list's first edge and first slot
-    const size_t nl1 = (size_t)list_count + 1;
-    std::vector<uint32_t> tab(2 * nl1);
-    uint32_t *lscan = tab.data(), *sbase = tab.data() + nl1;
-    ListRouter router(c->device);
-    bool too_long = false;
-    uint64_t nslot = 0;
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            lscan[o] = at;
-            sbase[o] = (uint32_t)nslot;
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            uint64_t edge_rows = 0;
-            too_long = !router.take(e, counts[o], height, o, &edge_rows) || too_long;
-            nslot += edge_rows / 2;
-            too_long = too_long || nslot >= 0x7FFFFFFFull;
-        }
-        lscan[list_count] = at;
-        sbase[list_count] = (uint32_t)nslot;
-    }
-    if (too_long) return PRK_ERR_LIMIT;
+// prk_span_records after its pass, for records in host memory or on the
+// device (kind).
+static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
+                     prk_span *spans, uint64_t capacity, uint32_t *span_counts, uint64_t *total_out) {
+    if (plan.too_long) return PRK_ERR_LIMIT;
+    ListRouter &router = plan.router;
+    const std::vector<uint32_t> &tab = plan.tab;
+    const uint32_t list_count = plan.list_count;
+    const size_t nl1 = plan.nl1;
+    const uint64_t nslot = plan.nslot;
     router.finish(list_count);
     const bool wg = router.routed() != 0;
     RESOLVE_COUNT(c);
@@ -3404,7 +3439,7 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
     router.note(c, list_count);
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const uint32_t n = (uint32_t)total;
+    const uint32_t n = plan.n;
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
     PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
     PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
@@ -3418,7 +3453,7 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
     const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1,
                    *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
     uint32_t *d_cnt = (uint32_t *)S.d_scnt.p, *d_cscan = (uint32_t *)S.d_soff.p;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
     if (wg)
         PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
@@ -3452,6 +3487,36 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
     PRK_TRY(hipStreamSynchronize(s));
     return PRK_OK;
 }
+int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                     int32_t height, prk_span *spans, uint64_t capacity, uint32_t *span_counts,
+                     uint64_t *total_out) {
+    if (!c || !total_out) return PRK_ERR_ARG;
+    *total_out = 0;
+    if ((!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) {
+        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    // lscan, then sbase: each list's first edge and first slot
+    WalkPlan plan(c->device, list_count, 2);
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            plan.open(o, at);
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            uint64_t edge_rows = 0;
+            const bool fits = plan.router.take(e, counts[o], height, o, &edge_rows);
+            plan.close(fits, edge_rows, 0);
+        }
+        plan.open(list_count, at);
+    }
+    return spans_run(c, plan, records, hipMemcpyHostToDevice, height, spans, capacity, span_counts, total_out);
+}
 
 // The row work records DrawModelOptimizedLines queues for every list of such
 // a batch (3509-3609: one buffer_line_render_work a row the walk reaches,
@@ -3465,50 +3530,17 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
 // than 1000 pairs, the reference's ThreadEdges[1000] -- the walk flags, and
 // the flag is read before anything is written.  rows == pairs == NULL: the
 // counting walk, no slots.
-int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
-                    int32_t height, prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs,
-                    uint64_t pair_capacity, uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
-    if (!c || !row_total_out || !pair_total_out) return PRK_ERR_ARG;
-    if ((!counts && list_count) || height < 0 || (rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
-    uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if (!records && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
-    if (list_count == 0 || total == 0) {
-        *row_total_out = *pair_total_out = 0;
-        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
-        return PRK_OK;
-    }
-    // lscan, sbase, rbase: each list's first edge, first pair slot and first row slot
-    const size_t nl1 = (size_t)list_count + 1;
-    std::vector<uint32_t> tab(3 * nl1);
-    uint32_t *lscan = tab.data(), *sbase = lscan + nl1, *rbase = sbase + nl1;
-    ListRouter router(c->device);
-    bool too_long = false;
-    uint64_t nslot = 0, nrslot = 0;
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            lscan[o] = at;
-            sbase[o] = (uint32_t)nslot;
-            rbase[o] = (uint32_t)nrslot;
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            uint64_t edge_rows = 0;
-            too_long = !router.take(e, counts[o], height, o, &edge_rows) || too_long;
-            nslot += edge_rows / 2;
-            if (counts[o]) {  // the walk's rows: [YMin[0], min(max YMax, height))
-                int32_t ymax = e[0].YMax;
-                for (uint32_t i = 1; i < counts[o]; ++i) ymax = std::max(ymax, e[i].YMax);
-                nrslot += (uint64_t)std::max(0, std::min(ymax, height) - e[0].YMin);
-            }
-            too_long = too_long || nslot >= 0x7FFFFFFFull || nrslot >= 0x7FFFFFFFull;
-        }
-        lscan[list_count] = at;
-        sbase[list_count] = (uint32_t)nslot;
-        rbase[list_count] = (uint32_t)nrslot;
-    }
-    if (too_long) return PRK_ERR_LIMIT;
+// prk_row_records after its pass, for records in host memory or on the
+// device (kind).
+static int rows_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
+                    prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs, uint64_t pair_capacity,
+                    uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
+    if (plan.too_long) return PRK_ERR_LIMIT;
+    ListRouter &router = plan.router;
+    const std::vector<uint32_t> &tab = plan.tab;
+    const uint32_t list_count = plan.list_count;
+    const size_t nl1 = plan.nl1;
+    const uint64_t nslot = plan.nslot, nrslot = plan.nrslot;
     router.finish(list_count);
     const bool wg = router.routed() != 0;
     RESOLVE_COUNT(c);
@@ -3516,7 +3548,7 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
     PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const uint32_t n = (uint32_t)total;
+    const uint32_t n = plan.n;
     const bool fill = rows != nullptr;
     router.note(c, list_count);
     PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
@@ -3535,7 +3567,7 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
                    *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
     uint32_t *d_pcnt = (uint32_t *)S.d_scnt.p, *d_pscan = (uint32_t *)S.d_soff.p;
     uint32_t *d_rcnt = (uint32_t *)S.d_rowcnt.p, *d_rscan = (uint32_t *)S.d_rowscan.p;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), hipMemcpyHostToDevice, s));
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
     if (wg)
         PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
@@ -3579,6 +3611,263 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
         PRK_TRY(hipMemcpyAsync(pairs, S.d_spanout.p, (size_t)npair * sizeof(prk_row_pair), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     return PRK_OK;
+}
+int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
+                    int32_t height, prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs,
+                    uint64_t pair_capacity, uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
+    if (!c || !row_total_out || !pair_total_out) return PRK_ERR_ARG;
+    if ((!counts && list_count) || height < 0 || (rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!records && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    if (list_count == 0 || total == 0) {
+        *row_total_out = *pair_total_out = 0;
+        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    // lscan, sbase, rbase: each list's first edge, first pair slot and first row slot
+    WalkPlan plan(c->device, list_count, 3);
+    {
+        const prk_edge *e = records;
+        uint32_t at = 0;
+        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
+            plan.open(o, at);
+            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+            uint64_t edge_rows = 0, walk_rows = 0;
+            const bool fits = plan.router.take(e, counts[o], height, o, &edge_rows);
+            if (counts[o]) {  // the walk's rows: [YMin[0], min(max YMax, height))
+                int32_t ymax = e[0].YMax;
+                for (uint32_t i = 1; i < counts[o]; ++i) ymax = std::max(ymax, e[i].YMax);
+                walk_rows = (uint64_t)std::max(0, std::min(ymax, height) - e[0].YMin);
+            }
+            plan.close(fits, edge_rows, walk_rows);
+        }
+        plan.open(list_count, at);
+    }
+    return rows_run(c, plan, records, hipMemcpyHostToDevice, height, rows, row_capacity, pairs, pair_capacity,
+                    row_counts, row_total_out, pair_total_out);
+}
+
+// ---- the record walks of a handle (prk.h) ----------------
+// What the device tells the host about one list (k_list_stats, k_list_most).
+struct ListStats {
+    uint64_t edge_rows = 0, scans = 0;
+    uint32_t most = 0;  // (of a route candidate; else 0)
+    int32_t ymin0 = 0, ymax_max = 0;
+};
+// list_walk_steps' value from the exact insertion scans: all earlier edges
+// bound the scans where that settles the matter, as there.  (The sweep there
+// stops adding once past the cap, the device's sum does not: the two differ
+// only in values above kAdvMaxSteps.)
+static uint64_t list_cost(uint64_t edge_rows, uint64_t scans, uint32_t n) {
+    const uint64_t all = (uint64_t)n * (n ? n - 1 : 0) / 2;
+    if (edge_rows > kAdvMaxSteps || edge_rows + all <= kAdvMaxSteps) return edge_rows + all;
+    return edge_rows + scans;
+}
+// The pass of a handle call over lists [first_list, first_list + list_count)
+// of R at `height` (not empty: `n` records from record r0, every list's flag
+// 1): the statistics kernels, their download -- a few words a list, no
+// records -- and ListRouter's decisions from them.  The device is idle.
+// stats_out: null, or list_count of them.
+static int records_plan(prk_context *c, const Records &R, uint32_t first_list, uint64_t r0, int32_t height,
+                        WalkPlan &plan, ListStats *stats_out) {
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const uint32_t nlist = plan.list_count;
+    const uint32_t *cnt = R.cnt.data() + first_list;
+    std::vector<uint32_t> lscan(plan.nl1);
+    uint32_t at = 0;
+    for (uint32_t o = 0; o < nlist; at += cnt[o], ++o) lscan[o] = at;
+    lscan[nlist] = at;
+    const void *rec = static_cast<const char *>(R.rec) + r0 * sizeof(prk_edge);
+    // device: lscan | the statistics (24 bytes a list) | the candidates | their most linked
+    const size_t stat_off = (plan.nl1 * 4 + 7) & ~(size_t)7, cand_off = stat_off + (size_t)nlist * 24;
+    PRK_TRY(S.d_lstat.ensure(cand_off + (size_t)nlist * 8));
+    char *base = static_cast<char *>(S.d_lstat.p);
+    const uint32_t *d_lscan = reinterpret_cast<const uint32_t *>(base);
+    uint32_t *d_cand = reinterpret_cast<uint32_t *>(base + cand_off), *d_most = d_cand + nlist;
+    PRK_TRY(hipMemcpyAsync(base, lscan.data(), plan.nl1 * 4, hipMemcpyHostToDevice, s));
+    PRK_TRY(prk_list_stats(rec, at, d_lscan, nlist, height, base + stat_off, s));
+    std::vector<uint64_t> raw(3 * (size_t)nlist);  // edge-rows, scans, {ymin0 ..., ymax_max ...}
+    PRK_TRY(hipMemcpyAsync(raw.data(), base + stat_off, (size_t)nlist * 24, hipMemcpyDeviceToHost, s));
+    PRK_TRY(hipStreamSynchronize(s));
+    const uint64_t *erows = raw.data(), *scans = erows + nlist;
+    const int32_t *ymin0 = reinterpret_cast<const int32_t *>(scans + nlist), *ymax_max = ymin0 + nlist;
+    ListRouter &router = plan.router;
+    std::vector<uint32_t> cand, most;
+    for (uint32_t o = 0; o < nlist; ++o)
+        if (router.candidate(cnt[o], list_cost(erows[o], scans[o], cnt[o]), erows[o])) cand.push_back(o);
+    if (!cand.empty()) {
+        most.resize(cand.size());
+        PRK_TRY(hipMemcpyAsync(d_cand, cand.data(), cand.size() * 4, hipMemcpyHostToDevice, s));
+        PRK_TRY(prk_list_most(rec, d_lscan, d_cand, (uint32_t)cand.size(), height, d_most, s));
+        PRK_TRY(hipMemcpyAsync(most.data(), d_most, cand.size() * 4, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipStreamSynchronize(s));
+    }
+    size_t k = 0;
+    for (uint32_t o = 0; o < nlist; ++o) {
+        plan.open(o, lscan[o]);
+        const uint32_t m = k < cand.size() && cand[k] == o ? most[k++] : 0u;
+        const bool fits = router.route(cnt[o], list_cost(erows[o], scans[o], cnt[o]), erows[o], m, o);
+        plan.close(fits, erows[o], (uint64_t)std::max(0, std::min(ymax_max[o], height) - ymin0[o]));
+        if (stats_out) {
+            ListStats &t = stats_out[o];
+            t.edge_rows = erows[o];
+            t.scans = scans[o];
+            t.most = m;
+            t.ymin0 = ymin0[o];
+            t.ymax_max = ymax_max[o];
+        }
+    }
+    plan.open(nlist, at);
+    return PRK_OK;
+}
+// What every handle call checks first, in the order of the host-input calls'
+// refusals: the handle and the range (PRK_ERR_ARG), the height
+// (PRK_ERR_LIMIT), the sorted flags of the range (PRK_ERR_UNSUPPORTED).
+// *n_out == 0: nothing to walk.
+static int records_range(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
+                         const Records **R_out, uint64_t *r0_out, uint64_t *n_out) {
+    const Records *R = records_of(c, handle);
+    if (!R || (uint64_t)first_list + list_count > R->cnt.size() || height < 0) return PRK_ERR_ARG;
+    if (height > 65536) return PRK_ERR_LIMIT;
+    uint64_t r0 = 0, n = 0;
+    for (uint32_t o = 0; o < first_list; ++o) r0 += R->cnt[o];
+    for (uint32_t o = 0; o < list_count; ++o) {
+        if (!R->flag[first_list + o]) return PRK_ERR_UNSUPPORTED;
+        n += R->cnt[first_list + o];
+    }
+    *R_out = R;
+    *r0_out = r0;
+    *n_out = n;
+    return PRK_OK;
+}
+// ... and what follows for a range with records: the device idle (frames in
+// flight read the scratch), then the pass.
+static int records_begin(prk_context *c, const Records &R, uint32_t first_list, uint64_t r0, int32_t height,
+                         WalkPlan &plan, ListStats *stats_out) {
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());
+    return records_plan(c, R, first_list, r0, height, plan, stats_out);
+}
+
+int prk_debug_list_stats(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
+                         uint64_t *out) {
+    const Records *R = nullptr;
+    uint64_t r0 = 0, n = 0;
+    if (!c || (!out && list_count)) return PRK_ERR_ARG;
+    const int rc = records_range(c, handle, first_list, list_count, height, &R, &r0, &n);
+    if (rc != PRK_OK) return rc;
+    std::vector<ListStats> st(list_count);
+    if (n) {
+        WalkPlan plan(c->device, list_count, 3);
+        const int rp = records_begin(c, *R, first_list, r0, height, plan, st.data());
+        if (rp != PRK_OK) return rp;
+    }
+    for (uint32_t o = 0; o < list_count; ++o) {
+        const ListStats &t = st[o];
+        uint64_t *w = out + 5 * (size_t)o;
+        w[0] = t.edge_rows;
+        w[1] = t.scans;
+        w[2] = t.most;
+        w[3] = (uint64_t)(int64_t)t.ymin0;
+        w[4] = (uint64_t)(int64_t)t.ymax_max;
+    }
+    return PRK_OK;
+}
+
+int prk_records_advance(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
+                        int32_t *advanced_out, prk_edge *records_out, int32_t *next_out) {
+    if (!c) return PRK_ERR_ARG;
+    if (advanced_out) *advanced_out = -1;
+    if (!advanced_out && !records_out && !next_out) return PRK_ERR_ARG;
+    const Records *R = nullptr;
+    uint64_t r0 = 0, n = 0;
+    const int rc = records_range(c, handle, first_list, list_count, height, &R, &r0, &n);
+    if (rc != PRK_OK) return rc;
+    if (advanced_out && c->recs.size() >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    Records A;  // the advanced lists' handle, if asked for
+    int ra = PRK_OK;
+    if (n) {
+        WalkPlan plan(c->device, list_count, 1);
+        ra = records_begin(c, *R, first_list, r0, height, plan, nullptr);
+        if (ra == PRK_OK)
+            ra = advance_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge),
+                             hipMemcpyDeviceToDevice, height, records_out, next_out, advanced_out ? &A : nullptr);
+    } else if (advanced_out) {
+        RESOLVE_COUNT(c);
+        ra = status_of(hipSetDevice(c->device));
+        if (ra == PRK_OK) ra = status_of(hipDeviceSynchronize());  // frames in flight use the scratch records_finish takes
+    }
+    if (!advanced_out || ra != PRK_OK) {
+        records_free(A);
+        return ra;
+    }
+    // the new handle (records_finish: the walk changes no YMin, YMax or Left,
+    // so k_list_rule finds every flag 1 again), then the host's outputs --
+    // nothing is written, and no handle is made, unless all of it succeeded
+    prk_context::SpanScratch &S = c->spans;
+    hipStream_t s = c->own_stream;
+    R = records_of(c, handle);
+    ra = records_tab_alloc(A, list_count);
+    if (ra == PRK_OK && list_count)
+        ra = status_of(hipMemcpyAsync(A.tab, R->d_cnt() + first_list, (size_t)list_count * 4,
+                                      hipMemcpyDeviceToDevice, s));
+    if (ra == PRK_OK) ra = records_finish(c, A, list_count, n);
+    if (ra == PRK_OK && n && records_out)
+        ra = status_of(hipMemcpyAsync(records_out, A.rec, (size_t)n * sizeof(prk_edge), hipMemcpyDeviceToHost, s));
+    if (ra == PRK_OK && n && next_out)
+        ra = status_of(hipMemcpyAsync(next_out, S.d_evals.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (ra == PRK_OK) ra = status_of(hipStreamSynchronize(s));
+    if (ra != PRK_OK) {
+        records_free(A);
+        return ra;
+    }
+    *advanced_out = (int32_t)c->recs.size();
+    c->recs.push_back(std::move(A));
+    return PRK_OK;
+}
+
+int prk_records_spans(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
+                      prk_span *spans, uint64_t capacity, uint32_t *span_counts, uint64_t *total_out) {
+    if (!c || !total_out) return PRK_ERR_ARG;
+    *total_out = 0;
+    const Records *R = nullptr;
+    uint64_t r0 = 0, n = 0;
+    const int rc = records_range(c, handle, first_list, list_count, height, &R, &r0, &n);
+    if (rc != PRK_OK) return rc;
+    if (n == 0) {
+        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    WalkPlan plan(c->device, list_count, 2);
+    const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
+    if (rp != PRK_OK) return rp;
+    return spans_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge), hipMemcpyDeviceToDevice,
+                     height, spans, capacity, span_counts, total_out);
+}
+
+int prk_records_rows(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
+                     prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs, uint64_t pair_capacity,
+                     uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
+    if (!c || !row_total_out || !pair_total_out) return PRK_ERR_ARG;
+    if ((rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
+    const Records *R = nullptr;
+    uint64_t r0 = 0, n = 0;
+    const int rc = records_range(c, handle, first_list, list_count, height, &R, &r0, &n);
+    if (rc != PRK_OK) return rc;
+    if (n == 0) {
+        *row_total_out = *pair_total_out = 0;
+        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
+        return PRK_OK;
+    }
+    WalkPlan plan(c->device, list_count, 3);
+    const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
+    if (rp != PRK_OK) return rp;
+    return rows_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge), hipMemcpyDeviceToDevice,
+                    height, rows, row_capacity, pairs, pair_capacity, row_counts, row_total_out, pair_total_out);
 }
 
 // ConstructSphere (projekt.cpp:4123-4289): the reference's only test mesh.

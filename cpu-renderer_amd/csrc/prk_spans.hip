@@ -4411,6 +4411,164 @@ __global__ void __launch_bounds__(256) k_list_rule(const uint32_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// The record walks of a handle (prk_records_advance / _spans / _rows): what
+// prk_api.hip's host pass takes from the caller's records -- list_walk_steps,
+// list_most_listed, the row slots -- from records that are only on the device
+// (DESIGN §4.4.8).  Every list holds the sorted rule (the handle's flag), so
+// within a list YMin is non-decreasing and 0 <= YMin <= YMax; the records
+// with YMin < height, the ones the walk ever inserts, are a prefix of m.
+//   k_list_stats  a lane per record j of its list: its edge-rows
+//                 max(0, min(YMax, height) - YMin); for j < m its insertion
+//                 scan ub_j - j - 1, ub_j = #{i < m : YMin[i] <= YMax[j]} by
+//                 an upper-bound search of the list's own YMin (edge j is
+//                 still linked when edge i > j is inserted iff YMax[j] >=
+//                 YMin[i], and every i <= j passes, so the search starts at
+//                 j + 1); YMin of record 0 and the largest YMax.  Summed by
+//                 wave and list, then one atomic each: integers, so the sums
+//                 do not depend on the order.
+//   k_list_most   a workgroup per candidate list: the most edges linked at
+//                 once, the largest over rows y of #{j < m : YMin[j] <= y <=
+//                 YMax[j]}.  A difference array over the rows YMin[0] ..
+//                 YMin[m - 1] in LDS windows of kMostRows (+1 at YMin, -1 at
+//                 YMax + 1), a workgroup scan with the carry of the windows
+//                 before, and the largest running count.  The count only
+//                 falls on a row that is no record's YMin, so the largest
+//                 over all rows is the largest over the YMin rows -- the heap
+//                 of list_most_listed after a tie group's last insertion.
+// The records are read where the handle keeps them (any dword address): the
+// three dwords of a record, 108 bytes apart, as in k_list_rule.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+__global__ void __launch_bounds__(256) k_list_stats(const uint32_t *__restrict__ rec, uint32_t nedge,
+                                                    const uint32_t *__restrict__ lscan, uint32_t nlist,
+                                                    int32_t height, unsigned long long *__restrict__ erows,
+                                                    unsigned long long *__restrict__ scans,
+                                                    int32_t *__restrict__ ymin0, int32_t *__restrict__ ymaxmax) {
+    const uint32_t tid = threadIdx.x, e = blockIdx.x * 256u + tid;
+    const bool on = e < nedge;
+    uint32_t l = 0;
+    unsigned long long er = 0, sc = 0;
+    int32_t ymax = 0;
+    if (on) {
+        uint32_t lo = 0, hi = nlist;  // the last list with lscan[l] <= e (an empty list is never the last)
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (lscan[mid] <= e) lo = mid;
+            else hi = mid;
+        }
+        l = lo;
+        const uint32_t l0 = lscan[l], n = lscan[l + 1] - l0, j = e - l0;
+        const uint32_t *r = rec + (size_t)27u * e;
+        ymax = (int32_t)r[0];
+        const int32_t ymin = (int32_t)r[7];
+        er = (unsigned long long)max(0, min(ymax, height) - ymin);
+        if (j == 0) ymin0[l] = ymin;
+        if (ymin < height) {
+            const int32_t key = min(ymax, height - 1);  // (YMin[i] <= key: i < m and YMin[i] <= YMax[j])
+            const uint32_t *y = rec + (size_t)27u * l0 + 7;
+            uint32_t a = j + 1, b = n;  // the first i in (j, n) with YMin[i] > key
+            while (a < b) {
+                const uint32_t mid = a + ((b - a) >> 1);
+                if ((int32_t)y[(size_t)27u * mid] <= key) a = mid + 1;
+                else b = mid;
+            }
+            sc = a - j - 1;
+        }
+    }
+    unsigned long long todo = __ballot(on);
+    while (todo) {  // (wave-uniform: one turn per list of the wave)
+        const int lead = __ffsll((long long)todo) - 1;
+        const uint32_t ll = (uint32_t)__builtin_amdgcn_readlane((int)l, lead);
+        const bool mine = on && l == ll;
+        const unsigned long long s_er = wave_sum_u64(mine ? er : 0ull), s_sc = wave_sum_u64(mine ? sc : 0ull);
+        int32_t top = mine ? ymax : 0;
+#pragma unroll
+        for (int off = 32; off; off >>= 1) top = max(top, __shfl_xor(top, off, 64));
+        if ((int)(tid & 63u) == lead) {
+            if (s_er) atomicAdd(&erows[ll], s_er);
+            if (s_sc) atomicAdd(&scans[ll], s_sc);
+            if (top) atomicMax(&ymaxmax[ll], top);
+        }
+        todo &= ~__ballot(mine);
+    }
+}
+constexpr uint32_t kMostRows = 8192;  // rows of a window of k_list_most: 32 KB of LDS, 65,536 rows in 8 windows
+__global__ void __launch_bounds__(256) k_list_most(const uint32_t *__restrict__ rec,
+                                                   const uint32_t *__restrict__ lscan,
+                                                   const uint32_t *__restrict__ cand, int32_t height,
+                                                   uint32_t *__restrict__ most) {
+    __shared__ int32_t diff[kMostRows];
+    __shared__ int32_t part[256];
+    const uint32_t tid = threadIdx.x, l = cand[blockIdx.x], l0 = lscan[l], n = lscan[l + 1] - l0;
+    const uint32_t *ymaxw = rec + (size_t)27u * l0, *yminw = ymaxw + 7;
+    // the first record with YMin > key among the first `end` (workgroup-uniform)
+    auto upper = [&](int32_t key, uint32_t end) {
+        uint32_t a = 0, b = end;
+        while (a < b) {
+            const uint32_t mid = a + ((b - a) >> 1);
+            if ((int32_t)yminw[(size_t)27u * mid] <= key) a = mid + 1;
+            else b = mid;
+        }
+        return a;
+    };
+    const uint32_t m = upper(height - 1, n);
+    if (m == 0) {
+        if (tid == 0) most[blockIdx.x] = 0u;
+        return;
+    }
+    const int32_t y0 = (int32_t)yminw[0], ylast = (int32_t)yminw[(size_t)27u * (m - 1)];  // (0 <= y0 <= ylast < 65536)
+    int32_t carry = 0, best = 0;
+    for (int32_t w0 = y0; w0 <= ylast; w0 += (int32_t)kMostRows) {
+        const uint32_t len = min(kMostRows, (uint32_t)(ylast - w0) + 1u);
+        const int32_t wend = w0 + (int32_t)len - 1;
+        for (uint32_t i = tid; i < len; i += 256u) diff[i] = 0;
+        __syncthreads();
+        // an edge whose YMin is past the window has YMax + 1 past it as well
+        const uint32_t hi = upper(wend, m);
+        for (uint32_t i = tid; i < hi; i += 256u) {
+            const int32_t ymin = (int32_t)yminw[(size_t)27u * i], ymax = (int32_t)ymaxw[(size_t)27u * i];
+            if (ymin >= w0) atomicAdd(&diff[ymin - w0], 1);
+            if (ymax < wend && ymax + 1 >= w0) atomicAdd(&diff[ymax + 1 - w0], -1);
+        }
+        __syncthreads();
+        // a run of consecutive rows a lane, the runs' sums scanned across the workgroup
+        const uint32_t chunk = (len + 255u) / 256u, b0 = min(len, tid * chunk), b1 = min(len, b0 + chunk);
+        int32_t sum = 0;
+        for (uint32_t k = b0; k < b1; ++k) sum += diff[k];
+        part[tid] = sum;
+        __syncthreads();
+        for (uint32_t off = 1; off < 256u; off <<= 1) {
+            const int32_t v = tid >= off ? part[tid - off] : 0;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        int32_t run = carry + (tid ? part[tid - 1] : 0);
+        for (uint32_t k = b0; k < b1; ++k) {
+            run += diff[k];
+            best = max(best, run);
+        }
+        carry += part[255];
+        __syncthreads();  // (diff and part are rewritten by the next window)
+    }
+    part[tid] = best;
+    __syncthreads();
+    for (uint32_t off = 128; off; off >>= 1) {
+        if (tid < off) part[tid] = max(part[tid], part[tid + off]);
+        __syncthreads();
+    }
+    if (tid == 0) most[blockIdx.x] = (uint32_t)part[0];
+}
+
+// ---------------------------------------------------------------------------
 // prk_advance_edge_lists: the list DrawModel* leaves in the caller's
 // edge_info array (3654-3869), for a batch of sorted lists and no frame:
 // k_adv_import (k_list_prep's import alone: list o's records at slots
@@ -5529,6 +5687,31 @@ hipError_t prk_list_rule(const void *records, uint32_t nedge, const uint32_t *ls
     if (e != hipSuccess || nedge == 0) return e;
     hipLaunchKernelGGL(prk::k_list_rule, dim3((nedge + 255) / 256), dim3(256), 0, s,
                        reinterpret_cast<const uint32_t *>(records), nedge, lscan, nlist, lflag);
+    return hipGetLastError();
+}
+// The walk statistics of every list of `nedge` packed records, which hold
+// the sorted rule (k_list_stats).  stats: 24 bytes a list, zeroed here --
+// nlist edge-row sums (u64), nlist insertion-scan sums (u64), nlist YMin of
+// the first record (i32), nlist largest YMax (i32).
+hipError_t prk_list_stats(const void *records, uint32_t nedge, const uint32_t *lscan, uint32_t nlist, int32_t height,
+                          void *stats, hipStream_t s) {
+    if (nlist == 0) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(stats, 0, (size_t)nlist * 24, s);
+    if (e != hipSuccess || nedge == 0) return e;
+    unsigned long long *erows = reinterpret_cast<unsigned long long *>(stats), *scans = erows + nlist;
+    int32_t *ymin0 = reinterpret_cast<int32_t *>(scans + nlist), *ymaxmax = ymin0 + nlist;
+    hipLaunchKernelGGL(prk::k_list_stats, dim3((nedge + 255) / 256), dim3(256), 0, s,
+                       reinterpret_cast<const uint32_t *>(records), nedge, lscan, nlist, height, erows, scans, ymin0,
+                       ymaxmax);
+    return hipGetLastError();
+}
+// The most edges linked at once of the `ncand` lists cand[] names, among the
+// same records (k_list_most); most: a word a candidate.
+hipError_t prk_list_most(const void *records, const uint32_t *lscan, const uint32_t *cand, uint32_t ncand,
+                         int32_t height, uint32_t *most, hipStream_t s) {
+    if (ncand == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_list_most, dim3(ncand), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(records),
+                       lscan, cand, height, most);
     return hipGetLastError();
 }
 // FillEdgeTable of the pass's object triangles: per-triangle edge and

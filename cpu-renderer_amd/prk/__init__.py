@@ -124,6 +124,13 @@ _SIGS = {
                                   C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "prk_draw_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32,
                                 C.c_int32]),
+    "prk_records_advance": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_int32),
+                                      C.c_void_p, C.c_void_p]),
+    "prk_records_spans": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.POINTER(C.c_uint64)]),
+    "prk_records_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "prk_debug_list_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -424,6 +431,74 @@ class Records:
         w = np.empty((self.total, 27), np.uint32)
         _check("prk_records_download", self._r._L.prk_records_download(self._r._h, self.handle, _ptr(w), self.total))
         return w
+
+    def _range(self, first_list, list_count):
+        first = int(first_list)
+        n = self.list_count - first if list_count is None else int(list_count)
+        if first < 0 or n < 0 or first + n > self.list_count:
+            raise ValueError("lists [%d, %d) of a handle of %d" % (first, first + n, self.list_count))
+        return first, n, int(self.counts()[first:first + n].sum(dtype=np.uint64))
+
+    def advance(self, height, first_list=0, list_count=None, keep=False, host=True):
+        """prk_records_advance: what DrawModel* leaves in lists [first_list,
+        first_list + list_count) over a frame of `height` rows, the records
+        never leaving the device.  host: (words_out, next) as
+        Renderer.advance_edge_lists returns them; keep: a new Records that
+        holds the advanced lists; both: (words_out, next, Records)."""
+        first, n, total = self._range(first_list, list_count)
+        if not (keep or host):
+            raise ValueError("advance: neither keep nor host")
+        out = np.empty((total, 27), np.uint32) if host else None
+        nxt = np.empty(total, np.int32) if host else None
+        h = C.c_int32(-1)
+        _check("prk_records_advance", self._r._L.prk_records_advance(
+            self._r._h, self.handle, first, n, int(height), C.byref(h) if keep else None,
+            _ptr(out) if host else None, _ptr(nxt) if host else None))
+        if not keep:
+            return out, nxt
+        adv = Records(self._r, h.value)
+        return (out, nxt, adv) if host else adv
+
+    def spans(self, height, first_list=0, list_count=None):
+        """prk_records_spans: what Renderer.span_records returns for the
+        same lists, (span_words uint32 [total, 25], span_counts)."""
+        first, n, _ = self._range(first_list, list_count)
+        L, rh = self._r._L, self._r._h
+        sc = np.zeros(n, np.uint32)
+        total = C.c_uint64(0)
+        _check("prk_records_spans", L.prk_records_spans(rh, self.handle, first, n, int(height), None, 0, _ptr(sc),
+                                                        C.byref(total)))
+        spans = np.empty((total.value, 25), np.uint32)
+        _check("prk_records_spans", L.prk_records_spans(rh, self.handle, first, n, int(height), _ptr(spans),
+                                                        total.value, _ptr(sc), C.byref(total)))
+        return spans, sc
+
+    def rows(self, height, first_list=0, list_count=None):
+        """prk_records_rows: what Renderer.row_records returns for the same
+        lists, (rows int32 [k, 2], pairs uint32 [m, 24], row_counts)."""
+        first, n, _ = self._range(first_list, list_count)
+        L, rh = self._r._L, self._r._h
+        rc = np.zeros(n, np.uint32)
+        nrow, npair = C.c_uint64(0), C.c_uint64(0)
+        _check("prk_records_rows", L.prk_records_rows(rh, self.handle, first, n, int(height), None, 0, None, 0,
+                                                      _ptr(rc), C.byref(nrow), C.byref(npair)))
+        rows = np.empty((nrow.value, 2), np.int32)
+        pairs = np.empty((npair.value, 24), np.uint32)
+        _check("prk_records_rows", L.prk_records_rows(rh, self.handle, first, n, int(height), _ptr(rows), nrow.value,
+                                                      _ptr(pairs), npair.value, _ptr(rc), C.byref(nrow),
+                                                      C.byref(npair)))
+        return rows, pairs, rc
+
+    def list_stats(self, height, first_list=0, list_count=None):
+        """prk_debug_list_stats: int64 [list_count, 5] -- each list's
+        edge-rows, insertion scans, most edges linked at once (0 unless a
+        route candidate), first YMin and largest YMax, as the device
+        computes them for the walks above."""
+        first, n, _ = self._range(first_list, list_count)
+        out = np.zeros((n, 5), np.uint64)
+        _check("prk_debug_list_stats", self._r._L.prk_debug_list_stats(self._r._h, self.handle, first, n, int(height),
+                                                                       _ptr(out)))
+        return out.view(np.int64)
 
     def close(self):
         """prk_records_destroy (the Renderer's close frees what is left)."""

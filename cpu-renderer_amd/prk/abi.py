@@ -93,6 +93,17 @@ ROW_PAIR_SPAN_WORD = ([h * 12 + k for k in range(5) for h in (0, 1)] + [5, 6, 7,
                       [9, 10, 11] + [21, 22, 23])
 
 
+# The record walks of a handle (prk.h): each entry point and its arguments
+RECORD_WALK_ARGS = {
+    "prk_records_advance": 8,
+    "prk_records_spans": 9,
+    "prk_records_rows": 12,
+    "prk_debug_list_stats": 6,
+}
+# prk_debug_list_stats: the words of a list
+LIST_STATS_FIELDS = ("edge_rows", "scans", "most", "ymin0", "ymax_max")
+
+
 def make_transform(D, F, M2P, cx, cy):
     t = PrkTransform()
     t.DistanceAboveTarget = D

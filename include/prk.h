@@ -872,6 +872,58 @@ int prk_draw_rows(prk_context *ctx, const prk_row *rows, uint64_t row_count,
                   const prk_row_pair *pairs, uint64_t pair_count,
                   int32_t semantics, int32_t phong, int32_t texture);
 
+/* The three record walks for lists [first_list, first_list + list_count) of a
+ * record handle (prk_records_*): FillEdgeTable once into the handle, then
+ * what DrawModel* leaves and queues every frame, without the records crossing
+ * to the host.  Each call returns the status of its host-input call
+ * (prk_advance_edge_lists, prk_span_records, prk_row_records) given
+ * prk_records_download's records of that range and the handle's counts, and
+ * writes the same words bit for bit: the range is copied on the device into
+ * the walk's input and the same kernels run.  The sizing calls (NULL arrays),
+ * the short-capacity behaviour, the limits and prk_debug_list_routes are
+ * those calls'.  Synchronous; needs no target, records no draw, touches no
+ * recorded draw and no prk_stats; frames in flight finish first.
+ *
+ * What the host-input calls decide in a host pass over the records -- the
+ * 2^21 cap, the thread / workgroup route and its slot class, every list's
+ * pair and row slots -- is decided here from a few words a list that the
+ * device computes where the records are, by the same code.
+ * The one difference: the host pass stops adding a list's insertion scans
+ * once its cost is past 2^21, the device's sum is exact.  The two costs can
+ * differ only in values above 2^21, and a route only where
+ * PRK_ADV_WG_MIN_STEPS is set between them; the exact sum governs here.
+ *
+ * Differences: a list of the range whose sorted flag is 0 is
+ * PRK_ERR_UNSUPPORTED before any walk (the flag is the sorted rule).
+ * PRK_ERR_ARG: a handle that does not exist or was destroyed, a range past
+ * the handle's lists, height < 0, a NULL context (and the NULL pointers the
+ * host-input calls refuse).  On any error but the short capacity nothing is
+ * written to any output.
+ *
+ * prk_records_advance: records_out (NULL, or as prk_advance_edge_lists'),
+ * next_out (NULL, or as there; it needs no records_out) and advanced_out
+ * (NULL, or receives a new handle of list_count lists that holds the
+ * advanced records: same counts, every flag 1 -- nothing crosses to the host,
+ * and prk_draw_records of it draws what prk_draw_edge_lists of records_out
+ * draws).  All three NULL: PRK_ERR_ARG.  On any error no handle is made and
+ * *advanced_out is -1.  The handle given is not changed.
+ *
+ * prk_debug_list_stats: the raw numbers, five words a list -- its edge-rows
+ * sum of max(0, min(YMax, height) - YMin), its insertion scans, its most
+ * edges linked at once (0 unless the list is a route candidate), YMin of its
+ * first record and its largest YMax. */
+int prk_records_advance(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
+                        int32_t height, int32_t *advanced_out, prk_edge *records_out, int32_t *next_out);
+int prk_records_spans(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
+                      int32_t height, prk_span *spans, uint64_t capacity, uint32_t *span_counts,
+                      uint64_t *total_out);
+int prk_records_rows(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
+                     int32_t height, prk_row *rows, uint64_t row_capacity,
+                     prk_row_pair *pairs, uint64_t pair_capacity,
+                     uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out);
+int prk_debug_list_stats(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
+                         int32_t height, uint64_t *out);
+
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
  * vertex count through *count_out. */
