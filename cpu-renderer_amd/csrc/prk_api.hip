@@ -101,6 +101,8 @@ hipError_t prk_row_pack(const void *, const void *, const uint32_t *, const uint
                         const uint32_t *, uint32_t, uint32_t, uint32_t, void *, void *, hipStream_t);
 hipError_t prk_rows_counts(const void *, uint32_t, uint32_t *, hipStream_t);
 hipError_t prk_rows_unpack(const void *, const uint32_t *, uint32_t, const void *, uint32_t, void *, hipStream_t);
+hipError_t prk_span_handle_walk(const prk::FrameParams *, uint32_t, uint32_t, uint32_t, const void *, uint32_t, uint32_t,
+                                const unsigned long long *, void *, void *, uint32_t *, hipStream_t);
 hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
                           void *, uint32_t, void *, hipStream_t);
 hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
@@ -241,6 +243,15 @@ struct Records {
     const uint32_t *d_flag() const { return tab + cnt.size() + 1; }
 };
 
+// A span batch (prk_spans_*): packed prk_span records kept in device memory.
+// The host keeps each list's span count and the total -- no spans.
+struct SpanBatch {
+    void *sp = nullptr;  // the packed spans, readable up to a multiple of 16 bytes (the spare dwords zero)
+    std::vector<uint32_t> cnt;
+    uint64_t total = 0;
+    bool live = false;
+};
+
 int status_of(hipError_t e) {
     if (e == hipSuccess) return PRK_OK;
     static const bool trace = std::getenv("PRK_TRACE_HIP") != nullptr;  // diagnostics: name the HIP error
@@ -283,6 +294,10 @@ struct prk_context {
     // prk_draw_records DrawRec: src_kind 4, geom the handle, geom_tri0 /
     // tri_count its lists, src_off / src_n their records within the handle.
     std::vector<Records> recs;
+    // span batches by handle, their own number space (a destroyed one keeps
+    // its slot, dead).  A prk_draw_span_records DrawRec: src_kind 5, geom the
+    // handle, src_off / src_n its spans within the handle.
+    std::vector<SpanBatch> sbatches;
     std::vector<prk::DrawRec> draws;
     uint32_t pending_tris = 0;
     std::vector<prk_edge> pend_edges;  // prk_draw_edges input of the pending frame
@@ -630,6 +645,7 @@ int prk_destroy(prk_context *c) {
         (void)hipFree(r.rec);
         (void)hipFree(r.tab);
     }
+    for (auto &b : c->sbatches) (void)hipFree(b.sp);
     if (c->owns_target) {
         (void)hipFree(c->color);
         (void)hipFree(c->zbuf);
@@ -1268,8 +1284,8 @@ static int draw_src(prk_context *c, uint32_t kind, uint32_t off, uint32_t n, uin
     int mode = prk::MODE_AVX;
     if (semantics == PRK_SEM_SCALAR) {
         // DrawModel on a caller's edge list (projekt.cpp:162-601); work
-        // records (kind 2) are FillLineOptimized spans only
-        if (kind == 2) return PRK_ERR_UNSUPPORTED;
+        // records (kind 2; kind 5: those of a span handle) are FillLineOptimized spans only
+        if (kind == 2 || kind == 5) return PRK_ERR_UNSUPPORTED;
         const bool tex = texture >= 0;
         mode = phong ? (tex ? prk::MODE_SC_PHONG_TEX : prk::MODE_SC_PHONG)
                      : (tex ? prk::MODE_SC_GOURAUD_TEX : prk::MODE_SC_GOURAUD);
@@ -1357,9 +1373,11 @@ int prk_draw_spans(prk_context *c, const prk_span *spans, uint32_t count, int32_
 // -- no host loop over the pairs, only the one over the rows that checks the
 // arguments -- and the spans come back into the pending frame's span input,
 // where the draw is prk_draw_spans' from then on.  The buffers are this
-// call's own: frames in flight keep the span scratch.
+// call's own: frames in flight keep the span scratch.  keep
+// (prk_spans_upload_rows; `out` is then NULL): the spans are written into
+// that device buffer (25 * npair dwords rounded up to four) and stay there.
 static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_row_pair *pairs,
-                         uint32_t npair, prk_span *out) {
+                         uint32_t npair, prk_span *out, void *keep = nullptr) {
     PRK_TRY(hipSetDevice(c->device));
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
@@ -1368,7 +1386,7 @@ static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, con
     PRK_TRY(S.d_dr_pairs.ensure((size_t)npair * sizeof(prk_row_pair)));
     PRK_TRY(S.d_dr_cnt.ensure(((size_t)nrow + 1) * 4));
     PRK_TRY(S.d_dr_scan.ensure(((size_t)nrow + 1) * 4));
-    PRK_TRY(S.d_dr_out.ensure(out_bytes));
+    if (!keep) PRK_TRY(S.d_dr_out.ensure(out_bytes));
     PRK_TRY(hipMemcpyAsync(S.d_dr_rows.p, rows, (size_t)nrow * sizeof(prk_row), hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemcpyAsync(S.d_dr_pairs.p, pairs, (size_t)npair * sizeof(prk_row_pair), hipMemcpyHostToDevice, s));
     PRK_TRY(prk_rows_counts(S.d_dr_rows.p, nrow, (uint32_t *)S.d_dr_cnt.p, s));
@@ -1377,8 +1395,8 @@ static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, con
     PRK_TRY(S.d_dr_temp.ensure(std::max<size_t>(tb, 16)));
     PRK_TRY(prk_scan_u32((const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, S.d_dr_temp.p, &tb, s));
     PRK_TRY(prk_rows_unpack(S.d_dr_rows.p, (const uint32_t *)S.d_dr_scan.p, nrow, S.d_dr_pairs.p, npair,
-                            S.d_dr_out.p, s));
-    PRK_TRY(hipMemcpyAsync(out, S.d_dr_out.p, (size_t)npair * sizeof(prk_span), hipMemcpyDeviceToHost, s));
+                            keep ? keep : S.d_dr_out.p, s));
+    if (!keep) PRK_TRY(hipMemcpyAsync(out, S.d_dr_out.p, (size_t)npair * sizeof(prk_span), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));  // (the caller's arrays are copied at the call)
     return PRK_OK;
 }
@@ -1977,6 +1995,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     for (const prk::DrawRec &d : draws) handles = handles || d.src_kind == 4;
     S.h_segs.clear();
     S.h_lsrc.clear();
+    struct HandleRun {  // a prk_draw_span_records draw: its launch after the thread walks
+        uint32_t draw, g0, obj0, first, n;
+        const void *sp;
+    };
+    std::vector<HandleRun> hruns;
     std::vector<uint8_t> seg_staged;
     auto add_seg = [&](uint64_t src, bool staged, uint32_t n) {
         if (!handles || !n) return;
@@ -2001,6 +2024,13 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         } else if (d.src_kind == 2) {
             if (!d.src_n) continue;
             S.h_runs.push_back(ObjRun{2u, di, (uint32_t)nobj64, d.src_n, 0u, 0u, d.first_global, 0u, 0u, d.src_off, 0u, 0u});
+            nobj64 += d.src_n;
+        } else if (d.src_kind == 5) {
+            // the spans stay where they are: a run of one-slot objects that
+            // k_span_handle_walk fills from the handle's buffer
+            if (!d.src_n) continue;
+            S.h_runs.push_back(ObjRun{4u, di, (uint32_t)nobj64, d.src_n, 0u, 0u, d.first_global, 0u, 0u, d.src_off, 0u, 0u});
+            hruns.push_back(HandleRun{di, d.first_global, (uint32_t)nobj64, d.src_off, d.src_n, c->sbatches[d.geom].sp});
             nobj64 += d.src_n;
         } else if (d.src_kind == 3 || d.src_kind == 4) {
             // one run for the batch; its sorted lists are routed like triangle
@@ -2591,6 +2621,9 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(prk_obj_walk(&fp, d_objs, nobj, escan, total0p, S.d_work.p, oslot, S.d_recs.p,
                          scalar ? S.d_srecs.p : nullptr, S.d_pos.p, (uint32_t *)S.d_span_tri.p, d_spans_in,
                          (uint32_t *)S.d_err.p, thread_links ? 1 : 0, d_segs, d_nseg, (uint32_t)max_segs, s));
+    for (const HandleRun &h : hruns)  // the span handles' draws, from their own buffers
+        PRK_TRY(prk_span_handle_walk(&fp, h.draw, h.g0, h.obj0, h.sp, h.first, h.n, oslot, S.d_recs.p, S.d_pos.p,
+                                     (uint32_t *)S.d_span_tri.p, s));
     for (const Group &g : groups) {
         if (g.big)
             PRK_TRY(prk_big_walk(&fp, g.mode, g.lds ? 1 : 0, d_objs, d_cbig + g.start, d_coff + g.start, d_ccap + g.start,
@@ -3422,10 +3455,15 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
 // at most, and in one pair a row), so no walk passes that.  spans == NULL:
 // the counting walk, no slots.
 // prk_span_records after its pass, for records in host memory or on the
-// device (kind).
+// device (kind).  keep (prk_spans_from_records; `spans` is then NULL and no
+// capacity applies): k_span_pack writes into a buffer of the batch's own and
+// nothing is copied to the host but the counts -- keep->sp, keep->cnt and
+// keep->total are set on PRK_OK only (sp stays NULL for no spans).
 static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
-                     prk_span *spans, uint64_t capacity, uint32_t *span_counts, uint64_t *total_out) {
+                     prk_span *spans, uint64_t capacity, uint32_t *span_counts, uint64_t *total_out,
+                     SpanBatch *keep = nullptr) {
     if (plan.too_long) return PRK_ERR_LIMIT;
+    const bool fill = spans || keep;
     ListRouter &router = plan.router;
     const std::vector<uint32_t> &tab = plan.tab;
     const uint32_t list_count = plan.list_count;
@@ -3446,7 +3484,7 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     PRK_TRY(S.d_scnt.ensure(nl1 * 4));
     PRK_TRY(S.d_soff.ensure(nl1 * 4));
     PRK_TRY(S.d_err.ensure(16));
-    if (spans) {
+    if (fill) {
         PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));  // prk_spans.hip PairRaw
         PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)nslot * 4, 16)));    // the slots' rows
     }
@@ -3462,10 +3500,10 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
     PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
     PRK_TRY(prk_span_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, d_sbase,
-                          spans ? S.d_raw.p : nullptr, spans ? (int32_t *)S.d_pos.p : nullptr, d_cnt,
+                          fill ? S.d_raw.p : nullptr, fill ? (int32_t *)S.d_pos.p : nullptr, d_cnt,
                           (uint32_t *)S.d_err.p, s));
-    PRK_TRY(router.launch(1, d_lists, d_lscan, height, S.d_work.p, d_sbase, nullptr, spans ? S.d_raw.p : nullptr,
-                          spans ? (int32_t *)S.d_pos.p : nullptr, nullptr, d_cnt, nullptr, (uint32_t *)S.d_err.p, s));
+    PRK_TRY(router.launch(1, d_lists, d_lscan, height, S.d_work.p, d_sbase, nullptr, fill ? S.d_raw.p : nullptr,
+                          fill ? (int32_t *)S.d_pos.p : nullptr, nullptr, d_cnt, nullptr, (uint32_t *)S.d_err.p, s));
     size_t tb = 0;
     PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, nullptr, &tb, s));
     PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
@@ -3477,6 +3515,24 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     if (err) return PRK_ERR_DEVICE;  // a walk passed its slot bound
     *total_out = nspan;
     if (span_counts) PRK_TRY(hipMemcpy(span_counts, d_cnt, (size_t)list_count * 4, hipMemcpyDeviceToHost));
+    if (keep) {  // the packed spans into the batch's own buffer; they stay there
+        std::vector<uint32_t> cnt(list_count);
+        PRK_TRY(hipMemcpy(cnt.data(), d_cnt, (size_t)list_count * 4, hipMemcpyDeviceToHost));
+        void *buf = nullptr;
+        if (nspan) {
+            PRK_TRY(hipMalloc(&buf, (((size_t)nspan * 25 + 3) / 4) * 16));
+            hipError_t e = prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, buf, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) {
+                (void)hipFree(buf);
+                return status_of(e);
+            }
+        }
+        keep->sp = buf;
+        keep->cnt = std::move(cnt);
+        keep->total = nspan;
+        return PRK_OK;
+    }
     if (!spans) return PRK_OK;
     if (capacity < nspan) return PRK_ERR_ARG;
     if (nspan == 0) return PRK_OK;
@@ -3868,6 +3924,151 @@ int prk_records_rows(prk_context *c, int32_t handle, uint32_t first_list, uint32
     if (rp != PRK_OK) return rp;
     return rows_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge), hipMemcpyDeviceToDevice,
                     height, rows, row_capacity, pairs, pair_capacity, row_counts, row_total_out, pair_total_out);
+}
+
+// ---- span handles (prk.h) ---------------------------------
+// Packed prk_span records that stay on the device: made by the span walk of a
+// record handle (spans_run with `keep`), uploaded once, or regrouped from row
+// work records (rows_to_spans with `keep`); drawn where they are
+// (flush_spans, src_kind 5 -> k_span_handle_walk).
+static SpanBatch *sbatch_of(prk_context *c, int32_t handle) {
+    if (!c || handle < 0 || (size_t)handle >= c->sbatches.size() || !c->sbatches[handle].live) return nullptr;
+    return &c->sbatches[handle];
+}
+static int sbatch_add(prk_context *c, SpanBatch &&B, int32_t *spans_out) {
+    B.live = true;
+    *spans_out = (int32_t)c->sbatches.size();
+    c->sbatches.push_back(std::move(B));
+    return PRK_OK;
+}
+
+int prk_spans_from_records(prk_context *c, int32_t records_handle, uint32_t first_list, uint32_t list_count,
+                           int32_t height, int32_t *spans_out, uint32_t *span_counts, uint64_t *total_out) {
+    if (!c || !spans_out) return PRK_ERR_ARG;
+    *spans_out = -1;
+    if (total_out) *total_out = 0;
+    const Records *R = nullptr;
+    uint64_t r0 = 0, n = 0;
+    const int rc = records_range(c, records_handle, first_list, list_count, height, &R, &r0, &n);
+    if (rc != PRK_OK) return rc;
+    if (c->sbatches.size() >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    SpanBatch B;
+    uint64_t total = 0;
+    if (n == 0) {
+        B.cnt.assign(list_count, 0u);
+        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+    } else {
+        WalkPlan plan(c->device, list_count, 2);
+        const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
+        if (rp != PRK_OK) return rp;
+        const int rs = spans_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge),
+                                 hipMemcpyDeviceToDevice, height, nullptr, 0, span_counts, &total, &B);
+        if (rs != PRK_OK) return rs;
+    }
+    if (total_out) *total_out = total;
+    return sbatch_add(c, std::move(B), spans_out);
+}
+
+int prk_spans_upload(prk_context *c, const prk_span *spans, uint32_t count, int32_t *spans_out) {
+    if (!c || !spans_out) return PRK_ERR_ARG;
+    *spans_out = -1;
+    if (!spans && count) return PRK_ERR_ARG;
+    // a handle's spans are indexed by 31 bits, as a frame's span input
+    if (count >= 0x7FFFFFFFu || c->sbatches.size() >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
+    SpanBatch B;
+    B.cnt.assign(1, count);
+    B.total = count;
+    if (count) {
+        PRK_TRY(hipSetDevice(c->device));
+        const size_t bytes = (((size_t)count * 25 + 3) / 4) * 16, used = (size_t)count * sizeof(prk_span);
+        PRK_TRY(hipMalloc(&B.sp, bytes));
+        hipError_t e = hipMemset(static_cast<char *>(B.sp) + bytes - 16, 0, 16);  // (the last piece's spare dwords)
+        if (e == hipSuccess) e = hipMemcpy(B.sp, spans, used, hipMemcpyHostToDevice);  // the one copy of the caller's spans
+        if (e != hipSuccess) {
+            (void)hipFree(B.sp);
+            return status_of(e);
+        }
+    }
+    return sbatch_add(c, std::move(B), spans_out);
+}
+
+int prk_spans_upload_rows(prk_context *c, const prk_row *rows, uint64_t row_count, const prk_row_pair *pairs,
+                          uint64_t pair_count, int32_t *spans_out) {
+    if (!c || !spans_out) return PRK_ERR_ARG;
+    *spans_out = -1;
+    if ((!rows && row_count) || (!pairs && pair_count)) return PRK_ERR_ARG;
+    uint64_t sum = 0;
+    for (uint64_t r = 0; r < row_count; ++r) {  // (prk_draw_rows' checks)
+        if (rows[r].RowIndex < 0) return PRK_ERR_ARG;
+        sum += rows[r].EdgeCount;
+    }
+    if (sum != pair_count) return PRK_ERR_ARG;
+    if (row_count >= 0x7FFFFFFFull || pair_count >= 0x7FFFFFFFull || c->sbatches.size() >= 0x7FFFFFFFull)
+        return PRK_ERR_LIMIT;
+    SpanBatch B;
+    const uint32_t n = row_count ? (uint32_t)pair_count : 0u;
+    B.cnt.assign(1, n);
+    B.total = n;
+    if (n) {
+        PRK_TRY(hipSetDevice(c->device));
+        PRK_TRY(hipMalloc(&B.sp, (((size_t)n * 25 + 3) / 4) * 16));
+        const int rc = rows_to_spans(c, rows, (uint32_t)row_count, pairs, n, nullptr, B.sp);
+        if (rc != PRK_OK) {
+            (void)hipFree(B.sp);
+            return rc;
+        }
+    }
+    return sbatch_add(c, std::move(B), spans_out);
+}
+
+int prk_spans_info(prk_context *c, int32_t handle, uint32_t *list_count_out, uint64_t *total_out) {
+    const SpanBatch *B = sbatch_of(c, handle);
+    if (!B) return PRK_ERR_ARG;
+    if (list_count_out) *list_count_out = (uint32_t)B->cnt.size();
+    if (total_out) *total_out = B->total;
+    return PRK_OK;
+}
+
+int prk_spans_lists(prk_context *c, int32_t handle, uint32_t *span_counts) {
+    const SpanBatch *B = sbatch_of(c, handle);
+    if (!B) return PRK_ERR_ARG;
+    if (span_counts && !B->cnt.empty()) std::memcpy(span_counts, B->cnt.data(), B->cnt.size() * 4);
+    return PRK_OK;
+}
+
+int prk_spans_download(prk_context *c, int32_t handle, prk_span *spans, uint64_t capacity) {
+    const SpanBatch *B = sbatch_of(c, handle);
+    if (!B || capacity < B->total || (!spans && B->total)) return PRK_ERR_ARG;
+    if (!B->total) return PRK_OK;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipMemcpy(spans, B->sp, (size_t)B->total * sizeof(prk_span), hipMemcpyDeviceToHost));
+    return PRK_OK;
+}
+
+int prk_spans_destroy(prk_context *c, int32_t handle) {
+    SpanBatch *B = sbatch_of(c, handle);
+    if (!B) return PRK_ERR_ARG;
+    for (const prk::DrawRec &d : c->draws)  // a recorded draw reads it at the flush (prk_reset_draws releases it)
+        if (d.src_kind == 5 && d.geom == handle) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight read it
+    (void)hipFree(B->sp);
+    *B = SpanBatch{};
+    return PRK_OK;
+}
+
+// One draw of spans [first_span, first_span + span_count) of a handle: what
+// prk_draw_spans records for the same spans, minus the copies.
+int prk_draw_span_records(prk_context *c, int32_t handle, uint32_t first_span, uint32_t span_count,
+                          int32_t semantics, int32_t phong, int32_t texture) {
+    const SpanBatch *B = sbatch_of(c, handle);
+    if (!B || (uint64_t)first_span + span_count > B->total) return PRK_ERR_ARG;
+    if (span_count == 0) return PRK_OK;
+    const int rc = draw_src(c, 5, first_span, span_count, span_count, semantics, phong, texture);
+    if (rc != PRK_OK) return rc;
+    c->draws.back().geom = handle;
+    return PRK_OK;
 }
 
 // ConstructSphere (projekt.cpp:4123-4289): the reference's only test mesh.

@@ -45,6 +45,7 @@ struct DrawRec {
                                   // > 1: one AET per object, drawn through the span path)
     uint32_t src_kind;            // 0: geometry; 1: a caller's edge list; 2: caller spans (span path)
     uint32_t src_off, src_n;      // kind 1/2: range of the flush's edge / span input
+                                  // (host: 3 / 4 a batch of lists / of a record handle, 5 spans of a span handle)
     int32_t geom;                 // host: the geometry handle (draw coalescing, geometry updates)
 };
 

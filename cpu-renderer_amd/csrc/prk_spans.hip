@@ -117,6 +117,11 @@ namespace prk {
 //           the sorted insertion cursor by every walk a kind-0 object takes.
 //           A batch's other lists are kind 1.  Either way src is kListSrc
 //           and tri0 the list's index among the pass's batch lists (lrows).
+//   kind 4: one span of a span handle (span src of the handle its draw names):
+//           kind 2's span, read where it is by k_span_handle_walk, a launch
+//           per draw.  It carries kObjWave, so the thread walks leave it alone
+//           as they leave every large object, and the host lists it for no
+//           other walk; like kind 2 it takes one slot (k_obj_bound).
 // g0 is the winner id (pass-local) of what it draws.
 struct ObjDesc {
     uint32_t draw;
@@ -145,7 +150,9 @@ constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 // lobj[l] = its object.  A prk_draw_records draw is a run of kind 3 too; in a
 // pass that has one, a kind-3 run also names where its lists' counts and
 // flags come from (tri0: 0 the staged tables, k the pass's k-th handle) and
-// its first list there (per), for k_list_tables to gather lcnt / lflag.
+// its first list there (per), for k_list_tables to gather lcnt / lflag.  A
+// prk_draw_span_records draw is a run of kind 4: one object per span, from
+// span src_off of its handle on.
 struct ObjRun {
     uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
 };
@@ -167,6 +174,8 @@ __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, ui
         objs[o] = ObjDesc{R.draw, R.first_global, 0u, 0u, 1u, R.src_off, R.src_n, R.k1off};
     } else if (R.kind == 2) {
         objs[o] = ObjDesc{R.draw, R.first_global + j, 0u, 0u, 2u, R.src_off + j, 1u, 0u};
+    } else if (R.kind == 4) {
+        objs[o] = ObjDesc{R.draw, R.first_global + j, 0u, 0u, 4u, R.src_off + j, 1u, kObjWave};
     } else if (R.kind == 3) {
         const uint32_t l = R.k0base + j, n = lcnt[l];
         const bool sorted = lflag[l] != 0;
@@ -5101,6 +5110,70 @@ __global__ void __launch_bounds__(256) k_rows_counts(const int2 *__restrict__ ro
 }
 
 // ---------------------------------------------------------------------------
+// Span handles (prk_spans_*, prk_draw_span_records): packed prk_span records
+// that stay in device memory, drawn from where they are.  One launch per
+// recorded draw: spans [first, first + count) of the handle's buffer `spans`
+// are the pass's objects obj0 .. obj0 + count - 1 (kind 4: one slot each, no
+// other walk takes them) and take the winner ids g0 .. g0 + count - 1.
+//
+// The mirror image of k_span_pack.  A workgroup takes kHandleSpans consecutive
+// spans: their 25 * ns dwords start at dword 25 * (first + j0) of the buffer,
+// which is 16-byte aligned only when first + j0 is a multiple of four (25 = 1
+// mod 4: the stretch starts `lead` = (first + j0) & 3 dwords into its first
+// piece).  Lane t of pass j loads piece t + 256 j of the pieces the stretch
+// touches (dwordx4, 1 KiB contiguous a wave instruction; the leading piece's
+// first `lead` dwords and the trailing piece's spare ones belong to the
+// neighbouring spans, or are the buffer's zero padding: read, never used) into
+// LDS as they are (ds_write_b128 of consecutive slots).  Lane t then reads its
+// span's 25 dwords at dword lead + 25 t: the stride is odd, so the 32 lanes of
+// a ds_read_b32 group fall on 32 different banks.  The buffer holds 25 * total
+// dwords rounded up to four (prk_span_pack's / k_rows_unpack's `out`), so the
+// trailing piece is inside it.
+//
+// From there a lane is k_obj_walk's kind-2 branch: the band and target clip
+// on Row, emit_span<MODE_AVX> with the draw's DRAW_ST and texture into the
+// object's slot, row -1 in a slot no span takes.
+constexpr int kHandleSpans = 256;
+constexpr uint32_t kHandlePieces = 25u * kHandleSpans / 4u + 1u;  // (a stretch that starts inside a piece)
+__global__ void __launch_bounds__(kHandleSpans) k_span_handle_walk(FrameParams fp, uint32_t draw, uint32_t g0,
+                                                                   uint32_t obj0, const uint4 *__restrict__ spans,
+                                                                   uint32_t first, uint32_t count,
+                                                                   const unsigned long long *__restrict__ soff,
+                                                                   SpanRecG *__restrict__ recs,
+                                                                   SpanPos *__restrict__ pos,
+                                                                   uint32_t *__restrict__ span_tri) {
+    __shared__ uint4 st4[kHandlePieces];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t j0 = blockIdx.x * (uint32_t)kHandleSpans;  // (< count: the grid)
+    const uint32_t ns = min((uint32_t)kHandleSpans, count - j0);
+    const unsigned long long w0 = 25ull * ((unsigned long long)first + j0);  // the stretch's first dword
+    const uint32_t lead = (uint32_t)(w0 & 3ull);
+    const uint32_t np = (lead + 25u * ns + 3u) / 4u;  // <= kHandlePieces
+    const uint4 *src = spans + (w0 >> 2);
+    for (uint32_t p = tid; p < np; p += (uint32_t)kHandleSpans) st4[p] = src[p];
+    __syncthreads();
+    if (tid >= ns) return;
+    const float *w = reinterpret_cast<const float *>(st4) + lead + 25u * tid;
+    SpanIn sp;
+    {
+        float v[25];
+#pragma unroll
+        for (int i = 0; i < 25; ++i) v[i] = w[i];
+        static_assert(sizeof(SpanIn) == sizeof(v), "prk_span is 25 dwords");
+        __builtin_memcpy(&sp, v, sizeof(sp));
+    }
+    const DrawRec &d = fp.draws[draw];
+    const bool st = (d.flags & DRAW_ST) != 0;
+    const uint32_t o = obj0 + j0 + tid;
+    const uint32_t base = (uint32_t)soff[o], bound = (uint32_t)(soff[o + 1] - soff[o]);
+    uint32_t used = 0;
+    if (sp.Row >= fp.row0 && sp.Row < fp.row1 && sp.Row < fp.H && bound)
+        used = emit_span<MODE_AVX>(fp, span_end_in(sp.L), span_end_in(sp.R), sp.Row, d, st, g0 + j0 + tid, true, base,
+                                   recs, nullptr, pos, span_tri) ? 1u : 0u;
+    for (uint32_t q = used; q < bound; ++q) pos[base + q] = SpanPos{-1, 0, 0, 0u};
+}
+
+// ---------------------------------------------------------------------------
 // Long lists of the three record calls: one workgroup walks one list, the
 // slot-list walk (walk_rows<M, false>'s row loop: read-ahead window,
 // insert_one_b / insert_batch_b, the expiry compaction, the m == 0 row skip,
@@ -5548,6 +5621,18 @@ hipError_t prk_rows_unpack(const void *rows, const uint32_t *rscan, uint32_t nro
     hipLaunchKernelGGL(prk::k_rows_unpack, dim3((npair + prk::kPackSpans - 1) / prk::kPackSpans),
                        dim3(prk::kPackSpans), 0, s, reinterpret_cast<const int2 *>(rows), rscan, nrow,
                        reinterpret_cast<const uint4 *>(pairs), npair, reinterpret_cast<uint4 *>(out));
+    return hipGetLastError();
+}
+// One prk_draw_span_records draw of the pass: spans [first, first + count) of
+// a handle's packed buffer into the slots of objects obj0 .. (k_span_handle_walk).
+hipError_t prk_span_handle_walk(const prk::FrameParams *fp, uint32_t draw, uint32_t g0, uint32_t obj0,
+                                const void *spans, uint32_t first, uint32_t count, const unsigned long long *soff,
+                                void *recs, void *pos, uint32_t *span_tri, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(prk::k_span_handle_walk, dim3((count + prk::kHandleSpans - 1) / prk::kHandleSpans),
+                       dim3(prk::kHandleSpans), 0, s, *fp, draw, g0, obj0, reinterpret_cast<const uint4 *>(spans),
+                       first, count, soff, reinterpret_cast<prk::SpanRecG *>(recs),
+                       reinterpret_cast<prk::SpanPos *>(pos), span_tri);
     return hipGetLastError();
 }
 hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {

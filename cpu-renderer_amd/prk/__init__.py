@@ -131,6 +131,17 @@ _SIGS = {
     "prk_records_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_uint64,
                                    C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "prk_debug_list_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p]),
+    "prk_spans_from_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32,
+                                         C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "prk_spans_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32)]),
+    "prk_spans_upload_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_int32)]),
+    "prk_spans_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "prk_spans_lists": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "prk_spans_download": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64]),
+    "prk_spans_destroy": (C.c_int, [C.c_void_p, C.c_int32]),
+    "prk_draw_span_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                        C.c_int32]),
     "prk_get_target": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]),
@@ -459,11 +470,18 @@ class Records:
         adv = Records(self._r, h.value)
         return (out, nxt, adv) if host else adv
 
-    def spans(self, height, first_list=0, list_count=None):
+    def spans(self, height, first_list=0, list_count=None, keep=False):
         """prk_records_spans: what Renderer.span_records returns for the
-        same lists, (span_words uint32 [total, 25], span_counts)."""
+        same lists, (span_words uint32 [total, 25], span_counts).  keep:
+        prk_spans_from_records instead -- a Spans that holds the same words
+        on the device (no span crosses to the host)."""
         first, n, _ = self._range(first_list, list_count)
         L, rh = self._r._L, self._r._h
+        if keep:
+            h = C.c_int32(-1)
+            _check("prk_spans_from_records", L.prk_spans_from_records(rh, self.handle, first, n, int(height),
+                                                                      C.byref(h), None, None))
+            return Spans(self._r, h.value)
         sc = np.zeros(n, np.uint32)
         total = C.c_uint64(0)
         _check("prk_records_spans", L.prk_records_spans(rh, self.handle, first, n, int(height), None, 0, _ptr(sc),
@@ -504,6 +522,36 @@ class Records:
         """prk_records_destroy (the Renderer's close frees what is left)."""
         if self.handle is not None and getattr(self._r, "_h", None):
             _check("prk_records_destroy", self._r._L.prk_records_destroy(self._r._h, self.handle))
+        self.handle = None
+
+
+class Spans:
+    """A span handle (prk_spans_*): packed prk_span records kept in device
+    memory by the Renderer that made it, drawn with
+    Renderer.draw_span_records any number of times."""
+
+    def __init__(self, renderer, handle):
+        self._r, self.handle = renderer, handle
+        n, t = C.c_uint32(0), C.c_uint64(0)
+        _check("prk_spans_info", renderer._L.prk_spans_info(renderer._h, handle, C.byref(n), C.byref(t)))
+        self.list_count, self.total = n.value, t.value
+
+    def counts(self):
+        """uint32 [list_count]: each list's spans."""
+        out = np.zeros(self.list_count, np.uint32)
+        _check("prk_spans_lists", self._r._L.prk_spans_lists(self._r._h, self.handle, _ptr(out)))
+        return out
+
+    def download(self):
+        """uint32 [total, 25]: the packed spans (span_records' words)."""
+        w = np.empty((self.total, 25), np.uint32)
+        _check("prk_spans_download", self._r._L.prk_spans_download(self._r._h, self.handle, _ptr(w), self.total))
+        return w
+
+    def close(self):
+        """prk_spans_destroy (the Renderer's close frees what is left)."""
+        if self.handle is not None and getattr(self._r, "_h", None):
+            _check("prk_spans_destroy", self._r._L.prk_spans_destroy(self._r._h, self.handle))
         self.handle = None
 
 
@@ -829,6 +877,35 @@ class Renderer:
         self._keep.append(w)
         _check("prk_draw_spans", self._L.prk_draw_spans(self._h, _ptr(w), w.shape[0], semantics, int(bool(phong)),
                                                         -1 if bitmap is None else bitmap))
+
+    def spans_upload(self, span_words):
+        """prk_spans_upload: the array draw_spans takes (uint32 [n, 25]),
+        copied to the device once -> Spans of one list."""
+        w = np.ascontiguousarray(span_words, np.uint32).reshape(-1, 25)
+        h = C.c_int32(-1)
+        _check("prk_spans_upload", self._L.prk_spans_upload(self._h, _ptr(w), w.shape[0], C.byref(h)))
+        return Spans(self, h.value)
+
+    def spans_upload_rows(self, rows, pairs):
+        """prk_spans_upload_rows: row work records (the arrays row_records
+        returns), regrouped into spans on the device and kept there ->
+        Spans of one list."""
+        r = np.ascontiguousarray(rows, np.int32).reshape(-1, 2)
+        p = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 24)
+        h = C.c_int32(-1)
+        _check("prk_spans_upload_rows", self._L.prk_spans_upload_rows(self._h, _ptr(r), r.shape[0], _ptr(p),
+                                                                      p.shape[0], C.byref(h)))
+        return Spans(self, h.value)
+
+    def draw_span_records(self, sp, first_span=0, span_count=None, semantics=abi.PRK_SEM_AVX, bitmap=None,
+                          phong=True):
+        """prk_draw_span_records: spans [first_span, first_span + span_count)
+        of a Spans (None: to its last span), drawn as draw_spans draws the
+        same spans from a host array -- from where they are on the device."""
+        n = sp.total - first_span if span_count is None else span_count
+        _check("prk_draw_span_records", self._L.prk_draw_span_records(self._h, sp.handle, first_span, n, semantics,
+                                                                      int(bool(phong)),
+                                                                      -1 if bitmap is None else bitmap))
 
     def row_records(self, words, counts, height):
         """prk_row_records: the row work DrawModelOptimizedLines queues for

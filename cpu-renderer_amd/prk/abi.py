@@ -100,6 +100,17 @@ RECORD_WALK_ARGS = {
     "prk_records_rows": 12,
     "prk_debug_list_stats": 6,
 }
+# Span handles (prk.h): each entry point and its arguments
+SPAN_HANDLE_ARGS = {
+    "prk_spans_from_records": 8,
+    "prk_spans_upload": 4,
+    "prk_spans_upload_rows": 6,
+    "prk_spans_info": 4,
+    "prk_spans_lists": 3,
+    "prk_spans_download": 4,
+    "prk_spans_destroy": 2,
+    "prk_draw_span_records": 7,
+}
 # prk_debug_list_stats: the words of a list
 LIST_STATS_FIELDS = ("edge_rows", "scans", "most", "ymin0", "ymax_max")
 

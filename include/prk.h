@@ -704,7 +704,8 @@ int prk_draw_records(prk_context *ctx, int32_t handle, uint32_t first_list, uint
 /* Debug/test: the bytes the most recent whole-object pass (any flush with a
  * whole-object, edge, span or record draw) copied from the host in its one
  * staging upload: the pass's tables, and the records of its prk_draw_edges /
- * prk_draw_edge_lists / prk_draw_spans draws -- none for prk_draw_records. */
+ * prk_draw_edge_lists / prk_draw_spans draws -- none for prk_draw_records
+ * and none for prk_draw_span_records (below). */
 int prk_debug_stage_bytes(prk_context *ctx, uint64_t *bytes_out);
 
 /* What DrawModel* leaves in the lists of a batch (projekt.cpp:3654-3869),
@@ -923,6 +924,76 @@ int prk_records_rows(prk_context *ctx, int32_t handle, uint32_t first_list, uint
                      uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out);
 int prk_debug_list_stats(prk_context *ctx, int32_t handle, uint32_t first_list, uint32_t list_count,
                          int32_t height, uint64_t *out);
+
+/* Span handles: packed prk_span records that stay in device memory -- the
+ * work records DrawModelOptimized(RenderQueue, ...) queues (projekt.cpp:
+ * 3756-3809), kept where the walk leaves them and drawn from there as
+ * DoLineRenderWork draws them (2336-2348): the span-queue counterpart of the
+ * record handles.  The context owns a batch and names it by a handle >= 0 in
+ * a number space of its own (not the record handles'); the host keeps the span
+ * count and each list's number of spans (4 bytes a list), and no copy of the
+ * spans.  A handle belongs to its context.  prk_destroy frees every handle.
+ *
+ * prk_spans_from_records: prk_records_spans' walk of lists [first_list,
+ * first_list + list_count) of a record handle, the packed spans written into
+ * the new handle's buffer instead of the caller's -- no span crosses to the
+ * host.  Its status is what prk_records_spans returns for the same handle,
+ * range and height with a sufficient `spans` buffer (the same PRK_ERR_ARG /
+ * PRK_ERR_UNSUPPORTED / PRK_ERR_LIMIT cases), and PRK_ERR_ARG for a NULL
+ * spans_out; the handle's contents are, bit for bit, the words that call
+ * writes.  span_counts (list_count words) and total_out may be NULL.  The
+ * handle has list_count lists; no lists or no spans: PRK_OK and a handle of no
+ * spans.  On any error no handle is made and *spans_out is -1.  Synchronous;
+ * needs no target, records no draw, touches no recorded draw and no prk_stats;
+ * frames in flight finish first.  A record handle's row work needs no handle
+ * of its own: pair k of prk_records_rows holds span k of prk_records_spans
+ * re-ordered and prk_draw_rows draws what prk_draw_spans draws (above), so
+ * this handle serves DrawModelOptimizedLines' callers too.
+ *
+ * prk_spans_upload: a caller's own spans, copied once at the call; the host
+ * does not read them.  One list of `count` spans; count == 0: an empty handle.
+ * PRK_ERR_ARG: NULL spans with count > 0.  PRK_ERR_LIMIT: count passes 31 bits.
+ *
+ * prk_spans_upload_rows: row work records (prk_row_records' output or a
+ * caller's), regrouped into spans on the device as prk_draw_rows regroups
+ * them; the spans stay there.  Argument checks and errors are prk_draw_rows'
+ * (the EdgeCounts must sum to pair_count, no negative RowIndex, 31-bit
+ * limits).  One list of pair_count spans; no rows or no pairs: an empty handle.
+ *
+ * prk_spans_info / prk_spans_lists: the handle's lists and spans; each list's
+ * number of spans (list_count words).  Any pointer may be NULL.  Host
+ * bookkeeping: no device work.
+ *
+ * prk_spans_download: the packed spans.  PRK_ERR_ARG: capacity (in spans)
+ * below the total.
+ *
+ * prk_spans_destroy: as prk_records_destroy.  Frames in flight finish first.
+ * PRK_ERR_ARG while a recorded, unflushed draw names the handle
+ * (prk_reset_draws releases it), and for a bad or destroyed handle. */
+int prk_spans_from_records(prk_context *ctx, int32_t records_handle, uint32_t first_list, uint32_t list_count,
+                           int32_t height, int32_t *spans_out, uint32_t *span_counts, uint64_t *total_out);
+int prk_spans_upload(prk_context *ctx, const prk_span *spans, uint32_t count, int32_t *spans_out);
+int prk_spans_upload_rows(prk_context *ctx, const prk_row *rows, uint64_t row_count,
+                          const prk_row_pair *pairs, uint64_t pair_count, int32_t *spans_out);
+int prk_spans_info(prk_context *ctx, int32_t handle, uint32_t *list_count_out, uint64_t *total_out);
+int prk_spans_lists(prk_context *ctx, int32_t handle, uint32_t *span_counts);
+int prk_spans_download(prk_context *ctx, int32_t handle, prk_span *spans, uint64_t capacity);
+int prk_spans_destroy(prk_context *ctx, int32_t handle);
+/* One draw of spans [first_span, first_span + span_count) of a span handle, at
+ * this point of the frame's submission order: the frame, the winner ids
+ * (base + k, one per span) and the semantics / phong / texture checks are
+ * exactly prk_draw_spans' for the same spans passed from host memory
+ * (PRK_SEM_SCALAR is PRK_ERR_UNSUPPORTED, the AVX semantics need a texture and
+ * phong, the frame's id capacity applies) -- but nothing is copied, at the
+ * call or at the flush: the flush reads the spans where they are, and its
+ * staging holds the pass's tables only.  A handle may be drawn any number of
+ * times, in one frame or across frames, mixed in one pass with every other
+ * kind of draw (prk_draw_spans' staged spans, record handles and edge lists,
+ * triangle objects, other span handles).  PRK_ERR_ARG: a bad handle, a range
+ * past the handle's spans.  span_count == 0: PRK_OK, nothing recorded.  On
+ * any error nothing is recorded. */
+int prk_draw_span_records(prk_context *ctx, int32_t handle, uint32_t first_span, uint32_t span_count,
+                          int32_t semantics, int32_t phong, int32_t texture);
 
 /* Host utility: the reference's test mesh, ConstructSphere
  * (projekt.cpp:4123-4289).  Arrays must hold 6624 vertices; returns the
