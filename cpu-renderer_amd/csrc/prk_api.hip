@@ -147,6 +147,8 @@ hipError_t prk_span_bin(const prk::FrameParams *, const void *, uint32_t, const 
 hipError_t prk_launch_spans(const prk::FrameParams *, const uint32_t *, const uint32_t *, const void *,
                             const void *, const void *, uint32_t, const uint32_t *, uint32_t *, uint32_t *,
                             hipStream_t);
+hipError_t prk_xform_launch(const void *, size_t, size_t, uint32_t, uint32_t, const float *, const float *,
+                            const float *, const float *, float *, float *, float *, float *, hipStream_t);
 }
 
 // prk_spans.hip's object descriptor, and the runs of objects the device
@@ -270,6 +272,14 @@ struct prk_context {
     hipStream_t copy_stream = nullptr;
     hipEvent_t in_ev = nullptr, read_ev = nullptr;
     bool in_wait = false, read_rec = false;
+    // prk_geometry_transform's tables (scan, runs, matrices): staged in pinned
+    // memory, copied on copy_stream ahead of the kernel; xf_ev: that copy is
+    // done (the next call refills the staging)
+    DevBuf d_xform;
+    void *h_xform = nullptr;
+    size_t h_xform_cap = 0;
+    hipEvent_t xf_ev = nullptr, xf_end_ev = nullptr;  // (timed: prk_debug_transform_ms)
+    bool xf_busy = false;
     // target
     void *color = nullptr;
     int32_t pitch = 0;
@@ -662,8 +672,11 @@ int prk_destroy(prk_context *c) {
         if (B.listed_ev) (void)hipEventDestroy(B.listed_ev);
         if (B.h_info) (void)hipHostFree(B.h_info);
     }
-    DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz};
+    DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz, &c->d_xform};
     for (DevBuf *b : bufs) b->release();
+    if (c->h_xform) (void)hipHostFree(c->h_xform);
+    if (c->xf_ev) (void)hipEventDestroy(c->xf_ev);
+    if (c->xf_end_ev) (void)hipEventDestroy(c->xf_end_ev);
     {
         auto &S = c->spans;
         DevBuf *sb[] = {&S.d_stage, &S.d_edges, &S.d_ord, &S.d_temp, &S.d_recs, &S.d_pos, &S.d_span_tri, &S.d_scnt,
@@ -1110,6 +1123,8 @@ int prk_geometry_update(prk_context *c, int32_t handle, const float *v, const fl
     return PRK_OK;
 }
 
+static int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end);
+
 int prk_geometry_write(prk_context *c, int32_t handle, uint32_t first_vertex, uint32_t vertex_count,
                        const float *v, const float *col, const float *n, const float *uv) {
     if (!c || handle < 0 || (size_t)handle >= c->geoms.size() || first_vertex % 3 || vertex_count % 3)
@@ -1124,16 +1139,45 @@ int prk_geometry_write(prk_context *c, int32_t handle, uint32_t first_vertex, ui
     const float *src[4] = {v, col, n, uv};
     const float **dst[4] = {&g.V, &g.C, &g.N, &g.UV};
     const size_t comp[4] = {3, 4, 3, 2};
-    // Buffers that must grow (an array that exists, or is given now): by
-    // half again at least, so a frame streamed in chunks reallocates rarely.
+    const bool given[4] = {v != nullptr, col != nullptr, n != nullptr, uv != nullptr};
+    {
+        const int rc = geometry_grow(c, handle, given, end);
+        if (rc != PRK_OK) return rc;
+    }
+    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->read_ev, 0));
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+        if (!src[k] || !vertex_count) continue;
+        const size_t off = (size_t)first_vertex * comp[k];
+        PRK_TRY(hipMemcpyAsync((void *)(*dst[k] + off), src[k], (size_t)vertex_count * comp[k] * sizeof(float),
+                               hipMemcpyHostToDevice, c->copy_stream));
+        any = true;
+    }
+    if (any) {
+        PRK_TRY(hipEventRecord(c->in_ev, c->copy_stream));
+        c->in_wait = true;
+    }
+    g.vertex_count = end;
+    return PRK_OK;
+}
+
+// Room for `end` vertices in a library-owned geometry's arrays that exist or
+// are wanted now (prk_geometry_write, prk_geometry_transform): buffers that
+// must grow do so by half again at least, so a frame streamed in chunks
+// reallocates rarely; contents kept, zeros past them (a new array: all zeros),
+// recorded draws repointed.  Growing waits for the device.
+static int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end) {
+    Geometry &g = c->geoms[handle];
+    const float **dst[4] = {&g.V, &g.C, &g.N, &g.UV};
+    const size_t comp[4] = {3, 4, 3, 2};
     bool grow = false;
-    for (int k = 0; k < 4; ++k) grow |= (src[k] || *dst[k]) && end > g.cap[k];
+    for (int k = 0; k < 4; ++k) grow |= (want[k] || *dst[k]) && end > g.cap[k];
     if (grow) {
         PRK_TRY(hipDeviceSynchronize());  // frames in flight and earlier writes read / fill the old buffers
         for (int k = 0; k < 4; ++k) {
-            if (!(src[k] || *dst[k]) || end <= g.cap[k]) continue;
-            const uint64_t want = std::max<uint64_t>(end, (uint64_t)g.cap[k] + g.cap[k] / 2);
-            const uint32_t cap = (uint32_t)std::min<uint64_t>(want, 0xFFFFFFF0ull);
+            if (!(want[k] || *dst[k]) || end <= g.cap[k]) continue;
+            const uint64_t need = std::max<uint64_t>(end, (uint64_t)g.cap[k] + g.cap[k] / 2);
+            const uint32_t cap = (uint32_t)std::min<uint64_t>(need, 0xFFFFFFF0ull);
             const size_t bytes = (size_t)cap * comp[k] * sizeof(float);
             const size_t old = *dst[k] ? (size_t)g.cap[k] * comp[k] * sizeof(float) : 0;
             float *d = nullptr;
@@ -1154,20 +1198,6 @@ int prk_geometry_write(prk_context *c, int32_t handle, uint32_t first_vertex, ui
             }
         c->read_rec = false;  // the device is idle
     }
-    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->read_ev, 0));
-    bool any = false;
-    for (int k = 0; k < 4; ++k) {
-        if (!src[k] || !vertex_count) continue;
-        const size_t off = (size_t)first_vertex * comp[k];
-        PRK_TRY(hipMemcpyAsync((void *)(*dst[k] + off), src[k], (size_t)vertex_count * comp[k] * sizeof(float),
-                               hipMemcpyHostToDevice, c->copy_stream));
-        any = true;
-    }
-    if (any) {
-        PRK_TRY(hipEventRecord(c->in_ev, c->copy_stream));
-        c->in_wait = true;
-    }
-    g.vertex_count = end;
     return PRK_OK;
 }
 
@@ -1183,6 +1213,146 @@ int prk_geometry_wrap_device(prk_context *c, const float *v, const float *col, c
     g.owned = false;
     *handle_out = (int32_t)c->geoms.size();
     c->geoms.push_back(g);
+    return PRK_OK;
+}
+
+int prk_geometry_alloc(prk_context *c, int32_t *handle_out) {
+    if (!c || !handle_out) return PRK_ERR_ARG;
+    Geometry g;  // no vertices, no arrays: prk_geometry_transform / prk_geometry_write give it both
+    g.owned = true;
+    *handle_out = (int32_t)c->geoms.size();
+    c->geoms.push_back(g);
+    return PRK_OK;
+}
+
+// Runs of src's triangles through a matrix each into dst (prk.h; kernel and
+// table layout: prk_xform.hip).  Ordered as prk_geometry_write orders its
+// copies: on copy_stream after read_ev, the next flush waits for in_ev.
+int prk_geometry_transform(prk_context *c, int32_t src, int32_t dst, const prk_xform_run *runs, uint32_t run_count,
+                           const prk_xform *xforms, uint32_t xform_count) {
+    if (!c || src < 0 || (size_t)src >= c->geoms.size() || dst < 0 || (size_t)dst >= c->geoms.size() || src == dst)
+        return PRK_ERR_ARG;
+    if (!c->geoms[dst].owned) return PRK_ERR_ARG;
+    if (run_count && (!runs || !xforms)) return PRK_ERR_ARG;
+    const uint32_t src_tris = c->geoms[src].vertex_count / 3;
+    uint64_t total = 0, top = 0;  // output triangles; one past the highest triangle written
+    uint32_t nruns = 0;
+    for (uint32_t i = 0; i < run_count; ++i) {
+        const prk_xform_run &r = runs[i];
+        if (!r.tri_count) continue;
+        if (r.xform >= xform_count) return PRK_ERR_ARG;
+        if ((uint64_t)r.src_first_tri + r.tri_count > src_tris) return PRK_ERR_ARG;
+        const uint64_t dend = (uint64_t)r.dst_first_tri + r.tri_count;
+        if (dend * 3 > 0xFFFFFFF0ull) return PRK_ERR_ARG;
+        top = std::max(top, dend);
+        total += r.tri_count;
+        ++nruns;
+    }
+    if (!nruns) return PRK_OK;
+    if (!c->geoms[src].V) return PRK_ERR_ARG;  // (a geometry written without positions)
+    if (total > (1ull << 31)) return PRK_ERR_LIMIT;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    // the tables: scan (nruns + 1 words), runs, matrices (prk_xform.hip)
+    const size_t runs_off = ((size_t)(nruns + 1) * 4 + 15) & ~(size_t)15;
+    const size_t xf_off = runs_off + (size_t)nruns * 16;
+    const size_t bytes = xf_off + (size_t)xform_count * sizeof(prk_xform);
+    if (c->xf_busy) {  // the staging's previous contents have been copied
+        PRK_TRY(hipEventSynchronize(c->xf_ev));
+        c->xf_busy = false;
+    }
+    if (bytes > c->h_xform_cap) {
+        if (c->h_xform) (void)hipHostFree(c->h_xform);
+        c->h_xform = nullptr;
+        c->h_xform_cap = 0;
+        const size_t want = bytes + bytes / 4;
+        PRK_TRY(hipHostMalloc(&c->h_xform, want, hipHostMallocDefault));
+        c->h_xform_cap = want;
+    }
+    if (!c->xf_ev) PRK_TRY(hipEventCreate(&c->xf_ev));
+    if (!c->xf_end_ev) PRK_TRY(hipEventCreate(&c->xf_end_ev));
+    {
+        uint8_t *h = static_cast<uint8_t *>(c->h_xform);
+        uint32_t *scan = reinterpret_cast<uint32_t *>(h);
+        uint32_t *rr = reinterpret_cast<uint32_t *>(h + runs_off);
+        uint32_t at = 0, k = 0;
+        for (uint32_t i = 0; i < run_count; ++i) {
+            const prk_xform_run &r = runs[i];
+            if (!r.tri_count) continue;
+            scan[k] = at;
+            rr[4 * k + 0] = r.src_first_tri;
+            rr[4 * k + 1] = r.dst_first_tri;
+            rr[4 * k + 2] = r.xform;
+            rr[4 * k + 3] = at;
+            at += r.tri_count;
+            ++k;
+        }
+        scan[nruns] = at;
+        std::memcpy(h + xf_off, xforms, (size_t)xform_count * sizeof(prk_xform));
+    }
+    // dst takes every array src has; its size covers the highest triangle written
+    Geometry &s = c->geoms[src];
+    const bool has[4] = {s.V != nullptr, s.C != nullptr, s.N != nullptr, s.UV != nullptr};
+    const uint32_t end = std::max<uint32_t>(c->geoms[dst].vertex_count, (uint32_t)(top * 3));
+    {
+        const int rc = geometry_grow(c, dst, has, end);
+        if (rc != PRK_OK) return rc;
+    }
+    Geometry &d = c->geoms[dst];
+    PRK_TRY(c->d_xform.ensure(bytes));  // (a larger buffer: hipFree waits for the kernels that read the old one)
+    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->read_ev, 0));
+    PRK_TRY(hipMemcpyAsync(c->d_xform.p, c->h_xform, bytes, hipMemcpyHostToDevice, c->copy_stream));
+    PRK_TRY(hipEventRecord(c->xf_ev, c->copy_stream));
+    c->xf_busy = true;
+    PRK_TRY(prk_xform_launch(c->d_xform.p, runs_off, xf_off, nruns, (uint32_t)total, s.V, s.C, s.N, s.UV,
+                             (float *)d.V, (float *)d.C, (float *)d.N, (float *)d.UV, c->copy_stream));
+    PRK_TRY(hipEventRecord(c->xf_end_ev, c->copy_stream));
+    PRK_TRY(hipEventRecord(c->in_ev, c->copy_stream));
+    c->in_wait = true;
+    d.vertex_count = end;
+    return PRK_OK;
+}
+
+int prk_geometry_info(prk_context *c, int32_t handle, uint32_t *vertex_count_out, uint32_t *arrays_out) {
+    if (!c || handle < 0 || (size_t)handle >= c->geoms.size()) return PRK_ERR_ARG;
+    const Geometry &g = c->geoms[handle];
+    if (vertex_count_out) *vertex_count_out = g.vertex_count;
+    if (arrays_out) *arrays_out = (g.V ? 1u : 0u) | (g.C ? 2u : 0u) | (g.N ? 4u : 0u) | (g.UV ? 8u : 0u);
+    return PRK_OK;
+}
+
+int prk_debug_transform_ms(prk_context *c, float *kernel_ms) {
+    if (!c || !kernel_ms || !c->xf_busy) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipEventSynchronize(c->xf_end_ev));
+    PRK_TRY(hipEventElapsedTime(kernel_ms, c->xf_ev, c->xf_end_ev));
+    return PRK_OK;
+}
+
+int prk_debug_geometry_stream(prk_context *c, void **stream) {
+    if (!c || !stream) return PRK_ERR_ARG;
+    *stream = (void *)c->copy_stream;
+    return PRK_OK;
+}
+
+int prk_geometry_download(prk_context *c, int32_t handle, uint32_t first_vertex, uint32_t vertex_count,
+                          float *v, float *col, float *n, float *uv) {
+    if (!c || handle < 0 || (size_t)handle >= c->geoms.size() || first_vertex % 3 || vertex_count % 3)
+        return PRK_ERR_ARG;
+    const Geometry &g = c->geoms[handle];
+    if ((uint64_t)first_vertex + vertex_count > g.vertex_count) return PRK_ERR_ARG;
+    float *dst[4] = {v, col, n, uv};
+    const float *src[4] = {g.V, g.C, g.N, g.UV};
+    const size_t comp[4] = {3, 4, 3, 2};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k] && !src[k]) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipStreamSynchronize(c->copy_stream));  // every queued write of a geometry runs there
+    for (int k = 0; k < 4; ++k) {
+        if (!dst[k] || !vertex_count) continue;
+        PRK_TRY(hipMemcpy(dst[k], src[k] + (size_t)first_vertex * comp[k],
+                          (size_t)vertex_count * comp[k] * sizeof(float), hipMemcpyDeviceToHost));
+    }
     return PRK_OK;
 }
 

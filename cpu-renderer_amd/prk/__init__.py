@@ -165,6 +165,8 @@ _SIGS = {
                                          C.c_void_p]),
 }
 
+_SIGS.update({name: (C.c_int, args) for name, args in abi.GEOMETRY_TRANSFORM_SIGS.items()})
+
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
 
@@ -694,6 +696,44 @@ class Renderer:
         _check("prk_geometry_wrap_device", self._L.prk_geometry_wrap_device(self._h, *ptrs, vertex_count,
                                                                             C.byref(h)))
         return h.value
+
+    def geometry_alloc(self):
+        """prk_geometry_alloc: an empty library-owned geometry, a destination
+        for geometry_transform."""
+        h = C.c_int32(-1)
+        _check("prk_geometry_alloc", self._L.prk_geometry_alloc(self._h, C.byref(h)))
+        return h.value
+
+    def geometry_transform(self, src, dst, runs, xforms):
+        """prk_geometry_transform: runs uint32 [n, 4] of (src_first_tri,
+        tri_count, dst_first_tri, xform), xforms float32 [m, 3, 4] row-major;
+        both are copied at the call, which does not wait for the device."""
+        r = np.ascontiguousarray(runs, np.uint32).reshape(-1, 4)
+        x = np.ascontiguousarray(xforms, np.float32).reshape(-1, 3, 4)
+        _check("prk_geometry_transform", self._L.prk_geometry_transform(
+            self._h, src, dst, C.cast(r.ctypes.data, C.POINTER(abi.PrkXformRun)), r.shape[0],
+            C.cast(x.ctypes.data, C.POINTER(abi.PrkXform)), x.shape[0]))
+
+    def geometry_download(self, geom, first_tri=0, tri_count=None, arrays=(True, True, True, True)):
+        """prk_geometry_download of triangles [first_tri, first_tri +
+        tri_count) (None: to the geometry's end, found by asking): (vertices
+        [n, 3], colors [n, 4], normals [n, 3], uvs [n, 2]), None for an array
+        the geometry lacks (or `arrays` leaves out)."""
+        nv, have = self.geometry_info(geom)
+        if tri_count is None:
+            tri_count = max(0, nv // 3 - first_tri)
+        n = 3 * tri_count
+        out = [np.empty((n, comp), np.float32) if arrays[k] and have[k] else None
+               for k, comp in enumerate((3, 4, 3, 2))]
+        _check("prk_geometry_download", self._L.prk_geometry_download(self._h, geom, 3 * first_tri, n,
+                                                                      *[_ptr(a) for a in out]))
+        return tuple(out)
+
+    def geometry_info(self, geom):
+        """prk_geometry_info: (vertex count, (has vertices, colors, normals, uvs))."""
+        n, m = C.c_uint32(0), C.c_uint32(0)
+        _check("prk_geometry_info", self._L.prk_geometry_info(self._h, geom, C.byref(n), C.byref(m)))
+        return n.value, tuple(bool(m.value >> k & 1) for k in range(4))
 
     def target(self):
         """prk_get_target: (color_ptr, pitch, z_ptr, W, H, row0, row1)."""

@@ -87,6 +87,31 @@ class PrkRow(C.Structure):
     _fields_ = [("RowIndex", C.c_int32), ("EdgeCount", C.c_uint32)]
 
 
+class PrkXform(C.Structure):
+    """prk_xform: a row-major 3x4 matrix, out = M[:, 0:3] * v + M[:, 3]."""
+    _fields_ = [("M", (C.c_float * 4) * 3)]
+
+
+class PrkXformRun(C.Structure):
+    """prk_xform_run: triangles [src_first_tri, +tri_count) of the source to
+    [dst_first_tri, +tri_count) of the destination through xforms[xform]."""
+    _fields_ = [("src_first_tri", C.c_uint32), ("tri_count", C.c_uint32), ("dst_first_tri", C.c_uint32),
+                ("xform", C.c_uint32)]
+
+
+# The device transform pass (prk.h): each entry point and its argument types
+GEOMETRY_TRANSFORM_SIGS = {
+    "prk_geometry_alloc": [C.c_void_p, C.POINTER(C.c_int32)],
+    "prk_geometry_transform": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(PrkXformRun), C.c_uint32,
+                               C.POINTER(PrkXform), C.c_uint32],
+    "prk_geometry_download": [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p],
+    "prk_geometry_info": [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "prk_debug_geometry_stream": [C.c_void_p, C.POINTER(C.c_void_p)],
+    "prk_debug_transform_ms": [C.c_void_p, C.c_void_p],
+}
+
+
 # prk_row_pair word w holds prk_span word ROW_PAIR_SPAN_WORD[w] (an end is
 # XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3]; Right at +12)
 ROW_PAIR_SPAN_WORD = ([h * 12 + k for k in range(5) for h in (0, 1)] + [5, 6, 7, 8] + [17, 18, 19, 20] +

@@ -292,6 +292,79 @@ int prk_geometry_wrap_device(prk_context *ctx, const float *vertices, const floa
                              const float *normals, const float *uvs, uint32_t vertex_count,
                              int32_t *handle_out);
 
+/* Objects that move: a transform pass on the device.  An EXTENSION of this
+ * build with its own definition: the reference's camera has
+ * no rotation and its callers re-fill Vertices on the host before every
+ * FillEdgeTable; here a resident source geometry is written through 3x4
+ * matrices into a resident destination geometry, and one prk_draw_objects or
+ * prk_records_from_geometry on the destination (P = 0) takes every object.
+ *
+ * prk_geometry_alloc: a library-owned geometry of 0 vertices and no arrays --
+ * a destination to transform (or prk_geometry_write) into.
+ *
+ * prk_geometry_transform: for every run, triangles [src_first_tri, +tri_count)
+ * of src go to triangles [dst_first_tri, +tri_count) of dst through
+ * M = xforms[run.xform].M (row-major):
+ *   positions, component i:  out[i] = ((M[i][0]*x + M[i][1]*y) + M[i][2]*z) + M[i][3]
+ *   normals:                 out[i] =  (M[i][0]*x + M[i][1]*y) + M[i][2]*z
+ *   colours, uvs:            copied bit for bit.
+ * Every product and every sum is rounded to f32 on its own, in this order;
+ * nothing is fused.  So the identity matrix returns values equal to the
+ * source's, except that a -0.0 may come out as +0.0 (-0.0 + 0.0).  Normals
+ * are NOT renormalised: pass rigid transforms (rotation + translation), or
+ * accept the normals as they come out.
+ * dst receives every array src has: one dst lacked is allocated, zero where
+ * no run writes; an array dst has and src lacks is left alone.  dst grows as
+ * prk_geometry_write grows a geometry (contents kept, zeros past them,
+ * recorded draws repointed); its vertex count becomes the larger of its old
+ * value and three times the highest triangle written.
+ * A run of 0 triangles is skipped.  The same source range may appear in many
+ * runs (instancing); runs may come in any order.  Destination ranges that
+ * overlap are NOT checked: the overlap holds unspecified values (of one run
+ * or another, per word), everything else what its run writes.
+ * PRK_ERR_ARG: a NULL context, a bad handle, src == dst, a dst that is wrapped
+ * (prk_geometry_wrap_device), run_count > 0 with NULL runs or xforms, a run
+ * whose xform >= xform_count, whose source range passes the end of src, or
+ * whose destination end passes prk_geometry_write's vertex limit.
+ * PRK_ERR_LIMIT: more than 2^31 output triangles in one call.  On any error
+ * nothing has been written.
+ * Ordering is prk_geometry_write's: the call returns without waiting (unless
+ * dst must grow); it runs after the frames already flushed have read dst,
+ * before the next prk_flush's kernels read it and before any later
+ * prk_records_from_geometry / prk_edge_records reads it.  runs and xforms are
+ * copied at the call.  src is read at that same point of the order: an earlier
+ * prk_geometry_write (or transform) to src is seen, a later one is not.
+ *
+ * prk_geometry_download: vertices [first_vertex, +vertex_count) of any
+ * geometry to host memory, after everything queued that writes it.  A NULL
+ * pointer skips that array.  PRK_ERR_ARG: an array asked for that the geometry
+ * lacks, a range past the vertex count, first_vertex or vertex_count no
+ * multiple of 3. */
+typedef struct prk_xform {
+    float M[3][4]; /* row-major: out = M[:, 0:3] * v + M[:, 3] */
+} prk_xform;
+typedef struct prk_xform_run {
+    uint32_t src_first_tri, tri_count, dst_first_tri, xform; /* xform: index into the call's xforms */
+} prk_xform_run;
+int prk_geometry_alloc(prk_context *ctx, int32_t *handle_out);
+int prk_geometry_transform(prk_context *ctx, int32_t src, int32_t dst,
+                           const prk_xform_run *runs, uint32_t run_count,
+                           const prk_xform *xforms, uint32_t xform_count);
+int prk_geometry_download(prk_context *ctx, int32_t handle, uint32_t first_vertex, uint32_t vertex_count,
+                          float *vertices, float *colors, float *normals, float *uvs);
+/* A geometry's vertex count and which arrays it has (bit 0 vertices, 1
+ * colours, 2 normals, 3 uvs), as the calls queued so far leave them; either
+ * pointer may be NULL.  Host bookkeeping: no device work. */
+int prk_geometry_info(prk_context *ctx, int32_t handle, uint32_t *vertex_count_out, uint32_t *arrays_out);
+/* Debug/bench: the stream (a hipStream_t) prk_geometry_write's copies and
+ * prk_geometry_transform's pass are queued on, for timing them with events
+ * (tools/xform_bench.py).  Queue nothing else there. */
+int prk_debug_geometry_stream(prk_context *ctx, void **stream);
+/* Debug/bench: the device time of the most recent prk_geometry_transform's
+ * kernel alone (events after its table upload and after the kernel); waits
+ * for it.  PRK_ERR_ARG before any transform. */
+int prk_debug_transform_ms(prk_context *ctx, float *kernel_ms);
+
 /* Record one draw: triangles [first_tri, first_tri+tri_count) of a geometry,
  * object offset P (render_entry_3d_object::P), semantics PRK_SEM_*,
  * PhongShading flag, texture handle (-1 = no Bitmap).

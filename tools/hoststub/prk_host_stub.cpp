@@ -61,6 +61,30 @@ int prk_geometry_write(prk_context *, int32_t, uint32_t, uint32_t, const float *
                        const float *) {
     return PRK_OK;
 }
+int prk_geometry_alloc(prk_context *, int32_t *h) {
+    *h = 0;
+    return PRK_OK;
+}
+int prk_geometry_transform(prk_context *, int32_t, int32_t, const prk_xform_run *, uint32_t, const prk_xform *,
+                           uint32_t) {
+    return PRK_OK;
+}
+int prk_geometry_download(prk_context *, int32_t, uint32_t, uint32_t, float *, float *, float *, float *) {
+    return PRK_OK;
+}
+int prk_geometry_info(prk_context *, int32_t, uint32_t *vertex_count_out, uint32_t *arrays_out) {
+    if (vertex_count_out) *vertex_count_out = 0;
+    if (arrays_out) *arrays_out = 0;
+    return PRK_OK;
+}
+int prk_debug_geometry_stream(prk_context *, void **stream) {
+    *stream = nullptr;
+    return PRK_OK;
+}
+int prk_debug_transform_ms(prk_context *, float *kernel_ms) {
+    *kernel_ms = 0.0f;
+    return PRK_OK;
+}
 int prk_get_stats(prk_context *, prk_stats *out) {
     std::memset(out, 0, sizeof *out);
     return PRK_OK;
