@@ -28,11 +28,8 @@
 #include "../../include/prk.h"
 #include "../../include/prk_edge_count.h"
 #include "prk_device.h"
+#include "prk_launch.h"  // the kernel files' launchers, and what the host shares with them
 
-extern "C" {
-hipError_t prk_launch_tri_draw(const prk::DrawRec *, uint32_t, uint32_t *, uint32_t, hipStream_t);
-hipError_t prk_bin_count(const prk::FrameParams *, uint32_t *, void *, uint32_t *, uint32_t *, uint8_t *, hipStream_t);
-hipError_t prk_band_records(const prk::FrameParams *, const uint32_t *, const uint32_t *, hipStream_t);
 #ifndef PRK_REC_AFTER_CS
 #define PRK_REC_AFTER_CS 1  // a band's k_band_rec queued after the counting sort's launches
 #endif
@@ -41,140 +38,24 @@ hipError_t prk_band_records(const prk::FrameParams *, const uint32_t *, const ui
                             // 0.084 -> 0.075 ms, but C3b N = 8 pipelined 0.186 -> 0.21-0.22 ms: the copy,
                             // which the host waits for, then queues behind k_vis)
 #endif
-uint32_t prk_cs_chunks(uint32_t);
-uint32_t prk_cs_nchunks(uint32_t, uint32_t);
-uint32_t prk_cs_band_runs_per_chunk(const prk::FrameParams *);
-uint32_t prk_bin_runs(uint32_t);
-uint32_t prk_bin_run_len(void);
-uint32_t prk_cs_max_tiles(void);
-uint32_t prk_cs_max_pairs(void);
-int prk_cs_ready(uint32_t);
-hipError_t prk_bin_cs(const prk::FrameParams *, const void *, const uint32_t *, uint32_t *, uint32_t *, uint32_t *,
-                      uint32_t *, uint32_t *, uint32_t, uint32_t *, uint32_t *, void *, uint32_t *, uint8_t *, uint32_t,
-                      uint8_t *, const uint32_t *, const uint32_t *, uint32_t, hipStream_t);
-hipError_t prk_launch_raster(const prk::FrameParams *, int, const uint32_t *, const void *, const uint32_t *,
-                             const uint32_t *, const void *, uint8_t *, uint8_t *, uint32_t *, void *, size_t,
-                             uint32_t *, uint32_t *, uint32_t *, void *, uint32_t *, hipEvent_t, hipEvent_t,
-                             hipStream_t, hipStream_t);
-hipError_t prk_walk_select_bytes(uint32_t, size_t *);
-hipError_t prk_selftest_div_launch(uint32_t n, uint64_t seed, unsigned long long *bad, hipStream_t s);
-hipError_t prk_selftest_ops_launch(int32_t op, uint32_t n, const uint32_t *in, uint32_t *out, hipStream_t s);
-hipError_t prk_obj_tables(const void *, uint32_t, uint32_t, uint32_t, void *, uint32_t *, uint32_t *, const uint32_t *,
-                          const uint32_t *, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
-hipError_t prk_list_prep(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *,
-                         const void *, const uint32_t *, uint32_t, void *, void *, unsigned long long *, hipStream_t);
-hipError_t prk_list_prep_segs(const prk::FrameParams *, const void *, uint32_t, uint32_t, const uint32_t *, uint32_t,
-                              const uint32_t *, const void *, const uint32_t *, uint32_t, void *, void *,
-                              unsigned long long *, hipStream_t);
-hipError_t prk_list_tables(const void *, uint32_t, uint32_t, const uint32_t *, const uint32_t *, const void *, uint32_t,
-                           uint32_t *, uint32_t *, hipStream_t);
-hipError_t prk_list_rule(const void *, uint32_t, const uint32_t *, uint32_t, uint32_t *, hipStream_t);
-hipError_t prk_list_stats(const void *, uint32_t, const uint32_t *, uint32_t, int32_t, void *, hipStream_t);
-hipError_t prk_list_most(const void *, const uint32_t *, const uint32_t *, uint32_t, int32_t, uint32_t *, hipStream_t);
-hipError_t prk_objtri_count(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
-                            uint32_t, uint32_t *, unsigned long long *, hipStream_t);
-hipError_t prk_objtri_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t,
-                           uint32_t, const uint32_t *, uint32_t, uint32_t, int32_t, void *, void *, uint32_t *, int,
-                           hipStream_t);
-hipError_t prk_obj_sort_local(const void *, const uint32_t *, uint32_t, const uint32_t *, const void *, const void *,
-                              void *, void *, uint32_t *, hipStream_t);
-hipError_t prk_obj_sort(void *, uint32_t *, void *, uint32_t *, uint32_t, uint32_t, void *, size_t *, hipStream_t);
-hipError_t prk_rec_emit(const prk::FrameParams *, const void *, const uint32_t *, const uint32_t *, uint32_t, uint32_t,
-                        const uint32_t *, int32_t, uint32_t, void *, void *, uint32_t *, int, hipStream_t);
-hipError_t prk_rec_counts(const void *, const uint32_t *, uint32_t, const uint32_t *, uint32_t *, hipStream_t);
-hipError_t prk_rec_export(const void *, const uint32_t *, uint64_t, void *, hipStream_t);
-hipError_t prk_adv_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
-                        hipStream_t);
-uint32_t prk_adv_wg_lcap(void);
-hipError_t prk_adv_walk_wg(int, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
-                           const uint32_t *, const uint32_t *, void *, int32_t *, void *, uint32_t *, uint32_t *,
-                           uint32_t *, hipStream_t);
-hipError_t prk_adv_next(const void *, uint32_t, int32_t *, hipStream_t);
-hipError_t prk_span_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
-                         const uint32_t *, void *, int32_t *, uint32_t *, uint32_t *, hipStream_t);
-hipError_t prk_span_pack(const void *, const int32_t *, const uint32_t *, const uint32_t *, uint32_t, uint32_t, void *,
-                         hipStream_t);
-hipError_t prk_row_walk(const void *, uint32_t, const uint32_t *, uint32_t, const uint32_t *, int32_t, void *,
-                        const uint32_t *, const uint32_t *, void *, void *, uint32_t *, uint32_t *, uint32_t *,
-                        hipStream_t);
-hipError_t prk_row_pack(const void *, const void *, const uint32_t *, const uint32_t *, const uint32_t *,
-                        const uint32_t *, uint32_t, uint32_t, uint32_t, void *, void *, hipStream_t);
-hipError_t prk_rows_counts(const void *, uint32_t, uint32_t *, hipStream_t);
-hipError_t prk_rows_unpack(const void *, const uint32_t *, uint32_t, const void *, uint32_t, void *, hipStream_t);
-hipError_t prk_span_handle_walk(const prk::FrameParams *, uint32_t, uint32_t, uint32_t, const void *, uint32_t, uint32_t,
-                                const unsigned long long *, void *, void *, uint32_t *, hipStream_t);
-hipError_t prk_obj_gather(const void *, const uint32_t *, const uint32_t *, const void *, const uint32_t *, uint32_t,
-                          void *, uint32_t, void *, hipStream_t);
-hipError_t prk_obj_bound(const prk::FrameParams *, const void *, uint32_t, const unsigned long long *, const void *,
-                         const unsigned long long *, unsigned long long *, hipStream_t);
-uint32_t prk_obj_walk_lcap(void);
-hipError_t prk_obj_walk(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, const uint32_t *, void *,
-                        const unsigned long long *, void *, void *, void *, uint32_t *, const void *, uint32_t *, int,
-                        const void *, const uint32_t *, uint32_t, hipStream_t);
-hipError_t prk_obj_seg(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, const uint32_t *,
-                       const void *, const unsigned long long *, uint32_t *, const uint32_t *, void *, void *, hipStream_t);
-uint32_t prk_obj_link_cap(void);
-hipError_t prk_obj_maxact(const prk::FrameParams *, const void *, const uint32_t *, uint32_t, const uint32_t *,
-                          const uint32_t *, const void *, int32_t *, uint32_t, hipStream_t);
-size_t prk_maxact_huge_scratch(void);
-hipError_t prk_obj_maxact_huge(const prk::FrameParams *, const void *, const uint32_t *, uint32_t, uint32_t, uint32_t,
-                               const uint32_t *, const uint32_t *, const void *, int32_t *, void *, hipStream_t);
-uint32_t prk_obj_walk_threads(uint32_t);
-hipError_t prk_obj_walk_group(const prk::FrameParams *, int32_t, uint32_t, const void *, const uint32_t *,
-                              const unsigned long long *, const uint32_t *, uint32_t, int32_t *, const uint32_t *,
-                              const uint32_t *, void *, const unsigned long long *, void *, void *, void *, void *,
-                              uint32_t *, uint32_t *, const uint32_t *, hipStream_t);
-uint32_t prk_big_max_entries(void);
-uint64_t prk_big_slice_ints(uint32_t, uint32_t, uint32_t);
-uint32_t prk_big_lds_cap(void);
-hipError_t prk_big_walk(const prk::FrameParams *, int32_t, int, const void *, const uint32_t *, const unsigned long long *,
-                        const uint32_t *, const uint32_t *, uint32_t, uint32_t, int32_t *, const uint32_t *,
-                        const uint32_t *, const void *, const unsigned long long *, void *, void *, uint32_t *,
-                        uint32_t *, const uint32_t *, hipStream_t);
-hipError_t prk_pr_walk_begin(const prk::FrameParams *, const prk::PrWalkArgs *, hipStream_t);
-hipError_t prk_pr_walk_group(const prk::FrameParams *, const prk::PrWalkArgs *, int32_t, uint32_t, const uint32_t *,
-                             uint32_t, uint32_t, hipStream_t);
-hipError_t prk_pr_walk_end(const prk::PrWalkArgs *, hipStream_t);
-uint32_t prk_pr_chunk_rows(void);
-int32_t prk_pr_max_row_entries(void);
-int32_t prk_pr_max_rows(void);
-hipError_t prk_span_finish(const prk::FrameParams *, const void *, uint32_t, void *, void *, void *, hipStream_t);
-hipError_t prk_scan_u32(const uint32_t *, uint32_t *, uint32_t, void *, size_t *, hipStream_t);
-hipError_t prk_scan_u64(const unsigned long long *, unsigned long long *, uint32_t, void *, size_t *, hipStream_t);
-hipError_t prk_span_count(const prk::FrameParams *, const void *, uint32_t, uint32_t *, hipStream_t);
-hipError_t prk_span_bin(const prk::FrameParams *, const void *, uint32_t, const uint32_t *, uint32_t *, uint32_t *,
-                        hipStream_t);
-hipError_t prk_launch_spans(const prk::FrameParams *, const uint32_t *, const uint32_t *, const void *,
-                            const void *, const void *, uint32_t, const uint32_t *, uint32_t *, uint32_t *,
-                            hipStream_t);
-hipError_t prk_xform_launch(const void *, size_t, size_t, uint32_t, uint32_t, const float *, const float *,
-                            const float *, const float *, float *, float *, float *, float *, hipStream_t);
-}
 
-// prk_spans.hip's object descriptor, and the runs of objects the device
-// expands into them (prk_spans.hip ObjRun).
-struct ObjDesc {
-    uint32_t draw, g0, tris, tri0, kind, src, nsrc, k1off;
-};
-struct ObjRun {
-    uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
-};
-// prk_spans.hip's segments of a pass's batch edges and list-table sources
-// (passes that draw from record handles).
-struct PrepSeg {
-    uint64_t src;  // (the device address of its first record)
-    uint32_t e0, n, blk0, pad;
-};
-struct ListSrc {
-    const uint32_t *cnt, *flag;
-};
-constexpr uint32_t kPrepEdges = 256;         // prk_spans.hip: edges a workgroup of k_list_prep* takes
+using prk::ListSrc;
+using prk::ObjDesc;
+using prk::ObjRun;
+using prk::PrepSeg;
+using prk::kAdvWgCaps;
+using prk::kObjEdgeBytes;
+using prk::kPairRawBytes;
+using prk::kPrepEdges;
+using prk::kScSpanRecBytes;
+using prk::kWaveListArrays;
+using prk::packed_edge_bytes;
+using prk::packed_span_bytes;
 constexpr uint32_t kObjWaveTris = 48;        // objects of this many triangles or more
 // ... and sorted edge lists (prk_draw_edge_lists) of this many edges or more
 // are large objects: the most edges the smallest large triangle object has
 constexpr uint32_t kObjWaveEdges = 3 * kObjWaveTris;
 constexpr uint64_t kPrMaxEntries = 1ull << 23;  // the chunked walk's list entries per pass (~3 GB of scratch)
-constexpr int kWaveListArrays = 9;           // prk_spans.hip WaveList: int32 arrays of cap + 2 entries
 
 // AVX frames shade through span records (k_walk + k_pix); must match
 // PRK_SPAN_RECORDS of prk_kernels.hip.
@@ -243,6 +124,7 @@ struct Records {
     bool live = false;
     const uint32_t *d_cnt() const { return tab; }
     const uint32_t *d_flag() const { return tab + cnt.size() + 1; }
+    const void *at(uint64_t r) const { return static_cast<const char *>(rec) + r * sizeof(prk_edge); }  // record r
 };
 
 // A span batch (prk_spans_*): packed prk_span records kept in device memory.
@@ -1551,7 +1433,7 @@ static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, con
     PRK_TRY(hipSetDevice(c->device));
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const size_t out_bytes = (((size_t)npair * 25 + 3) / 4) * 16;
+    const size_t out_bytes = packed_span_bytes(npair);
     PRK_TRY(S.d_dr_rows.ensure((size_t)nrow * sizeof(prk_row)));
     PRK_TRY(S.d_dr_pairs.ensure((size_t)npair * sizeof(prk_row_pair)));
     PRK_TRY(S.d_dr_cnt.ensure(((size_t)nrow + 1) * 4));
@@ -2174,11 +2056,11 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     auto add_seg = [&](uint64_t src, bool staged, uint32_t n) {
         if (!handles || !n) return;
         if (!S.h_segs.empty() && seg_staged.back() == (staged ? 1 : 0) &&
-            S.h_segs.back().src + sizeof(prk_edge) * (uint64_t)S.h_segs.back().n == src) {
+            reinterpret_cast<uintptr_t>(S.h_segs.back().src) + sizeof(prk_edge) * (uint64_t)S.h_segs.back().n == src) {
             S.h_segs.back().n += n;  // (the records go on where the previous segment's end)
             return;
         }
-        S.h_segs.push_back(PrepSeg{src, (uint32_t)nle, n, 0u, 0u});
+        S.h_segs.push_back(PrepSeg{reinterpret_cast<const uint32_t *>(src), (uint32_t)nle, n, 0u, 0u});
         seg_staged.push_back(staged ? 1 : 0);
     };
     bool thread_links = false;  // a thread-walked triangle object small enough for LDS list links
@@ -2350,7 +2232,9 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     }
     PRK_TRY(S.d_stage.ensure(stage_bytes));
     for (size_t i = 0; i < S.h_segs.size(); ++i)  // the staged segments' records, where the staging puts them
-        if (seg_staged[i]) S.h_segs[i].src += reinterpret_cast<uintptr_t>(S.d_stage.p) + parts[T_LEDGES].off;
+        if (seg_staged[i])  // (src held the record's byte offset till now)
+            S.h_segs[i].src = reinterpret_cast<const uint32_t *>(static_cast<const char *>(S.d_stage.p) + parts[T_LEDGES].off +
+                                                                 reinterpret_cast<uintptr_t>(S.h_segs[i].src));
     for (const Part &pt : parts)
         if (pt.bytes && pt.src) std::memcpy(S.h_stage + pt.off, pt.src, pt.bytes);
     PRK_TRY(hipMemcpyAsync(S.d_stage.p, S.h_stage, stage_bytes, hipMemcpyHostToDevice, s));
@@ -2405,7 +2289,7 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(S.d_escan.ensure(((size_t)nt + 1) * 4));
     PRK_TRY(S.d_rcnt.ensure(((size_t)nt + 1) * 8));
     PRK_TRY(S.d_rscan.ensure(((size_t)nt + 1) * 8));
-    PRK_TRY(S.d_edges.ensure(es * 112));  // prk_spans.hip ObjEdge
+    PRK_TRY(S.d_edges.ensure(es * kObjEdgeBytes));
     PRK_TRY(S.d_ekeys.ensure(es * 8));
     PRK_TRY(S.d_ekeys2.ensure(es * 8));
     PRK_TRY(S.d_evals.ensure(es * 4));
@@ -2455,7 +2339,7 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     // the batch lists), and each large object's most active edges (read back
     // with the slot total: they size its walk's workgroup).
     const uint32_t nwork = 3 * nt + (uint32_t)nk1 + nledge;
-    PRK_TRY(S.d_work.ensure(std::max<size_t>(nwork, 1) * 112));
+    PRK_TRY(S.d_work.ensure(std::max<size_t>(nwork, 1) * kObjEdgeBytes));
     // The small triangle objects' segments (prk_spans.hip k_obj_seg, below):
     // a thread per stretch of rows with a non-empty list (PRK_OBJ_SEGMENTS=0:
     // a thread per object).
@@ -2527,8 +2411,8 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(S.d_recs.ensure(ns * 64));
     PRK_TRY(S.d_pos.ensure(ns * 16));
     PRK_TRY(S.d_span_tri.ensure(ns * 4));
-    if (scalar) PRK_TRY(S.d_srecs.ensure(ns * 96));  // DrawModel span records (prk_spans.hip ScSpanRecG)
-    if (nbig_all) PRK_TRY(S.d_raw.ensure(ns * 96));   // the slot walks' pairs (prk_spans.hip PairRaw)
+    if (scalar) PRK_TRY(S.d_srecs.ensure(ns * kScSpanRecBytes));  // DrawModel span records
+    if (nbig_all) PRK_TRY(S.d_raw.ensure(ns * kPairRawBytes));     // the slot walks' pairs
     // slots no span takes stay row -1: binned nowhere.  Without large objects
     // every slot belongs to the thread or segment walks (walk_object,
     // k_obj_seg), which mark their unused ones themselves (C3b as 16-triangle
@@ -2719,9 +2603,9 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         if (ae == hipSuccess) ae = S.d_prsm.ensure((size_t)pr_chunks * 4);
         if (ae == hipSuccess) ae = S.d_prsidx.ensure(pr_ents * 4);
         if (ae == hipSuccess) ae = S.d_prkey.ensure(pr_ents * 16);
-        if (ae == hipSuccess) ae = S.d_prest.ensure(pr_ents * 112);  // prk_spans.hip ObjEdge
-        if (ae == hipSuccess) ae = S.d_prsst.ensure(pr_ents * 112);
-        if (ae == hipSuccess) ae = S.d_preend.ensure(pr_ents * 112);
+        if (ae == hipSuccess) ae = S.d_prest.ensure(pr_ents * kObjEdgeBytes);
+        if (ae == hipSuccess) ae = S.d_prsst.ensure(pr_ents * kObjEdgeBytes);
+        if (ae == hipSuccess) ae = S.d_preend.ensure(pr_ents * kObjEdgeBytes);
         if (ae == hipErrorOutOfMemory) {
             (void)hipGetLastError();
             DevBuf *big[] = {&S.d_prsidx, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend};
@@ -3117,10 +3001,10 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
     *total_out = total;
     const bool fill = keep || (records != nullptr && capacity >= total);
     if (fill && total) {
-        PRK_TRY(S.d_edges.ensure(es * 112));  // prk_spans.hip ObjEdge
+        PRK_TRY(S.d_edges.ensure(es * kObjEdgeBytes));
         PRK_TRY(S.d_ekeys.ensure(es * 8));
         PRK_TRY(S.d_evals.ensure(es * 4));
-        const size_t out_bytes = (((size_t)total * 27 + 3) / 4) * 16;
+        const size_t out_bytes = packed_edge_bytes(total);
         void *d_out = nullptr;
         if (keep) {
             PRK_TRY(hipMalloc(&d_out, out_bytes));
@@ -3135,7 +3019,7 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
         PRK_TRY(prk_rec_emit(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, escan, setup, pbits, S.d_edges.p,
                              S.d_ekeys.p, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
         if (local_sort) {
-            PRK_TRY(S.d_work.ensure(es * 112));
+            PRK_TRY(S.d_work.ensure(es * kObjEdgeBytes));
             PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nobj, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, nullptr,
                                        (uint32_t *)S.d_err.p, s));
             PRK_TRY(prk_rec_export(S.d_work.p, nullptr, total, d_out, s));
@@ -3258,7 +3142,7 @@ int prk_records_upload(prk_context *c, const prk_edge *records, const uint32_t *
     Records R;
     int rc = records_tab_alloc(R, list_count);
     if (rc == PRK_OK && total) {
-        rc = status_of(hipMalloc(&R.rec, (((size_t)total * 27 + 3) / 4) * 16));
+        rc = status_of(hipMalloc(&R.rec, packed_edge_bytes(total)));
         if (rc == PRK_OK)  // the one copy of the caller's records
             rc = status_of(hipMemcpy(R.rec, records, (size_t)total * sizeof(prk_edge), hipMemcpyHostToDevice));
     }
@@ -3417,7 +3301,7 @@ static uint32_t list_most_listed(const prk_edge *e, uint32_t n, int32_t height, 
 // device is not asked for its slot classes, no route word is made or
 // uploaded, and the thread kernels get a null route.
 constexpr uint64_t kAdvWgMinSteps = 3432;  // (the sweep's square_48x48: 48 * 48 + 48 * 47 / 2)
-constexpr uint32_t kAdvWgCaps[5] = {62, 126, 254, 510, 1022};
+// (kAdvWgCaps, prk_launch.h: the workgroup walks' five slot classes)
 struct ListRouter {
     struct Cand {
         uint32_t o, cls;
@@ -3486,19 +3370,6 @@ struct ListRouter {
         c->spans.list_routes[0] = list_count - (uint32_t)cand.size();
         for (int ci = 0; ci < 5; ++ci) c->spans.list_routes[1 + ci] = ncls[ci];
     }
-    // The workgroup kernels, a launch per occupied class (d_lists: the words after the route words).
-    hipError_t launch(int kind, const uint32_t *d_lists, const uint32_t *lscan, int32_t height, void *work,
-                      const uint32_t *sbase, const uint32_t *rbase, void *raw, int32_t *prow, void *rows,
-                      uint32_t *cnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) const {
-        if (cand.empty()) return hipSuccess;
-        for (int ci = 0; ci < 5; ++ci) {
-            const hipError_t e = prk_adv_walk_wg(kind, kAdvWgCaps[ci], d_lists, ncls[ci], lscan, height, work, sbase,
-                                                 rbase, raw, prow, rows, cnt, rcnt, err, s);
-            if (e != hipSuccess) return e;
-            d_lists += ncls[ci];
-        }
-        return hipSuccess;
-    }
 };
 // The host side of a record call's pass over its lists: each list's first
 // edge (lscan), its first pair slot (sbase: prk_span_records, prk_row_records)
@@ -3534,6 +3405,122 @@ struct WalkPlan {
         too_long = too_long || nslot >= 0x7FFFFFFFull || nrslot >= 0x7FFFFFFFull;
     }
 };
+// The host-input calls' pass over the caller's lists (counts: list_count of
+// them); PRK_ERR_UNSUPPORTED: a list breaks the sorted rule.  The walk's rows,
+// [YMin[0], min(max YMax, height)), are found for a plan with row slots only:
+// the pass is on the timed path of large batches.
+static int plan_lists(WalkPlan &plan, const prk_edge *e, const uint32_t *counts, int32_t height) {
+    uint32_t at = 0;
+    for (uint32_t o = 0; o < plan.list_count; e += counts[o], at += counts[o], ++o) {
+        plan.open(o, at);
+        if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
+        uint64_t edge_rows = 0, walk_rows = 0;
+        const bool fits = plan.router.take(e, counts[o], height, o, &edge_rows);
+        if (plan.tables > 2 && counts[o]) {
+            int32_t ymax = e[0].YMax;
+            for (uint32_t i = 1; i < counts[o]; ++i) ymax = std::max(ymax, e[i].YMax);
+            walk_rows = (uint64_t)std::max(0, std::min(ymax, height) - e[0].YMin);
+        }
+        plan.close(fits, edge_rows, walk_rows);
+    }
+    plan.open(plan.list_count, at);
+    return PRK_OK;
+}
+// What the host-input record calls check first, in this order: the counts and
+// the height (PRK_ERR_ARG), the buffers a batch with records needs (have_bufs;
+// PRK_ERR_ARG), the limits (PRK_ERR_LIMIT).  *total_out == 0: an empty batch.
+static int lists_check(const uint32_t *counts, uint32_t list_count, int32_t height, bool have_bufs,
+                       uint64_t *total_out) {
+    if ((!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    uint64_t total = 0;
+    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
+    if (!have_bufs && total) return PRK_ERR_ARG;
+    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    *total_out = total;
+    return PRK_OK;
+}
+// An empty batch's per-list counts.
+static void zero_counts(uint32_t *counts_out, uint32_t list_count) {
+    if (counts_out) std::fill(counts_out, counts_out + list_count, 0u);
+}
+// What advance_run, spans_run and rows_run begin with: a too-long plan
+// refused, the router finished, the device idle, the walk's scratch sized --
+// for plan.tables - 1, the walk's kind, and with slots to fill or not --, the
+// records (host or device memory: kind), the plan's tables and the route words
+// uploaded, the counts and the error word cleared, all of it waited for.
+// *a: the walk's arguments; *d_lists: the routed lists by class (null: none).
+// A plan of one table without a routed list is prk_advance_edge_lists as it
+// was before there was a route: no error word is sized or cleared.
+static int walk_begin(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
+                      bool fill, prk::ListWalkArgs *a, const uint32_t **d_lists) {
+    if (plan.too_long) return PRK_ERR_LIMIT;
+    ListRouter &router = plan.router;
+    const std::vector<uint32_t> &tab = plan.tab;
+    const size_t nl1 = plan.nl1;
+    const int tables = plan.tables;
+    router.finish(plan.list_count);
+    const bool wg = router.routed() != 0, use_err = wg || tables > 1;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    router.note(c, plan.list_count);
+    hipStream_t s = c->own_stream;
+    prk_context::SpanScratch &S = c->spans;
+    const uint32_t n = plan.n;
+    PRK_TRY(S.d_recout.ensure(packed_edge_bytes(n)));
+    PRK_TRY(S.d_work.ensure((size_t)n * kObjEdgeBytes));
+    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
+    if (tables > 1) {
+        PRK_TRY(S.d_scnt.ensure(nl1 * 4));
+        PRK_TRY(S.d_soff.ensure(nl1 * 4));
+    }
+    if (tables > 2) {
+        PRK_TRY(S.d_rowcnt.ensure(nl1 * 4));
+        PRK_TRY(S.d_rowscan.ensure(nl1 * 4));
+    }
+    if (use_err) PRK_TRY(S.d_err.ensure(16));
+    if (fill) {
+        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)plan.nslot * kPairRawBytes, 16)));
+        if (tables == 2) PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)plan.nslot * 4, 16)));      // the slots' rows
+        if (tables == 3) PRK_TRY(S.d_rowslot.ensure(std::max<size_t>((size_t)plan.nrslot * 8, 16)));  // {row, pairs}
+    }
+    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
+    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+    if (wg)
+        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
+                               hipMemcpyHostToDevice, s));
+    if (tables > 1) PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scans read list_count + 1 counts)
+    if (tables > 2) PRK_TRY(hipMemsetAsync(S.d_rowcnt.p, 0, nl1 * 4, s));
+    if (use_err) PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
+    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's; records may be an output)
+    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_route = wg ? d_lscan + tab.size() : nullptr;
+    *d_lists = wg ? d_route + nl1 : nullptr;
+    a->work = S.d_work.p;
+    a->lscan = d_lscan;
+    a->nlist = plan.list_count;
+    a->route = d_route;
+    a->height = height;
+    a->sbase = tables > 1 ? d_lscan + nl1 : nullptr;
+    a->rbase = tables > 2 ? d_lscan + 2 * nl1 : nullptr;
+    a->raw = fill ? S.d_raw.p : nullptr;
+    a->prow = fill && tables == 2 ? (int32_t *)S.d_pos.p : nullptr;
+    a->rows = fill && tables == 3 ? S.d_rowslot.p : nullptr;
+    a->cnt = tables > 1 ? (uint32_t *)S.d_scnt.p : nullptr;
+    a->rcnt = tables > 2 ? (uint32_t *)S.d_rowcnt.p : nullptr;
+    a->err = (uint32_t *)S.d_err.p;
+    return PRK_OK;
+}
+// ... and the walk itself: the import and the thread kernel, then the
+// workgroup kernels, a launch per occupied slot class.
+static hipError_t walk_launch(prk_context *c, const WalkPlan &plan, const prk::ListWalkArgs &a,
+                              const uint32_t *d_lists) {
+    const int kind = plan.tables - 1;
+    const uint32_t *ncls = plan.router.ncls;
+    hipError_t e = prk_list_walk(kind, c->spans.d_recout.p, plan.n, &a, c->own_stream);
+    for (int ci = 0; ci < 5 && d_lists && e == hipSuccess; d_lists += ncls[ci], ++ci)
+        e = prk_list_walk_wg(kind, kAdvWgCaps[ci], d_lists, ncls[ci], &a, c->own_stream);
+    return e;
+}
 // prk_advance_edge_lists after its pass, for records in host memory or on the
 // device (kind).  records_out, next_out: null, or host memory.  keep: null,
 // or a handle in the making, which gets a buffer of its own that k_rec_export
@@ -3541,44 +3528,22 @@ struct WalkPlan {
 // are then left to the caller, which copies them once the handle stands.
 static int advance_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
                        prk_edge *records_out, int32_t *next_out, Records *keep) {
-    if (plan.too_long) return PRK_ERR_LIMIT;
-    ListRouter &router = plan.router;
-    const std::vector<uint32_t> &tab = plan.tab;
-    const uint32_t list_count = plan.list_count;
-    const size_t nl1 = plan.nl1;
-    router.finish(list_count);
-    const bool wg = router.routed() != 0;  // (else: the call as it was before there was a route)
-    RESOLVE_COUNT(c);
-    PRK_TRY(hipSetDevice(c->device));
-    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
-    router.note(c, list_count);
+    prk::ListWalkArgs a;
+    const uint32_t *d_lists = nullptr;
+    const int rb = walk_begin(c, plan, records, kind, height, false, &a, &d_lists);
+    if (rb != PRK_OK) return rb;
+    const bool wg = plan.router.routed() != 0;  // (else: the call as it was before there was a route)
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
     const uint32_t n = plan.n;
     const size_t rec_bytes = (size_t)n * sizeof(prk_edge);
-    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
-    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
-    if (wg) PRK_TRY(S.d_err.ensure(16));
     if (next_out) PRK_TRY(S.d_evals.ensure((size_t)n * 4));
     void *d_out = S.d_recout.p;
     if (keep) {
-        PRK_TRY(hipMalloc(&keep->rec, (((size_t)n * 27 + 3) / 4) * 16));  // (the caller frees it, whatever follows)
+        PRK_TRY(hipMalloc(&keep->rec, packed_edge_bytes(n)));  // (the caller frees it, whatever follows)
         d_out = keep->rec;
     }
-    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_route = wg ? d_lscan + tab.size() : nullptr,
-                   *d_lists = wg ? d_route + nl1 : nullptr;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, rec_bytes, kind, s));
-    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-    if (wg) {
-        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
-                               hipMemcpyHostToDevice, s));
-        PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
-    }
-    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's; records may be records_out)
-    PRK_TRY(prk_adv_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, s));
-    PRK_TRY(router.launch(0, d_lists, d_lscan, height, S.d_work.p, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, (uint32_t *)S.d_err.p, s));
+    PRK_TRY(walk_launch(c, plan, a, d_lists));
     if (records_out || keep) PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, d_out, s));
     if (next_out) PRK_TRY(prk_adv_next(S.d_work.p, n, (int32_t *)S.d_evals.p, s));
     uint32_t err = 0;
@@ -3593,23 +3558,14 @@ static int advance_run(prk_context *c, WalkPlan &plan, const void *records, hipM
 }
 int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32_t *counts, uint32_t list_count,
                            int32_t height, prk_edge *records_out, int32_t *next_out) {
-    if (!c || (!counts && list_count) || height < 0) return PRK_ERR_ARG;
+    if (!c) return PRK_ERR_ARG;
     uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if ((!records || !records_out) && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    const int rc = lists_check(counts, list_count, height, records && records_out, &total);
+    if (rc != PRK_OK) return rc;
     if (list_count == 0 || total == 0) return PRK_OK;
     WalkPlan plan(c->device, list_count, 1);
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            plan.open(o, at);
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            plan.close(plan.router.take(e, counts[o], height, o, nullptr), 0, 0);
-        }
-        plan.open(list_count, at);
-    }
+    const int rp = plan_lists(plan, records, counts, height);
+    if (rp != PRK_OK) return rp;
     return advance_run(c, plan, records, hipMemcpyHostToDevice, height, records_out, next_out, nullptr);
 }
 
@@ -3632,48 +3588,16 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
 static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
                      prk_span *spans, uint64_t capacity, uint32_t *span_counts, uint64_t *total_out,
                      SpanBatch *keep = nullptr) {
-    if (plan.too_long) return PRK_ERR_LIMIT;
-    const bool fill = spans || keep;
-    ListRouter &router = plan.router;
-    const std::vector<uint32_t> &tab = plan.tab;
-    const uint32_t list_count = plan.list_count;
-    const size_t nl1 = plan.nl1;
-    const uint64_t nslot = plan.nslot;
-    router.finish(list_count);
-    const bool wg = router.routed() != 0;
-    RESOLVE_COUNT(c);
-    PRK_TRY(hipSetDevice(c->device));
-    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
-    router.note(c, list_count);
+    prk::ListWalkArgs a;
+    const uint32_t *d_lists = nullptr;
+    const int rb = walk_begin(c, plan, records, kind, height, spans || keep, &a, &d_lists);
+    if (rb != PRK_OK) return rb;
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const uint32_t n = plan.n;
-    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
-    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
-    PRK_TRY(S.d_scnt.ensure(nl1 * 4));
-    PRK_TRY(S.d_soff.ensure(nl1 * 4));
-    PRK_TRY(S.d_err.ensure(16));
-    if (fill) {
-        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));  // prk_spans.hip PairRaw
-        PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)nslot * 4, 16)));    // the slots' rows
-    }
-    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1,
-                   *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
-    uint32_t *d_cnt = (uint32_t *)S.d_scnt.p, *d_cscan = (uint32_t *)S.d_soff.p;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
-    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-    if (wg)
-        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
-                               hipMemcpyHostToDevice, s));
-    PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scan reads list_count + 1 counts)
-    PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
-    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
-    PRK_TRY(prk_span_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, d_sbase,
-                          fill ? S.d_raw.p : nullptr, fill ? (int32_t *)S.d_pos.p : nullptr, d_cnt,
-                          (uint32_t *)S.d_err.p, s));
-    PRK_TRY(router.launch(1, d_lists, d_lscan, height, S.d_work.p, d_sbase, nullptr, fill ? S.d_raw.p : nullptr,
-                          fill ? (int32_t *)S.d_pos.p : nullptr, nullptr, d_cnt, nullptr, (uint32_t *)S.d_err.p, s));
+    const uint32_t list_count = plan.list_count;
+    const uint32_t *d_sbase = a.sbase;
+    uint32_t *d_cnt = a.cnt, *d_cscan = (uint32_t *)S.d_soff.p;
+    PRK_TRY(walk_launch(c, plan, a, d_lists));
     size_t tb = 0;
     PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, nullptr, &tb, s));
     PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
@@ -3690,7 +3614,7 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
         PRK_TRY(hipMemcpy(cnt.data(), d_cnt, (size_t)list_count * 4, hipMemcpyDeviceToHost));
         void *buf = nullptr;
         if (nspan) {
-            PRK_TRY(hipMalloc(&buf, (((size_t)nspan * 25 + 3) / 4) * 16));
+            PRK_TRY(hipMalloc(&buf, packed_span_bytes(nspan)));
             hipError_t e = prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, buf, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) {
@@ -3706,7 +3630,7 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     if (!spans) return PRK_OK;
     if (capacity < nspan) return PRK_ERR_ARG;
     if (nspan == 0) return PRK_OK;
-    PRK_TRY(S.d_spanout.ensure((((size_t)nspan * 25 + 3) / 4) * 16));
+    PRK_TRY(S.d_spanout.ensure(packed_span_bytes(nspan)));
     PRK_TRY(prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, S.d_spanout.p, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to `spans` unless the kernel ran
     PRK_TRY(hipMemcpyAsync(spans, S.d_spanout.p, (size_t)nspan * sizeof(prk_span), hipMemcpyDeviceToHost, s));
@@ -3718,29 +3642,17 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
                      uint64_t *total_out) {
     if (!c || !total_out) return PRK_ERR_ARG;
     *total_out = 0;
-    if ((!counts && list_count) || height < 0) return PRK_ERR_ARG;
     uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if (!records && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    const int rc = lists_check(counts, list_count, height, records != nullptr, &total);
+    if (rc != PRK_OK) return rc;
     if (list_count == 0 || total == 0) {
-        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        zero_counts(span_counts, list_count);
         return PRK_OK;
     }
     // lscan, then sbase: each list's first edge and first slot
     WalkPlan plan(c->device, list_count, 2);
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            plan.open(o, at);
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            uint64_t edge_rows = 0;
-            const bool fits = plan.router.take(e, counts[o], height, o, &edge_rows);
-            plan.close(fits, edge_rows, 0);
-        }
-        plan.open(list_count, at);
-    }
+    const int rp = plan_lists(plan, records, counts, height);
+    if (rp != PRK_OK) return rp;
     return spans_run(c, plan, records, hipMemcpyHostToDevice, height, spans, capacity, span_counts, total_out);
 }
 
@@ -3761,52 +3673,18 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
 static int rows_run(prk_context *c, WalkPlan &plan, const void *records, hipMemcpyKind kind, int32_t height,
                     prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs, uint64_t pair_capacity,
                     uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
-    if (plan.too_long) return PRK_ERR_LIMIT;
-    ListRouter &router = plan.router;
-    const std::vector<uint32_t> &tab = plan.tab;
-    const uint32_t list_count = plan.list_count;
-    const size_t nl1 = plan.nl1;
-    const uint64_t nslot = plan.nslot, nrslot = plan.nrslot;
-    router.finish(list_count);
-    const bool wg = router.routed() != 0;
-    RESOLVE_COUNT(c);
-    PRK_TRY(hipSetDevice(c->device));
-    PRK_TRY(hipDeviceSynchronize());  // frames in flight use the scratch below
+    const bool fill = rows != nullptr;
+    prk::ListWalkArgs a;
+    const uint32_t *d_lists = nullptr;
+    const int rb = walk_begin(c, plan, records, kind, height, fill, &a, &d_lists);
+    if (rb != PRK_OK) return rb;
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
-    const uint32_t n = plan.n;
-    const bool fill = rows != nullptr;
-    router.note(c, list_count);
-    PRK_TRY(S.d_recout.ensure((((size_t)n * 27 + 3) / 4) * 16));
-    PRK_TRY(S.d_work.ensure((size_t)n * 112));  // prk_spans.hip ObjEdge
-    PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
-    PRK_TRY(S.d_scnt.ensure(nl1 * 4));
-    PRK_TRY(S.d_soff.ensure(nl1 * 4));
-    PRK_TRY(S.d_rowcnt.ensure(nl1 * 4));
-    PRK_TRY(S.d_rowscan.ensure(nl1 * 4));
-    PRK_TRY(S.d_err.ensure(16));
-    if (fill) {
-        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)nslot * 96, 16)));     // prk_spans.hip PairRaw
-        PRK_TRY(S.d_rowslot.ensure(std::max<size_t>((size_t)nrslot * 8, 16)));  // {row, pairs}
-    }
-    const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_sbase = d_lscan + nl1, *d_rbase = d_sbase + nl1,
-                   *d_route = wg ? d_lscan + tab.size() : nullptr, *d_lists = wg ? d_route + nl1 : nullptr;
-    uint32_t *d_pcnt = (uint32_t *)S.d_scnt.p, *d_pscan = (uint32_t *)S.d_soff.p;
-    uint32_t *d_rcnt = (uint32_t *)S.d_rowcnt.p, *d_rscan = (uint32_t *)S.d_rowscan.p;
-    PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
-    PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
-    if (wg)
-        PRK_TRY(hipMemcpyAsync((uint32_t *)S.d_escan.p + tab.size(), router.words.data(), router.words.size() * 4,
-                               hipMemcpyHostToDevice, s));
-    PRK_TRY(hipMemsetAsync(S.d_scnt.p, 0, nl1 * 4, s));  // (the scans read list_count + 1 counts)
-    PRK_TRY(hipMemsetAsync(S.d_rowcnt.p, 0, nl1 * 4, s));
-    PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
-    PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's)
-    PRK_TRY(prk_row_walk(S.d_recout.p, n, d_lscan, list_count, d_route, height, S.d_work.p, d_sbase, d_rbase,
-                         fill ? S.d_raw.p : nullptr, fill ? S.d_rowslot.p : nullptr, d_pcnt, d_rcnt,
-                         (uint32_t *)S.d_err.p, s));
-    PRK_TRY(router.launch(2, d_lists, d_lscan, height, S.d_work.p, d_sbase, d_rbase, fill ? S.d_raw.p : nullptr,
-                          nullptr, fill ? S.d_rowslot.p : nullptr, d_pcnt, d_rcnt, (uint32_t *)S.d_err.p, s));
+    const uint32_t list_count = plan.list_count;
+    const uint32_t *d_sbase = a.sbase, *d_rbase = a.rbase;
+    uint32_t *d_pcnt = a.cnt, *d_pscan = (uint32_t *)S.d_soff.p;
+    uint32_t *d_rcnt = a.rcnt, *d_rscan = (uint32_t *)S.d_rowscan.p;
+    PRK_TRY(walk_launch(c, plan, a, d_lists));
     size_t tb = 0;
     PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, nullptr, &tb, s));
     PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
@@ -3842,35 +3720,19 @@ int prk_row_records(prk_context *c, const prk_edge *records, const uint32_t *cou
                     int32_t height, prk_row *rows, uint64_t row_capacity, prk_row_pair *pairs,
                     uint64_t pair_capacity, uint32_t *row_counts, uint64_t *row_total_out, uint64_t *pair_total_out) {
     if (!c || !row_total_out || !pair_total_out) return PRK_ERR_ARG;
-    if ((!counts && list_count) || height < 0 || (rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
+    if ((rows == nullptr) != (pairs == nullptr)) return PRK_ERR_ARG;
     uint64_t total = 0;
-    for (uint32_t o = 0; o < list_count; ++o) total += counts[o];
-    if (!records && total) return PRK_ERR_ARG;
-    if (total >= 0x7FFFFFFFull || list_count >= 0x7FFFFFFFu || height > 65536) return PRK_ERR_LIMIT;
+    const int rc = lists_check(counts, list_count, height, records != nullptr, &total);
+    if (rc != PRK_OK) return rc;
     if (list_count == 0 || total == 0) {
         *row_total_out = *pair_total_out = 0;
-        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
+        zero_counts(row_counts, list_count);
         return PRK_OK;
     }
     // lscan, sbase, rbase: each list's first edge, first pair slot and first row slot
     WalkPlan plan(c->device, list_count, 3);
-    {
-        const prk_edge *e = records;
-        uint32_t at = 0;
-        for (uint32_t o = 0; o < list_count; e += counts[o], at += counts[o], ++o) {
-            plan.open(o, at);
-            if (!list_walks_sorted(e, counts[o])) return PRK_ERR_UNSUPPORTED;
-            uint64_t edge_rows = 0, walk_rows = 0;
-            const bool fits = plan.router.take(e, counts[o], height, o, &edge_rows);
-            if (counts[o]) {  // the walk's rows: [YMin[0], min(max YMax, height))
-                int32_t ymax = e[0].YMax;
-                for (uint32_t i = 1; i < counts[o]; ++i) ymax = std::max(ymax, e[i].YMax);
-                walk_rows = (uint64_t)std::max(0, std::min(ymax, height) - e[0].YMin);
-            }
-            plan.close(fits, edge_rows, walk_rows);
-        }
-        plan.open(list_count, at);
-    }
+    const int rp = plan_lists(plan, records, counts, height);
+    if (rp != PRK_OK) return rp;
     return rows_run(c, plan, records, hipMemcpyHostToDevice, height, rows, row_capacity, pairs, pair_capacity,
                     row_counts, row_total_out, pair_total_out);
 }
@@ -3906,7 +3768,7 @@ static int records_plan(prk_context *c, const Records &R, uint32_t first_list, u
     uint32_t at = 0;
     for (uint32_t o = 0; o < nlist; at += cnt[o], ++o) lscan[o] = at;
     lscan[nlist] = at;
-    const void *rec = static_cast<const char *>(R.rec) + r0 * sizeof(prk_edge);
+    const void *rec = R.at(r0);
     // device: lscan | the statistics (24 bytes a list) | the candidates | their most linked
     const size_t stat_off = (plan.nl1 * 4 + 7) & ~(size_t)7, cand_off = stat_off + (size_t)nlist * 24;
     PRK_TRY(S.d_lstat.ensure(cand_off + (size_t)nlist * 8));
@@ -4020,8 +3882,8 @@ int prk_records_advance(prk_context *c, int32_t handle, uint32_t first_list, uin
         WalkPlan plan(c->device, list_count, 1);
         ra = records_begin(c, *R, first_list, r0, height, plan, nullptr);
         if (ra == PRK_OK)
-            ra = advance_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge),
-                             hipMemcpyDeviceToDevice, height, records_out, next_out, advanced_out ? &A : nullptr);
+            ra = advance_run(c, plan, R->at(r0), hipMemcpyDeviceToDevice, height, records_out, next_out,
+                             advanced_out ? &A : nullptr);
     } else if (advanced_out) {
         RESOLVE_COUNT(c);
         ra = status_of(hipSetDevice(c->device));
@@ -4065,14 +3927,13 @@ int prk_records_spans(prk_context *c, int32_t handle, uint32_t first_list, uint3
     const int rc = records_range(c, handle, first_list, list_count, height, &R, &r0, &n);
     if (rc != PRK_OK) return rc;
     if (n == 0) {
-        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        zero_counts(span_counts, list_count);
         return PRK_OK;
     }
     WalkPlan plan(c->device, list_count, 2);
     const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
     if (rp != PRK_OK) return rp;
-    return spans_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge), hipMemcpyDeviceToDevice,
-                     height, spans, capacity, span_counts, total_out);
+    return spans_run(c, plan, R->at(r0), hipMemcpyDeviceToDevice, height, spans, capacity, span_counts, total_out);
 }
 
 int prk_records_rows(prk_context *c, int32_t handle, uint32_t first_list, uint32_t list_count, int32_t height,
@@ -4086,14 +3947,14 @@ int prk_records_rows(prk_context *c, int32_t handle, uint32_t first_list, uint32
     if (rc != PRK_OK) return rc;
     if (n == 0) {
         *row_total_out = *pair_total_out = 0;
-        if (row_counts) std::fill(row_counts, row_counts + list_count, 0u);
+        zero_counts(row_counts, list_count);
         return PRK_OK;
     }
     WalkPlan plan(c->device, list_count, 3);
     const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
     if (rp != PRK_OK) return rp;
-    return rows_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge), hipMemcpyDeviceToDevice,
-                    height, rows, row_capacity, pairs, pair_capacity, row_counts, row_total_out, pair_total_out);
+    return rows_run(c, plan, R->at(r0), hipMemcpyDeviceToDevice, height, rows, row_capacity, pairs, pair_capacity,
+                    row_counts, row_total_out, pair_total_out);
 }
 
 // ---- span handles (prk.h) ---------------------------------
@@ -4126,13 +3987,13 @@ int prk_spans_from_records(prk_context *c, int32_t records_handle, uint32_t firs
     uint64_t total = 0;
     if (n == 0) {
         B.cnt.assign(list_count, 0u);
-        if (span_counts) std::fill(span_counts, span_counts + list_count, 0u);
+        zero_counts(span_counts, list_count);
     } else {
         WalkPlan plan(c->device, list_count, 2);
         const int rp = records_begin(c, *R, first_list, r0, height, plan, nullptr);
         if (rp != PRK_OK) return rp;
-        const int rs = spans_run(c, plan, static_cast<const char *>(R->rec) + r0 * sizeof(prk_edge),
-                                 hipMemcpyDeviceToDevice, height, nullptr, 0, span_counts, &total, &B);
+        const int rs = spans_run(c, plan, R->at(r0), hipMemcpyDeviceToDevice, height, nullptr, 0, span_counts, &total,
+                                 &B);
         if (rs != PRK_OK) return rs;
     }
     if (total_out) *total_out = total;
@@ -4150,7 +4011,7 @@ int prk_spans_upload(prk_context *c, const prk_span *spans, uint32_t count, int3
     B.total = count;
     if (count) {
         PRK_TRY(hipSetDevice(c->device));
-        const size_t bytes = (((size_t)count * 25 + 3) / 4) * 16, used = (size_t)count * sizeof(prk_span);
+        const size_t bytes = packed_span_bytes(count), used = (size_t)count * sizeof(prk_span);
         PRK_TRY(hipMalloc(&B.sp, bytes));
         hipError_t e = hipMemset(static_cast<char *>(B.sp) + bytes - 16, 0, 16);  // (the last piece's spare dwords)
         if (e == hipSuccess) e = hipMemcpy(B.sp, spans, used, hipMemcpyHostToDevice);  // the one copy of the caller's spans
@@ -4181,7 +4042,7 @@ int prk_spans_upload_rows(prk_context *c, const prk_row *rows, uint64_t row_coun
     B.total = n;
     if (n) {
         PRK_TRY(hipSetDevice(c->device));
-        PRK_TRY(hipMalloc(&B.sp, (((size_t)n * 25 + 3) / 4) * 16));
+        PRK_TRY(hipMalloc(&B.sp, packed_span_bytes(n)));
         const int rc = rows_to_spans(c, rows, (uint32_t)row_count, pairs, n, nullptr, B.sp);
         if (rc != PRK_OK) {
             (void)hipFree(B.sp);

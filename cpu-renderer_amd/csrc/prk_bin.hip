@@ -16,6 +16,7 @@
 #include <atomic>
 
 #include "prk_device.h"
+#include "prk_launch.h"
 
 namespace prk {
 
@@ -922,7 +923,6 @@ hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, void *rang
 // A row band's setup records (k_band_rec) once k_bin_band has listed the
 // runs; nothing to do unless the frame keeps records (fp->trec) and is a
 // band frame with run lists.  The caller queues it on a stream of its own.
-uint32_t prk_bin_runs(uint32_t tri_count);
 hipError_t prk_band_records(const prk::FrameParams *fp, const uint32_t *runlist, const uint32_t *run_n,
                             hipStream_t s) {
     if (!PRK_BAND_REC_KERNEL || !fp->trec || !runlist || !fp->tri_count) return hipSuccess;
@@ -935,8 +935,6 @@ hipError_t prk_band_records(const prk::FrameParams *fp, const uint32_t *runlist,
 // runs per chunk: about one whole-frame chunk's worth (kCsChunk) of the
 // band's share of the triangles, so a narrow band has few chunks (and a
 // small chunk x tile histogram).  0: not a band (whole-frame chunks).
-uint32_t prk_bin_runs(uint32_t tri_count);
-uint32_t prk_bin_run_len(void);
 #ifndef PRK_BAND_MIN_CHUNKS
 #define PRK_BAND_MIN_CHUNKS 128  // > 0: at least about this many chunks (smaller ones) per band frame
                                  // (C3b N = 8: 31 chunks of 1024 threads left the sort on 31 CUs;

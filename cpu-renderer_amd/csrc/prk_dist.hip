@@ -23,10 +23,10 @@
 #include <vector>
 
 #include "../../include/prk.h"
+#include "prk_launch.h"  // prk_resolve_pending (prk_api.hip)
 
 static_assert(PRK_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 
-extern "C" int prk_resolve_pending(prk_context *c, void *stream);  // prk_api.hip (library-internal)
 namespace {
 
 struct Rccl {

@@ -23,6 +23,7 @@
 //            a pixel and shades only their winning fragments.
 
 #include "prk_device.h"
+#include "prk_launch.h"
 #include "../../include/prk.h"  // PRK_OP_* (k_selftest_ops)
 
 // Diagnostic builds only (tools/diag): 1 = skip the shading sweep, 2 = skip

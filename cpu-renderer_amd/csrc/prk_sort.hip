@@ -16,6 +16,8 @@
 
 #include <cstdint>
 
+#include "prk_launch.h"
+
 namespace prk {
 namespace {
 

@@ -83,6 +83,7 @@
 #include <atomic>
 
 #include "prk_device.h"
+#include "prk_launch.h"
 
 namespace prk {
 // Diagnostic builds (-DPRK_WPROF=1): the whole-object slot-list walk
@@ -123,15 +124,7 @@ namespace prk {
 //           as they leave every large object, and the host lists it for no
 //           other walk; like kind 2 it takes one slot (k_obj_bound).
 // g0 is the winner id (pass-local) of what it draws.
-struct ObjDesc {
-    uint32_t draw;
-    uint32_t g0;
-    uint32_t tris;
-    uint32_t tri0;      // kind 0: its first triangle among the pass's object triangles
-    uint32_t kind, src, nsrc;
-    uint32_t k1off;     // kind 1, 3: its first edge slot after the pass's triangle edges;
-                        // bit 31 (kObjWave): a large object (k_obj_maxact, then its walk)
-};
+// (struct ObjDesc: prk_launch.h)
 constexpr uint32_t kObjWave = 0x80000000u;
 constexpr uint32_t kListSrc = 0xFFFFFFFFu;  // ObjDesc::src of a batch's list
 // Kinds whose edges are sorted by YMin: every walk but the whole-list scan.
@@ -153,9 +146,7 @@ constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 // its first list there (per), for k_list_tables to gather lcnt / lflag.  A
 // prk_draw_span_records draw is a run of kind 4: one object per span, from
 // span src_off of its handle on.
-struct ObjRun {
-    uint32_t kind, draw, obj0, count, per, tri_count, first_global, tri0, k0base, src_off, src_n, k1off;
-};
+// (struct ObjRun: prk_launch.h)
 __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris,
                              ObjDesc *__restrict__ objs, uint32_t *__restrict__ k0obj, uint32_t *__restrict__ k0tri0,
                              const uint32_t *__restrict__ lcnt, const uint32_t *__restrict__ lflag,
@@ -214,7 +205,7 @@ struct ObjEdge {
     int32_t YMin, YMax, Left, Next;
     float C0, C1, C2, C3, CG0, CG1, CG2, CG3;  // MinColor / ColorGradient (DrawModel's Gouraud colour)
 };
-static_assert(sizeof(ObjEdge) == 112, "ObjEdge is seven dwordx4");
+static_assert(sizeof(ObjEdge) == kObjEdgeBytes, "ObjEdge is seven dwordx4");
 
 // Span of the span path: its row and pixel range [minx, maxx) (half-open,
 // 1588-1592), DRAW_ST in flags.
@@ -235,7 +226,7 @@ struct ScSpanRecG {
     float f[22];
     int32_t tex, pad;
 };
-static_assert(sizeof(ScSpanRecG) == 96, "scalar span record is six dwordx4");
+static_assert(sizeof(ScSpanRecG) == kScSpanRecBytes, "scalar span record is six dwordx4");
 
 
 __device__ __forceinline__ void obj_edge_store(ObjEdge &o, const Edge &E) {
@@ -1206,7 +1197,7 @@ __global__ void __launch_bounds__(kLinkThreads) k_obj_walk_seg(FrameParams fp, c
 //                          left-to-right sequence equals the two parallel
 //                          passes.  An odd last entry neither pairs nor steps.
 // ---------------------------------------------------------------------------
-constexpr int kWaveListArrays = 9;   // int32 arrays of cap + 2 entries each
+// (kWaveListArrays, prk_launch.h: int32 arrays of cap + 2 entries each)
 constexpr uint32_t kSlotCapLds = 1022;  // the slot-list walk's largest LDS capacity (listed edges; 1024 threads)
 struct WaveList {
     int32_t *idx;
@@ -1692,6 +1683,11 @@ __host__ __device__ constexpr size_t slot_lds_bytes(uint32_t cap) {
     return ((((size_t)kSlotListArrays * (cap + 2) + 4 * (size_t)slot_threads(cap) + cap) * 4 + 15) & ~(size_t)15) +
            (size_t)cap * sizeof(ObjEdge);
 }
+// The record calls' slot classes (prk_launch.h): each fills its workgroup, the largest is the LDS capacity.
+static_assert(slot_threads(kAdvWgCaps[0]) == kAdvWgCaps[0] + 2 && slot_threads(kAdvWgCaps[1]) == kAdvWgCaps[1] + 2 &&
+                  slot_threads(kAdvWgCaps[2]) == kAdvWgCaps[2] + 2 && slot_threads(kAdvWgCaps[3]) == kAdvWgCaps[3] + 2 &&
+                  slot_threads(kAdvWgCaps[4]) == kAdvWgCaps[4] + 2 && kAdvWgCaps[4] == kSlotCapLds,
+              "kAdvWgCaps are the slot walk's classes");
 
 // Workgroup reductions and scans over thread order (R: the waves' partials;
 // every caller reaches them with the whole workgroup).
@@ -1907,7 +1903,7 @@ constexpr uint32_t SPAN_RAW = 0x40000000u;
 struct PairRaw {
     float4 l0, l1, l2, r0, r1, r2;  // X Z W U | V N0 N1 N2 | C0 C1 C2 C3, left then right edge
 };
-static_assert(sizeof(PairRaw) == 96, "six dwordx4");
+static_assert(sizeof(PairRaw) == kPairRawBytes, "six dwordx4");
 // One edge's half of a PairRaw (pair_raw_in reads it back).
 __device__ __forceinline__ void pair_raw_half(const ObjEdge &e, float4 &q0, float4 &q1, float4 &q2) {
     q0 = make_float4(e.X, e.Z, e.W, e.U);
@@ -4201,7 +4197,7 @@ __global__ void __launch_bounds__(256) k_rec_export(const ObjEdge *__restrict__ 
 //   ebase  the first batch edge's slot after the triangle edges (*total0p)
 //   wy     null, or (YMin, YMax) per working-copy slot for k_obj_seg
 // ---------------------------------------------------------------------------
-constexpr int kPrepEdges = 256;
+// (kPrepEdges, prk_launch.h: the edges a workgroup takes)
 struct PrepMap {
     uint8_t f[28];  // ObjEdge dword -> prk_edge field (27: none, the link)
 };
@@ -4323,14 +4319,7 @@ __global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const 
 //                  list there in per
 //   k_list_rule    prk_api.hip's list_walks_sorted for every list of a handle
 // ---------------------------------------------------------------------------
-struct PrepSeg {
-    const uint32_t *src;  // its first record
-    uint32_t e0, n;       // its first edge among the pass's batch edges, its edges
-    uint32_t blk0, pad;   // its first workgroup
-};
-struct ListSrc {
-    const uint32_t *cnt, *flag;
-};
+// (struct PrepSeg, struct ListSrc: prk_launch.h)
 __global__ void __launch_bounds__(kPrepEdges) k_list_prep_segs(FrameParams fp, const PrepSeg *__restrict__ segs,
                                                                uint32_t nseg, const uint32_t *__restrict__ lscan,
                                                                uint32_t nlist, const uint32_t *__restrict__ lobj,
@@ -5521,42 +5510,46 @@ hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total
     return hipGetLastError();
 }
 
-// prk_advance_edge_lists: `total` packed records (readable up to a multiple
-// of 16 bytes) of nlist lists (lscan: nlist + 1 first edges) into the working
-// copy, walked over `height` rows there; prk_rec_export(work, nullptr, ...)
-// packs the result, prk_adv_next its links.
-hipError_t prk_adv_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
-                        const uint32_t *route, int32_t height, void *work, hipStream_t s) {
+// The record calls' thread walks.  `total` packed records (readable up to a
+// multiple of 16 bytes) of a->nlist lists (a->lscan: their first edges) into
+// the working copy a->work, walked over a->height rows there by a thread a
+// list (lists with a route word are left to prk_list_walk_wg).
+//   kind 0, prk_advance_edge_lists: prk_rec_export(work, nullptr, ...) packs
+//     the result, prk_adv_next its links.
+//   kind 1, prk_span_records: the walk with the emission: list o's pairs into
+//     PairRaw slots [sbase[o], sbase[o + 1]) and their rows (prow), its count
+//     into cnt[o]; err |= 1 should a list pass its slots.
+//   kind 2, prk_row_records: the walk with the row emission: list o's pairs
+//     into its PairRaw slots, its row records into row slots [rbase[o],
+//     rbase[o + 1]), its counts into cnt[o] / rcnt[o]; err |= 1 as above, |= 2
+//     when a row holds more than 1000 pairs.
+// raw == nullptr (kinds 1, 2): the counts and err alone (no slots are read or
+// written).
+hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const prk::ListWalkArgs *a, hipStream_t s) {
+    if (kind < 0 || kind > 2) return hipErrorInvalidValue;
+    const uint32_t nlist = a->nlist;
     if (total == 0 || nlist == 0) return hipSuccess;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
-    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
-                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(prk::k_adv_walk, dim3((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads),
-                       dim3(prk::kLinkThreads), 0, s, w, lscan, nlist, route, height);
-    return hipGetLastError();
-}
-// prk_span_records: prk_adv_walk's import, then the walk with the emission:
-// list o's pairs into PairRaw slots [sbase[o], sbase[o + 1]) and their rows,
-// its count into cnt[o]; err |= 1 should a list pass its slots.  raw ==
-// nullptr: the counts alone (no slots are read or written).
-hipError_t prk_span_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
-                         const uint32_t *route, int32_t height, void *work, const uint32_t *sbase, void *raw,
-                         int32_t *row, uint32_t *cnt, uint32_t *err, hipStream_t s) {
-    if (total == 0 || nlist == 0) return hipSuccess;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
     hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
                        dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
-    if (raw)
-        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, lscan, nlist, route, height, sbase,
-                           reinterpret_cast<prk::PairRaw *>(raw), row, cnt, err);
+    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
+    if (kind == 0)
+        hipLaunchKernelGGL(prk::k_adv_walk, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height);
+    else if (kind == 1 && pr)
+        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
+                           a->sbase, pr, a->prow, a->cnt, a->err);
+    else if (kind == 1)
+        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
+                           a->sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, a->cnt, a->err);
+    else if (pr)
+        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
+                           a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt, a->rcnt, a->err);
     else
-        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, lscan, nlist, route, height, sbase,
-                           (prk::PairRaw *)nullptr, (int32_t *)nullptr, cnt, err);
+        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
+                           a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt, a->rcnt, a->err);
     return hipGetLastError();
 }
 // The `total` spans the walk left (cscan: the scanned counts, nlist + 1) as
@@ -5567,30 +5560,6 @@ hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sb
     hipLaunchKernelGGL(prk::k_span_pack, dim3((total + prk::kPackSpans - 1) / prk::kPackSpans),
                        dim3(prk::kPackSpans), 0, s, reinterpret_cast<const prk::PairRaw *>(raw), row, sbase, cscan,
                        nlist, total, reinterpret_cast<uint4 *>(out));
-    return hipGetLastError();
-}
-// prk_row_records: the import, then the walk with the row emission: list o's
-// pairs into PairRaw slots [sbase[o], sbase[o + 1]), its row records into row
-// slots [rbase[o], rbase[o + 1]), its counts into pcnt[o] / rcnt[o]; err |= 1
-// should a list pass its slots, |= 2 when a row holds more than 1000 pairs.
-// raw == nullptr: the counts and err alone (no slots are read or written).
-hipError_t prk_row_walk(const void *records, uint32_t total, const uint32_t *lscan, uint32_t nlist,
-                        const uint32_t *route, int32_t height, void *work, const uint32_t *sbase,
-                        const uint32_t *rbase, void *raw, void *rows, uint32_t *pcnt, uint32_t *rcnt, uint32_t *err,
-                        hipStream_t s) {
-    if (total == 0 || nlist == 0) return hipSuccess;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
-    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
-                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
-    if (raw)
-        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, lscan, nlist, route, height, sbase, rbase,
-                           reinterpret_cast<prk::PairRaw *>(raw), reinterpret_cast<int2 *>(rows), pcnt, rcnt, err);
-    else
-        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, lscan, nlist, route, height, sbase, rbase,
-                           (prk::PairRaw *)nullptr, (int2 *)nullptr, pcnt, rcnt, err);
     return hipGetLastError();
 }
 // The npair pairs and nrow rows the walk left (pscan, rscan: the scanned
@@ -5674,38 +5643,38 @@ uint32_t prk_adv_wg_lcap(void) {
     return (uint32_t)(c - 1);
 }
 // The nl lists lists[0, nl) of slot class lcap, a workgroup each, after the
-// call's import (prk_adv_walk / prk_span_walk / prk_row_walk, whose thread
-// kernels skip them).  kind 0: prk_advance_edge_lists; 1: prk_span_records
-// (cnt: the lists' pairs); 2: prk_row_records (cnt, rcnt: pairs and rows).
-// raw == nullptr: the counting variants.  err as the thread kernels'.
-hipError_t prk_adv_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint32_t nl, const uint32_t *lscan,
-                           int32_t height, void *work, const uint32_t *sbase, const uint32_t *rbase, void *raw,
-                           int32_t *prow, void *rows, uint32_t *cnt, uint32_t *rcnt, uint32_t *err, hipStream_t s) {
+// call's import (prk_list_walk, whose thread kernels skip them); kind, a->raw
+// and a->err as there.
+hipError_t prk_list_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint32_t nl,
+                            const prk::ListWalkArgs *a, hipStream_t s) {
     if (nl == 0) return hipSuccess;
     if (lcap == 0 || lcap > prk_adv_wg_lcap()) return hipErrorInvalidValue;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(work);
+    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
     const dim3 grid(nl), block(prk::slot_threads(lcap));
     const size_t bytes = prk::slot_lds_bytes(lcap);
-    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(raw);
+    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
     switch (kind) {
         case 0:
-            hipLaunchKernelGGL(prk::k_adv_walk_wg, grid, block, bytes, s, w, lscan, lists, lcap, height, err);
+            hipLaunchKernelGGL(prk::k_adv_walk_wg, grid, block, bytes, s, w, a->lscan, lists, lcap, a->height,
+                               a->err);
             break;
         case 1:
-            if (raw)
-                hipLaunchKernelGGL(prk::k_span_walk_wg<true>, grid, block, bytes, s, w, lscan, lists, lcap, height,
-                                   sbase, pr, prow, cnt, err);
+            if (pr)
+                hipLaunchKernelGGL(prk::k_span_walk_wg<true>, grid, block, bytes, s, w, a->lscan, lists, lcap,
+                                   a->height, a->sbase, pr, a->prow, a->cnt, a->err);
             else
-                hipLaunchKernelGGL(prk::k_span_walk_wg<false>, grid, block, bytes, s, w, lscan, lists, lcap, height,
-                                   sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, cnt, err);
+                hipLaunchKernelGGL(prk::k_span_walk_wg<false>, grid, block, bytes, s, w, a->lscan, lists, lcap,
+                                   a->height, a->sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, a->cnt, a->err);
             break;
         case 2:
-            if (raw)
-                hipLaunchKernelGGL(prk::k_row_walk_wg<true>, grid, block, bytes, s, w, lscan, lists, lcap, height,
-                                   sbase, rbase, pr, reinterpret_cast<int2 *>(rows), cnt, rcnt, err);
+            if (pr)
+                hipLaunchKernelGGL(prk::k_row_walk_wg<true>, grid, block, bytes, s, w, a->lscan, lists, lcap,
+                                   a->height, a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt,
+                                   a->rcnt, a->err);
             else
-                hipLaunchKernelGGL(prk::k_row_walk_wg<false>, grid, block, bytes, s, w, lscan, lists, lcap, height,
-                                   sbase, rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, cnt, rcnt, err);
+                hipLaunchKernelGGL(prk::k_row_walk_wg<false>, grid, block, bytes, s, w, a->lscan, lists, lcap,
+                                   a->height, a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt,
+                                   a->rcnt, a->err);
             break;
         default: return hipErrorInvalidValue;
     }

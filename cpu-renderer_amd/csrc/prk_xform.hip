@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "prk_launch.h"
+
 #pragma clang fp contract(off)
 
 namespace {

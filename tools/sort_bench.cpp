@@ -11,12 +11,7 @@
 #include <random>
 #include <vector>
 
-extern "C" {
-hipError_t prk_obj_sort(void *keys_in, uint32_t *vals_in, void *keys_out, uint32_t *vals_out, uint32_t n,
-                        uint32_t end_bit, void *temp, size_t *temp_bytes, hipStream_t s);
-hipError_t prk_scan_u32(const uint32_t *in, uint32_t *out, uint32_t n, void *temp, size_t *temp_bytes,
-                        hipStream_t s);
-}
+#include "../cpu-renderer_amd/csrc/prk_launch.h"  // prk_obj_sort, prk_scan_u32
 
 #define CK(x)                                                                          \
     do {                                                                               \
