@@ -834,6 +834,74 @@ int prk_texture_update(prk_context *c, int32_t handle, const prk_bitmap *b) {
     return PRK_OK;
 }
 
+int prk_texture_alloc(prk_context *c, int32_t width, int32_t height, int32_t *handle_out) {
+    if (!c || width <= 0 || height <= 0 || width > INT32_MAX / 4 || !handle_out) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    Texture t;
+    t.w = width;
+    t.h = height;
+    t.pitch = 4 * width;
+    const size_t bytes = (size_t)t.pitch * ((size_t)height + 1);  // (the guard row with them)
+    PRK_TRY(hipMalloc((void **)&t.mem, bytes));
+    hipError_t e = hipMemset(t.mem, 0, bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the context's streams do not wait for that stream)
+    if (e != hipSuccess) {
+        (void)hipFree(t.mem);
+        return status_of(e);
+    }
+    *handle_out = (int32_t)c->texs.size();
+    c->texs.push_back(t);
+    return PRK_OK;
+}
+
+// A rectangle of the target's colour into a rectangle of a texture (prk.h;
+// kernel: prk_tex.hip).  Ordered as prk_target_upload_async orders its copies:
+// on copy_stream after read_ev (the frames already flushed wrote the target
+// and sampled the texture) and after what own_stream holds (clears, uploads);
+// the next flush waits for in_ev.
+int prk_texture_from_target(prk_context *c, int32_t texture, int32_t x0, int32_t y0, int32_t width, int32_t height,
+                            int32_t factor, int32_t dst_x, int32_t dst_y) {
+    if (!c || texture < 0 || (size_t)texture >= c->texs.size()) return PRK_ERR_ARG;
+    if (factor != 1 && factor != 2 && factor != 4) return PRK_ERR_ARG;
+    if (width <= 0 || height <= 0 || width % factor || height % factor) return PRK_ERR_ARG;
+    if (!c->color) return PRK_ERR_NO_TARGET;
+    const Texture &t = c->texs[texture];
+    const int32_t dw = width / factor, dh = height / factor;
+    if (x0 < 0 || (int64_t)x0 + width > c->W || y0 < c->row0 || (int64_t)y0 + height > c->row1) return PRK_ERR_ARG;
+    if (dst_x < 0 || (int64_t)dst_x + dw > t.w || dst_y < 0 || (int64_t)dst_y + dh > t.h) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    const uint8_t *src = static_cast<const uint8_t *>(c->color) + (size_t)(y0 - c->row0) * c->pitch + (size_t)x0 * 4;
+    uint8_t *dst = t.mem + (size_t)dst_y * t.pitch + (size_t)dst_x * 4;
+    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->read_ev, 0));
+    PRK_TRY(hipEventRecord(c->s_mark, c->own_stream));
+    PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->s_mark, 0));
+    PRK_TRY(prk_tex_from_target_launch(src, (size_t)c->pitch, dst, (size_t)t.pitch, (uint32_t)dw, (uint32_t)dh, factor,
+                                       c->copy_stream));
+    PRK_TRY(hipEventRecord(c->in_ev, c->copy_stream));
+    c->in_wait = true;
+    return PRK_OK;
+}
+
+int prk_texture_download(prk_context *c, int32_t handle, void *memory, int32_t pitch_bytes) {
+    if (!c || handle < 0 || (size_t)handle >= c->texs.size() || !memory) return PRK_ERR_ARG;
+    const Texture &t = c->texs[handle];
+    if (pitch_bytes < 4 * t.w || (pitch_bytes & 3)) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipStreamSynchronize(c->copy_stream));  // every queued prk_texture_from_target runs there
+    PRK_TRY(hipMemcpy2D(memory, pitch_bytes, t.mem, t.pitch, (size_t)t.w * 4, t.h, hipMemcpyDeviceToHost));
+    return PRK_OK;
+}
+
+int prk_texture_info(prk_context *c, int32_t handle, int32_t *width, int32_t *height, int32_t *pitch_bytes) {
+    if (!c || handle < 0 || (size_t)handle >= c->texs.size()) return PRK_ERR_ARG;
+    const Texture &t = c->texs[handle];
+    if (width) *width = t.w;
+    if (height) *height = t.h;
+    if (pitch_bytes) *pitch_bytes = t.pitch;
+    return PRK_OK;
+}
+
 // Allocations of 2 MB and more: heap memory on transparent huge pages,
 // page-locked with hipHostRegister, instead of hipHostMalloc's 4-KB pinned
 // pages -- the drop-in's staging arena takes ~150 MB of per-call vertex

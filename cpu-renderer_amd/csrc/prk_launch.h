@@ -144,6 +144,12 @@ hipError_t prk_xform_launch(const void *tables, size_t runs_off, size_t xf_off, 
                             const float *sV, const float *sC, const float *sN, const float *sUV, float *dV,
                             float *dC, float *dN, float *dUV, hipStream_t s);
 
+// ---- prk_tex.hip --------------------------------------------------------------
+// prk_texture_from_target: the factor*dw x factor*dh pixels at src (rows spitch bytes apart) box-filtered
+// into the dw x dh texels at dst (rows dpitch bytes apart); factor 1, 2 or 4, both addresses 4-byte aligned.
+hipError_t prk_tex_from_target_launch(const void *src, size_t spitch, void *dst, size_t dpitch, uint32_t dw,
+                                      uint32_t dh, int32_t factor, hipStream_t s);
+
 // ---- prk_spans.hip: the record calls -------------------------------------------
 // prk_edge_records: the object triangles' edges with their true-YMin MergeSort keys ...
 hipError_t prk_rec_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj, const uint32_t *k0tri0,

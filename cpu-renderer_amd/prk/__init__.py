@@ -166,6 +166,7 @@ _SIGS = {
 }
 
 _SIGS.update({name: (C.c_int, args) for name, args in abi.GEOMETRY_TRANSFORM_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.TEXTURE_TARGET_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
@@ -656,6 +657,36 @@ class Renderer:
         texels = np.ascontiguousarray(tex.texels, np.uint32)
         bm = abi.PrkBitmap(texels.ctypes.data, tex.width, tex.height, texels.shape[1] * 4)
         _check("prk_texture_update", self._L.prk_texture_update(self._h, handle, C.byref(bm)))
+
+    def texture_alloc(self, width, height):
+        """prk_texture_alloc: a zeroed library-owned texture, a destination
+        for texture_from_target."""
+        h = C.c_int32(-1)
+        _check("prk_texture_alloc", self._L.prk_texture_alloc(self._h, int(width), int(height), C.byref(h)))
+        return h.value
+
+    def texture_from_target(self, tex, rect=None, factor=1, dst=(0, 0)):
+        """prk_texture_from_target: the target's colour over rect = (x0, y0,
+        width, height) in frame pixels (None: the whole band), box-filtered
+        by factor 1, 2 or 4 into texture `tex` at texel dst = (x, y).  Does
+        not wait for the device."""
+        x0, y0, w, h = (0, self.row0, self.width, self.row1 - self.row0) if rect is None else rect
+        _check("prk_texture_from_target", self._L.prk_texture_from_target(
+            self._h, tex, int(x0), int(y0), int(w), int(h), int(factor), int(dst[0]), int(dst[1])))
+
+    def texture_info(self, tex):
+        """prk_texture_info: (width, height, pitch in bytes)."""
+        v = [C.c_int32(0) for _ in range(3)]
+        _check("prk_texture_info", self._L.prk_texture_info(self._h, tex, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def texture_download(self, tex):
+        """prk_texture_download: uint32 [height, width], the texture's texels
+        (without the guard row) after everything queued that writes them."""
+        w, h, _ = self.texture_info(tex)
+        out = np.empty((h, w), np.uint32)
+        _check("prk_texture_download", self._L.prk_texture_download(self._h, tex, _ptr(out), 4 * w))
+        return out
 
     def geometry_update(self, handle, vertices, colors=None, normals=None, uvs=None):
         arrs = [None if a is None else np.ascontiguousarray(a, np.float32)

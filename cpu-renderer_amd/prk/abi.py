@@ -111,6 +111,15 @@ GEOMETRY_TRANSFORM_SIGS = {
     "prk_debug_transform_ms": [C.c_void_p, C.c_void_p],
 }
 
+# Render to texture (prk.h): each entry point and its argument types
+TEXTURE_TARGET_SIGS = {
+    "prk_texture_alloc": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
+    "prk_texture_from_target": [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_int32, C.c_int32],
+    "prk_texture_download": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32],
+    "prk_texture_info": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+}
+
 
 # prk_row_pair word w holds prk_span word ROW_PAIR_SPAN_WORD[w] (an end is
 # XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3]; Right at +12)

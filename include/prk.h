@@ -262,6 +262,58 @@ int prk_texture_create(prk_context *ctx, const prk_bitmap *bitmap, int32_t *hand
 int prk_texture_update(prk_context *ctx, int32_t handle, const prk_bitmap *bitmap);
 int prk_texture_set_filter(prk_context *ctx, int32_t handle, int32_t filter);  /* PRK_FILTER_* */
 
+/* Render to texture: a frame this library drew, sampled by the next one
+ * without leaving the device.  An EXTENSION of this build with its own
+ * definition: the reference's textures are host bitmaps.
+ *
+ * prk_texture_alloc: a library-owned texture of width x height texels (both
+ * > 0), pitch 4 * width, every texel and the guard row (row `height`) zero,
+ * filter PRK_FILTER_NEAREST -- a destination for prk_texture_from_target.
+ *
+ * prk_texture_from_target: the colour of the bound target, pixels
+ * [x0, x0 + width) x [y0, y0 + height) in FRAME coordinates, box-filtered by
+ * `factor` (1, 2 or 4) into texels [dst_x, dst_x + width / factor) x
+ * [dst_y, dst_y + height / factor) of `texture` (any texture handle, at the
+ * pitch it was made with).  Per texel and per 8-bit channel of the 0xAARRGGBB
+ * word, in integers:
+ *   out = (sum of the factor * factor source channel values + factor * factor / 2)
+ *         >> (2 * log2(factor))
+ * so factor 1 copies the word bit for bit, and the result is exact and the
+ * same on every device.  Rendering at 2W x 2H or 4W x 4H and resolving by 2
+ * or 4 is a supersampled frame of W x H.
+ * Nothing else is written: texels outside the destination rectangle and the
+ * guard row keep their contents; the target and z are only read.
+ * The source is the target as the frames already flushed and the clears and
+ * uploads already queued leave it; a prk_target_clear_on_flush not yet flushed
+ * is not in it.  The source rectangle must lie inside [0, W) x [row0, row1):
+ * a band context reads its own rows only.
+ * Ordering is prk_geometry_write's: the call returns without waiting and
+ * allocates nothing; it runs after the frames already flushed (which wrote the
+ * target and sampled the texture) and after the clears and uploads queued so
+ * far, before the next prk_flush's kernels, and before a later
+ * prk_target_clear / prk_target_upload / prk_texture_update changes either
+ * side.  A draw recorded before the call and flushed after it samples the new
+ * contents.
+ * PRK_ERR_ARG: a NULL context, a bad texture handle, a factor other than 1, 2
+ * or 4, a width or height that is not positive or no multiple of factor, a
+ * source rectangle outside the target's band, a destination rectangle outside
+ * the texture's width x height.  PRK_ERR_NO_TARGET: no target bound.  On any
+ * error nothing has been written.
+ *
+ * prk_texture_download: rows [0, height) of any texture (the guard row is not
+ * returned) to host rows of pitch_bytes bytes (>= 4 * width, a multiple of 4),
+ * after everything queued that writes the texture.
+ *
+ * prk_texture_info: a texture's width, height and pitch; any pointer may be
+ * NULL.  Host bookkeeping: no device work. */
+int prk_texture_alloc(prk_context *ctx, int32_t width, int32_t height, int32_t *handle_out);
+int prk_texture_from_target(prk_context *ctx, int32_t texture,
+                            int32_t x0, int32_t y0, int32_t width, int32_t height, /* source, frame pixels */
+                            int32_t factor,                                        /* 1, 2 or 4 */
+                            int32_t dst_x, int32_t dst_y);
+int prk_texture_download(prk_context *ctx, int32_t handle, void *memory, int32_t pitch_bytes);
+int prk_texture_info(prk_context *ctx, int32_t handle, int32_t *width, int32_t *height, int32_t *pitch_bytes);
+
 /* Geometry: non-indexed SoA vertex arrays exactly as render_entry_3d_object
  * (projekt.h:2-15): positions v3, colours v4, normals v3, uvs v2, three
  * vertices per triangle.  Copied to HBM once; a draw references a range. */
