@@ -379,6 +379,37 @@ void exit_guard(int status, void *) {
     _exit(status);
 }
 std::atomic<bool> g_guarded{false};
+
+// prk_selftest_sort / _scan: a device buffer of `bytes` payload bytes and
+// kGuardBytes of kGuardByte after them, filled and read with copies only.
+constexpr size_t kGuardBytes = 4096;
+constexpr unsigned char kGuardByte = 0xA5;
+struct GuardedBuf {
+    char *p = nullptr;
+    size_t bytes = 0;
+    std::vector<unsigned char> host;  // what the buffer was last filled with, then what it holds
+    ~GuardedBuf() {
+        if (p) (void)hipFree(p);
+    }
+    // the pattern everywhere, then `src` (may be null) over the payload
+    hipError_t fill(size_t payload, const void *src) {
+        if (!p) {
+            bytes = payload;
+            const hipError_t e = hipMalloc(&p, bytes + kGuardBytes);
+            if (e != hipSuccess) return e;
+        }
+        host.assign(bytes + kGuardBytes, kGuardByte);
+        if (src && bytes) std::memcpy(host.data(), src, bytes);
+        return hipMemcpy(p, host.data(), host.size(), hipMemcpyHostToDevice);
+    }
+    hipError_t read() { return hipMemcpy(host.data(), p, host.size(), hipMemcpyDeviceToHost); }
+    bool guard_intact() const {
+        for (size_t i = bytes; i < host.size(); ++i)
+            if (host[i] != kGuardByte) return false;
+        return true;
+    }
+    bool holds(const void *src) const { return bytes == 0 || std::memcmp(host.data(), src, bytes) == 0; }
+};
 }  // namespace
 
 extern "C" {
@@ -471,6 +502,75 @@ int prk_selftest_ops(int32_t device, int32_t op, uint32_t n, const uint32_t *a, 
     (void)hipFree(din);
     if (dout) (void)hipFree(dout);
     return status_of(e);
+}
+
+// The radix sort on the caller's pairs (prk.h): guarded buffers, the temp
+// buffer at exactly the queried size and left as it is between the repeats.
+int prk_selftest_sort(int32_t device, uint32_t n, uint32_t end_bit, const uint64_t *keys, const uint32_t *vals,
+                      uint32_t repeats, uint64_t *keys_out, uint32_t *vals_out, uint32_t *damage) {
+    if (device < 0 || !keys || !vals || !keys_out || !vals_out || !damage || repeats == 0) return PRK_ERR_ARG;
+    size_t tb = 0;
+    PRK_TRY(prk_obj_sort(nullptr, nullptr, nullptr, nullptr, n, end_bit, nullptr, &tb, nullptr));  // (host only)
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(device));
+    const size_t kb = (size_t)n * 8, vb = (size_t)n * 4;
+    GuardedBuf kin, vin, kout, vout, temp;
+    PRK_TRY(kin.fill(kb, keys));
+    PRK_TRY(vin.fill(vb, vals));
+    PRK_TRY(temp.fill(tb, nullptr));
+    for (uint32_t r = 0; r < repeats; ++r) {
+        PRK_TRY(kout.fill(kb, nullptr));
+        PRK_TRY(vout.fill(vb, nullptr));
+        PRK_TRY(prk_obj_sort(kin.p, (uint32_t *)vin.p, kout.p, (uint32_t *)vout.p, n, end_bit, temp.p, &tb, nullptr));
+        PRK_TRY(hipDeviceSynchronize());
+    }
+    PRK_TRY(kin.read());
+    PRK_TRY(vin.read());
+    PRK_TRY(kout.read());
+    PRK_TRY(vout.read());
+    PRK_TRY(temp.read());
+    *damage = (kin.holds(keys) && vin.holds(vals) && kin.guard_intact() && vin.guard_intact() ? 0u : PRK_DAMAGE_INPUT) |
+              (kout.guard_intact() && vout.guard_intact() ? 0u : PRK_DAMAGE_OUTPUT_GUARD) |
+              (temp.guard_intact() ? 0u : PRK_DAMAGE_TEMP_GUARD);
+    if (n) {
+        std::memcpy(keys_out, kout.host.data(), kb);
+        std::memcpy(vals_out, vout.host.data(), vb);
+    }
+    return PRK_OK;
+}
+
+// An exclusive scan on the caller's words (prk.h), in and out distinct.
+int prk_selftest_scan(int32_t device, int32_t width, uint32_t n, const void *in, void *out, uint32_t *damage) {
+    if (device < 0 || (width != 32 && width != 64) || !in || !out || !damage) return PRK_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(device));
+    const size_t bytes = (size_t)n * (size_t)(width / 8);
+    size_t tb = 0;
+    GuardedBuf din, dout, temp;
+    PRK_TRY(din.fill(bytes, in));
+    PRK_TRY(dout.fill(bytes, nullptr));
+    if (width == 32) {
+        PRK_TRY(prk_scan_u32(nullptr, nullptr, n, nullptr, &tb, nullptr));
+        PRK_TRY(temp.fill(tb, nullptr));
+        PRK_TRY(prk_scan_u32((const uint32_t *)din.p, (uint32_t *)dout.p, n, temp.p, &tb, nullptr));
+    } else {
+        PRK_TRY(prk_scan_u64(nullptr, nullptr, n, nullptr, &tb, nullptr));
+        PRK_TRY(temp.fill(tb, nullptr));
+        PRK_TRY(prk_scan_u64((const unsigned long long *)din.p, (unsigned long long *)dout.p, n, temp.p, &tb,
+                             nullptr));
+    }
+    PRK_TRY(hipDeviceSynchronize());
+    PRK_TRY(din.read());
+    PRK_TRY(dout.read());
+    PRK_TRY(temp.read());
+    *damage = (din.holds(in) && din.guard_intact() ? 0u : PRK_DAMAGE_INPUT) |
+              (dout.guard_intact() ? 0u : PRK_DAMAGE_OUTPUT_GUARD) | (temp.guard_intact() ? 0u : PRK_DAMAGE_TEMP_GUARD);
+    if (bytes) std::memcpy(out, dout.host.data(), bytes);
+    return PRK_OK;
 }
 
 int prk_create(int device, prk_context **out) {

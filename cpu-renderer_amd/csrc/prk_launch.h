@@ -134,7 +134,18 @@ hipError_t prk_scan_u32(const uint32_t *in, uint32_t *out, uint32_t n, void *tem
                         hipStream_t s);
 hipError_t prk_scan_u64(const unsigned long long *in, unsigned long long *out, uint32_t n, void *temp,
                         size_t *temp_bytes, hipStream_t s);
-// Stable sort of n (u64 key, u32 value) pairs by the keys' low end_bit bits (temp == nullptr: size query).
+// Stable sort of n (u64 key, u32 value) pairs (temp == nullptr: size query).  The contract, stated here only:
+//   * The order is by the keys' low 8 * ceil(end_bit / 8) bits: whole 8-bit digits, so the bits from end_bit up
+//     to the next multiple of 8 TAKE PART in the order; only the bits above that are ignored.  Every key bit,
+//     ignored or not, arrives unchanged in keys_out.  end_bit = 0: the input order.
+//   * A caller whose order is defined by exactly end_bit bits keeps the bits [end_bit, 8 * ceil(end_bit / 8))
+//     equal in every key it wants ordered that way.  Both callers (prk_api.hip: the object passes and the edge
+//     records) do: a real key is (object, YMin, path) < 2^end_bit, zero above, and its lowest path bit is 0
+//     (prk_spans.hip merge_path: pbits exceeds the recursion's depth); a pad key is all ones, so under either
+//     mask it is larger than every real key and the pads end up last, in input order.
+//   * Equal masked keys keep their input order.  keys_in / vals_in are not written; keys_out / vals_out get n
+//     words each; temp is written inside [0, *temp_bytes) of the size query only, and need not be zeroed.
+//   * hipErrorInvalidValue, before anything is touched, for end_bit > 64 or n > 2^30 - 1.
 hipError_t prk_obj_sort(void *keys_in, uint32_t *vals_in, void *keys_out, uint32_t *vals_out, uint32_t n,
                         uint32_t end_bit, void *temp, size_t *temp_bytes, hipStream_t s);
 

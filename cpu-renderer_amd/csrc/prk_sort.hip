@@ -8,7 +8,8 @@
 //       then each tile scanned with its offset, which the tile adds up from
 //       the earlier sums itself (two launches).
 //   prk_obj_sort   LSD radix sort of (u64 key, u32 value) pairs over the key's
-//       low end_bit bits, 8 bits a pass, stable (wave-ballot ranks), one
+//       low ceil(end_bit / 8) digits, 8 bits a pass (the last pass is a whole
+//       digit too: prk_launch.h), stable (wave-ballot ranks), one
 //       launch a pass with decoupled look-back between the tiles (below).  The object path's keys are (object, YMin, MergeSort
 //       recursion path) of projekt.cpp:2-72 (prk_spans.hip SortKeyBits): a
 //       stable order of those keys IS MergeSort's order.
@@ -333,8 +334,8 @@ hipError_t prk_scan_u64(const unsigned long long *in, unsigned long long *out, u
                                     temp, temp_bytes, s);
 }
 
-// Stable sort of n (key, value) pairs by the keys' low end_bit bits
-// (temp == nullptr: size query).  keys_in / vals_in are not written.
+// Stable sort of n (key, value) pairs by the keys' low ceil(end_bit / 8)
+// whole digits (temp == nullptr: size query); the contract is in prk_launch.h.
 hipError_t prk_obj_sort(void *keys_in, uint32_t *vals_in, void *keys_out, uint32_t *vals_out, uint32_t n,
                         uint32_t end_bit, void *temp, size_t *temp_bytes, hipStream_t s) {
     using namespace prk;

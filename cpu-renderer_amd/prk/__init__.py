@@ -167,6 +167,7 @@ _SIGS = {
 
 _SIGS.update({name: (C.c_int, args) for name, args in abi.GEOMETRY_TRANSFORM_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.TEXTURE_TARGET_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.SORT_SELFTEST_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
@@ -313,6 +314,35 @@ def selftest_ops(op, a, b=None, c=None, d=None, device=0):
     _check("prk_selftest_ops", lib().prk_selftest_ops(device, int(op), n, *[_ptr(x) for x in ins],
                                                        *[_ptr(x) for x in outs]))
     return tuple(outs)
+
+
+def selftest_sort(keys, vals, end_bit, repeats=1, device=0):
+    """prk_selftest_sort: the span path's radix sort (prk_obj_sort) of the
+    (keys[i], vals[i]) pairs, `repeats` times on one temp buffer.  Returns
+    (keys_out uint64, vals_out uint32, damage): damage is 0 or abi.PRK_DAMAGE_*
+    bits (inputs changed, a guard after an output or after temp changed)."""
+    k = np.ascontiguousarray(keys, np.uint64)
+    v = np.ascontiguousarray(vals, np.uint32)
+    n = k.shape[0]
+    assert k.shape == (n,) and v.shape == (n,)
+    ko, vo = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    dmg = C.c_uint32(0xFFFFFFFF)
+    _check("prk_selftest_sort", lib().prk_selftest_sort(device, n, int(end_bit), _ptr(k), _ptr(v), int(repeats),
+                                                        _ptr(ko), _ptr(vo), C.byref(dmg)))
+    return ko, vo, dmg.value
+
+
+def selftest_scan(x, width, device=0):
+    """prk_selftest_scan: the span path's exclusive scan (prk_scan_u32 /
+    prk_scan_u64) of x as `width`-bit words.  Returns (out, damage)."""
+    dt = {32: np.uint32, 64: np.uint64}.get(int(width), np.uint64)
+    a = np.ascontiguousarray(x, dt)
+    assert a.ndim == 1
+    out = np.zeros(a.shape[0], dt)
+    dmg = C.c_uint32(0xFFFFFFFF)
+    _check("prk_selftest_scan", lib().prk_selftest_scan(device, int(width), a.shape[0], _ptr(a), _ptr(out),
+                                                        C.byref(dmg)))
+    return out, dmg.value
 
 
 def band_rows(height, rank, nranks):

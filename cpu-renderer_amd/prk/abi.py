@@ -37,6 +37,17 @@ PRK_FILTER_BILINEAR = 1  # extension (AVX semantics)
  PRK_OP_MUL16_TRICK, PRK_OP_U8_UNIT, PRK_OP_ZKEY, PRK_OP_PAIR_TAG, PRK_OP_TAG_PAIR, PRK_OP_SPAN_ENDS,
  PRK_OP_SPAN_OFFSET, PRK_OP_COUNT) = range(27)
 
+# prk_selftest_sort / prk_selftest_scan: the damage word's bits, and each
+# entry point's argument types
+PRK_DAMAGE_INPUT = 1
+PRK_DAMAGE_OUTPUT_GUARD = 2
+PRK_DAMAGE_TEMP_GUARD = 4
+SORT_SELFTEST_SIGS = {
+    "prk_selftest_sort": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                          C.c_void_p, C.POINTER(C.c_uint32)],
+    "prk_selftest_scan": [C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)],
+}
+
 STATUS_NAMES = {
     PRK_OK: "PRK_OK", PRK_ERR_ARG: "PRK_ERR_ARG", PRK_ERR_UNSUPPORTED: "PRK_ERR_UNSUPPORTED",
     PRK_ERR_DEVICE: "PRK_ERR_DEVICE", PRK_ERR_NOMEM: "PRK_ERR_NOMEM",

@@ -645,6 +645,33 @@ int prk_selftest_ops(int32_t device, int32_t op, uint32_t n, const uint32_t *a, 
                      const uint32_t *c, const uint32_t *d, uint32_t *out0, uint32_t *out1, uint32_t *out2,
                      uint32_t *fast);
 
+/* Test: the span path's radix sort and exclusive scans (csrc/prk_sort.hip)
+ * on the caller's host arrays, synchronously on `device`, no context needed.
+ * Every device buffer is followed by a guard region of a known pattern, the
+ * outputs and the temp buffer start out as that pattern, and the temp buffer
+ * is exactly as large as the size query answered.  *damage gets the
+ * PRK_DAMAGE_* bits, found by copying back and comparing on the host: an
+ * input buffer changed, the guard after an output changed, the guard after
+ * the temp buffer changed.  tests/test_gpu_sort_scan.py holds both to the
+ * definitions in tests/sortref.py, every word equal and *damage == 0.
+ *
+ * prk_selftest_sort: `repeats` (>= 1) stable sorts of the n (keys[i],
+ * vals[i]) pairs with the same temp buffer, left as the sort before left it;
+ * the outputs are reset to the guard pattern before each.  The order is by
+ * the keys' low 8 * ceil(end_bit / 8) bits (whole 8-bit digits; the bits
+ * above are ignored and carried).  keys_out / vals_out: n words each, of the
+ * last sort.  PRK_ERR_ARG: a NULL pointer, repeats == 0, a bad device.  A
+ * size the sort refuses (end_bit > 64, n > 2^30 - 1) returns the status of
+ * hipErrorInvalidValue (PRK_ERR_DEVICE) before anything is allocated or read.
+ *
+ * prk_selftest_scan: out[i] = in[0] + ... + in[i - 1] modulo 2^width over n
+ * words of `width` (32 or 64) bits; in and out are distinct device buffers.
+ * PRK_ERR_ARG: a NULL pointer, another width, a bad device. */
+enum { PRK_DAMAGE_INPUT = 1, PRK_DAMAGE_OUTPUT_GUARD = 2, PRK_DAMAGE_TEMP_GUARD = 4 };
+int prk_selftest_sort(int32_t device, uint32_t n, uint32_t end_bit, const uint64_t *keys, const uint32_t *vals,
+                      uint32_t repeats, uint64_t *keys_out, uint32_t *vals_out, uint32_t *damage);
+int prk_selftest_scan(int32_t device, int32_t width, uint32_t n, const void *in, void *out, uint32_t *damage);
+
 /* The bound target (any pointer may be NULL) and the context's device and
  * own stream (a hipStream_t; prk_flush(ctx, NULL) runs on it). */
 int prk_get_target(prk_context *ctx, void **color, int32_t *pitch_bytes, float **zbuf, int32_t *width,
