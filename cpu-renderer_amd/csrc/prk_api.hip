@@ -144,9 +144,151 @@ int status_of(hipError_t e) {
     return PRK_ERR_DEVICE;
 }
 
+// An exclusive scan, or the objects' radix sort, with its temporary storage
+// in `temp`: the size query, the buffer, the run.
+hipError_t scan_u32(DevBuf &temp, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_scan_u32(in, out, n, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_scan_u32(in, out, n, temp.p, &tb, s);
+    return e;
+}
+hipError_t scan_u64(DevBuf &temp, const unsigned long long *in, unsigned long long *out, uint32_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_scan_u64(in, out, n, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_scan_u64(in, out, n, temp.p, &tb, s);
+    return e;
+}
+hipError_t obj_sort(DevBuf &temp, void *keys_in, uint32_t *vals_in, void *keys_out, uint32_t *vals_out, uint32_t n,
+                    uint32_t end_bit, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_obj_sort(keys_in, vals_in, keys_out, vals_out, n, end_bit, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_obj_sort(keys_in, vals_in, keys_out, vals_out, n, end_bit, temp.p, &tb, s);
+    return e;
+}
+
+// The state a pass is queued with and an overflow re-run (resolve_count)
+// runs with again: the target, the tile, the cameras and lights, the clear.
+// The context holds its own as its base (prk_context), so this is the one
+// list of these fields: pass_state() copies them out, apply_pass_state() in.
+struct PassState {
+    // target
+    void *color = nullptr;
+    int32_t pitch = 0;
+    float *zbuf = nullptr;
+    int32_t W = 0, H = 0, row0 = 0, row1 = 0;
+    int32_t tile_w = 256, tile_h = 8;  // measured best for C3b (DESIGN.md §4.3)
+    // camera + lights: transform / lights set the draws up (FillEdgeTable's
+    // ProjectVertex and Gouraud lighting), shade_* shade their spans (Phong and
+    // UnprojectVertex, read when DrawModel* runs); prk_set_camera sets both
+    prk_transform transform{};
+    prk_light_data lights{};
+    prk_transform shade_transform{};
+    prk_light_data shade_lights{};
+    bool clear_pending = false;  // prk_target_clear_on_flush
+    uint32_t clear_color = 0;
+    float clear_z = 0.0f;
+    bool debug = false;
+};
+
+// The switches a span pass (flush_spans) obeys, read from the environment at
+// the start of every pass: tests set and unset them between the flushes of
+// one process.
+struct SpanSwitches {
+    // PRK_OBJ_LOCAL_SORT=0: one radix sort of the padded keys even when no
+    // object has more than 64 edges (else per object, k_obj_sort_local)
+    bool local_sort = !off("PRK_OBJ_LOCAL_SORT");
+    // PRK_OBJ_SEGMENTS=0: the small objects a thread per object, not a thread
+    // per stretch of rows with a non-empty list (k_obj_seg)
+    bool segments = !off("PRK_OBJ_SEGMENTS");
+    // PRK_OBJ_HUGE_EDGES=n (tests): objects of n edges or more, not of 2^18,
+    // are sized by many workgroups each (k_maxact_huge_*)
+    uint32_t huge_edges = 1u << 18;
+    // PRK_OBJ_BIG=0: an object past the slot classes is always walked by one
+    // wave (k_obj_walk_wave), never by the huge-object walk
+    bool big = !off("PRK_OBJ_BIG");
+    // PRK_OBJ_LDSWALK=0: the huge-object walk never in its LDS form (k_obj_walk_lds)
+    bool ldswalk = !off("PRK_OBJ_LDSWALK");
+    // PRK_OBJ_BIG_MIN=n (tests): objects of more than n active edges skip the
+    // walk groups' slot classes (the chunked walk's groups do not look at it)
+    int64_t big_min = INT64_MAX;
+    // PRK_OBJ_ROWS=0: no chunked walk; every large object takes the workgroup walk alone
+    bool rows = !off("PRK_OBJ_ROWS");
+    // PRK_OBJ_CHUNK_WARMUP=0 (tests: every fix-up path): the chunked walk without its warm-up
+    bool chunk_warmup = !off("PRK_OBJ_CHUNK_WARMUP");
+    // PRK_POS_MEMSET=1: the span slots are marked unused by a memset even in a
+    // pass without large objects (whose walks mark their own)
+    bool pos_memset = false;
+    // PRK_PR_DEBUG: a line about the pass's chunked walk on stderr
+    bool pr_debug = std::getenv("PRK_PR_DEBUG") != nullptr;
+    SpanSwitches() {
+        if (const char *env = std::getenv("PRK_OBJ_HUGE_EDGES")) huge_edges = (uint32_t)std::max(1l, std::atol(env));
+        if (const char *env = std::getenv("PRK_OBJ_BIG_MIN")) big_min = std::atoll(env);
+        const char *env = std::getenv("PRK_POS_MEMSET");
+        pos_memset = env && env[0] == '1';
+    }
+    static bool off(const char *name) {
+        const char *env = std::getenv(name);
+        return env && env[0] == '0';
+    }
+};
+
+// The slot class of a large object whose list holds `most` entries at the
+// most: the smallest of the slot walk's LDS capacities (kAdvWgCaps) that holds
+// them and that the device grants (lcap), or 0 for none.
+uint32_t slot_class(int32_t most, uint32_t lcap) {
+    if (most < 0) return 0;
+    for (const uint32_t cap : kAdvWgCaps)
+        if (cap <= lcap && (uint32_t)most <= cap) return cap;
+    return 0;
+}
+
+// The classification block of a pass with n large objects (SpanScratch
+// h_cls, d_cls), one layout for the host's pinned copy and the device's:
+// (most, rows, entries) as k_obj_maxact writes them (12 n bytes), then the
+// walk groups' objects, pool offsets and list capacities, the chunked walk's
+// table (prk_spans.hip PrObj, 8 words an object) and its objects by group,
+// and the huge walk's (rows, entries) per object in walk-group order.
+struct ClsView {
+    int32_t *most, *rows, *ents;
+    uint32_t *big;
+    unsigned long long *off;
+    uint32_t *cap, *pr, *grp, *meta;
+};
+struct ClsLayout {
+    size_t n, big, off, cap, pr, grp, meta, end;
+    explicit ClsLayout(uint32_t nbig = 0) : n(nbig) {
+        big = 12 * n;
+        off = (big + 4 * n + 7) & ~(size_t)7;
+        cap = off + 8 * n;
+        pr = cap + 4 * n;
+        grp = pr + 32 * n;
+        meta = grp + 4 * n;
+        end = meta + 8 * n;
+    }
+    size_t alloc_bytes() const { return end + 64; }  // (never empty)
+    // what the host uploads after the readback: [big, end)
+    size_t upload_bytes() const { return end - big; }
+    ClsView view(void *base) const {
+        char *b = static_cast<char *>(base);
+        int32_t *m = reinterpret_cast<int32_t *>(b);
+        return ClsView{m,
+                       m + n,
+                       m + 2 * n,
+                       reinterpret_cast<uint32_t *>(b + big),
+                       reinterpret_cast<unsigned long long *>(b + off),
+                       reinterpret_cast<uint32_t *>(b + cap),
+                       reinterpret_cast<uint32_t *>(b + pr),
+                       reinterpret_cast<uint32_t *>(b + grp),
+                       reinterpret_cast<uint32_t *>(b + meta)};
+    }
+};
+
 }  // namespace
 
-struct prk_context {
+struct prk_context : PassState {  // (the target, tile, cameras, lights, clear and debug flag: PassState)
     int device = 0;
     hipStream_t own_stream = nullptr;
     // prk_geometry_write: copies on copy_stream after read_ev (the end of the
@@ -162,23 +304,8 @@ struct prk_context {
     size_t h_xform_cap = 0;
     hipEvent_t xf_ev = nullptr, xf_end_ev = nullptr;  // (timed: prk_debug_transform_ms)
     bool xf_busy = false;
-    // target
-    void *color = nullptr;
-    int32_t pitch = 0;
-    float *zbuf = nullptr;
-    int32_t W = 0, H = 0, row0 = 0, row1 = 0;
     bool owns_target = false;
-    // camera + lights: transform / lights set the draws up (FillEdgeTable's
-    // ProjectVertex and Gouraud lighting), shade_* shade their spans (Phong and
-    // UnprojectVertex, read when DrawModel* runs); prk_set_camera sets both
-    prk_transform transform{};
-    prk_light_data lights{};
-    prk_transform shade_transform{};
-    prk_light_data shade_lights{};
     bool have_camera = false;
-    bool clear_pending = false;  // prk_target_clear_on_flush
-    uint32_t clear_color = 0;
-    float clear_z = 0.0f;
     // resources
     std::vector<Geometry> geoms;
     std::vector<Texture> texs;
@@ -235,7 +362,6 @@ struct prk_context {
     hipEvent_t s_mark = nullptr;  // flush-stream point the bin stream waits for (prior target contents)
     uint32_t *h_total = nullptr;  // pinned
     uint32_t pair_hint = 0;       // entry count of the last frame (counting-sort capacity)
-    int32_t tile_w = 256, tile_h = 8;  // measured best for C3b (DESIGN.md §4.3)
     // Automatic tile (until prk_set_tile): 256x8, or narrower tiles for frames
     // with few bin entries per tile (under one wave's 64-entry chunk per
     // tile: 32x8, C2; under 8: 64x8, C1 — the binning's per-tile passes then
@@ -255,7 +381,6 @@ struct prk_context {
     // all-AVX frames: per-triangle setup records; the AVX k_vis / k_walk read
     // them (prk_kernels.hip PRK_SETUP_REC), so they are not optional
     bool setup_rec = true;
-    bool debug = false;
     bool winners_valid = false;
     prk_stats stats{};
     // Timing ring: 6 events per flush.
@@ -282,20 +407,13 @@ struct prk_context {
         hipStream_t s = nullptr;
         std::vector<prk::DrawRec> draws;
         uint32_t T = 0, win_base = 0, ntiles = 0;
-        bool fuse = false, debug = false;
-        void *color = nullptr;
-        int32_t pitch = 0;
-        float *zbuf = nullptr;
-        int32_t W = 0, H = 0, row0 = 0, row1 = 0, tile_w = 0, tile_h = 0;
-        prk_transform transform{}, shade_transform{};
-        prk_light_data lights{}, shade_lights{};
-        uint32_t clear_color = 0;
-        float clear_z = 0.0f;
+        bool fuse = false;  // the pass folded a pending clear in: the re-run's clear_pending
+        PassState state;
     } pcount;
     // Span path (whole-object AETs) scratch, reused frame to frame.
     struct SpanScratch {
-        DevBuf d_stage, d_edges, d_ord, d_temp, d_recs, d_pos, d_span_tri, d_scnt, d_soff, d_keys_a, d_vals_a,
-            d_keys_b, d_vals_b, d_offs, d_nwin, d_wtag, d_srecs, d_work, d_ekeys, d_ekeys2, d_evals, d_ecnt, d_escan,
+        DevBuf d_stage, d_edges, d_ord, d_temp, d_recs, d_pos, d_span_tri, d_scnt, d_soff, d_vals_b,
+            d_offs, d_nwin, d_wtag, d_srecs, d_work, d_ekeys, d_ekeys2, d_evals, d_ecnt, d_escan,
             d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
             d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
             d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
@@ -315,11 +433,10 @@ struct prk_context {
         bool stage_busy = false;
         // host tables of the pass, kept until their asynchronous uploads ran
         std::vector<ObjRun> h_runs;
-        std::vector<uint32_t> h_big_gl, h_big_cap, h_k1src, h_lcnt, h_lflag;
+        std::vector<uint32_t> h_big_gl, h_k1src, h_lcnt;
         std::vector<PrepSeg> h_segs;     // a pass with handle draws: its batch edges' segments
         std::vector<ListSrc> h_lsrc;     // ... and the handles its runs take their list tables from
         size_t last_stage_bytes = 0;     // debug (prk_debug_stage_bytes): the last pass's staging upload
-        std::vector<unsigned long long> h_big_off;
         std::vector<prk::DrawRec> h_draws;
         std::vector<prk::TexRec> h_texs;
         uint32_t *h_rb = nullptr;  // pinned readback words
@@ -335,6 +452,9 @@ struct prk_context {
         uint32_t list_routes[6] = {};
     } spans;
 };
+
+static PassState pass_state(const prk_context *c) { return *c; }
+static void apply_pass_state(prk_context *c, const PassState &p) { static_cast<PassState &>(*c) = p; }
 
 static int resolve_count(prk_context *c);
 // Calls that read or replace the target, or change what a re-run of the
@@ -662,7 +782,7 @@ int prk_destroy(prk_context *c) {
     {
         auto &S = c->spans;
         DevBuf *sb[] = {&S.d_stage, &S.d_edges, &S.d_ord, &S.d_temp, &S.d_recs, &S.d_pos, &S.d_span_tri, &S.d_scnt,
-                        &S.d_soff, &S.d_keys_a, &S.d_vals_a, &S.d_keys_b, &S.d_vals_b, &S.d_offs, &S.d_nwin,
+                        &S.d_soff, &S.d_vals_b, &S.d_offs, &S.d_nwin,
                         &S.d_wtag, &S.d_srecs, &S.d_work, &S.d_ekeys, &S.d_ekeys2, &S.d_evals, &S.d_ecnt,
                         &S.d_escan, &S.d_rcnt, &S.d_rscan, &S.d_bound, &S.d_oslot, &S.d_pool, &S.d_err,
                         &S.d_raw, &S.d_most, &S.d_cls, &S.d_prrow, &S.d_prcnt, &S.d_preoff, &S.d_prfge,
@@ -1610,10 +1730,7 @@ static int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, con
     PRK_TRY(hipMemcpyAsync(S.d_dr_rows.p, rows, (size_t)nrow * sizeof(prk_row), hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemcpyAsync(S.d_dr_pairs.p, pairs, (size_t)npair * sizeof(prk_row_pair), hipMemcpyHostToDevice, s));
     PRK_TRY(prk_rows_counts(S.d_dr_rows.p, nrow, (uint32_t *)S.d_dr_cnt.p, s));
-    size_t tb = 0;
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, nullptr, &tb, s));
-    PRK_TRY(S.d_dr_temp.ensure(std::max<size_t>(tb, 16)));
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, S.d_dr_temp.p, &tb, s));
+    PRK_TRY(scan_u32(S.d_dr_temp, (const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, s));
     PRK_TRY(prk_rows_unpack(S.d_dr_rows.p, (const uint32_t *)S.d_dr_scan.p, nrow, S.d_dr_pairs.p, npair,
                             keep ? keep : S.d_dr_out.p, s));
     if (!keep) PRK_TRY(hipMemcpyAsync(out, S.d_dr_out.p, (size_t)npair * sizeof(prk_span), hipMemcpyDeviceToHost, s));
@@ -2090,13 +2207,7 @@ static int flush_tris(prk_context *c, hipStream_t s, const std::vector<prk::Draw
         P.win_base = win_base;
         P.ntiles = ntiles;
         P.fuse = fuse;
-        P.debug = c->debug;
-        P.color = c->color; P.pitch = c->pitch; P.zbuf = c->zbuf;
-        P.W = c->W; P.H = c->H; P.row0 = c->row0; P.row1 = c->row1;
-        P.tile_w = c->tile_w; P.tile_h = c->tile_h;
-        P.transform = c->transform; P.lights = c->lights;
-        P.shade_transform = c->shade_transform; P.shade_lights = c->shade_lights;
-        P.clear_color = c->clear_color; P.clear_z = c->clear_z;
+        P.state = pass_state(c);
         P.active = true;
         if (!(defer && c->pair_hint)) return resolve_count(c);
     }
@@ -2118,109 +2229,249 @@ static int resolve_count(prk_context *c) {
     const uint32_t total = B.h_info[0];
     c->stats.bin_entries = total;
     c->pair_hint = total;
-    if (c->tile_auto && !c->auto_small && P.tile_w == 256 && total < 64u * P.ntiles &&
+    const PassState &Q = P.state;
+    if (c->tile_auto && !c->auto_small && Q.tile_w == 256 && total < 64u * P.ntiles &&
         8u * P.ntiles <= prk_cs_max_tiles()) {  // (32x8 tiles stay within the counting sort)
         c->auto_small = total < 8u * P.ntiles ? 64 : 32;  // (from the next frame on)
         c->auto_T = P.T;
-        c->auto_px = P.W * (P.row1 - P.row0);
+        c->auto_px = Q.W * (Q.row1 - Q.row0);
     }
     // (a row band's entries against its share of the triangles, T * rows / H)
-    if (c->tile_auto && !c->auto_small && !c->auto_wide && P.tile_w == 256 && P.tile_h == 8 && P.T && P.H > 0 &&
-        2ull * total * (uint64_t)P.H >= 9ull * P.T * (uint64_t)std::max(1, P.row1 - P.row0) &&
+    if (c->tile_auto && !c->auto_small && !c->auto_wide && Q.tile_w == 256 && Q.tile_h == 8 && P.T && Q.H > 0 &&
+        2ull * total * (uint64_t)Q.H >= 9ull * P.T * (uint64_t)std::max(1, Q.row1 - Q.row0) &&
         std::all_of(P.draws.begin(), P.draws.end(), [](const prk::DrawRec &d) { return d.mode == prk::MODE_AVX; })) {
         c->auto_wide = 512;  // (from the next frame on)
         c->auto_T = P.T;
-        c->auto_px = P.W * (P.row1 - P.row0);
+        c->auto_px = Q.W * (Q.row1 - Q.row0);
     }
     if (!B.h_info[1]) return PRK_OK;
     if (total > prk_cs_max_pairs()) return PRK_ERR_LIMIT;  // 29-bit pair index in the bins
     // re-run with the pass's own state, then give the caller's back
-    struct Saved {
-        void *color; int32_t pitch; float *zbuf; int32_t W, H, row0, row1, tile_w, tile_h;
-        prk_transform transform, shade_transform; prk_light_data lights, shade_lights;
-        uint32_t clear_color; float clear_z; bool clear_pending, debug;
-    } sv{c->color, c->pitch, c->zbuf, c->W, c->H, c->row0, c->row1, c->tile_w, c->tile_h,
-         c->transform, c->shade_transform, c->lights, c->shade_lights, c->clear_color, c->clear_z,
-         c->clear_pending, c->debug};
-    c->color = P.color; c->pitch = P.pitch; c->zbuf = P.zbuf;
-    c->W = P.W; c->H = P.H; c->row0 = P.row0; c->row1 = P.row1;
-    c->tile_w = P.tile_w; c->tile_h = P.tile_h;
-    c->transform = P.transform; c->lights = P.lights;
-    c->shade_transform = P.shade_transform; c->shade_lights = P.shade_lights;
-    c->clear_color = P.clear_color; c->clear_z = P.clear_z;
+    const PassState callers = pass_state(c);
+    apply_pass_state(c, P.state);
     c->clear_pending = P.fuse;
-    c->debug = P.debug;
     const std::vector<prk::DrawRec> draws = std::move(P.draws);
     const int rc = flush_tris(c, P.s, draws, P.T, P.win_base);
     c->read_rec = hipEventRecord(c->read_ev, P.s) == hipSuccess;  // (geometry writes wait for the re-run)
     c->z_early = false;  // (a re-run: the download takes z after everything)
-    c->color = sv.color; c->pitch = sv.pitch; c->zbuf = sv.zbuf;
-    c->W = sv.W; c->H = sv.H; c->row0 = sv.row0; c->row1 = sv.row1;
-    c->tile_w = sv.tile_w; c->tile_h = sv.tile_h;
-    c->transform = sv.transform; c->lights = sv.lights;
-    c->shade_transform = sv.shade_transform; c->shade_lights = sv.shade_lights;
-    c->clear_color = sv.clear_color; c->clear_z = sv.clear_z;
-    c->clear_pending = sv.clear_pending;
-    c->debug = sv.debug;
+    apply_pass_state(c, callers);
     return rc;
 }
 
-// One pass of whole-object AETs (prk_spans.hip): FillEdgeTable per triangle,
-// MergeSort per object (one radix sort), one walk of every object's AET into
-// span records (each object writing into its own slots, as many as its edges'
-// active rows allow), bin the spans to tiles, then visibility + shading.
-// Stream-ordered on s; the host waits at the two sizes it reads back (the
-// span slots, the bin entry count).
-static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::DrawRec> &draws, uint32_t T,
-                       uint32_t win_base) {
-    c->z_early = false;  // (k_pix / k_span_shade write a span pass's z)
+// ---- the span pass (flush_spans) and its phases ----------------------------
+namespace {
+struct HandleRun {  // a prk_draw_span_records draw: its launch after the thread walks
+    uint32_t draw, g0, obj0, first, n;
+    const void *sp;
+};
+// Walk groups: per mode, the large objects by the workgroup their list needs
+// (slot_threads(lcap) >= most + 2, lcap <= the device's), the rest (more than
+// lcap, or rows past k_obj_maxact's histogram) the huge-object walk or one
+// wave each with the list in a pool slice.
+struct WalkGroup {
+    int32_t mode;
+    uint32_t lcap, start, count;
+    bool big;           // the huge-object walk (k_obj_walk_big / k_obj_walk_lds)
+    uint32_t max_rows;  // (big: its objects' most rows)
+    bool lds;           // (big: the list in LDS, k_obj_walk_lds)
+};
+// The chunked walk's groups: its objects by (mode, LDS capacity class).
+struct PrGroup {
+    int32_t mode;
+    uint32_t cap, start, count, max_chunks;
+};
+// What classify() decides about a pass's large objects (with the h_cls tables).
+struct ObjWalks {
+    std::vector<WalkGroup> groups;
+    std::vector<PrGroup> prgroups;
+    uint64_t pool = 0;  // the pool slices' ints
+    uint32_t npr = 0, pr_rows = 0, pr_chunks = 0, pr_max_edges = 0;  // the chunked walk's objects, rows, chunks
+    uint64_t pr_ents = 0;
+};
+// The large objects of a pass by mode (the object, its edges), and as the
+// readback lists them: mode after mode (SpanScratch h_big_gl's order).
+struct BigObjs {
+    std::vector<uint32_t> obj[prk::MODE_COUNT], edges[prk::MODE_COUNT];
+    std::vector<uint32_t> all_edges;
+};
+// A host table of the pass in the pinned staging, and where the one upload puts it.
+struct StagePart {
+    const void *src = nullptr;
+    size_t bytes = 0, off = 0;
+};
+
+// The walk groups of a pass, from what k_obj_maxact read back (h.most, rows,
+// ents): the objects of every group into h.big / off / cap / meta, one group
+// after the other.  Objects whose lists outgrow the slot walk's LDS classes
+// take the huge-object walk (a workgroup of 1024: k_obj_walk_lds with the
+// whole list in LDS when it fits prk_big_lds_cap() entries, else
+// k_obj_walk_big with it in device memory) when their sizes are known and
+// fit, else one wave each (k_obj_walk_wave).
+static void classify_walks(const SpanSwitches &sw, uint32_t lcap, const BigObjs &B, const ClsView &h, ObjWalks &out,
+                           uint32_t routes[9]) {
+    uint32_t k = 0, b = 0;
+    for (int mo = 0; mo < prk::MODE_COUNT; ++mo) {
+        const std::vector<uint32_t> &objs = B.obj[mo];
+        const uint32_t b0 = b;
+        for (int ci = 0; ci <= 7; ++ci) {  // ci 5 / 6: the huge-object walk in LDS / device memory, 7: one wave each
+            const uint32_t capc = ci < 5 ? kAdvWgCaps[ci] : 0u;
+            if (ci < 5 && capc > lcap) continue;
+            const uint32_t start = k;
+            uint32_t gmax = 0;  // (the huge walk: its objects' most rows)
+            for (uint32_t i = 0; i < objs.size(); ++i) {
+                const uint32_t bi = b0 + i;
+                const int32_t most = h.most[bi];
+                // (big_min is a test switch of these groups alone: it sends
+                // objects that fit a slot class to the walks past them; the
+                // chunked walk's groups keep the plain rule)
+                if ((most <= sw.big_min ? slot_class(most, lcap) : 0u) != capc) continue;
+                const int32_t rows = h.rows[bi], ents = h.ents[bi];
+                const bool huge = ci == 5 || ci == 6;
+                if (ci >= 5) {
+                    const bool hb = sw.big && most > 0 && (uint32_t)most <= prk_big_max_entries() && rows > 0 &&
+                                    rows < INT32_MAX && ents >= 0 && ents < INT32_MAX && objs.size() <= 65535;
+                    const bool hl = hb && sw.ldswalk && (uint32_t)most <= prk_big_lds_cap() && rows < 16000;
+                    if ((hb ? (hl ? 5 : 6) : 7) != ci) continue;
+                }
+                const uint32_t cap = huge ? (uint32_t)most : B.edges[mo][i];
+                if (huge) out.pool = (out.pool + 3) & ~3ull;  // (16-B aligned slices)
+                h.big[k] = objs[i];
+                h.off[k] = capc ? 0ull : out.pool;
+                h.cap[k] = capc ? 0u : cap;
+                h.meta[2 * k] = huge ? (uint32_t)rows : 0u;
+                h.meta[2 * k + 1] = huge ? (uint32_t)ents : 0u;
+                if (!capc)
+                    out.pool += huge ? prk_big_slice_ints(cap, (uint32_t)rows, (uint32_t)ents)
+                                     : (uint64_t)kWaveListArrays * (cap + 2);
+                if (huge) gmax = std::max(gmax, (uint32_t)rows);
+                ++routes[ci];
+                ++k;
+            }
+            if (k > start) out.groups.push_back(WalkGroup{mo, capc, start, k - start, ci == 5 || ci == 6, gmax, ci == 5});
+        }
+        b += (uint32_t)objs.size();
+    }
+}
+
+// The chunked walk (prk_spans.hip k_pr_*): the large objects walked with
+// their lists in LDS whose rows fit its histogram, by (mode, slot class) as
+// the walk groups; its table into h.pr, its objects by group into h.grp.
+static void classify_chunked(const SpanSwitches &sw, uint32_t lcap, const BigObjs &B, const std::vector<uint32_t> &big_gl,
+                      const ClsView &h, ObjWalks &out) {
+    const uint32_t K = prk_pr_chunk_rows();
+    uint32_t b = 0;
+    for (int mo = 0; sw.rows && mo < prk::MODE_COUNT; ++mo) {
+        const uint32_t b0 = b;
+        for (const uint32_t capc : kAdvWgCaps) {
+            if (capc > lcap) continue;
+            PrGroup g{mo, capc, out.npr, 0, 0};
+            for (uint32_t i = 0; i < B.obj[mo].size(); ++i) {
+                const uint32_t bi = b0 + i;
+                const int32_t most = h.most[bi], rows = h.rows[bi];
+                if (most <= 0 || most > prk_pr_max_row_entries() || rows <= 0 || rows > prk_pr_max_rows()) continue;
+                if (slot_class(most, lcap) != capc) continue;
+                const uint32_t nch = ((uint32_t)rows + K - 1) / K;
+                const uint64_t ents = (uint64_t)most * nch;
+                if (out.pr_ents + ents > kPrMaxEntries || out.npr >= 65535 ||
+                    (uint64_t)out.pr_rows + rows + 1 > 0x7FFFFFFFull)
+                    continue;
+                uint32_t *q = h.pr + 8 * (size_t)out.npr;
+                q[0] = big_gl[bi];
+                q[1] = out.pr_rows;
+                q[2] = (uint32_t)rows;
+                q[3] = out.pr_chunks;
+                q[4] = (uint32_t)most;
+                q[5] = (uint32_t)out.pr_ents;
+                q[6] = q[7] = 0;
+                h.grp[out.npr] = out.npr;
+                out.pr_rows += (uint32_t)rows + 1;
+                out.pr_chunks += nch;
+                out.pr_ents += ents;
+                out.pr_max_edges = std::max(out.pr_max_edges, B.all_edges[bi]);
+                g.max_chunks = std::max(g.max_chunks, nch);
+                ++g.count;
+                ++out.npr;
+            }
+            if (g.count) out.prgroups.push_back(g);
+        }
+        b += (uint32_t)B.obj[mo].size();
+    }
+}
+
+// One span pass: what its phases share.  flush_spans runs them in order.
+struct SpanPass {
+    prk_context *c;
+    prk_context::SpanScratch &S;
+    hipStream_t s;
+    const std::vector<prk::DrawRec> &draws;
+    const SpanSwitches sw;
     prk::FrameParams fp;
-    frame_params(c, fp);
-    fp.tri_count = T;
-    fp.ndraws = (uint32_t)draws.size();
-    fp.win_base = win_base;
-    const uint32_t ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
-    const bool fuse = c->clear_pending && T > 0;
-    c->clear_pending = false;
-    fp.clear_fused = fuse ? 1 : 0;
-    if (T == 0) return PRK_OK;
-    prk_context::SpanScratch &S = c->spans;
-    if (!S.h_rb) PRK_TRY(hipHostMalloc((void **)&S.h_rb, 8 * sizeof(uint32_t), hipHostMallocDefault));
-    const uint32_t lcap = prk_obj_walk_lcap();  // LDS list capacity of the wave walk (edges)
-    // Objects in submission order (ObjDesc kinds: prk_spans.hip): kind 0
-    // objects' triangles numbered 0..ntri-1 in order (FillEdgeTable runs per
-    // triangle), caller edge lists' edges after the triangles' edges.  Objects
-    // of kObjWaveTris triangles or more are walked by one wave each, their
-    // list in LDS when their most active edges fit the launch's LDS capacity
-    // (min(lcap, the largest such object's edges)), else in their pool slice.
-    // (the objects themselves are expanded on the device from runs: a draw
-    // of kind 0 is a run of ceil(tris / obj_tris) objects, kind 2 one of its
-    // spans; only the large objects are listed here)
+    uint32_t ntiles = 0;
+    uint32_t lcap = 0;  // LDS list capacity of the wave walk (edges)
+    // plan(): objects, kind-0 objects, triangles; the prk_draw_edges edges.
+    // The pass's batches (prk_draw_edge_lists) take consecutive records and
+    // lists of the frame's: [le0, le0 + nhe) and [ll0, ll0 + nhl).  With the
+    // handle draws' (prk_draw_records) the pass has nle batch edges and nll
+    // batch lists, in submission order.
+    uint32_t nobj = 0, nk0 = 0, nt = 0, nbig = 0, le0 = 0, ll0 = 0, nsegblk = 0;
+    uint64_t nk1 = 0, nle = 0, nll = 0, nhe = 0, nhl = 0;
+    uint64_t maxn = 1, small_tris = 0, small_ledges = 0;
+    uint32_t pbits = 0, ybits = 0, obits = 0;  // MergeSort key: (object, min(YMin, H), recursion path)
+    bool handles = false;                      // a pass with handle draws (prk_draw_records)
+    bool thread_links = false;  // a thread-walked triangle object small enough for LDS list links
+    BigObjs big;
+    std::vector<HandleRun> hruns;
+    std::vector<uint8_t> seg_staged;  // per h_segs segment: its records are staged ones
+    // upload(): the staged tables, in the staging's order
+    StagePart st_draws, st_texs, st_runs, st_big, st_k1src, st_edges, st_spans, st_lcnt, st_lflag, st_ledges, st_lseg,
+        st_lsrc;
+    // edges(): the pass's span kinds (bit per Mode), the sort and the small objects' walk
+    uint32_t modes = 0;
+    bool scalar = false, local_sort = false, segmented = false;
+    uint64_t max_segs = 0;
+    void *d_objs = nullptr;
+    uint32_t *escan = nullptr;
+    const uint32_t *total0p = nullptr;
+    unsigned long long *oslot = nullptr;
+    // sizes(): the span slots; the classification block
+    uint32_t nslot = 0;
+    ClsLayout cls;
+    ObjWalks walks;
+    const uint32_t *d_prstat = nullptr;  // the chunked walk ran: its objects' status
+
+    SpanPass(prk_context *ctx, hipStream_t stream, const std::vector<prk::DrawRec> &d)
+        : c(ctx), S(ctx->spans), s(stream), draws(d) {}
+    void *dev(const StagePart &p) const { return static_cast<char *>(S.d_stage.p) + p.off; }
+    void *srecs() const { return scalar ? S.d_srecs.p : nullptr; }  // DrawModel span records
+    void *wy() const { return segmented ? S.d_wy.p : nullptr; }
+    int plan();
+    int upload();
+    int edges();
+    int sizes();
+    void classify();
+    int chunked();
+    int walk();
+    int bin_shade(uint32_t T);
+};
+
+// The loop over the draws, host only.  Objects in submission order (ObjDesc
+// kinds: prk_spans.hip): kind 0 objects' triangles numbered 0..ntri-1 in order
+// (FillEdgeTable runs per triangle), caller edge lists' edges after the
+// triangles' edges.  Objects of kObjWaveTris triangles or more are large.
+// (the objects themselves are expanded on the device from runs: a draw of
+// kind 0 is a run of ceil(tris / obj_tris) objects, kind 2 one of its spans;
+// only the large objects are listed here)
+int SpanPass::plan() {
     S.h_runs.clear();
     S.h_big_gl.clear();
-    S.h_big_off.clear();
-    S.h_big_cap.clear();
     S.h_k1src.clear();
-    uint64_t ntri = 0, nk1 = 0, pool = 0, maxn = 1, small_tris = 0, nobj64 = 0, nk064 = 0;
-    // the pass's batches (prk_draw_edge_lists) take consecutive records and
-    // lists of the frame's: [le0, le0 + nhe) and [ll0, ll0 + nhl); the small
-    // sorted lists' edges bound their segments.  With the handle draws'
-    // (prk_draw_records) the pass has nle batch edges and nll batch lists, in
-    // submission order; only a pass with handle draws lists the segments of
-    // its batch edges (h_segs; a staged segment's src: its record among the
-    // staged ones, until the staging has its address).
-    uint64_t nle = 0, nll = 0, nhe = 0, nhl = 0, small_ledges = 0;
-    uint32_t le0 = 0, ll0 = 0;
-    bool handles = false;
-    for (const prk::DrawRec &d : draws) handles = handles || d.src_kind == 4;
     S.h_segs.clear();
     S.h_lsrc.clear();
-    struct HandleRun {  // a prk_draw_span_records draw: its launch after the thread walks
-        uint32_t draw, g0, obj0, first, n;
-        const void *sp;
-    };
-    std::vector<HandleRun> hruns;
-    std::vector<uint8_t> seg_staged;
+    uint64_t ntri = 0, nobj64 = 0, nk064 = 0;
+    for (const prk::DrawRec &d : draws) handles = handles || d.src_kind == 4;
+    // only a pass with handle draws lists the segments of its batch edges
+    // (h_segs; a staged segment's src: its record among the staged ones, until
+    // the staging has its address)
     auto add_seg = [&](uint64_t src, bool staged, uint32_t n) {
         if (!handles || !n) return;
         if (!S.h_segs.empty() && seg_staged.back() == (staged ? 1 : 0) &&
@@ -2231,8 +2482,6 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         S.h_segs.push_back(PrepSeg{reinterpret_cast<const uint32_t *>(src), (uint32_t)nle, n, 0u, 0u});
         seg_staged.push_back(staged ? 1 : 0);
     };
-    bool thread_links = false;  // a thread-walked triangle object small enough for LDS list links
-    std::vector<uint32_t> bigm[prk::MODE_COUNT], bige[prk::MODE_COUNT];  // wave-walked objects by mode, their edges
     for (uint32_t di = 0; di < draws.size(); ++di) {
         const prk::DrawRec &d = draws[di];
         if (d.src_kind == 1) {
@@ -2286,8 +2535,8 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                 const uint32_t n = lcnt[j];
                 if (!lflag[j]) continue;
                 if (n >= kObjWaveEdges) {
-                    bigm[d.mode].push_back((uint32_t)(nobj64 + j));
-                    bige[d.mode].push_back(n);
+                    big.obj[d.mode].push_back((uint32_t)(nobj64 + j));
+                    big.edges[d.mode].push_back(n);
                 } else {
                     small_ledges += n;
                     thread_links = thread_links || (n && n <= prk_obj_link_cap());
@@ -2307,8 +2556,8 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
                 for (uint32_t j = 0; j < cnt; ++j) {
                     const uint32_t n = std::min(per, d.tri_count - j * per);
                     if (n >= kObjWaveTris) {
-                        bigm[d.mode].push_back((uint32_t)(nobj64 + j));
-                        bige[d.mode].push_back(3u * n);
+                        big.obj[d.mode].push_back((uint32_t)(nobj64 + j));
+                        big.edges[d.mode].push_back(3u * n);
                     } else {
                         small_tris += n;
                         thread_links = thread_links || 3ull * n <= prk_obj_link_cap();
@@ -2326,11 +2575,10 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         }
         if (nobj64 >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
     }
-    std::vector<uint32_t> big_edges;  // (h_big_gl order)
     for (int mo = 0; mo < prk::MODE_COUNT; ++mo)  // the large objects, by mode (their walk groups: after the readback)
-        for (size_t i = 0; i < bigm[mo].size(); ++i) {
-            S.h_big_gl.push_back(bigm[mo][i]);
-            big_edges.push_back(bige[mo][i]);
+        for (size_t i = 0; i < big.obj[mo].size(); ++i) {
+            S.h_big_gl.push_back(big.obj[mo][i]);
+            big.all_edges.push_back(big.edges[mo][i]);
         }
     // edge slots (3 per triangle + the caller edges) are indexed by 31 bits
     if (3 * ntri + nk1 + nle >= 0x7FFFFFFFull) return PRK_ERR_LIMIT;
@@ -2338,50 +2586,49 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         if (r.kind == 3) r.k1off = (uint32_t)nk1;
     S.h_lcnt.assign(c->pend_lcnt.begin() + ll0, c->pend_lcnt.begin() + ll0 + nhl);
     S.h_lcnt.push_back(0u);  // (the scan's total)
-    uint32_t nsegblk = 0;
     for (PrepSeg &sg : S.h_segs) {
         sg.blk0 = nsegblk;
         nsegblk += (sg.n + kPrepEdges - 1) / kPrepEdges;
     }
-    const uint32_t nobj = (uint32_t)nobj64, nk0 = (uint32_t)nk064;
-    const uint32_t nt = (uint32_t)ntri, nbig_all = (uint32_t)S.h_big_gl.size();
+    nobj = (uint32_t)nobj64;
+    nk0 = (uint32_t)nk064;
+    nt = (uint32_t)ntri;
+    nbig = (uint32_t)S.h_big_gl.size();
     // MergeSort key: (object, min(YMin, H), recursion path) in one radix sort
     auto bitlen = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
-    const uint32_t pbits = bitlen(maxn) + 1, ybits = std::max(1u, bitlen((uint64_t)c->H));
-    const uint32_t obits = std::max(1u, bitlen(nk0 > 0 ? nk0 - 1 : 0));
+    pbits = bitlen(maxn) + 1;
+    ybits = std::max(1u, bitlen((uint64_t)c->H));
+    obits = std::max(1u, bitlen(nk0 > 0 ? nk0 - 1 : 0));
     if (obits + ybits + pbits > 64) return PRK_ERR_LIMIT;
     S.h_texs.resize(c->texs.size());
     for (size_t i = 0; i < S.h_texs.size(); ++i)
         S.h_texs[i] = prk::TexRec{c->texs[i].mem, c->texs[i].w, c->texs[i].h, c->texs[i].pitch, c->texs[i].filter};
     S.h_draws = draws;
-    // (the scratch below is reused frame to frame: stream order on s covers it)
-    // The pass's host tables go up in one copy from pinned staging (a pageable
-    // hipMemcpyAsync per table held the host for each).
-    enum { T_DRAWS, T_TEXS, T_OBJS, T_K0OBJ, T_K0TRI0, T_BIG, T_BIG_OFF, T_BIG_CAP, T_K1SRC, T_EDGES, T_SPANS,
-           T_LCNT, T_LFLAG, T_LEDGES, T_LSEG, T_LSRC, T_N };  // (T_OBJS: the runs)
-    struct Part {
-        const void *src;
-        size_t bytes, off;
-    } parts[T_N] = {{S.h_draws.data(), S.h_draws.size() * sizeof(prk::DrawRec), 0},
-                    {S.h_texs.data(), S.h_texs.size() * sizeof(prk::TexRec), 0},
-                    {S.h_runs.data(), S.h_runs.size() * sizeof(ObjRun), 0},
-                    {nullptr, 0, 0},
-                    {nullptr, 0, 0},
-                    {S.h_big_gl.data(), S.h_big_gl.size() * 4, 0},
-                    {nullptr, 0, 0},
-                    {nullptr, 0, 0},
-                    {S.h_k1src.data(), S.h_k1src.size() * 4, 0},
-                    {c->pend_edges.data(), c->pend_edges.size() * sizeof(prk_edge), 0},
-                    {c->pend_spans.data(), c->pend_spans.size() * sizeof(prk_span), 0},
-                    {S.h_lcnt.data(), nhl ? S.h_lcnt.size() * 4 : 0, 0},
-                    {c->pend_lflag.data() + ll0, (size_t)nhl * 4, 0},
-                    {c->pend_ledges.data() + le0, (size_t)nhe * sizeof(prk_edge), 0},
-                    {S.h_segs.data(), S.h_segs.size() * sizeof(PrepSeg), 0},
-                    {S.h_lsrc.data(), S.h_lsrc.size() * sizeof(ListSrc), 0}};
+    return PRK_OK;
+}
+
+// The pass's host tables go up in one copy from pinned staging (a pageable
+// hipMemcpyAsync per table held the host for each).
+// (the scratch is reused frame to frame: stream order on s covers it)
+int SpanPass::upload() {
+    st_draws = {S.h_draws.data(), S.h_draws.size() * sizeof(prk::DrawRec)};
+    st_texs = {S.h_texs.data(), S.h_texs.size() * sizeof(prk::TexRec)};
+    st_runs = {S.h_runs.data(), S.h_runs.size() * sizeof(ObjRun)};
+    st_big = {S.h_big_gl.data(), S.h_big_gl.size() * 4};
+    st_k1src = {S.h_k1src.data(), S.h_k1src.size() * 4};
+    st_edges = {c->pend_edges.data(), c->pend_edges.size() * sizeof(prk_edge)};
+    st_spans = {c->pend_spans.data(), c->pend_spans.size() * sizeof(prk_span)};
+    st_lcnt = {S.h_lcnt.data(), nhl ? S.h_lcnt.size() * 4 : 0};
+    st_lflag = {c->pend_lflag.data() + ll0, (size_t)nhl * 4};
+    st_ledges = {c->pend_ledges.data() + le0, (size_t)nhe * sizeof(prk_edge)};
+    st_lseg = {S.h_segs.data(), S.h_segs.size() * sizeof(PrepSeg)};
+    st_lsrc = {S.h_lsrc.data(), S.h_lsrc.size() * sizeof(ListSrc)};
+    StagePart *parts[] = {&st_draws, &st_texs,  &st_runs,   &st_big,  &st_k1src, &st_edges,
+                          &st_spans, &st_lcnt, &st_lflag, &st_ledges, &st_lseg, &st_lsrc};
     size_t stage_bytes = 0;
-    for (Part &pt : parts) {
-        pt.off = stage_bytes;
-        stage_bytes = (stage_bytes + pt.bytes + 255) & ~(size_t)255;
+    for (StagePart *pt : parts) {
+        pt->off = stage_bytes;
+        stage_bytes = (stage_bytes + pt->bytes + 255) & ~(size_t)255;
     }
     stage_bytes = std::max<size_t>(stage_bytes, 256);
     S.last_stage_bytes = stage_bytes;
@@ -2401,32 +2648,36 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(S.d_stage.ensure(stage_bytes));
     for (size_t i = 0; i < S.h_segs.size(); ++i)  // the staged segments' records, where the staging puts them
         if (seg_staged[i])  // (src held the record's byte offset till now)
-            S.h_segs[i].src = reinterpret_cast<const uint32_t *>(static_cast<const char *>(S.d_stage.p) + parts[T_LEDGES].off +
+            S.h_segs[i].src = reinterpret_cast<const uint32_t *>(static_cast<const char *>(dev(st_ledges)) +
                                                                  reinterpret_cast<uintptr_t>(S.h_segs[i].src));
-    for (const Part &pt : parts)
-        if (pt.bytes && pt.src) std::memcpy(S.h_stage + pt.off, pt.src, pt.bytes);
+    for (const StagePart *pt : parts)
+        if (pt->bytes && pt->src) std::memcpy(S.h_stage + pt->off, pt->src, pt->bytes);
     PRK_TRY(hipMemcpyAsync(S.d_stage.p, S.h_stage, stage_bytes, hipMemcpyHostToDevice, s));
     PRK_TRY(hipEventRecord(S.stage_ev, s));
     S.stage_busy = true;
-    auto dev = [&](int t) -> void * { return static_cast<char *>(S.d_stage.p) + parts[t].off; };
-    fp.draws = (const prk::DrawRec *)dev(T_DRAWS);
-    fp.texs = (const prk::TexRec *)dev(T_TEXS);
+    fp.draws = (const prk::DrawRec *)dev(st_draws);
+    fp.texs = (const prk::TexRec *)dev(st_texs);
     fp.draw0 = draws[0];
     fp.tex0 = prk::TexRec{};
     if (fp.draw0.tex >= 0 && (size_t)fp.draw0.tex < S.h_texs.size()) fp.tex0 = S.h_texs[fp.draw0.tex];
-    void *d_edges_in = dev(T_EDGES), *d_spans_in = dev(T_SPANS);
+    return PRK_OK;
+}
+
+// The object tables, FillEdgeTable per triangle (counts, scans, edges +
+// MergeSort keys), the sort, the walk's working copy, each object's bound
+// and its scan into the objects' first span slots.
+int SpanPass::edges() {
     // the objects (ObjDesc), the kind-0 objects' indices and first triangles
     PRK_TRY(S.d_objtab.ensure((size_t)std::max<uint32_t>(nobj, 1) * sizeof(ObjDesc)));
     PRK_TRY(S.d_k0tab.ensure((size_t)std::max<uint32_t>(nk0, 1) * 8));
-    void *d_objs = S.d_objtab.p;
+    d_objs = S.d_objtab.p;
     uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
     const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nk0;
     // the batch lists' first edges: the scan of their counts
     const uint32_t nlist = (uint32_t)nll, nledge = (uint32_t)nle;
     uint32_t *lscan = nullptr, *lobj = nullptr;
-    const uint32_t *d_lcnt = (const uint32_t *)dev(T_LCNT), *d_lflag = (const uint32_t *)dev(T_LFLAG);
+    const uint32_t *d_lcnt = (const uint32_t *)dev(st_lcnt), *d_lflag = (const uint32_t *)dev(st_lflag);
     if (nlist) {
-        size_t lb = 0;
         PRK_TRY(S.d_lscan.ensure(((size_t)nlist + 1) * 4));
         PRK_TRY(S.d_lobj.ensure((size_t)nlist * 4));
         PRK_TRY(S.d_lrows.ensure((size_t)nlist * 8));
@@ -2435,22 +2686,18 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         if (handles) {  // the lists' tables from their sources, on the device
             PRK_TRY(S.d_ltab.ensure((2 * (size_t)nlist + 1) * 4));
             uint32_t *lt = (uint32_t *)S.d_ltab.p;
-            PRK_TRY(prk_list_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, (const uint32_t *)dev(T_LCNT),
-                                    (const uint32_t *)dev(T_LFLAG), dev(T_LSRC), nlist, lt, lt + nlist + 1, s));
+            PRK_TRY(prk_list_tables(dev(st_runs), (uint32_t)S.h_runs.size(), nobj, d_lcnt, d_lflag, dev(st_lsrc), nlist,
+                                    lt, lt + nlist + 1, s));
             d_lcnt = lt;
             d_lflag = lt + nlist + 1;
         }
-        PRK_TRY(prk_scan_u32(d_lcnt, lscan, nlist + 1, nullptr, &lb, s));
-        PRK_TRY(S.d_temp.ensure(std::max<size_t>(lb, 16)));
-        PRK_TRY(prk_scan_u32(d_lcnt, lscan, nlist + 1, S.d_temp.p, &lb, s));
+        PRK_TRY(scan_u32(S.d_temp, d_lcnt, lscan, nlist + 1, s));
     }
-    PRK_TRY(prk_obj_tables(dev(T_OBJS), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0,
+    PRK_TRY(prk_obj_tables(dev(st_runs), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0,
                            d_lcnt, d_lflag, lscan, kObjWaveEdges, lobj, s));
-    const uint32_t *d_big = (const uint32_t *)dev(T_BIG);
-    const uint32_t *d_k1src = (const uint32_t *)dev(T_K1SRC);
-    uint32_t modes = 0;  // the pass's span kinds: bit per Mode
+    const uint32_t *d_k1src = (const uint32_t *)dev(st_k1src);
     for (const auto &d : draws) modes |= 1u << d.mode;
-    const bool scalar = (modes & ~(1u << prk::MODE_AVX)) != 0;
+    scalar = (modes & ~(1u << prk::MODE_AVX)) != 0;
     // FillEdgeTable per triangle: counts, scans, edges + MergeSort keys.
     const size_t es = std::max<size_t>(3 * (size_t)nt, 1);
     PRK_TRY(S.d_ecnt.ensure(((size_t)nt + 1) * 4));
@@ -2464,11 +2711,10 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(S.d_ord.ensure(es * 4));
     PRK_TRY(S.d_err.ensure(16));
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));  // (error bits, then the chunked walk's tally)
-    uint32_t *escan = (uint32_t *)S.d_escan.p, *ord = (uint32_t *)S.d_ord.p;
+    escan = (uint32_t *)S.d_escan.p;
+    uint32_t *ord = (uint32_t *)S.d_ord.p;
     unsigned long long *rscan = (unsigned long long *)S.d_rscan.p;
-    const uint32_t *total0p = escan + nt;
-    size_t tb = 0;
-    auto temp = [&](size_t b) -> hipError_t { return S.d_temp.ensure(std::max<size_t>(b, 16)); };
+    total0p = escan + nt;
     if (nt) {
         PRK_TRY(prk_objtri_count(&fp, d_objs, d_k0obj, d_k0tri0, nk0,
                                  nt, (uint32_t *)S.d_ecnt.p, (unsigned long long *)S.d_rcnt.p, s));
@@ -2476,410 +2722,248 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
         PRK_TRY(hipMemsetAsync(S.d_ecnt.p, 0, 4, s));
         PRK_TRY(hipMemsetAsync(S.d_rcnt.p, 0, 8, s));
     }
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, nullptr, &tb, s));
-    PRK_TRY(temp(tb));
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, S.d_temp.p, &tb, s));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_rcnt.p, rscan, nt + 1, nullptr, &tb, s));
-    PRK_TRY(temp(tb));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_rcnt.p, rscan, nt + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(scan_u32(S.d_temp, (const uint32_t *)S.d_ecnt.p, escan, nt + 1, s));
+    PRK_TRY(scan_u64(S.d_temp, (const unsigned long long *)S.d_rcnt.p, rscan, nt + 1, s));
     // MergeSort of every object: per object when none has more than 64
     // edges (k_obj_sort_local, with the gather), else one radix sort of the
-    // padded keys (prk_spans.hip); PRK_OBJ_LOCAL_SORT=0 forces the radix sort
-    bool local_sort = nt && maxn <= 64;
-    {
-        const char *env = std::getenv("PRK_OBJ_LOCAL_SORT");
-        if (env && env[0] == '0') local_sort = false;
-    }
+    // padded keys (prk_spans.hip)
+    local_sort = nt && maxn <= 64 && sw.local_sort;
     PRK_TRY(prk_objtri_emit(&fp, d_objs, d_k0obj, d_k0tri0, nk0, nt, escan, pbits, ybits, c->H, S.d_edges.p,
                             S.d_ekeys.p, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
-    if (nt && !local_sort) {
-        const uint32_t end_bit = obits + ybits + pbits;
-        PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt, end_bit, nullptr, &tb,
-                             s));
-        PRK_TRY(temp(tb));
-        PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt, end_bit, S.d_temp.p,
-                             &tb, s));
-    }
+    if (nt && !local_sort)
+        PRK_TRY(obj_sort(S.d_temp, S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt,
+                         obits + ybits + pbits, s));
     PRK_TRY(S.d_bound.ensure(((size_t)nobj + 1) * 8));
     PRK_TRY(S.d_oslot.ensure(((size_t)nobj + 1) * 8));
-    unsigned long long *oslot = (unsigned long long *)S.d_oslot.p;
+    oslot = (unsigned long long *)S.d_oslot.p;
     // The walk's working copy (the triangle edges, the prk_draw_edges lists,
-    // the batch lists), and each large object's most active edges (read back
-    // with the slot total: they size its walk's workgroup).
+    // the batch lists).
     const uint32_t nwork = 3 * nt + (uint32_t)nk1 + nledge;
     PRK_TRY(S.d_work.ensure(std::max<size_t>(nwork, 1) * kObjEdgeBytes));
-    // The small triangle objects' segments (prk_spans.hip k_obj_seg, below):
-    // a thread per stretch of rows with a non-empty list (PRK_OBJ_SEGMENTS=0:
-    // a thread per object).
-    const uint64_t max_segs = 3 * small_tris + small_ledges;  // (a segment has an edge at least)
-    bool segmented = false;
-    {
-        const char *env = std::getenv("PRK_OBJ_SEGMENTS");
-        segmented = max_segs && max_segs < 0x7FFFFFFFull && !(env && env[0] == '0');
-    }
+    // The small triangle objects' segments (prk_spans.hip k_obj_seg, walk()):
+    // a thread per stretch of rows with a non-empty list.
+    max_segs = 3 * small_tris + small_ledges;  // (a segment has an edge at least)
+    segmented = max_segs && max_segs < 0x7FFFFFFFull && sw.segments;
     if (segmented) PRK_TRY(S.d_wy.ensure((size_t)std::max<uint32_t>(nwork, 1) * 8));
     if (local_sort)
-        PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nk0, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p,
-                                   segmented ? S.d_wy.p : nullptr, (uint32_t *)S.d_err.p, s));
+        PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nk0, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, wy(),
+                                   (uint32_t *)S.d_err.p, s));
     if (!local_sort || nk1)
-        PRK_TRY(prk_obj_gather(S.d_edges.p, local_sort ? nullptr : ord, total0p, d_edges_in, d_k1src, (uint32_t)nk1,
-                               S.d_work.p, 3 * nt + (uint32_t)nk1, segmented ? S.d_wy.p : nullptr, s));
+        PRK_TRY(prk_obj_gather(S.d_edges.p, local_sort ? nullptr : ord, total0p, dev(st_edges), d_k1src, (uint32_t)nk1,
+                               S.d_work.p, 3 * nt + (uint32_t)nk1, wy(), s));
     // the batch lists' records into it, with their lists' row sums; then the
     // span slots: each object's bound, exclusive-scanned into its first slot
     if (handles)
-        PRK_TRY(prk_list_prep_segs(&fp, dev(T_LSEG), (uint32_t)S.h_segs.size(), nsegblk, lscan, nlist, lobj, d_objs,
-                                   total0p, (uint32_t)nk1, S.d_work.p, segmented ? S.d_wy.p : nullptr,
-                                   (unsigned long long *)S.d_lrows.p, s));
+        PRK_TRY(prk_list_prep_segs(&fp, dev(st_lseg), (uint32_t)S.h_segs.size(), nsegblk, lscan, nlist, lobj, d_objs,
+                                   total0p, (uint32_t)nk1, S.d_work.p, wy(), (unsigned long long *)S.d_lrows.p, s));
     else
-        PRK_TRY(prk_list_prep(&fp, dev(T_LEDGES), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1,
-                              S.d_work.p, segmented ? S.d_wy.p : nullptr, (unsigned long long *)S.d_lrows.p, s));
-    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, d_edges_in, (const unsigned long long *)S.d_lrows.p,
+        PRK_TRY(prk_list_prep(&fp, dev(st_ledges), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1,
+                              S.d_work.p, wy(), (unsigned long long *)S.d_lrows.p, s));
+    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, dev(st_edges), (const unsigned long long *)S.d_lrows.p,
                           (unsigned long long *)S.d_bound.p, s));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, nullptr, &tb, s));
-    PRK_TRY(temp(tb));
-    PRK_TRY(prk_scan_u64((const unsigned long long *)S.d_bound.p, oslot, nobj + 1, S.d_temp.p, &tb, s));
-    // per large object: most, rows, entries (12, k_obj_maxact) | big (4) |
-    // off (8) | cap (4) | the chunked walk's table (32, prk_spans.hip PrObj)
-    // and groups (4)
-    // | the huge walk's (rows, ents) (8)
-    const size_t cls_bytes = (size_t)nbig_all * 72 + 64;
-    if (cls_bytes > S.cls_cap) {
+    PRK_TRY(scan_u64(S.d_temp, (const unsigned long long *)S.d_bound.p, oslot, nobj + 1, s));
+    return PRK_OK;
+}
+
+// Each large object's most active edges, rows and entries (they size its
+// walk), read back with the slot total: the pass's first wait.  Then the
+// span slots' buffers.
+int SpanPass::sizes() {
+    cls = ClsLayout(nbig);
+    if (cls.alloc_bytes() > S.cls_cap) {
         if (S.h_cls) (void)hipHostFree(S.h_cls);
         S.h_cls = nullptr;
         S.cls_cap = 0;
-        PRK_TRY(hipHostMalloc((void **)&S.h_cls, cls_bytes + cls_bytes / 4, hipHostMallocDefault));
-        S.cls_cap = cls_bytes + cls_bytes / 4;
+        const size_t want = cls.alloc_bytes() + cls.alloc_bytes() / 4;
+        PRK_TRY(hipHostMalloc((void **)&S.h_cls, want, hipHostMallocDefault));
+        S.cls_cap = want;
     }
-    int32_t *h_most = reinterpret_cast<int32_t *>(S.h_cls);
-    if (nbig_all) {
-        PRK_TRY(S.d_most.ensure((size_t)nbig_all * 12));
-        // (objects of kMaxactHugeEdges edges or more: many workgroups each;
-        // PRK_OBJ_HUGE_EDGES=n (tests): n instead)
-        const char *henv = std::getenv("PRK_OBJ_HUGE_EDGES");
-        const uint32_t kMaxactHugeEdges = henv ? (uint32_t)std::max(1l, std::atol(henv)) : (1u << 18);
-        PRK_TRY(prk_obj_maxact(&fp, d_objs, d_big, nbig_all, escan, total0p, S.d_work.p, (int32_t *)S.d_most.p,
-                               kMaxactHugeEdges, s));
+    if (nbig) {
+        const uint32_t *d_big = (const uint32_t *)dev(st_big);
+        PRK_TRY(S.d_most.ensure((size_t)nbig * 12));
+        PRK_TRY(prk_obj_maxact(&fp, d_objs, d_big, nbig, escan, total0p, S.d_work.p, (int32_t *)S.d_most.p,
+                               sw.huge_edges, s));
         for (uint32_t &r : S.walk_routes) r = 0;  // (prk_debug_walk_routes: this pass's)
-        for (uint32_t b = 0; b < nbig_all; ++b)
-            if (big_edges[b] >= kMaxactHugeEdges) {
+        for (uint32_t b = 0; b < nbig; ++b)  // (objects of sw.huge_edges edges or more: many workgroups each)
+            if (big.all_edges[b] >= sw.huge_edges) {
                 ++S.walk_routes[8];
                 PRK_TRY(S.d_mhuge.ensure(prk_maxact_huge_scratch()));
-                PRK_TRY(prk_obj_maxact_huge(&fp, d_objs, d_big, b, nbig_all, big_edges[b], escan, total0p,
-                                            S.d_work.p, (int32_t *)S.d_most.p, S.d_mhuge.p, s));
+                PRK_TRY(prk_obj_maxact_huge(&fp, d_objs, d_big, b, nbig, big.all_edges[b], escan, total0p, S.d_work.p,
+                                            (int32_t *)S.d_most.p, S.d_mhuge.p, s));
             }
-        PRK_TRY(hipMemcpyAsync(h_most, S.d_most.p, (size_t)nbig_all * 12, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipMemcpyAsync(S.h_cls, S.d_most.p, (size_t)nbig * 12, hipMemcpyDeviceToHost, s));
     }
     PRK_TRY(hipMemcpyAsync(S.h_rb, oslot + nobj, 8, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     uint64_t nslot64;
     std::memcpy(&nslot64, S.h_rb, 8);
     if (nslot64 >= prk::kMaxPairs) return PRK_ERR_LIMIT;  // 31-bit span tags
-    const uint32_t nslot = (uint32_t)nslot64;
+    nslot = (uint32_t)nslot64;
     const size_t ns = std::max<uint32_t>(nslot, 1);
     PRK_TRY(S.d_recs.ensure(ns * 64));
     PRK_TRY(S.d_pos.ensure(ns * 16));
     PRK_TRY(S.d_span_tri.ensure(ns * 4));
-    if (scalar) PRK_TRY(S.d_srecs.ensure(ns * kScSpanRecBytes));  // DrawModel span records
-    if (nbig_all) PRK_TRY(S.d_raw.ensure(ns * kPairRawBytes));     // the slot walks' pairs
+    if (scalar) PRK_TRY(S.d_srecs.ensure(ns * kScSpanRecBytes));
+    if (nbig) PRK_TRY(S.d_raw.ensure(ns * kPairRawBytes));  // the slot walks' pairs
     // slots no span takes stay row -1: binned nowhere.  Without large objects
     // every slot belongs to the thread or segment walks (walk_object,
     // k_obj_seg), which mark their unused ones themselves (C3b as 16-triangle
     // objects: ~21 M slots, a 0.34-GB memset); the large objects' walks rely
-    // on this one.  PRK_POS_MEMSET=1 forces it.
+    // on this one.
+    if (nbig || sw.pos_memset) PRK_TRY(hipMemsetAsync(S.d_pos.p, 0xFF, ns * 16, s));
+    return PRK_OK;
+}
+
+// The large objects' walks from the readback, on the host alone.
+void SpanPass::classify() {
+    const ClsView h = cls.view(S.h_cls);
+    if (nbig) {
+        S.walk_sizes[0] = h.most[0];
+        S.walk_sizes[1] = h.rows[0];
+        S.walk_sizes[2] = h.ents[0];
+    }
+    classify_walks(sw, lcap, big, h, walks, S.walk_routes);
+    classify_chunked(sw, lcap, big, S.h_big_gl, h, walks);
+}
+
+// The chunked walk of the objects classify() gave it.  It is an
+// optimisation: when its scratch (up to kPrMaxEntries * ~356 B) cannot be
+// had, every object takes the workgroup walk instead (d_prstat stays null) --
+// never PRK_ERR_NOMEM.
+int SpanPass::chunked() {
+    ObjWalks &w = walks;
+    if (!w.npr) return PRK_OK;
+    hipError_t ae = S.d_prstat.ensure((size_t)nobj * 4);
+    if (ae == hipSuccess) ae = S.d_prrow.ensure((size_t)w.npr * 8);
+    if (ae == hipSuccess) ae = S.d_prcnt.ensure((size_t)w.pr_rows * 4);
+    if (ae == hipSuccess) ae = S.d_preoff.ensure((size_t)w.pr_rows * 4);
+    if (ae == hipSuccess) ae = S.d_prfge.ensure((size_t)w.pr_rows * 4);
+    if (ae == hipSuccess) ae = S.d_prccur.ensure((size_t)w.pr_chunks * 4);
+    if (ae == hipSuccess) ae = S.d_preendm.ensure((size_t)w.pr_chunks * 4);
+    if (ae == hipSuccess) ae = S.d_prmatch.ensure((size_t)w.pr_chunks * 4);
+    if (ae == hipSuccess) ae = S.d_prsm.ensure((size_t)w.pr_chunks * 4);
+    if (ae == hipSuccess) ae = S.d_prsidx.ensure(w.pr_ents * 4);
+    if (ae == hipSuccess) ae = S.d_prkey.ensure(w.pr_ents * 16);
+    if (ae == hipSuccess) ae = S.d_prest.ensure(w.pr_ents * kObjEdgeBytes);
+    if (ae == hipSuccess) ae = S.d_prsst.ensure(w.pr_ents * kObjEdgeBytes);
+    if (ae == hipSuccess) ae = S.d_preend.ensure(w.pr_ents * kObjEdgeBytes);
+    if (ae == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        DevBuf *bufs[] = {&S.d_prsidx, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend};
+        for (DevBuf *b : bufs) b->release();
+        w.npr = 0;
+        return PRK_OK;
+    }
+    PRK_TRY(ae);
+    PRK_TRY(hipMemsetAsync(S.d_prstat.p, 0, (size_t)nobj * 4, s));
+    const ClsView d = cls.view(S.d_cls.p);
+    prk::PrWalkArgs pa{};
+    pa.objs = d_objs;
+    pa.pro = d.pr;
+    pa.npr = w.npr;
+    pa.nchunks = w.pr_chunks;
+    pa.max_edges = w.pr_max_edges;
+    pa.escan = escan;
+    pa.total0p = total0p;
+    pa.work = S.d_work.p;
+    pa.prrow = S.d_prrow.p;
+    pa.cnt = (uint32_t *)S.d_prcnt.p;
+    pa.eoff = (uint32_t *)S.d_preoff.p;
+    pa.fge = (uint32_t *)S.d_prfge.p;
+    pa.ccur = (uint32_t *)S.d_prccur.p;
+    pa.key = S.d_prkey.p;
+    pa.est = S.d_prest.p;
+    pa.sst = S.d_prsst.p;
+    pa.eend = S.d_preend.p;
+    pa.eend_m = (uint32_t *)S.d_preendm.p;
+    pa.match = (uint32_t *)S.d_prmatch.p;
+    pa.sidx = (uint32_t *)S.d_prsidx.p;
+    pa.s_m = (uint32_t *)S.d_prsm.p;
+    pa.prstat = (uint32_t *)S.d_prstat.p;
+    pa.soff = oslot;
+    pa.raw = S.d_raw.p;
+    pa.pos = S.d_pos.p;
+    pa.span_tri = (uint32_t *)S.d_span_tri.p;
+    pa.err = (uint32_t *)S.d_err.p;
+    pa.warmup = sw.chunk_warmup;
+    PRK_TRY(prk_pr_walk_begin(&fp, &pa, s));
+    for (const PrGroup &g : w.prgroups)
+        PRK_TRY(prk_pr_walk_group(&fp, &pa, g.mode, g.cap, d.grp + g.start, g.count, g.max_chunks, s));
+    PRK_TRY(prk_pr_walk_end(&pa, s));
+    d_prstat = (const uint32_t *)S.d_prstat.p;
+    return PRK_OK;
+}
+
+// The classification's upload and every walk: the chunked walk, the small
+// objects' segments and thread walk, the span handles, the walk groups; then
+// the slot walks' pairs into span records.
+int SpanPass::walk() {
+    if (nbig) {
+        PRK_TRY(S.d_cls.ensure(cls.end));
+        PRK_TRY(hipMemcpyAsync(static_cast<char *>(S.d_cls.p) + cls.big, S.h_cls + cls.big, cls.upload_bytes(),
+                               hipMemcpyHostToDevice, s));
+        if (walks.pool) PRK_TRY(S.d_pool.ensure(walks.pool * 4));
+    }
     {
-        const char *env = std::getenv("PRK_POS_MEMSET");
-        if (nbig_all || (env && env[0] == '1')) PRK_TRY(hipMemsetAsync(S.d_pos.p, 0xFF, ns * 16, s));
-    }
-    // Walk groups: per mode, the large objects by the workgroup their list
-    // needs (slot_threads(lcap) >= most + 2, lcap <= the device's), the rest
-    // (more than lcap, or rows past k_obj_maxact's histogram) one wave each
-    // with the list in a pool slice.
-    struct Group {
-        int32_t mode;
-        uint32_t lcap, start, count;
-        bool big;             // the huge-object walk (k_obj_walk_big / k_obj_walk_lds)
-        uint32_t max_rows;    // (big: its objects' most rows)
-        bool lds;             // (big: the list in LDS, k_obj_walk_lds)
-    };
-    std::vector<Group> groups;
-    uint32_t *cls_big = reinterpret_cast<uint32_t *>(S.h_cls + (size_t)nbig_all * 12);
-    unsigned long long *cls_off = reinterpret_cast<unsigned long long *>(S.h_cls + ((((size_t)nbig_all * 16) + 7) & ~(size_t)7));
-    uint32_t *cls_cap = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(cls_off) + (size_t)nbig_all * 8);
-    uint32_t *cls_pr = cls_cap + nbig_all;  // PrObj[npr] (8 words each)
-    uint32_t *cls_grp = cls_pr + 8 * (size_t)nbig_all;  // its objects grouped by (mode, LDS capacity)
-    uint32_t *cls_meta = cls_grp + nbig_all;           // (rows, ents) per object, walk-group order
-    // Objects whose lists outgrow the workgroup walk's LDS slots take the
-    // huge-object walk (a workgroup of 1024: k_obj_walk_lds with the whole
-    // list in LDS when it fits prk_big_lds_cap() entries, else k_obj_walk_big
-    // with it in device memory) when their sizes are known (k_obj_maxact) and
-    // fit, else one wave each (k_obj_walk_wave).  PRK_OBJ_BIG=0: always the
-    // wave; PRK_OBJ_LDSWALK=0: never the LDS form; PRK_OBJ_BIG_MIN=n (tests):
-    // objects of more than n active edges skip the LDS slot classes.
-    {
-        const char *benv = std::getenv("PRK_OBJ_BIG"), *menv = std::getenv("PRK_OBJ_BIG_MIN"),
-                   *lenv = std::getenv("PRK_OBJ_LDSWALK");
-        const bool big_on = !(benv && benv[0] == '0'), lds_on = !(lenv && lenv[0] == '0');
-        const int64_t big_min = menv ? std::atoll(menv) : INT64_MAX;
-        const int32_t *h_rows = h_most + nbig_all, *h_ents = h_most + 2 * (size_t)nbig_all;
-        if (nbig_all) {
-            S.walk_sizes[0] = h_most[0];
-            S.walk_sizes[1] = h_rows[0];
-            S.walk_sizes[2] = h_ents[0];
-        }
-        static const uint32_t kCaps[] = {62, 126, 254, 510, 1022};
-        uint32_t k = 0, b = 0;
-        for (int mo = 0; mo < prk::MODE_COUNT; ++mo) {
-            const uint32_t b0 = b;
-            for (int ci = 0; ci <= 7; ++ci) {  // ci 5 / 6: the huge-object walk in LDS / device memory, 7: one wave each
-                const uint32_t capc = ci < 5 ? kCaps[ci] : 0u;
-                if (ci < 5 && capc > lcap) continue;
-                const uint32_t start = k;
-                uint32_t gmax = 0;  // (the huge walk: its objects' most rows)
-                for (uint32_t i = 0; i < bigm[mo].size(); ++i) {
-                    const uint32_t bi = b0 + i;
-                    const int32_t most = h_most[bi];
-                    uint32_t want = 0;  // the class this object takes
-                    for (int cj = 0; cj < 5; ++cj)
-                        if (kCaps[cj] <= lcap && most >= 0 && (uint32_t)most <= kCaps[cj] && most <= big_min) {
-                            want = kCaps[cj];
-                            break;
-                        }
-                    if (want != capc) continue;
-                    const int32_t rows = h_rows[bi], ents = h_ents[bi];
-                    const bool huge = ci == 5 || ci == 6;
-                    if (ci >= 5) {
-                        const bool hb = big_on && most > 0 && (uint32_t)most <= prk_big_max_entries() && rows > 0 &&
-                                        rows < INT32_MAX && ents >= 0 && ents < INT32_MAX &&
-                                        bigm[mo].size() <= 65535;
-                        const bool hl = hb && lds_on && (uint32_t)most <= prk_big_lds_cap() && rows < 16000;
-                        if ((hb ? (hl ? 5 : 6) : 7) != ci) continue;
-                    }
-                    const uint32_t cap = huge ? (uint32_t)most : bige[mo][i];
-                    if (huge) pool = (pool + 3) & ~3ull;  // (16-B aligned slices)
-                    cls_big[k] = bigm[mo][i];
-                    cls_off[k] = capc ? 0ull : pool;
-                    cls_cap[k] = capc ? 0u : cap;
-                    cls_meta[2 * k] = huge ? (uint32_t)rows : 0u;
-                    cls_meta[2 * k + 1] = huge ? (uint32_t)ents : 0u;
-                    if (!capc)
-                        pool += huge ? prk_big_slice_ints(cap, (uint32_t)rows, (uint32_t)ents)
-                                     : (uint64_t)kWaveListArrays * (cap + 2);
-                    if (huge) gmax = std::max(gmax, (uint32_t)rows);
-                    ++S.walk_routes[ci];
-                    ++k;
-                }
-                if (k > start) groups.push_back(Group{mo, capc, start, k - start, ci == 5 || ci == 6, gmax, ci == 5});
-            }
-            b += (uint32_t)bigm[mo].size();
-        }
-    }
-    // The chunked walk (prk_spans.hip k_pr_*): the large objects walked with
-    // their lists in LDS whose rows fit its histogram (PRK_OBJ_ROWS=0: none;
-    // every object then takes the workgroup walk alone).  Objects by
-    // (mode, LDS capacity class), as the walk groups.
-    struct PrGroup {
-        int32_t mode;
-        uint32_t cap, start, count, max_chunks;
-    };
-    std::vector<PrGroup> prgroups;
-    uint32_t npr = 0, pr_rows = 0, pr_chunks = 0, pr_max_edges = 0;
-    uint64_t pr_ents = 0;
-    {
-        const char *env = std::getenv("PRK_OBJ_ROWS");
-        const bool on = !(env && env[0] == '0');
-        const uint32_t K = prk_pr_chunk_rows();
-        const int32_t *h_rows = h_most + nbig_all;
-        static const uint32_t kCapsPr[] = {62, 126, 254, 510, 1022};
-        uint32_t b = 0;
-        for (int mo = 0; on && mo < prk::MODE_COUNT; ++mo) {
-            const uint32_t b0 = b;
-            for (int ci = 0; ci < 5; ++ci) {
-                const uint32_t capc = kCapsPr[ci];
-                if (capc > lcap) continue;
-                PrGroup g{mo, capc, npr, 0, 0};
-                for (uint32_t i = 0; i < bigm[mo].size(); ++i) {
-                    const uint32_t bi = b0 + i;
-                    const int32_t most = h_most[bi], rows = h_rows[bi];
-                    if (most <= 0 || most > prk_pr_max_row_entries() || rows <= 0 || rows > prk_pr_max_rows())
-                        continue;
-                    uint32_t want = 0;  // its capacity class (the walk groups' rule)
-                    for (int cj = 0; cj < 5; ++cj)
-                        if (kCapsPr[cj] <= lcap && (uint32_t)most <= kCapsPr[cj]) {
-                            want = kCapsPr[cj];
-                            break;
-                        }
-                    if (want != capc) continue;
-                    const uint32_t nch = ((uint32_t)rows + K - 1) / K;
-                    const uint64_t ents = (uint64_t)most * nch;
-                    if (pr_ents + ents > kPrMaxEntries || npr >= 65535 || (uint64_t)pr_rows + rows + 1 > 0x7FFFFFFFull)
-                        continue;
-                    uint32_t *q = cls_pr + 8 * (size_t)npr;
-                    q[0] = S.h_big_gl[bi];
-                    q[1] = pr_rows;
-                    q[2] = (uint32_t)rows;
-                    q[3] = pr_chunks;
-                    q[4] = (uint32_t)most;
-                    q[5] = (uint32_t)pr_ents;
-                    q[6] = q[7] = 0;
-                    cls_grp[npr] = npr;
-                    pr_rows += (uint32_t)rows + 1;
-                    pr_chunks += nch;
-                    pr_ents += ents;
-                    pr_max_edges = std::max(pr_max_edges, big_edges[bi]);
-                    g.max_chunks = std::max(g.max_chunks, nch);
-                    ++g.count;
-                    ++npr;
-                }
-                if (g.count) prgroups.push_back(g);
-            }
-            b += (uint32_t)bigm[mo].size();
-        }
-    }
-    const uint32_t *d_cbig = nullptr, *d_ccap = nullptr, *d_cmeta = nullptr;
-    const unsigned long long *d_coff = nullptr;
-    const void *d_cpr = nullptr;
-    const uint32_t *d_cgrp = nullptr;
-    if (nbig_all) {
-        const size_t lo = (size_t)nbig_all * 12, hi = reinterpret_cast<char *>(cls_meta + 2 * (size_t)nbig_all) - S.h_cls;
-        PRK_TRY(S.d_cls.ensure(hi));
-        PRK_TRY(hipMemcpyAsync(static_cast<char *>(S.d_cls.p) + lo, S.h_cls + lo, hi - lo, hipMemcpyHostToDevice, s));
-        d_cbig = reinterpret_cast<const uint32_t *>(static_cast<char *>(S.d_cls.p) + lo);
-        d_coff = reinterpret_cast<const unsigned long long *>(static_cast<char *>(S.d_cls.p) +
-                                                              (reinterpret_cast<char *>(cls_off) - S.h_cls));
-        d_ccap = reinterpret_cast<const uint32_t *>(static_cast<char *>(S.d_cls.p) +
-                                                    (reinterpret_cast<char *>(cls_cap) - S.h_cls));
-        d_cpr = static_cast<char *>(S.d_cls.p) + (reinterpret_cast<char *>(cls_pr) - S.h_cls);
-        d_cgrp = reinterpret_cast<const uint32_t *>(static_cast<char *>(S.d_cls.p) +
-                                                    (reinterpret_cast<char *>(cls_grp) - S.h_cls));
-        d_cmeta = reinterpret_cast<const uint32_t *>(static_cast<char *>(S.d_cls.p) +
-                                                     (reinterpret_cast<char *>(cls_meta) - S.h_cls));
-        if (pool) PRK_TRY(S.d_pool.ensure(pool * 4));
-    }
-    const uint32_t *d_prstat = nullptr;
-    if (npr) {
-        // The chunked walk is an optimisation: when its scratch (up to
-        // kPrMaxEntries * ~356 B) cannot be had, every object takes the
-        // workgroup walk instead (d_prstat stays null) -- never PRK_ERR_NOMEM.
-        hipError_t ae = S.d_prstat.ensure((size_t)nobj * 4);
-        if (ae == hipSuccess) ae = S.d_prrow.ensure((size_t)npr * 8);
-        if (ae == hipSuccess) ae = S.d_prcnt.ensure((size_t)pr_rows * 4);
-        if (ae == hipSuccess) ae = S.d_preoff.ensure((size_t)pr_rows * 4);
-        if (ae == hipSuccess) ae = S.d_prfge.ensure((size_t)pr_rows * 4);
-        if (ae == hipSuccess) ae = S.d_prccur.ensure((size_t)pr_chunks * 4);
-        if (ae == hipSuccess) ae = S.d_preendm.ensure((size_t)pr_chunks * 4);
-        if (ae == hipSuccess) ae = S.d_prmatch.ensure((size_t)pr_chunks * 4);
-        if (ae == hipSuccess) ae = S.d_prsm.ensure((size_t)pr_chunks * 4);
-        if (ae == hipSuccess) ae = S.d_prsidx.ensure(pr_ents * 4);
-        if (ae == hipSuccess) ae = S.d_prkey.ensure(pr_ents * 16);
-        if (ae == hipSuccess) ae = S.d_prest.ensure(pr_ents * kObjEdgeBytes);
-        if (ae == hipSuccess) ae = S.d_prsst.ensure(pr_ents * kObjEdgeBytes);
-        if (ae == hipSuccess) ae = S.d_preend.ensure(pr_ents * kObjEdgeBytes);
-        if (ae == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            DevBuf *big[] = {&S.d_prsidx, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend};
-            for (DevBuf *b : big) b->release();
-            npr = 0;
-        } else {
-            PRK_TRY(ae);
-        }
-    }
-    if (npr) {
-        PRK_TRY(hipMemsetAsync(S.d_prstat.p, 0, (size_t)nobj * 4, s));
-        prk::PrWalkArgs pa{};
-        pa.objs = d_objs;
-        pa.pro = d_cpr;
-        pa.npr = npr;
-        pa.nchunks = pr_chunks;
-        pa.max_edges = pr_max_edges;
-        pa.escan = escan;
-        pa.total0p = total0p;
-        pa.work = S.d_work.p;
-        pa.prrow = S.d_prrow.p;
-        pa.cnt = (uint32_t *)S.d_prcnt.p;
-        pa.eoff = (uint32_t *)S.d_preoff.p;
-        pa.fge = (uint32_t *)S.d_prfge.p;
-        pa.ccur = (uint32_t *)S.d_prccur.p;
-        pa.key = S.d_prkey.p;
-        pa.est = S.d_prest.p;
-        pa.sst = S.d_prsst.p;
-        pa.eend = S.d_preend.p;
-        pa.eend_m = (uint32_t *)S.d_preendm.p;
-        pa.match = (uint32_t *)S.d_prmatch.p;
-        pa.sidx = (uint32_t *)S.d_prsidx.p;
-        pa.s_m = (uint32_t *)S.d_prsm.p;
-        pa.prstat = (uint32_t *)S.d_prstat.p;
-        pa.soff = oslot;
-        pa.raw = S.d_raw.p;
-        pa.pos = S.d_pos.p;
-        pa.span_tri = (uint32_t *)S.d_span_tri.p;
-        pa.err = (uint32_t *)S.d_err.p;
-        const char *warm = std::getenv("PRK_OBJ_CHUNK_WARMUP");  // 0: no warm-up (tests: every fix-up path)
-        pa.warmup = !(warm && warm[0] == '0');
-        PRK_TRY(prk_pr_walk_begin(&fp, &pa, s));
-        for (const PrGroup &g : prgroups)
-            PRK_TRY(prk_pr_walk_group(&fp, &pa, g.mode, g.cap, d_cgrp + g.start, g.count, g.max_chunks, s));
-        PRK_TRY(prk_pr_walk_end(&pa, s));
-        d_prstat = (const uint32_t *)S.d_prstat.p;
+        const int rc = chunked();
+        if (rc != PRK_OK) return rc;
     }
     const void *d_segs = nullptr;  // (the segments)
     const uint32_t *d_nseg = nullptr;
-    {
-        if (segmented) {
-            PRK_TRY(S.d_segcnt.ensure(((size_t)nobj + 1) * 4));
-            PRK_TRY(S.d_segoff.ensure(((size_t)nobj + 1) * 4));
-            PRK_TRY(S.d_segs.ensure((size_t)max_segs * 24));  // prk_spans.hip ObjSeg
-            uint32_t *segcnt = (uint32_t *)S.d_segcnt.p, *segoff = (uint32_t *)S.d_segoff.p;
-            PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, nullptr, nullptr,
-                                s));
-            PRK_TRY(prk_scan_u32(segcnt, segoff, nobj + 1, nullptr, &tb, s));
-            PRK_TRY(temp(tb));
-            PRK_TRY(prk_scan_u32(segcnt, segoff, nobj + 1, S.d_temp.p, &tb, s));
-            PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, S.d_segs.p,
-                                S.d_pos.p, s));
-            d_segs = S.d_segs.p;
-            d_nseg = segoff + nobj;
-        }
+    if (segmented) {
+        PRK_TRY(S.d_segcnt.ensure(((size_t)nobj + 1) * 4));
+        PRK_TRY(S.d_segoff.ensure(((size_t)nobj + 1) * 4));
+        PRK_TRY(S.d_segs.ensure((size_t)max_segs * 24));  // prk_spans.hip ObjSeg
+        uint32_t *segcnt = (uint32_t *)S.d_segcnt.p, *segoff = (uint32_t *)S.d_segoff.p;
+        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, nullptr, nullptr, s));
+        PRK_TRY(scan_u32(S.d_temp, segcnt, segoff, nobj + 1, s));
+        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, S.d_segs.p, S.d_pos.p,
+                            s));
+        d_segs = S.d_segs.p;
+        d_nseg = segoff + nobj;
     }
-    PRK_TRY(prk_obj_walk(&fp, d_objs, nobj, escan, total0p, S.d_work.p, oslot, S.d_recs.p,
-                         scalar ? S.d_srecs.p : nullptr, S.d_pos.p, (uint32_t *)S.d_span_tri.p, d_spans_in,
-                         (uint32_t *)S.d_err.p, thread_links ? 1 : 0, d_segs, d_nseg, (uint32_t)max_segs, s));
+    uint32_t *span_tri = (uint32_t *)S.d_span_tri.p, *err = (uint32_t *)S.d_err.p;
+    PRK_TRY(prk_obj_walk(&fp, d_objs, nobj, escan, total0p, S.d_work.p, oslot, S.d_recs.p, srecs(), S.d_pos.p, span_tri,
+                         dev(st_spans), err, thread_links ? 1 : 0, d_segs, d_nseg, (uint32_t)max_segs, s));
     for (const HandleRun &h : hruns)  // the span handles' draws, from their own buffers
         PRK_TRY(prk_span_handle_walk(&fp, h.draw, h.g0, h.obj0, h.sp, h.first, h.n, oslot, S.d_recs.p, S.d_pos.p,
-                                     (uint32_t *)S.d_span_tri.p, s));
-    for (const Group &g : groups) {
+                                     span_tri, s));
+    const ClsView d = cls.view(S.d_cls.p);
+    for (const WalkGroup &g : walks.groups) {
         if (g.big)
-            PRK_TRY(prk_big_walk(&fp, g.mode, g.lds ? 1 : 0, d_objs, d_cbig + g.start, d_coff + g.start, d_ccap + g.start,
-                                 d_cmeta + 2 * (size_t)g.start, g.count, g.max_rows, (int32_t *)S.d_pool.p, escan,
-                                 total0p, S.d_work.p, oslot, S.d_raw.p, S.d_pos.p, (uint32_t *)S.d_span_tri.p,
-                                 (uint32_t *)S.d_err.p, d_prstat, s));
+            PRK_TRY(prk_big_walk(&fp, g.mode, g.lds ? 1 : 0, d_objs, d.big + g.start, d.off + g.start, d.cap + g.start,
+                                 d.meta + 2 * (size_t)g.start, g.count, g.max_rows, (int32_t *)S.d_pool.p, escan,
+                                 total0p, S.d_work.p, oslot, S.d_raw.p, S.d_pos.p, span_tri, err, d_prstat, s));
         else
-            PRK_TRY(prk_obj_walk_group(&fp, g.mode, g.lcap, d_objs, d_cbig + g.start, d_coff + g.start,
-                                       d_ccap + g.start, g.count, (int32_t *)S.d_pool.p, escan, total0p, S.d_work.p,
-                                       oslot, S.d_recs.p, scalar ? S.d_srecs.p : nullptr, S.d_raw.p, S.d_pos.p,
-                                       (uint32_t *)S.d_span_tri.p, (uint32_t *)S.d_err.p, d_prstat, s));
+            PRK_TRY(prk_obj_walk_group(&fp, g.mode, g.lcap, d_objs, d.big + g.start, d.off + g.start, d.cap + g.start,
+                                       g.count, (int32_t *)S.d_pool.p, escan, total0p, S.d_work.p, oslot, S.d_recs.p,
+                                       srecs(), S.d_raw.p, S.d_pos.p, span_tri, err, d_prstat, s));
     }
-    if (nbig_all)  // the slot walks' pairs into span records
-        PRK_TRY(prk_span_finish(&fp, S.d_raw.p, nslot, S.d_recs.p, scalar ? S.d_srecs.p : nullptr, S.d_pos.p, s));
-    // span -> tile bin entries: the tiles' counts and their scan (the
-    // total comes back with the walk's status), then every span placed
+    if (nbig)  // the slot walks' pairs into span records
+        PRK_TRY(prk_span_finish(&fp, S.d_raw.p, nslot, S.d_recs.p, srecs(), S.d_pos.p, s));
+    return PRK_OK;
+}
+
+// span -> tile bin entries: the tiles' counts and their scan (the total comes
+// back with the walks' status: the pass's second wait), then every span
+// placed; visibility and shading.
+int SpanPass::bin_shade(uint32_t T) {
     PRK_TRY(S.d_scnt.ensure(((size_t)ntiles + 1) * 4));
     PRK_TRY(S.d_offs.ensure(((size_t)ntiles + 1) * 4));
     uint32_t *tcnt = (uint32_t *)S.d_scnt.p, *toff = (uint32_t *)S.d_offs.p;
     PRK_TRY(prk_span_count(&fp, S.d_pos.p, nslot, tcnt, s));
-    PRK_TRY(prk_scan_u32(tcnt, toff, ntiles + 1, nullptr, &tb, s));
-    PRK_TRY(temp(tb));
-    PRK_TRY(prk_scan_u32(tcnt, toff, ntiles + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(scan_u32(S.d_temp, tcnt, toff, ntiles + 1, s));
     PRK_TRY(hipMemcpyAsync(S.h_rb + 2, toff + ntiles, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipMemcpyAsync(S.h_rb + 3, S.d_err.p, 16, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
     const uint32_t total = S.h_rb[2];
     if (S.h_rb[3]) return PRK_ERR_DEVICE;  // a walk outside its LDS list or span slots (never)
-    if (std::getenv("PRK_PR_DEBUG"))
+    if (sw.pr_debug)
         std::fprintf(stderr, "prk: large objects %u, chunked: taken %u done %u failed %u; chunks %u, walked again %u\n",
-                     nbig_all, npr, S.h_rb[4], S.h_rb[5], pr_chunks, S.h_rb[6]);
+                     nbig, walks.npr, S.h_rb[4], S.h_rb[5], walks.pr_chunks, S.h_rb[6]);
     c->stats.objects_chunked += S.h_rb[4];
-    c->stats.objects_walked += nbig_all - S.h_rb[4];
-    c->stats.object_chunks += pr_chunks;
+    c->stats.objects_walked += nbig - S.h_rb[4];
+    c->stats.object_chunks += walks.pr_chunks;
     c->stats.object_chunks_rewalked += S.h_rb[6];
     c->stats.triangles = T;
     c->stats.tiles = ntiles;
@@ -2888,11 +2972,45 @@ static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::Dra
     PRK_TRY(prk_span_bin(&fp, S.d_pos.p, nslot, toff, tcnt, (uint32_t *)S.d_vals_b.p, s));
     PRK_TRY(S.d_nwin.ensure((size_t)ntiles * 4));
     PRK_TRY(S.d_wtag.ensure((size_t)ntiles * fp.tile_w * fp.tile_h * 4));
-    PRK_TRY(prk_launch_spans(&fp, (const uint32_t *)S.d_offs.p, (const uint32_t *)S.d_vals_b.p, S.d_pos.p,
-                             S.d_recs.p, scalar ? S.d_srecs.p : nullptr, modes, (const uint32_t *)S.d_span_tri.p,
-                             (uint32_t *)S.d_nwin.p, (uint32_t *)S.d_wtag.p, s));
+    PRK_TRY(prk_launch_spans(&fp, (const uint32_t *)S.d_offs.p, (const uint32_t *)S.d_vals_b.p, S.d_pos.p, S.d_recs.p,
+                             srecs(), modes, (const uint32_t *)S.d_span_tri.p, (uint32_t *)S.d_nwin.p,
+                             (uint32_t *)S.d_wtag.p, s));
     return PRK_OK;
 }
+}  // namespace
+
+// One pass of whole-object AETs (prk_spans.hip): FillEdgeTable per triangle,
+// MergeSort per object (one radix sort), one walk of every object's AET into
+// span records (each object writing into its own slots, as many as its edges'
+// active rows allow), bin the spans to tiles, then visibility + shading.
+// Stream-ordered on s; the host waits at the two sizes it reads back (the
+// span slots in sizes(), the bin entry count in bin_shade()).
+static int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::DrawRec> &draws, uint32_t T,
+                       uint32_t win_base) {
+    c->z_early = false;  // (k_pix / k_span_shade write a span pass's z)
+    const bool fuse = c->clear_pending && T > 0;
+    SpanPass P(c, s, draws);
+    frame_params(c, P.fp);
+    P.fp.tri_count = T;
+    P.fp.ndraws = (uint32_t)draws.size();
+    P.fp.win_base = win_base;
+    P.ntiles = (uint32_t)(P.fp.tiles_x * P.fp.tiles_y);
+    c->clear_pending = false;
+    P.fp.clear_fused = fuse ? 1 : 0;
+    if (T == 0) return PRK_OK;
+    if (!P.S.h_rb) PRK_TRY(hipHostMalloc((void **)&P.S.h_rb, 8 * sizeof(uint32_t), hipHostMallocDefault));
+    P.lcap = prk_obj_walk_lcap();
+    int rc = P.plan();
+    if (rc == PRK_OK) rc = P.upload();
+    if (rc == PRK_OK) rc = P.edges();
+    if (rc == PRK_OK) rc = P.sizes();
+    if (rc != PRK_OK) return rc;
+    P.classify();
+    rc = P.walk();
+    if (rc == PRK_OK) rc = P.bin_shade(T);
+    return rc;
+}
+
 
 int prk_flush(prk_context *c, void *stream) {
     if (!c) return PRK_ERR_ARG;
@@ -3155,12 +3273,9 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
     PRK_TRY(S.d_err.ensure(16));
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));
     uint32_t *escan = (uint32_t *)S.d_escan.p;
-    size_t tb = 0;
     PRK_TRY(prk_objtri_count(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, (uint32_t *)S.d_ecnt.p,
                              (unsigned long long *)S.d_rcnt.p, s));
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, nullptr, &tb, s));
-    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
-    PRK_TRY(prk_scan_u32((const uint32_t *)S.d_ecnt.p, escan, nt + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(scan_u32(S.d_temp, (const uint32_t *)S.d_ecnt.p, escan, nt + 1, s));
     PRK_TRY(prk_rec_counts(d_objs, d_k0obj, nobj, escan, (uint32_t *)S.d_reccnt.p, s));
     // the total sizes the records (and decides whether the caller's buffer holds them)
     uint32_t total = 0;
@@ -3194,12 +3309,8 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
         } else {
             PRK_TRY(S.d_ekeys2.ensure(es * 8));
             PRK_TRY(S.d_ord.ensure(es * 4));
-            const uint32_t end_bit = obits + ybits + pbits;
-            PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
-                                 end_bit, nullptr, &tb, s));
-            PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
-            PRK_TRY(prk_obj_sort(S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
-                                 end_bit, S.d_temp.p, &tb, s));
+            PRK_TRY(obj_sort(S.d_temp, S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
+                             obits + ybits + pbits, s));
             PRK_TRY(prk_rec_export(S.d_edges.p, (const uint32_t *)S.d_ord.p, total, d_out, s));
         }
         uint32_t err = 0;
@@ -3245,13 +3356,10 @@ static int records_finish(prk_context *c, Records &R, uint32_t nlist, uint64_t t
     R.flag.assign(nlist, 0u);
     if (nlist) {
         uint32_t *d_cnt = R.tab, *d_flag = R.tab + nlist + 1;
-        size_t tb = 0;
         PRK_TRY(hipMemsetAsync(d_cnt + nlist, 0, 4, s));  // (the scan's total)
         PRK_TRY(S.d_lscan.ensure(((size_t)nlist + 1) * 4));
         uint32_t *lscan = (uint32_t *)S.d_lscan.p;
-        PRK_TRY(prk_scan_u32(d_cnt, lscan, nlist + 1, nullptr, &tb, s));
-        PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
-        PRK_TRY(prk_scan_u32(d_cnt, lscan, nlist + 1, S.d_temp.p, &tb, s));
+        PRK_TRY(scan_u32(S.d_temp, d_cnt, lscan, nlist + 1, s));
         PRK_TRY(prk_list_rule(R.rec, (uint32_t)total, lscan, nlist, d_flag, s));
         PRK_TRY(hipMemcpyAsync(R.cnt.data(), d_cnt, (size_t)nlist * 4, hipMemcpyDeviceToHost, s));
         PRK_TRY(hipMemcpyAsync(R.flag.data(), d_flag, (size_t)nlist * 4, hipMemcpyDeviceToHost, s));
@@ -3766,10 +3874,7 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     const uint32_t *d_sbase = a.sbase;
     uint32_t *d_cnt = a.cnt, *d_cscan = (uint32_t *)S.d_soff.p;
     PRK_TRY(walk_launch(c, plan, a, d_lists));
-    size_t tb = 0;
-    PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, nullptr, &tb, s));
-    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
-    PRK_TRY(prk_scan_u32(d_cnt, d_cscan, list_count + 1, S.d_temp.p, &tb, s));
+    PRK_TRY(scan_u32(S.d_temp, d_cnt, d_cscan, list_count + 1, s));
     uint32_t nspan = 0, err = 0;
     PRK_TRY(hipMemcpyAsync(&nspan, d_cscan + list_count, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
@@ -3853,11 +3958,9 @@ static int rows_run(prk_context *c, WalkPlan &plan, const void *records, hipMemc
     uint32_t *d_pcnt = a.cnt, *d_pscan = (uint32_t *)S.d_soff.p;
     uint32_t *d_rcnt = a.rcnt, *d_rscan = (uint32_t *)S.d_rowscan.p;
     PRK_TRY(walk_launch(c, plan, a, d_lists));
-    size_t tb = 0;
-    PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, nullptr, &tb, s));
-    PRK_TRY(S.d_temp.ensure(std::max<size_t>(tb, 16)));
-    PRK_TRY(prk_scan_u32(d_pcnt, d_pscan, list_count + 1, S.d_temp.p, &tb, s));
-    PRK_TRY(prk_scan_u32(d_rcnt, d_rscan, list_count + 1, S.d_temp.p, &tb, s));
+    // (two scans of one length: the second finds the buffer the first ensured)
+    PRK_TRY(scan_u32(S.d_temp, d_pcnt, d_pscan, list_count + 1, s));
+    PRK_TRY(scan_u32(S.d_temp, d_rcnt, d_rscan, list_count + 1, s));
     uint32_t npair = 0, nrow = 0, err = 0;
     PRK_TRY(hipMemcpyAsync(&npair, d_pscan + list_count, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipMemcpyAsync(&nrow, d_rscan + list_count, 4, hipMemcpyDeviceToHost, s));
