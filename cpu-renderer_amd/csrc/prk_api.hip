@@ -113,6 +113,15 @@ struct Texture {
     int32_t filter = 0;  // PRK_FILTER_*
 };
 
+// A target layer (prk_layer_*): a rectangle of (colour, z) pixels in device
+// memory, the library's (prk_layer_alloc) or the caller's (wrapped: read-only).
+struct Layer {
+    uint8_t *color = nullptr;
+    float *z = nullptr;  // rows of w floats
+    int32_t w = 0, h = 0, pitch = 0;
+    bool wrapped = false, live = false;
+};
+
 // A record batch (prk_records_*): lists in prk_edge_records' packed layout,
 // kept in device memory.  The host keeps each list's edge count and whether
 // it takes the sorted walks (flush_spans routes by them) -- no records.
@@ -317,6 +326,9 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     // its slot, dead).  A prk_draw_span_records DrawRec: src_kind 5, geom the
     // handle, src_off / src_n its spans within the handle.
     std::vector<SpanBatch> sbatches;
+    // target layers by handle, their own number space (a destroyed one keeps
+    // its slot, dead)
+    std::vector<Layer> layers;
     std::vector<prk::DrawRec> draws;
     uint32_t pending_tris = 0;
     std::vector<prk_edge> pend_edges;  // prk_draw_edges input of the pending frame
@@ -758,6 +770,11 @@ int prk_destroy(prk_context *c) {
         (void)hipFree(r.tab);
     }
     for (auto &b : c->sbatches) (void)hipFree(b.sp);
+    for (auto &l : c->layers)
+        if (l.live && !l.wrapped) {
+            (void)hipFree(l.color);
+            (void)hipFree(l.z);
+        }
     if (c->owns_target) {
         (void)hipFree(c->color);
         (void)hipFree(c->zbuf);
@@ -1119,6 +1136,149 @@ int prk_texture_info(prk_context *c, int32_t handle, int32_t *width, int32_t *he
     if (width) *width = t.w;
     if (height) *height = t.h;
     if (pitch_bytes) *pitch_bytes = t.pitch;
+    return PRK_OK;
+}
+
+// ---- target layers (prk.h; kernel: prk_layer.hip) -------------------------------
+static Layer *layer_of(prk_context *c, int32_t handle) {
+    if (!c || handle < 0 || (size_t)handle >= c->layers.size() || !c->layers[handle].live) return nullptr;
+    return &c->layers[handle];
+}
+
+int prk_layer_alloc(prk_context *c, int32_t width, int32_t height, int32_t *handle_out) {
+    if (!c || width <= 0 || height <= 0 || width > INT32_MAX / 4 || !handle_out) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    Layer l;
+    l.w = width;
+    l.h = height;
+    l.pitch = 4 * width;
+    l.live = true;
+    const size_t px = (size_t)width * (size_t)height;
+    hipError_t e = hipMalloc((void **)&l.color, px * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&l.z, px * 4);
+    if (e == hipSuccess) e = hipMemset(l.color, 0, px * 4);
+    if (e == hipSuccess) e = hipMemsetD32((hipDeviceptr_t)l.z, (int)0xFF7FFFFFu, px);  // -FLT_MAX
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the context's streams do not wait for that stream)
+    if (e != hipSuccess) {
+        (void)hipFree(l.color);
+        (void)hipFree(l.z);
+        return status_of(e);
+    }
+    *handle_out = (int32_t)c->layers.size();
+    c->layers.push_back(l);
+    return PRK_OK;
+}
+
+int prk_layer_wrap_device(prk_context *c, const void *color, int32_t pitch_bytes, const float *zbuf, int32_t width,
+                          int32_t height, int32_t *handle_out) {
+    if (!c || !color || !zbuf || width <= 0 || height <= 0 || width > INT32_MAX / 4 || !handle_out) return PRK_ERR_ARG;
+    if (pitch_bytes < 4 * width || (pitch_bytes & 3)) return PRK_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(color) & 3) || (reinterpret_cast<uintptr_t>(zbuf) & 3)) return PRK_ERR_ARG;
+    Layer l;
+    l.color = static_cast<uint8_t *>(const_cast<void *>(color));  // (never written: no call takes it as destination)
+    l.z = const_cast<float *>(zbuf);
+    l.w = width;
+    l.h = height;
+    l.pitch = pitch_bytes;
+    l.wrapped = l.live = true;
+    *handle_out = (int32_t)c->layers.size();
+    c->layers.push_back(l);
+    return PRK_OK;
+}
+
+// Do a layer's rectangle at (lx, ly) and the target's at frame pixel (x0, y0), both width x height, lie inside?
+static bool layer_rects_ok(const prk_context *c, const Layer &l, int32_t lx, int32_t ly, int32_t x0, int32_t y0,
+                           int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return false;
+    if (x0 < 0 || (int64_t)x0 + width > c->W || y0 < c->row0 || (int64_t)y0 + height > c->row1) return false;
+    return lx >= 0 && (int64_t)lx + width <= l.w && ly >= 0 && (int64_t)ly + height <= l.h;
+}
+
+// One pass between a layer's rectangle at (lx, ly) and the target's at frame
+// pixel (x0, y0): rule < 0 saves target to layer, else the layer goes to the
+// target under rule.  Ordered as prk_texture_from_target: on copy_stream
+// after read_ev (the frames already flushed) and after what own_stream holds
+// (clears, uploads); the next flush, clear, upload or layer call waits for
+// in_ev.
+static int layer_pass(prk_context *c, const Layer &l, int32_t lx, int32_t ly, int32_t x0, int32_t y0, int32_t width,
+                      int32_t height, int32_t rule) {
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    const size_t toff = (size_t)(y0 - c->row0) * c->W + (size_t)x0, loff = (size_t)ly * l.w + (size_t)lx;
+    uint8_t *tc = static_cast<uint8_t *>(c->color) + (size_t)(y0 - c->row0) * c->pitch + (size_t)x0 * 4;
+    uint8_t *lc = l.color + (size_t)ly * l.pitch + (size_t)lx * 4;
+    float *tz = c->zbuf + toff, *lz = l.z + loff;
+    const size_t tzp = (size_t)c->W * 4, lzp = (size_t)l.w * 4;
+    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->read_ev, 0));
+    PRK_TRY(hipEventRecord(c->s_mark, c->own_stream));
+    PRK_TRY(hipStreamWaitEvent(c->copy_stream, c->s_mark, 0));
+    if (rule < 0)
+        PRK_TRY(prk_layer_launch(tc, (size_t)c->pitch, tz, tzp, lc, (size_t)l.pitch, lz, lzp, (uint32_t)width,
+                                 (uint32_t)height, PRK_MERGE_COPY, c->copy_stream));
+    else
+        PRK_TRY(prk_layer_launch(lc, (size_t)l.pitch, lz, lzp, tc, (size_t)c->pitch, tz, tzp, (uint32_t)width,
+                                 (uint32_t)height, rule, c->copy_stream));
+    PRK_TRY(hipEventRecord(c->in_ev, c->copy_stream));
+    c->in_wait = true;
+    return PRK_OK;
+}
+
+int prk_layer_from_target(prk_context *c, int32_t layer, int32_t x0, int32_t y0, int32_t width, int32_t height,
+                          int32_t dst_x, int32_t dst_y) {
+    const Layer *l = layer_of(c, layer);
+    if (!l || l->wrapped) return PRK_ERR_ARG;
+    if (width <= 0 || height <= 0) return PRK_ERR_ARG;
+    if (!c->color) return PRK_ERR_NO_TARGET;
+    if (!layer_rects_ok(c, *l, dst_x, dst_y, x0, y0, width, height)) return PRK_ERR_ARG;
+    return layer_pass(c, *l, dst_x, dst_y, x0, y0, width, height, -1);
+}
+
+int prk_target_from_layer(prk_context *c, int32_t layer, int32_t src_x, int32_t src_y, int32_t width, int32_t height,
+                          int32_t x0, int32_t y0, int32_t rule) {
+    const Layer *l = layer_of(c, layer);
+    if (!l) return PRK_ERR_ARG;
+    if (rule != PRK_MERGE_COPY && rule != PRK_MERGE_GREATER && rule != PRK_MERGE_GREATER_EQUAL) return PRK_ERR_ARG;
+    if (width <= 0 || height <= 0) return PRK_ERR_ARG;
+    if (!c->color) return PRK_ERR_NO_TARGET;
+    if (!layer_rects_ok(c, *l, src_x, src_y, x0, y0, width, height)) return PRK_ERR_ARG;
+    c->z_early = false;  // (z written outside a frame)
+    return layer_pass(c, *l, src_x, src_y, x0, y0, width, height, rule);
+}
+
+int prk_layer_download(prk_context *c, int32_t layer, uint32_t *color_host, int32_t host_pitch, float *z_host) {
+    const Layer *l = layer_of(c, layer);
+    if (!l) return PRK_ERR_ARG;
+    if (color_host && (host_pitch < 4 * l->w || (host_pitch & 3))) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipStreamSynchronize(c->copy_stream));  // every queued layer call runs there
+    if (color_host)
+        PRK_TRY(hipMemcpy2D(color_host, host_pitch, l->color, l->pitch, (size_t)l->w * 4, l->h, hipMemcpyDeviceToHost));
+    if (z_host) PRK_TRY(hipMemcpy(z_host, l->z, (size_t)l->w * l->h * 4, hipMemcpyDeviceToHost));
+    return PRK_OK;
+}
+
+int prk_layer_info(prk_context *c, int32_t layer, int32_t *width, int32_t *height, int32_t *pitch_bytes,
+                   int32_t *wrapped) {
+    const Layer *l = layer_of(c, layer);
+    if (!l) return PRK_ERR_ARG;
+    if (width) *width = l->w;
+    if (height) *height = l->h;
+    if (pitch_bytes) *pitch_bytes = l->pitch;
+    if (wrapped) *wrapped = l->wrapped ? 1 : 0;
+    return PRK_OK;
+}
+
+int prk_layer_destroy(prk_context *c, int32_t layer) {
+    Layer *l = layer_of(c, layer);
+    if (!l) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());  // frames in flight and queued layer calls first
+    if (!l->wrapped) {
+        (void)hipFree(l->color);
+        (void)hipFree(l->z);
+    }
+    *l = Layer();  // (the slot stays, dead)
     return PRK_OK;
 }
 

@@ -161,6 +161,14 @@ hipError_t prk_xform_launch(const void *tables, size_t runs_off, size_t xf_off, 
 hipError_t prk_tex_from_target_launch(const void *src, size_t spitch, void *dst, size_t dpitch, uint32_t dw,
                                       uint32_t dh, int32_t factor, hipStream_t s);
 
+// ---- prk_layer.hip ------------------------------------------------------------
+// prk_layer_from_target / prk_target_from_layer: the w x h pixels (colour words at src_color, rows src_cpitch
+// bytes apart; z words at src_z, rows src_zpitch bytes apart) into the pixels at dst_color / dst_z under
+// rule (a PRK_MERGE_*: every pixel, or those whose source z wins); all four addresses 4-byte aligned.
+hipError_t prk_layer_launch(const void *src_color, size_t src_cpitch, const float *src_z, size_t src_zpitch,
+                            void *dst_color, size_t dst_cpitch, float *dst_z, size_t dst_zpitch, uint32_t w,
+                            uint32_t h, int32_t rule, hipStream_t s);
+
 // ---- prk_spans.hip: the record calls -------------------------------------------
 // prk_edge_records: the object triangles' edges with their true-YMin MergeSort keys ...
 hipError_t prk_rec_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj, const uint32_t *k0tri0,

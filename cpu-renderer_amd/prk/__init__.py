@@ -167,6 +167,7 @@ _SIGS = {
 
 _SIGS.update({name: (C.c_int, args) for name, args in abi.GEOMETRY_TRANSFORM_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.TEXTURE_TARGET_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.TARGET_LAYER_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.SORT_SELFTEST_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
@@ -717,6 +718,62 @@ class Renderer:
         out = np.empty((h, w), np.uint32)
         _check("prk_texture_download", self._L.prk_texture_download(self._h, tex, _ptr(out), 4 * w))
         return out
+
+    # ---- target layers ----------------------------------------------------
+    def layer_alloc(self, width, height):
+        """prk_layer_alloc: a library-owned layer of width x height (colour,
+        z) pixels, every colour word 0 and every z -FLT_MAX."""
+        h = C.c_int32(-1)
+        _check("prk_layer_alloc", self._L.prk_layer_alloc(self._h, int(width), int(height), C.byref(h)))
+        return h.value
+
+    def layer_wrap(self, color_ptr, pitch_bytes, z_ptr, width, height):
+        """prk_layer_wrap_device: a read-only layer over caller-owned device
+        memory (a peer context's target after its synchronize(), a torch
+        tensor's data_ptr()); no copy is made."""
+        h = C.c_int32(-1)
+        _check("prk_layer_wrap_device", self._L.prk_layer_wrap_device(
+            self._h, C.c_void_p(color_ptr), int(pitch_bytes), C.c_void_p(z_ptr), int(width), int(height), C.byref(h)))
+        return h.value
+
+    def layer_from_target(self, layer, rect=None, dst=(0, 0)):
+        """prk_layer_from_target: colour and z of the target over rect = (x0,
+        y0, width, height) in frame pixels (None: the whole band) into layer
+        `layer` at pixel dst = (x, y).  Does not wait for the device."""
+        x0, y0, w, h = (0, self.row0, self.width, self.row1 - self.row0) if rect is None else rect
+        _check("prk_layer_from_target", self._L.prk_layer_from_target(
+            self._h, layer, int(x0), int(y0), int(w), int(h), int(dst[0]), int(dst[1])))
+
+    def target_from_layer(self, layer, rect=None, dst=None, rule=abi.PRK_MERGE_COPY):
+        """prk_target_from_layer: the layer's pixels over rect = (src_x,
+        src_y, width, height) (None: the whole layer) into the target at frame
+        pixel dst = (x0, y0) (None: the band's first pixel), every pixel
+        (PRK_MERGE_COPY) or where the layer's z wins (PRK_MERGE_GREATER,
+        PRK_MERGE_GREATER_EQUAL).  Does not wait for the device."""
+        sx, sy, w, h = (0, 0) + self.layer_info(layer)[:2] if rect is None else rect
+        x0, y0 = (0, self.row0) if dst is None else dst
+        _check("prk_target_from_layer", self._L.prk_target_from_layer(
+            self._h, layer, int(sx), int(sy), int(w), int(h), int(x0), int(y0), int(rule)))
+
+    def layer_info(self, layer):
+        """prk_layer_info: (width, height, colour pitch in bytes, wrapped)."""
+        v = [C.c_int32(0) for _ in range(4)]
+        _check("prk_layer_info", self._L.prk_layer_info(self._h, layer, *[C.byref(x) for x in v]))
+        return v[0].value, v[1].value, v[2].value, bool(v[3].value)
+
+    def layer_download(self, layer):
+        """prk_layer_download: (uint32 [height, width], float32 [height,
+        width]), the layer's colour and z after everything queued that writes
+        them."""
+        w, h = self.layer_info(layer)[:2]
+        color = np.empty((h, w), np.uint32)
+        z = np.empty((h, w), np.float32)
+        _check("prk_layer_download", self._L.prk_layer_download(self._h, layer, _ptr(color), 4 * w, _ptr(z)))
+        return color, z
+
+    def layer_destroy(self, layer):
+        """prk_layer_destroy (the Renderer's close frees what is left)."""
+        _check("prk_layer_destroy", self._L.prk_layer_destroy(self._h, layer))
 
     def geometry_update(self, handle, vertices, colors=None, normals=None, uvs=None):
         arrs = [None if a is None else np.ascontiguousarray(a, np.float32)

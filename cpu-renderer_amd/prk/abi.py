@@ -131,6 +131,21 @@ TEXTURE_TARGET_SIGS = {
     "prk_texture_info": [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
 }
 
+# Target layers (prk.h): the merge rules, and each entry point and its argument types
+PRK_MERGE_COPY = 0           # every pixel of the rectangle
+PRK_MERGE_GREATER = 1        # where zs > zd  (DrawModel, FillLineOptimized: the earliest of equals wins)
+PRK_MERGE_GREATER_EQUAL = 2  # where zs >= zd (the single-thread overload: the latest wins)
+TARGET_LAYER_SIGS = {
+    "prk_layer_alloc": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],
+    "prk_layer_wrap_device": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                              C.POINTER(C.c_int32)],
+    "prk_layer_from_target": [C.c_void_p] + [C.c_int32] * 7,
+    "prk_target_from_layer": [C.c_void_p] + [C.c_int32] * 8,
+    "prk_layer_download": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p],
+    "prk_layer_info": [C.c_void_p, C.c_int32] + [C.POINTER(C.c_int32)] * 4,
+    "prk_layer_destroy": [C.c_void_p, C.c_int32],
+}
+
 
 # prk_row_pair word w holds prk_span word ROW_PAIR_SPAN_WORD[w] (an end is
 # XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3]; Right at +12)

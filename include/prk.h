@@ -314,6 +314,95 @@ int prk_texture_from_target(prk_context *ctx, int32_t texture,
 int prk_texture_download(prk_context *ctx, int32_t handle, void *memory, int32_t pitch_bytes);
 int prk_texture_info(prk_context *ctx, int32_t handle, int32_t *width, int32_t *height, int32_t *pitch_bytes);
 
+/* Target layers: a drawn (colour, z) frame kept on the device, put back
+ * before the next frame, or merged into it by depth.  An EXTENSION of this
+ * build with its own definition: the reference keeps one
+ * framebuffer.
+ *
+ * A LAYER is a rectangle of width x height pixels, each a 0xAARRGGBB colour
+ * word and an f32 z.  The context owns it and names it by a handle >= 0, in a
+ * number space of its own (like span handles); a destroyed handle stays dead.
+ *
+ * prk_layer_alloc: a library-owned layer, colour pitch 4 * width, z rows of
+ * width floats; every colour word 0 and every z -FLT_MAX (bits 0xFF7FFFFF).
+ *
+ * prk_layer_wrap_device: a READ-ONLY layer over device memory that the caller
+ * keeps alive until prk_layer_destroy or prk_destroy; no copy is made.  Colour
+ * rows are pitch_bytes apart (>= 4 * width, a multiple of 4), z rows width
+ * floats.  Both addresses are 4-byte aligned; nothing more is asked.  Intended
+ * sources: another context's target on the same device (prk_get_target), a
+ * torch tensor.  The caller guarantees that the memory is complete and stays
+ * unchanged while a queued call reads it: for a peer context's target that
+ * means prk_synchronize on the peer before the call here, and no draw into it
+ * until this context has finished (prk_synchronize, or a download).  The
+ * memory must not overlap this context's bound target.
+ *
+ * prk_layer_from_target (save): colour and z of the target's pixels
+ * [x0, x0 + width) x [y0, y0 + height), in FRAME coordinates, bit for bit into
+ * the layer's pixels at (dst_x, dst_y).  The rectangle must lie inside
+ * [0, W) x [row0, row1) (a band context reads its own rows only) and its
+ * destination inside the layer.  Nothing else in the layer is written; the
+ * target is only read.  A wrapped layer as destination is PRK_ERR_ARG.
+ *
+ * prk_target_from_layer (restore, merge): for every pixel of the layer's
+ * rectangle [src_x, src_x + width) x [src_y, src_y + height), with (cs, zs)
+ * the layer's pixel and (cd, zd) the target's pixel at the same offset from
+ * (x0, y0) in FRAME coordinates:
+ *   PRK_MERGE_COPY           (cd, zd) = (cs, zs)
+ *   PRK_MERGE_GREATER        the same where zs >  zd
+ *   PRK_MERGE_GREATER_EQUAL  the same where zs >= zd
+ * The comparison is IEEE f32: a NaN on either side loses (the target keeps its
+ * pixel), -0.0 equals +0.0, denormals compare by value.  Words move as bits; a
+ * pixel that does not win keeps both its words.  No pixel outside the
+ * rectangle is touched, nor the pad bytes of a caller-bound target's pitch.
+ * The rules are the reference's z tests: DrawModel and FillLineOptimized keep
+ * the earliest of equal fragments (GREATER: the layer holds the LATER draws),
+ * the single-thread overload the latest (GREATER_EQUAL).  So two frames drawn
+ * from the same clear, whose z is below every fragment's, one of a frame's
+ * draws [0, k) and one of its draws [k, n), merge into exactly the frame of
+ * all n draws: restore or keep the first, merge the second under its
+ * semantics' rule.
+ * Winner ids are not merged: prk_download_winners stays "of the last flush".
+ * prk_get_stats is untouched.
+ *
+ * Ordering of both calls is prk_texture_from_target's: the call returns
+ * without waiting and allocates nothing; the pending frame is resolved first
+ * (an overflowed one re-run); it runs after the frames already flushed and the
+ * clears and uploads queued so far, before the next prk_flush's kernels, and
+ * before a later prk_target_clear / prk_target_upload / layer or texture call.
+ * A draw recorded before prk_target_from_layer and flushed after it is drawn
+ * on top of what the call wrote.  A prk_target_clear_on_flush not yet flushed
+ * is not in what prk_layer_from_target reads, and still clears at its flush:
+ * it discards what prk_target_from_layer wrote, as it discards an upload.
+ *
+ * prk_layer_download: the layer's colour (rows host_pitch_bytes apart,
+ * >= 4 * width, a multiple of 4) and z (rows of width floats) after every
+ * queued call that writes it; either host pointer may be NULL.
+ * prk_layer_info: width, height, colour pitch and whether it is wrapped; any
+ * pointer may be NULL.  Host bookkeeping: no device work.
+ * prk_layer_destroy: after the frames in flight and the queued layer calls;
+ * frees a library-owned layer's memory.  prk_destroy frees every layer.
+ *
+ * PRK_ERR_ARG: a NULL context, a bad or destroyed handle, an unknown rule, a
+ * width or height <= 0, a rectangle outside the layer or outside the target's
+ * band, a bad pitch or address.  PRK_ERR_NO_TARGET: no target bound.  On any
+ * error nothing has been written. */
+enum prk_merge {
+    PRK_MERGE_COPY = 0,          /* every pixel of the rectangle: colour and z replaced            */
+    PRK_MERGE_GREATER = 1,       /* where zs > zd  (DrawModel, FillLineOptimized: earliest wins)   */
+    PRK_MERGE_GREATER_EQUAL = 2  /* where zs >= zd (the single-thread overload: latest wins)       */
+};
+int prk_layer_alloc(prk_context *ctx, int32_t width, int32_t height, int32_t *handle_out);
+int prk_layer_wrap_device(prk_context *ctx, const void *color, int32_t pitch_bytes, const float *zbuf,
+                          int32_t width, int32_t height, int32_t *handle_out);
+int prk_layer_from_target(prk_context *ctx, int32_t layer, int32_t x0, int32_t y0, int32_t width, int32_t height,
+                          int32_t dst_x, int32_t dst_y);
+int prk_target_from_layer(prk_context *ctx, int32_t layer, int32_t src_x, int32_t src_y, int32_t width,
+                          int32_t height, int32_t x0, int32_t y0, int32_t rule);
+int prk_layer_download(prk_context *ctx, int32_t layer, uint32_t *color_host, int32_t host_pitch_bytes, float *z_host);
+int prk_layer_info(prk_context *ctx, int32_t layer, int32_t *width, int32_t *height, int32_t *pitch_bytes, int32_t *wrapped);
+int prk_layer_destroy(prk_context *ctx, int32_t layer);
+
 /* Geometry: non-indexed SoA vertex arrays exactly as render_entry_3d_object
  * (projekt.h:2-15): positions v3, colours v4, normals v3, uvs v2, three
  * vertices per triangle.  Copied to HBM once; a draw references a range. */
