@@ -463,6 +463,15 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
         // on the thread walk, then in each slot class of the workgroup walk
         uint32_t list_routes[6] = {};
     } spans;
+    // debug (prk_debug_bins): the last per-triangle pass of the most recent
+    // flush, if it was queued with the debug flag on -- its scratch set and
+    // the frame sizes its binning ran with
+    struct BinsDebug {
+        bool valid = false, rerun = false;
+        int set = 0;
+        uint32_t T = 0, per = 0;
+        int32_t tile_w = 0, tile_h = 0, tiles_x = 0, tiles_y = 0, row0 = 0, row1 = 0;
+    } bdbg;
 };
 
 static PassState pass_state(const prk_context *c) { return *c; }
@@ -2010,6 +2019,54 @@ int prk_debug_list_routes(prk_context *c, uint32_t *out, int32_t n) {
     return PRK_OK;
 }
 
+int prk_debug_bins(prk_context *c, prk_bins_info *info, uint32_t *tri_n, uint16_t *ranges, uint32_t *tri_off,
+                   uint8_t *listed, uint64_t tri_capacity, uint32_t *offs, uint64_t tile_capacity, uint32_t *bins,
+                   uint32_t *pair_tri, uint64_t entry_capacity) {
+    if (!c || !info) return PRK_ERR_ARG;
+    RESOLVE_COUNT(c);  // (an overflowed pass is re-run here: bdbg then names the re-run's set)
+    const prk_context::BinsDebug &D = c->bdbg;
+    if (!D.valid) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(c->device));
+    PRK_TRY(hipDeviceSynchronize());
+    const prk_context::BinSet &B = c->bset[D.set];
+    const uint32_t T = D.T, ntiles = (uint32_t)(D.tiles_x * D.tiles_y), total = B.h_info[0];
+    *info = prk_bins_info{D.tile_w, D.tile_h, D.tiles_x, D.tiles_y, D.row0, D.row1, T, total, D.rerun ? 1u : 0u,
+                          D.per};
+    if ((tri_n || ranges || tri_off || listed) && tri_capacity < T) return PRK_ERR_ARG;
+    if (offs && tile_capacity < ntiles) return PRK_ERR_ARG;
+    if ((bins || pair_tri) && entry_capacity < total) return PRK_ERR_ARG;
+    if (tri_n) PRK_TRY(hipMemcpy(tri_n, B.d_tri_n.p, (size_t)T * 4, hipMemcpyDeviceToHost));
+    if (ranges) PRK_TRY(hipMemcpy(ranges, B.d_ranges.p, (size_t)T * 16, hipMemcpyDeviceToHost));
+    if (tri_off) PRK_TRY(hipMemcpy(tri_off, B.d_tri_off.p, ((size_t)T + 1) * 4, hipMemcpyDeviceToHost));
+    if (listed) std::memset(listed, D.per ? 0 : 1, T);
+    if (D.per && (tri_n || ranges || tri_off || listed)) {
+        // a row band: k_bin_band and k_cs_emit wrote only the triangles of the
+        // run lists; the others hold what an earlier frame left
+        const uint32_t nruns = prk_bin_runs(T), len = prk_bin_run_len();
+        std::vector<uint32_t> run_n(nruns), list((size_t)nruns * len);
+        std::vector<uint8_t> in(T, 0);
+        PRK_TRY(hipMemcpy(run_n.data(), B.d_run_n.p, (size_t)nruns * 4, hipMemcpyDeviceToHost));
+        PRK_TRY(hipMemcpy(list.data(), B.d_runlist.p, list.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < nruns; ++r)
+            for (uint32_t i = 0; i < std::min(run_n[r], len); ++i) {
+                const uint32_t g = list[(size_t)r * len + i];
+                if (g < T) in[g] = 1;
+            }
+        static const uint16_t kEmpty[8] = {1, 1, 0, 0, 1, 0, 0, 0};
+        for (uint32_t g = 0; g < T; ++g) {
+            if (listed) listed[g] = in[g];
+            if (in[g]) continue;
+            if (tri_n) tri_n[g] = 0;
+            if (ranges) std::memcpy(ranges + 8 * (size_t)g, kEmpty, sizeof(kEmpty));
+            if (tri_off) tri_off[g] = UINT32_MAX;
+        }
+    }
+    if (offs) PRK_TRY(hipMemcpy(offs, B.d_offs.p, ((size_t)ntiles + 1) * 4, hipMemcpyDeviceToHost));
+    if (bins && total) PRK_TRY(hipMemcpy(bins, B.d_bins.p, (size_t)total * 8, hipMemcpyDeviceToHost));
+    if (pair_tri && total) PRK_TRY(hipMemcpy(pair_tri, B.d_pair_tri.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+    return PRK_OK;
+}
+
 // The frame parameters every pass of a flush shares (camera, lights, target, tiling).
 static void frame_params(const prk_context *c, prk::FrameParams &fp) {
     fp = prk::FrameParams{};
@@ -2354,6 +2411,20 @@ static int flush_tris(prk_context *c, hipStream_t s, const std::vector<prk::Draw
     c->last_slot = slot;
     c->frame++;
     guard.ok = true;
+    c->bdbg.valid = c->debug;
+    if (c->debug) {  // (prk_debug_bins reads this set once the frame is done)
+        prk_context::BinsDebug &D = c->bdbg;
+        D.rerun = false;
+        D.set = si;
+        D.T = T;
+        D.per = prk_cs_band_runs_per_chunk(&fp);
+        D.tile_w = fp.tile_w;
+        D.tile_h = fp.tile_h;
+        D.tiles_x = fp.tiles_x;
+        D.tiles_y = fp.tiles_y;
+        D.row0 = fp.row0;
+        D.row1 = fp.row1;
+    }
     {
         // The whole frame is queued; now the entry count (the binning's first
         // few kernels) decides whether it fitted — read here, or, for the
@@ -2412,6 +2483,10 @@ static int resolve_count(prk_context *c) {
     c->clear_pending = P.fuse;
     const std::vector<prk::DrawRec> draws = std::move(P.draws);
     const int rc = flush_tris(c, P.s, draws, P.T, P.win_base);
+    // (the re-run ran with the pass's own debug flag, P.state: a prk_set_debug
+    // since the flush does not change what prk_debug_bins answers for)
+    if (rc == PRK_OK) c->bdbg.rerun = true;
+    else c->bdbg.valid = false;
     c->read_rec = hipEventRecord(c->read_ev, P.s) == hipSuccess;  // (geometry writes wait for the re-run)
     c->z_early = false;  // (a re-run: the download takes z after everything)
     apply_pass_state(c, callers);
@@ -3212,6 +3287,7 @@ int prk_flush(prk_context *c, void *stream) {
         PRK_TRY(hipMemsetAsync(c->d_negz.p, 0, 4, s));
     }
     c->z_early = false;  // (the passes below say whether the frame's last one allows it)
+    c->bdbg.valid = false;  // (prk_debug_bins: this flush's last per-triangle pass, if any)
     if (c->debug) {
         PRK_TRY(c->d_winners.ensure((size_t)c->W * (c->row1 - c->row0) * 4));
         PRK_TRY(hipMemsetAsync(c->d_winners.p, 0xFF, (size_t)c->W * (c->row1 - c->row0) * 4, s));

@@ -1,4 +1,8 @@
-// prk_bin.hip — triangle -> tile binning with bins in submission order.
+// prk_bin.hip — triangle -> tile binning: pairs numbered in submission order,
+// each tile's bin the exact set of its pairs, grouped by row class within
+// windows of kCsClassWindow slots and in no particular order inside a class
+// (tests/binref.py states the ranges and entries, tests/test_gpu_bins.py
+// holds the kernels to it through prk_debug_bins).
 //
 //   k_bin_count   1 thread / triangle: ProjectVertex + back-face cull
 //                 (projekt.cpp:74-93, 3926-3943) -> conservative tile range ->

@@ -94,6 +94,7 @@ _SIGS = {
     "prk_debug_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
     "prk_debug_walk_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]),
     "prk_debug_list_routes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]),
+    "prk_debug_bins": (C.c_int, abi.DEBUG_BINS_ARGS),
     "prk_set_tile": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "prk_construct_sphere": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_uint32)]),
@@ -1142,6 +1143,27 @@ class Renderer:
         out = (C.c_uint32 * 6)()
         _check("prk_debug_list_routes", self._L.prk_debug_list_routes(self._h, out, 6))
         return dict(thread=out[0], slots=tuple(out[1:6]))
+
+    def debug_bins(self):
+        """The tile binning of the last per-triangle pass of the most recent
+        flush made with set_debug on (prk_debug_bins): a dict of the frame's
+        sizes (abi.PrkBinsInfo's fields) and the arrays tri_n [T], ranges
+        [T, 8] uint16 (abi.TILE_RANGE_FIELDS), tri_off [T + 1], listed [T]
+        uint8, offs [ntiles + 1], bins [entries, 2] (triangle, pair) and
+        pair_tri [entries]."""
+        fn = self._L.prk_debug_bins
+        info = abi.PrkBinsInfo()
+        _check("prk_debug_bins", fn(self._h, C.byref(info), None, None, None, None, 0, None, 0, None, None, 0))
+        T, ne, nt = info.tri_count, info.entry_count, info.tiles_x * info.tiles_y
+        out = dict(tri_n=np.zeros(T, np.uint32), ranges=np.zeros((T, 8), np.uint16),
+                   tri_off=np.zeros(T + 1, np.uint32), listed=np.zeros(T, np.uint8),
+                   offs=np.zeros(nt + 1, np.uint32), bins=np.zeros((ne, 2), np.uint32),
+                   pair_tri=np.zeros(ne, np.uint32))
+        p = {k: v.ctypes.data_as(C.c_void_p) for k, v in out.items()}
+        _check("prk_debug_bins", fn(self._h, C.byref(info), p["tri_n"], p["ranges"], p["tri_off"], p["listed"], T,
+                                    p["offs"], nt, p["bins"], p["pair_tri"], ne))
+        out.update({k: getattr(info, k) for k, _ in abi.PrkBinsInfo._fields_})
+        return out
 
     def stats(self):
         s = abi.PrkStats()

@@ -175,6 +175,19 @@ SPAN_HANDLE_ARGS = {
 LIST_STATS_FIELDS = ("edge_rows", "scans", "most", "ymin0", "ymax_max")
 
 
+class PrkBinsInfo(C.Structure):
+    """prk_bins_info: the frame sizes prk_debug_bins answers for."""
+    _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("row0", C.c_int32), ("row1", C.c_int32), ("tri_count", C.c_uint32), ("entry_count", C.c_uint32),
+                ("rerun", C.c_uint32), ("band_per", C.c_uint32)]
+
+
+# prk_debug_bins: a triangle's eight range words, and the call's argument types
+TILE_RANGE_FIELDS = ("tx0", "ty0", "tx1", "ty1", "oty0", "oty1", "pad0", "pad1")
+DEBUG_BINS_ARGS = [C.c_void_p, C.POINTER(PrkBinsInfo), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+
+
 def make_transform(D, F, M2P, cx, cy):
     t = PrkTransform()
     t.DistanceAboveTarget = D

@@ -93,11 +93,16 @@ def random_texture(rng, w=256, h=256):
     return Texture(tex, w, h)
 
 
-def _unproject(sx, sy, z, cam):
+def unproject(sx, sy, z, cam):
+    """Camera-space (x, y) of the screen points (sx, sy) at depth z under
+    cam = (D, F, M2P, cx, cy): ProjectVertex inverted (float64)."""
     D, F, M2P, cx, cy = cam
     x = (sx - cx) * (D - z) / M2P / F
     y = (sy - cy) * (D - z) / M2P / F
     return x, y
+
+
+_unproject = unproject  # (the generators below and tools/ call it by this name)
 
 
 def random_soup(n_tris, width, height, radius=16.0, seed=0, textured=True, lights=None,

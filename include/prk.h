@@ -676,6 +676,52 @@ int prk_debug_walk_routes(prk_context *ctx, uint32_t *out, int32_t n);
  * in the slot classes of 62 / 126 / 254 / 510 / 1022 entries.  A refused call
  * leaves the words of the call before it.  n <= 6 words are written. */
 int prk_debug_list_routes(prk_context *ctx, uint32_t *out, int32_t n);
+/* Debug/test: the tile binning of the last per-triangle pass (draws of one
+ * triangle per object) of the most recent flush, as the binning kernels left
+ * it.  Requires prk_set_debug(ctx, 1) before that flush; PRK_ERR_ARG before
+ * any such flush, without debug, or when the flush had no per-triangle pass.
+ * The pending entry count is resolved first: a pass whose entries overflowed
+ * the scratch is re-run, and the call answers for the re-run (info->rerun).
+ * It then waits for the frame and copies to host memory; no kernel runs for
+ * it, and a flush without debug records nothing for it.
+ *
+ * Triangles are numbered from 0 within the pass, pairs (bin entries) in
+ * triangle order: triangle g's entries are pairs tri_off[g] .. tri_off[g] +
+ * tri_n[g] - 1, in the order rectangle row-major (ty, then tx), then the
+ * column-0 row-overflow tiles oty0..oty1 that are not in the rectangle.
+ *   tri_n    [tri_count]      entries of each triangle (0: culled or outside)
+ *   ranges   [tri_count][8]   tx0 ty0 tx1 ty1 oty0 oty1 pad0 pad1 (an empty
+ *                             rectangle or overflow range reads 1, 0; pad0 /
+ *                             pad1: the band rows [r0, r1) the triangle can
+ *                             cover, meaningful only where tri_n != 0)
+ *   tri_off  [tri_count + 1]  first pair of each triangle; the last word is
+ *                             the entry count
+ *   listed   [tri_count]      1 where the binning wrote the three above.  A
+ *                             whole-frame pass writes every triangle.  A row
+ *                             band's pass writes only the triangles with
+ *                             entries (its run lists); the others read
+ *                             tri_n 0, an empty range and tri_off UINT32_MAX
+ *   offs     [ntiles + 1]     bin starts, tile = ty * tiles_x + tx
+ *   bins     [entry_count][2] (triangle, pair) of every bin slot, grouped by
+ *                             row class within windows of 2048 slots, in no
+ *                             particular order within a class
+ *   pair_tri [entry_count]    the triangle of each pair
+ * Any of the array pointers may be NULL (not wanted).  Sizing follows
+ * prk_edge_records: *info is always written; a wanted array whose capacity
+ * (tri_capacity triangles, tile_capacity tiles, entry_capacity entries) is
+ * short of the frame's gives PRK_ERR_ARG and copies nothing. */
+typedef struct prk_bins_info {
+    int32_t tile_w, tile_h, tiles_x, tiles_y; /* the frame's tile (as widened to fit the sort) */
+    int32_t row0, row1;                       /* the band the pass drew */
+    uint32_t tri_count, entry_count;
+    uint32_t rerun;                           /* 1: the pass overflowed its scratch and was run again */
+    uint32_t band_per;                        /* 0: a whole-frame pass.  Else a row band, binned through run
+                                               * lists (see listed) of 2048 triangles: the runs one chunk of
+                                               * the counting sort takes (1..64) */
+} prk_bins_info;
+int prk_debug_bins(prk_context *ctx, prk_bins_info *info, uint32_t *tri_n, uint16_t *ranges, uint32_t *tri_off,
+                   uint8_t *listed, uint64_t tri_capacity, uint32_t *offs, uint64_t tile_capacity,
+                   uint32_t *bins, uint32_t *pair_tri, uint64_t entry_capacity);
 
 /* Test: the raster kernels divide several values by one divisor through a
  * shared reciprocal; this checks n hashed (x, d) draws and

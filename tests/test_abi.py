@@ -67,6 +67,21 @@ def test_argument_errors_without_device():
     assert L.prk_version() .startswith(b"prk")
 
 
+def test_debug_bins_boundary():
+    """prk_debug_bins: exported with the binding's argument list, its info
+    struct as the header lays it out, and a NULL context or info refused."""
+    assert "prk_debug_bins" in declared() and "prk_debug_bins" in prk.exported_symbols()
+    L = prk.lib()
+    assert L.prk_debug_bins.argtypes == abi.DEBUG_BINS_ARGS and len(abi.DEBUG_BINS_ARGS) == 12
+    assert C.sizeof(abi.PrkBinsInfo) == 40
+    assert [n for n, _ in abi.PrkBinsInfo._fields_] == ["tile_w", "tile_h", "tiles_x", "tiles_y", "row0", "row1",
+                                                       "tri_count", "entry_count", "rerun", "band_per"]
+    assert len(abi.TILE_RANGE_FIELDS) == 8
+    info = abi.PrkBinsInfo()
+    assert L.prk_debug_bins(None, C.byref(info), None, None, None, None, 0, None, 0, None, None, 0) == abi.PRK_ERR_ARG
+    assert L.prk_debug_bins(None, None, None, None, None, None, 0, None, 0, None, None, 0) == abi.PRK_ERR_ARG
+
+
 def test_construct_sphere_host():
     V, Cc, N, UV = prk.construct_sphere()
     assert V.shape == (6624, 3)
