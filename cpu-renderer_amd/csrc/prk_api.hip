@@ -1878,7 +1878,7 @@ int prk_draw_spans(prk_context *c, const prk_span *spans, uint32_t count, int32_
 
 // Row work records (prk_row_records' output, or a caller's own) as a draw of
 // their pairs: the rows and pairs go up as they are, k_rows_unpack
-// (prk_spans.hip) turns every pair into the prk_span of its row on the device
+// (prk_records.hip) turns every pair into the prk_span of its row on the device
 // -- no host loop over the pairs, only the one over the rows that checks the
 // arguments -- and the spans come back into the pending frame's span input,
 // where the draw is prk_draw_spans' from then on.  The buffers are this
@@ -3734,7 +3734,7 @@ int prk_debug_stage_bytes(prk_context *c, uint64_t *bytes_out) {
 // The lists DrawModel* leaves (prk_advance_edge_records' result) for a batch
 // of sorted lists, walked on the GPU: k_adv_import -> k_adv_walk (one thread
 // per list) and k_adv_walk_wg (one workgroup per long list, ListRouter below)
-// -> k_rec_export + k_adv_next (prk_spans.hip).  Every refusal is decided on
+// -> k_rec_export + k_adv_next (prk_records.hip, prk_spans.hip).  Every refusal is decided on
 // the host, in the one pass over the records that checks the sorted rule
 // (list_walks_sorted), sizes each list's walk and routes it -- a list over
 // kAdvMaxSteps is refused before anything is launched.  The scratch is the
@@ -4086,7 +4086,7 @@ int prk_advance_edge_lists(prk_context *c, const prk_edge *records, const uint32
 // and the row), from prk_advance_edge_lists' walk with the emission hook:
 // k_adv_import -> k_span_walk (one thread per list: pairs into the list's
 // slots, its count) and k_span_walk_wg (a workgroup per routed list, the same
-// slots and count) -> scan of the counts -> k_span_pack (prk_spans.hip).
+// slots and count) -> scan of the counts -> k_span_pack (prk_records.hip).
 // The refusals and the one host pass are prk_advance_edge_lists'; the pass
 // also sizes each list's slots, floor(edge-rows / 2): a pair uses up one row
 // of each of two listed edges (each listed on rows [YMin, min(YMax, height))
@@ -4171,7 +4171,7 @@ int prk_span_records(prk_context *c, const prk_edge *records, const uint32_t *co
 // walk with the row hook: k_adv_import -> k_row_walk (one thread per list:
 // pairs into the list's pair slots, a row record a row into its row slots, its
 // two counts) and k_row_walk_wg (a workgroup per routed list) -> two scans ->
-// k_row_pack (prk_spans.hip).  The refusals and the one host pass are
+// k_row_pack (prk_records.hip).  The refusals and the one host pass are
 // prk_span_records'; the pass also sizes each list's row slots, the rows of
 // its walk.  What the pass cannot know -- a row with more
 // than 1000 pairs, the reference's ThreadEdges[1000] -- the walk flags, and

@@ -1591,8 +1591,8 @@ __global__ void __launch_bounds__(256) k_pix(FrameParams fp, const uint32_t *__r
 // DrawModel spans (ScSpanRec, SPAN_SCALAR) its scalar chunk items
 // (item_scalar), the one-past-the-row pixel included.
 // ---------------------------------------------------------------------------
-struct SpanPosK { int32_t row, minx, maxx; uint32_t flags; };  // == prk_spans.hip SpanPos
-struct ScSpanRec { float f[22]; int32_t tex, pad; };          // == prk_spans.hip ScSpanRecG
+struct SpanPosK { int32_t row, minx, maxx; uint32_t flags; };  // == prk_spans_dev.h SpanPos
+struct ScSpanRec { float f[22]; int32_t tex, pad; };          // == prk_spans_dev.h ScSpanRecG
 static_assert(sizeof(ScSpanRec) == 96, "scalar span record");
 constexpr int32_t kAvxSlot = -2;  // SI_OVF of a slot holding a FillLineOptimized span
 

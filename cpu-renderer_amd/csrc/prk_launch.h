@@ -169,7 +169,7 @@ hipError_t prk_layer_launch(const void *src_color, size_t src_cpitch, const floa
                             void *dst_color, size_t dst_cpitch, float *dst_z, size_t dst_zpitch, uint32_t w,
                             uint32_t h, int32_t rule, hipStream_t s);
 
-// ---- prk_spans.hip: the record calls -------------------------------------------
+// ---- prk_spans.hip: prk_edge_records ---------------------------------------------
 // prk_edge_records: the object triangles' edges with their true-YMin MergeSort keys ...
 hipError_t prk_rec_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj, const uint32_t *k0tri0,
                         uint32_t nk0, uint32_t ntri, const uint32_t *escan, int32_t setup, uint32_t pbits,
@@ -179,6 +179,8 @@ hipError_t prk_rec_counts(const void *objs, const uint32_t *k0obj, uint32_t nk0,
                           uint32_t *counts, hipStream_t s);
 // ... and `total` edges (ord: null, or their order) as packed prk_edge records.
 hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total, void *out, hipStream_t s);
+
+// ---- prk_records.hip: the record calls' walks, packing and unpacking -------------
 // `total` packed records into a->work, then the thread walk of `kind` over a's lists.
 hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const prk::ListWalkArgs *a, hipStream_t s);
 // The largest slot class the current device grants the workgroup walks (0: none).

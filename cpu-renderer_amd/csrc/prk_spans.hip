@@ -68,22 +68,17 @@
 //                 the 64-bit key max (tag = span index in submission order).
 //   k_pix (prk_kernels.hip, span records indexed by span)  shading.
 //
-// prk_edge_records (FillEdgeTable's records handed back, no frame) runs the
-// same count / scan / sort with k_rec_emit (every edge_info field, the key on
-// the true YMin), k_rec_counts and k_rec_export (packed prk_edge), at the end
-// of this file; k_list_prep, k_rec_export's reverse for prk_draw_edge_lists,
-// follows them, and then prk_advance_edge_lists' kernels (the list DrawModel*
-// leaves, no frame): k_adv_import (k_list_prep's import), k_adv_walk (a
-// thread per list, every field stepped), k_adv_next (the links); then
-// prk_span_records' (the spans that walk queues): k_span_walk (the same walk
-// with the emission hook) and k_span_pack (packed prk_span); last,
-// prk_row_records' (DrawModelOptimizedLines' row work): k_row_walk (the walk
-// with the row hook too), k_row_pack (packed prk_row / prk_row_pair), and
-// prk_draw_rows' k_rows_unpack (such records back into packed prk_span).
+// Where things are:
+//   prk_spans_dev.h  the types and row arithmetic shared with prk_records.hip
+//   prk_wave.h       wave and workgroup primitives (DPP scans, LKey, blk_*)
+//   prk_slot.h       the slot list of the workgroup walks, here and there
+//   prk_spans.hip    every kernel of a pass named above, and prk_edge_records'
+//                    k_rec_emit, k_rec_counts, k_rec_export (FillEdgeTable's
+//                    records, with k_list_prep, their reverse)
+//   prk_records.hip  the record calls' walks of edge lists, no frame
 #include <atomic>
 
-#include "prk_device.h"
-#include "prk_launch.h"
+#include "prk_slot.h"
 
 namespace prk {
 // Diagnostic builds (-DPRK_WPROF=1): the whole-object slot-list walk
@@ -179,214 +174,6 @@ __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, ui
         k0obj[R.k0base + j] = o;
         k0tri0[R.k0base + j] = R.tri0 + t;
     }
-}
-
-// Caller edges (prk_edge = edge_info without Next, prk.h) and spans (prk_span).
-struct EdgeIn {
-    int32_t YMax;
-    float XMin, ZMin, OneOverZMin, Gradient, ZGradient, OneOverZGradient;
-    int32_t YMin;
-    float UMin, VMin, UGradient, VGradient;
-    int32_t Left;
-    float MinColor[4], ColorGradient[4], MinNormal[3], NormalGradient[3];
-};
-struct SpanEndIn {
-    float XMin, ZMin, OneOverZMin, UMin, VMin, MinColor[4], MinNormal[3];
-};
-struct SpanIn {
-    SpanEndIn L, R;
-    int32_t Row;
-};
-
-// Mutable edge_info of the object's AET (projekt.h:17-37) in global memory.
-struct ObjEdge {
-    float X, G, Z, ZG, W, WG, U, UG, V, VG;
-    float N0, N1, N2, NG0, NG1, NG2;
-    int32_t YMin, YMax, Left, Next;
-    float C0, C1, C2, C3, CG0, CG1, CG2, CG3;  // MinColor / ColorGradient (DrawModel's Gouraud colour)
-};
-static_assert(sizeof(ObjEdge) == kObjEdgeBytes, "ObjEdge is seven dwordx4");
-
-// Span of the span path: its row and pixel range [minx, maxx) (half-open,
-// 1588-1592), DRAW_ST in flags.
-struct SpanPos {
-    int32_t row, minx, maxx;
-    uint32_t flags;
-};
-
-struct SpanRecG {  // == SpanRec of prk_kernels.hip (FillLineOptimized lane init)
-    float4 q0, q1, q2, q3;
-};
-// A DrawModel span (scalar semantics) of the span path: the values at MinX
-// after the left clip (308-412) and the per-pixel increments, in the float
-// slot order of the scalar sweeps (prk_kernels.hip SS_*), plus its texture.
-// Its SpanRecG slot carries kScalarSpan in its first word, its SpanPos the
-// half-open [MinX, MaxX + 1) and SPAN_SCALAR | mode << 8 (prk_device.h).
-struct ScSpanRecG {
-    float f[22];
-    int32_t tex, pad;
-};
-static_assert(sizeof(ScSpanRecG) == kScSpanRecBytes, "scalar span record is six dwordx4");
-
-
-__device__ __forceinline__ void obj_edge_store(ObjEdge &o, const Edge &E) {
-    o.X = E.X; o.G = E.G; o.Z = E.Z; o.ZG = E.ZG; o.W = E.W; o.WG = E.WG;
-    o.U = E.U; o.UG = E.UG; o.V = E.V; o.VG = E.VG;
-    o.N0 = E.N0; o.N1 = E.N1; o.N2 = E.N2; o.NG0 = E.NG0; o.NG1 = E.NG1; o.NG2 = E.NG2;
-    o.YMin = E.YMin; o.YMax = E.YMax; o.Left = E.Left; o.Next = -1;
-    o.C0 = E.C0; o.C1 = E.C1; o.C2 = E.C2; o.C3 = E.C3;
-    o.CG0 = E.CG0; o.CG1 = E.CG1; o.CG2 = E.CG2; o.CG3 = E.CG3;
-}
-
-// AET insertion order (3663-3667).
-__device__ __forceinline__ bool obj_before(const ObjEdge &A, const ObjEdge &B) {
-    return A.X < B.X || (A.X == B.X && (A.G < B.G || (A.G == B.G && A.Left < B.Left)));
-}
-
-// Edge step (3811-3829 / DrawModel 542-560), the fields mode M reads: AVX
-// semantics X, Z, the normal, U, V, 1/z (the colour lanes are dead,
-// 2029-2032); DrawModel also the colour (Gouraud) and drops what its mode
-// never reads (ModeTraits).
-template <int M>
-__device__ __forceinline__ void obj_step(ObjEdge &E) {
-    using TR = ModeTraits<M>;
-    E.X += E.G;
-    E.Z += E.ZG;
-    if (TR::color) { E.C0 += E.CG0; E.C1 += E.CG1; E.C2 += E.CG2; E.C3 += E.CG3; }
-    if (TR::phong) {
-        float x = E.N0 + E.NG0, y = E.N1 + E.NG1, z = E.N2 + E.NG2;
-        normalize_rcp(x, y, z);
-        E.N0 = x; E.N1 = y; E.N2 = z;
-    }
-    if (TR::tex) {
-        E.U += E.UG;
-        E.V += E.VG;
-        E.W += E.WG;
-    }
-}
-
-// FillLineOptimized span setup (1543-1835) of the pair (L, R) at Row: the
-// lane-init record and the covered range [MinX, MaxX).  False when the span
-// covers nothing.
-__device__ __forceinline__ bool obj_span(const FrameParams &fp, const ObjEdge &L, const ObjEdge &R, int32_t Row,
-                                         int32_t texi, bool st, SpanRecG &rec, SpanPos &pos) {
-    float XOffset;
-    int32_t MinX, MaxX, XDiff;
-    if (!span_ends(L.X, R.X, fp.W, st, MinX, MaxX, XDiff, XOffset)) return false;  // 1545-1592
-    if (MinX >= MaxX) return false;
-    int32_t LeftXa = MinX;
-    if (MinX & 7) {  // 1594-1609
-        LeftXa = MinX & ~7;
-        XOffset -= (float)(MinX & 7) * 1.0f;
-    }
-    const float fXD = (float)XDiff;
-    float IW = 0, IU = 0, IV = 0, IZ = 0, IN0 = 0, IN1 = 0, IN2 = 0;
-    if (XDiff != 0) {  // 1666-1835
-        // the span's increments over XDiff (div_all: one shared reciprocal)
-        float q[7] = {R.W - L.W, R.U - L.U, R.V - L.V, R.N0 - L.N0, R.N1 - L.N1, R.N2 - L.N2, R.Z - L.Z};
-        div_all(fXD, q);
-        IW = q[0]; IU = q[1]; IV = q[2]; IN0 = q[3]; IN1 = q[4]; IN2 = q[5]; IZ = q[6];
-    }
-    rec.q0 = make_float4(__int_as_float((LeftXa & 0xFFFF) | (texi << 16)), XOffset, L.W, L.U);
-    rec.q1 = make_float4(L.V, L.Z, IW, IU);
-    rec.q2 = make_float4(IV, IZ, L.N0, L.N1);
-    rec.q3 = make_float4(L.N2, IN0, IN1, IN2);
-    pos.row = Row;
-    pos.minx = MinX;
-    pos.maxx = MaxX;
-    pos.flags = st ? DRAW_ST : 0u;
-    return true;
-}
-
-// DrawModel span setup (projekt.cpp:298-412) of the pair (L, R) at Row for
-// mode M: the values at MinX (Current* += XOffset * Increment) and the
-// per-pixel increments, as span_setup_scalar (prk_kernels.hip) computes them
-// for the per-triangle sweeps, and the inclusive range [MinX, MaxX] (MaxX may
-// be W: the one-past-the-row store into (Row + 1, 0)).  False when the span
-// draws nothing (a NaN end: pinned).
-template <int M>
-__device__ __forceinline__ bool obj_span_scalar(const FrameParams &fp, const ObjEdge &L, const ObjEdge &R, int32_t Row,
-                                                int32_t texi, ScSpanRecG &rec, SpanPos &pos) {
-    using TR = ModeTraits<M>;
-    const int32_t W = fp.W;
-    float XOffset = 0.0f;
-    const float XDiff = roundf(R.X - L.X);  // 311-312
-    float IW = 0, IU = 0, IV = 0, IZ = 0, IN0 = 0, IN1 = 0, IN2 = 0;
-    float IC0 = 0, IC1 = 0, IC2 = 0, IC3 = 0;
-    if (XDiff != 0.0f) {  // 329-360
-        constexpr bool kT = TR::tex, kP = TR::phong, kC = TR::color;
-        float q[1 + (kT ? 3 : 0) + (kP ? 3 : 0) + (kC ? 4 : 0)];
-        int qi = 0;
-        q[qi++] = R.Z - L.Z;
-        if (kT) { q[qi++] = R.W - L.W; q[qi++] = R.U - L.U; q[qi++] = R.V - L.V; }
-        if (kP) { q[qi++] = R.N0 - L.N0; q[qi++] = R.N1 - L.N1; q[qi++] = R.N2 - L.N2; }
-        if (kC) { q[qi++] = R.C0 - L.C0; q[qi++] = R.C1 - L.C1; q[qi++] = R.C2 - L.C2; q[qi++] = R.C3 - L.C3; }
-        div_all(XDiff, q);
-        qi = 0;
-        IZ = q[qi++];
-        if (kT) { IW = q[qi++]; IU = q[qi++]; IV = q[qi++]; }
-        if (kP) { IN0 = q[qi++]; IN1 = q[qi++]; IN2 = q[qi++]; }
-        if (kC) { IC0 = q[qi++]; IC1 = q[qi++]; IC2 = q[qi++]; IC3 = q[qi++]; }
-    }
-    float LeftX = L.X;  // 381-400
-    if (LeftX < 0) { XOffset = -L.X; LeftX = 0; }
-    else if (LeftX >= W) LeftX = (float)W - 1;
-    float RightX = R.X;
-    if (RightX < 0) RightX = 0;
-    else if (RightX >= W) RightX = (float)W - 1;
-    if (LeftX != LeftX || RightX != RightX) return false;
-    const int32_t MinX = round_s32(LeftX), MaxX = round_s32(RightX);  // 402-406
-    if (MaxX < MinX) return false;
-    for (int k = 0; k < 22; ++k) rec.f[k] = 0.0f;
-    rec.f[0] = L.Z + XOffset * IZ;  // 408-412 (SS_Z, SS_IZ)
-    rec.f[1] = IZ;
-    if (TR::tex) {  // SS_W, SS_U, SS_V, SS_IW, SS_IU, SS_IV
-        rec.f[2] = L.W + XOffset * IW; rec.f[5] = IW;
-        rec.f[3] = L.U + XOffset * IU; rec.f[6] = IU;
-        rec.f[4] = L.V + XOffset * IV; rec.f[7] = IV;
-    }
-    if (TR::phong) {  // SS_N0..2, SS_IN0..2
-        rec.f[8] = L.N0 + XOffset * IN0; rec.f[11] = IN0;
-        rec.f[9] = L.N1 + XOffset * IN1; rec.f[12] = IN1;
-        rec.f[10] = L.N2 + XOffset * IN2; rec.f[13] = IN2;
-    }
-    if (TR::color) {  // SS_C0..3, SS_IC0..3
-        rec.f[14] = L.C0 + XOffset * IC0; rec.f[18] = IC0;
-        rec.f[15] = L.C1 + XOffset * IC1; rec.f[19] = IC1;
-        rec.f[16] = L.C2 + XOffset * IC2; rec.f[20] = IC2;
-        rec.f[17] = L.C3 + XOffset * IC3; rec.f[21] = IC3;
-    }
-    rec.tex = TR::tex ? texi : 0;
-    rec.pad = 0;
-    pos.row = Row;
-    pos.minx = MinX;
-    pos.maxx = MaxX + 1;
-    pos.flags = SPAN_SCALAR | ((uint32_t)M << 8);
-    return true;
-}
-
-// One thread per object.  pass 0: span counts -> counts[o]; pass 1: spans at
-// offs[o] + k.  edges / ord / tmp: 3 slots per triangle of the pass.
-__device__ __forceinline__ void obj_edge_in(ObjEdge &o, const EdgeIn &e) {
-    o.X = e.XMin; o.G = e.Gradient; o.Z = e.ZMin; o.ZG = e.ZGradient; o.W = e.OneOverZMin;
-    o.WG = e.OneOverZGradient; o.U = e.UMin; o.UG = e.UGradient; o.V = e.VMin; o.VG = e.VGradient;
-    o.N0 = e.MinNormal[0]; o.N1 = e.MinNormal[1]; o.N2 = e.MinNormal[2];
-    o.NG0 = e.NormalGradient[0]; o.NG1 = e.NormalGradient[1]; o.NG2 = e.NormalGradient[2];
-    o.YMin = e.YMin; o.YMax = e.YMax; o.Left = e.Left; o.Next = -1;
-    o.C0 = e.MinColor[0]; o.C1 = e.MinColor[1]; o.C2 = e.MinColor[2]; o.C3 = e.MinColor[3];
-    o.CG0 = e.ColorGradient[0]; o.CG1 = e.ColorGradient[1]; o.CG2 = e.ColorGradient[2];
-    o.CG3 = e.ColorGradient[3];
-}
-__device__ __forceinline__ ObjEdge span_end_in(const SpanEndIn &e) {  // FillLinesOptimized 648-670
-    ObjEdge o;
-    o.X = e.XMin; o.Z = e.ZMin; o.W = e.OneOverZMin; o.U = e.UMin; o.V = e.VMin;
-    o.N0 = e.MinNormal[0]; o.N1 = e.MinNormal[1]; o.N2 = e.MinNormal[2];
-    o.G = o.ZG = o.WG = o.UG = o.VG = o.NG0 = o.NG1 = o.NG2 = 0.0f;
-    o.C0 = e.MinColor[0]; o.C1 = e.MinColor[1]; o.C2 = e.MinColor[2]; o.C3 = e.MinColor[3];
-    o.CG0 = o.CG1 = o.CG2 = o.CG3 = 0.0f;
-    o.YMin = o.YMax = o.Left = 0;
-    o.Next = -1;
-    return o;
 }
 
 // ---------------------------------------------------------------------------
@@ -607,55 +394,7 @@ __device__ __forceinline__ void obj_range(const ObjDesc &od, const uint32_t *__r
     }
 }
 
-// One span of the pair (L, R) at Row, written at span slot `at` (when `write`).
-template <int M>
-__device__ __forceinline__ bool emit_span(const FrameParams &fp, const ObjEdge &L, const ObjEdge &R, int32_t Row,
-                                          const DrawRec &d, bool st, uint32_t g0, bool write, uint32_t at,
-                                          SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
-                                          SpanPos *__restrict__ pos, uint32_t *__restrict__ span_tri) {
-    SpanPos sp;
-    if constexpr (M != MODE_AVX) {
-        ScSpanRecG srec;
-        if (!obj_span_scalar<M>(fp, L, R, Row, d.tex, srec, sp)) return false;
-        if (write) {
-            SpanRecG mark;
-            mark.q0 = make_float4(__uint_as_float(kScalarSpan), 0.0f, 0.0f, 0.0f);
-            mark.q1 = mark.q2 = mark.q3 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            recs[at] = mark;
-            srecs[at] = srec;
-        }
-    } else {
-        SpanRecG rec;
-        if (!obj_span(fp, L, R, Row, d.tex, st, rec, sp)) return false;
-        if (write) recs[at] = rec;
-    }
-    if (write) {
-        pos[at] = sp;
-        span_tri[at] = g0;
-    }
-    return true;
-}
-
-// The list fields of the thread walk (links, keys, row range), read and
-// written through one of two stores: the working copy itself (GLinks), or
-// per-thread LDS mirrors (LLinks: objects of at most kLinkCap edges), so the
-// list's chains of dependent accesses (insertion scans, expiry, pairing and
-// swaps) run at LDS latency; the edge records stay in device memory, read
-// for a span and stepped per pair, off those chains.  LLinks steps its X
-// mirror with obj_step's own add.
-struct GLinks {
-    ObjEdge *E;
-    __device__ __forceinline__ int32_t next(int i) const { return E[i].Next; }
-    __device__ __forceinline__ void set_next(int i, int32_t v) const { E[i].Next = v; }
-    __device__ __forceinline__ float x(int i) const { return E[i].X; }
-    __device__ __forceinline__ int32_t ymin(int i) const { return E[i].YMin; }
-    __device__ __forceinline__ int32_t ymax(int i) const { return E[i].YMax; }
-    __device__ __forceinline__ bool before(int a, int b) const { return obj_before(E[a], E[b]); }
-    __device__ __forceinline__ void stepped(int) const {}  // (obj_step stepped E[i].X)
-    static constexpr bool kCache = false;  // (the list reads the records' X and links)
-};
 constexpr int kLinkCap = 48;     // edges per object with LDS links (C3b as 16-triangle objects: 48)
-constexpr int kLinkThreads = 64;  // k_obj_walk's workgroup
 // 13 B per edge (YMax relative to the object's first row; YMin is read from
 // the working copy, only where the sorted insertion scan advances), so four
 // 64-thread workgroups fit a CU's LDS.
@@ -692,54 +431,6 @@ struct LLinksT {
     static constexpr bool kCache = PRK_OBJ_PAIR_CACHE;
 };
 using LLinks = LLinksT<kLinkCap>;
-
-// An edge record held in seven named float4 registers (ObjEdge's layout): a
-// loop-carried ObjEdge went to scratch.
-#define PRK_ER(w) float4 w##0, w##1, w##2, w##3, w##4, w##5, w##6
-#define PRK_ER_ZERO(w) \
-    do { w##0 = w##1 = w##2 = w##3 = w##4 = w##5 = w##6 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); } while (0)
-#define PRK_ER_LOAD(w, p)                                                      \
-    do {                                                                       \
-        const float4 *s_ = reinterpret_cast<const float4 *>(p);               \
-        w##0 = s_[0]; w##1 = s_[1]; w##2 = s_[2]; w##3 = s_[3];               \
-        w##4 = s_[4]; w##5 = s_[5]; w##6 = s_[6];                             \
-    } while (0)
-#define PRK_ER_STORE(p, w)                                                     \
-    do {                                                                       \
-        float4 *d_ = reinterpret_cast<float4 *>(p);                           \
-        d_[0] = w##0; d_[1] = w##1; d_[2] = w##2; d_[3] = w##3;               \
-        d_[4] = w##4; d_[5] = w##5; d_[6] = w##6;                             \
-    } while (0)
-#define PRK_ER_SWAP(a, b)                                                                 \
-    do {                                                                                  \
-        float4 t_;                                                                        \
-        t_ = a##0; a##0 = b##0; b##0 = t_; t_ = a##1; a##1 = b##1; b##1 = t_;             \
-        t_ = a##2; a##2 = b##2; b##2 = t_; t_ = a##3; a##3 = b##3; b##3 = t_;             \
-        t_ = a##4; a##4 = b##4; b##4 = t_; t_ = a##5; a##5 = b##5; b##5 = t_;             \
-        t_ = a##6; a##6 = b##6; b##6 = t_;                                                \
-    } while (0)
-__device__ __forceinline__ ObjEdge er_edge(float4 q0, float4 q1, float4 q2, float4 q3, float4 q4, float4 q5,
-                                           float4 q6) {
-    ObjEdge e;
-    e.X = q0.x; e.G = q0.y; e.Z = q0.z; e.ZG = q0.w;
-    e.W = q1.x; e.WG = q1.y; e.U = q1.z; e.UG = q1.w;
-    e.V = q2.x; e.VG = q2.y; e.N0 = q2.z; e.N1 = q2.w;
-    e.N2 = q3.x; e.NG0 = q3.y; e.NG1 = q3.z; e.NG2 = q3.w;
-    e.YMin = __float_as_int(q4.x); e.YMax = __float_as_int(q4.y); e.Left = __float_as_int(q4.z);
-    e.Next = __float_as_int(q4.w);
-    e.C0 = q5.x; e.C1 = q5.y; e.C2 = q5.z; e.C3 = q5.w;
-    e.CG0 = q6.x; e.CG1 = q6.y; e.CG2 = q6.z; e.CG3 = q6.w;
-    return e;
-}
-#define PRK_ER_EDGE(w) er_edge(w##0, w##1, w##2, w##3, w##4, w##5, w##6)
-#define PRK_ER_FROM(w, e)                                                                              \
-    do {                                                                                               \
-        w##0 = make_float4((e).X, (e).G, (e).Z, (e).ZG);                                               \
-        w##1 = make_float4((e).W, (e).WG, (e).U, (e).UG);                                              \
-        w##2 = make_float4((e).V, (e).VG, (e).N0, (e).N1);                                             \
-        w##3 = make_float4((e).N2, (e).NG0, (e).NG1, (e).NG2);                                         \
-        w##5 = make_float4((e).C0, (e).C1, (e).C2, (e).C3);                                            \
-    } while (0)  /* (q4, q6: row range, link, colour gradient — not stepped) */
 
 // MergeSort of objects of at most 64 edges without the device radix sort:
 // one wave per object, lane i ranks edge i's key (object, min(YMin, H),
@@ -1198,7 +889,6 @@ __global__ void __launch_bounds__(kLinkThreads) k_obj_walk_seg(FrameParams fp, c
 //                          passes.  An odd last entry neither pairs nor steps.
 // ---------------------------------------------------------------------------
 // (kWaveListArrays, prk_launch.h: int32 arrays of cap + 2 entries each)
-constexpr uint32_t kSlotCapLds = 1022;  // the slot-list walk's largest LDS capacity (listed edges; 1024 threads)
 struct WaveList {
     int32_t *idx;
     float *x, *g;
@@ -1234,82 +924,6 @@ __device__ __forceinline__ void list_sync() {
     } else {
         wave_lds_sync();
     }
-}
-
-// Lane moves without the LDS (DPP, GFX9): row_shr:n inside each 16-lane row,
-// row_bcast:15 / row_bcast:31 across rows; a lane without a source keeps
-// `old`.  (__shfl* go through
-// ds_bpermute: an LDS round trip each, the one-wave walks' critical path.)
-template <int CTRL, int ROW = 0xf>
-__device__ __forceinline__ int32_t dpp_i(int32_t old, int32_t v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW, 0xf, false);
-}
-template <int CTRL, int ROW = 0xf>
-__device__ __forceinline__ float dpp_f(float old, float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW, 0xf, false));
-}
-constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShr4 = 0x114, kDppShr8 = 0x118;
-constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143;
-__device__ __forceinline__ int32_t wave_incl_sum_i32(int32_t v) {
-    v += dpp_i<kDppShr1>(0, v);
-    v += dpp_i<kDppShr2>(0, v);
-    v += dpp_i<kDppShr4>(0, v);
-    v += dpp_i<kDppShr8>(0, v);
-    v += dpp_i<kDppBcast15, 0xa>(0, v);
-    v += dpp_i<kDppBcast31, 0xc>(0, v);
-    return v;
-}
-__device__ __forceinline__ int32_t wave_incl_max_i32(int32_t v) {
-    v = max(v, dpp_i<kDppShr1>(INT32_MIN, v));
-    v = max(v, dpp_i<kDppShr2>(INT32_MIN, v));
-    v = max(v, dpp_i<kDppShr4>(INT32_MIN, v));
-    v = max(v, dpp_i<kDppShr8>(INT32_MIN, v));
-    v = max(v, dpp_i<kDppBcast15, 0xa>(INT32_MIN, v));
-    v = max(v, dpp_i<kDppBcast31, 0xc>(INT32_MIN, v));
-    return v;
-}
-__device__ __forceinline__ int32_t readlane_i(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ float readlane_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ int wave_max_i32(int v) { return readlane_i(wave_incl_max_i32(v), 63); }
-__device__ __forceinline__ int32_t lane_rank(unsigned long long bal) {
-    return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
-
-// The insertion order as a key.  "Cur sorts before E" (3663-3667) is
-// key(E) > key(Cur) for keys compared (X, Gradient, Left) lexicographically
-// with float compares, once NaNs are mapped out: an entry with a NaN X never
-// compares greater than a new edge (lowest key), one with a NaN Gradient only
-// by X (lowest Gradient and Left).  (New edges with a NaN in their key take
-// the one-at-a-time insertion.)  +0 and -0 compare equal, as in the reference.
-struct LKey {
-    float x, g;
-    int32_t l;
-};
-__device__ __forceinline__ LKey entry_key(float x, float g, int32_t l) {
-    if (x != x) return LKey{-INFINITY, -INFINITY, INT32_MIN};
-    if (g != g) return LKey{x, -INFINITY, INT32_MIN};
-    return LKey{x, g, l};
-}
-__device__ __forceinline__ bool key_gt(const LKey &a, const LKey &b) {
-    return a.x > b.x || (a.x == b.x && (a.g > b.g || (a.g == b.g && a.l > b.l)));
-}
-// Inclusive prefix maximum of the lanes' keys (lane order), with the lane
-// position of a maximum as payload.
-template <int CTRL, int ROW = 0xf>
-__device__ __forceinline__ void key_max_step(LKey &k, int32_t &p) {
-    const LKey o{dpp_f<CTRL, ROW>(-INFINITY, k.x), dpp_f<CTRL, ROW>(-INFINITY, k.g), dpp_i<CTRL, ROW>(INT32_MIN, k.l)};
-    const int32_t op = dpp_i<CTRL, ROW>(-1, p);
-    if (key_gt(o, k)) { k = o; p = op; }
-}
-__device__ __forceinline__ void wave_key_prefix_max(LKey &k, int32_t &p) {
-    key_max_step<kDppShr1>(k, p);
-    key_max_step<kDppShr2>(k, p);
-    key_max_step<kDppShr4>(k, p);
-    key_max_step<kDppShr8>(k, p);
-    key_max_step<kDppBcast15, 0xa>(k, p);
-    key_max_step<kDppBcast31, 0xc>(k, p);
 }
 
 // One new edge E[c] inserted as the reference does (3654-3713): before the
@@ -1631,296 +1245,6 @@ __device__ void walk_object_wave(const FrameParams &fp, const ObjDesc &od, const
     }
 }
 
-// ---------------------------------------------------------------------------
-// The same walk by a whole workgroup, everything in LDS (objects whose most
-// active edges fit the launch's capacity C <= 1022): the listed edges'
-// mutable state in C slots (a free-slot stack), and the list as an array of
-// slot numbers only — its operations move one int per entry and read the
-// keys (X, Gradient, Left, YMax) from the slots.  The workgroup has NT >= C + 2
-// threads, so every list operation is one step: thread q holds entry q, the
-// scans and searches are workgroup scans (a DPP wave scan plus the waves'
-// totals through LDS).  A lone wave walking a long list in 64-entry chunks
-// ran each row's chain of dependent steps chunk after chunk (C2 as one
-// object: ~80 k clocks a row); here a row is ~20 barriers.  A row touches
-// device memory only for the sorted edges it inserts (read ahead NT at a
-// time, one per thread) and the pairs it writes.  Pairing: thread k holds
-// pair k, does its first swap (3831-3841) itself and its second (3843-3853)
-// against pair k-1's second entry through LDS.
-// ---------------------------------------------------------------------------
-constexpr int kSlotListArrays = 5;  // int arrays of cap + 2: idx (slots), aux, nb, bk, bk2
-constexpr uint32_t kSlotMaxThreads = 1024;
-__host__ __device__ constexpr uint32_t slot_threads(uint32_t cap) {  // NT: >= cap + 2, a multiple of 64
-    return ((cap + 2 + 63) / 64) * 64 > kSlotMaxThreads ? kSlotMaxThreads : ((cap + 2 + 63) / 64) * 64;
-}
-struct SlotLds {
-    int32_t *idx;  // the list: slot of each entry, in list order
-    int32_t *aux, *nb, *bk, *bk2;  // insertion / pairing scratch
-    float *nkx, *nkg;              // the batch's new edges: keys (x, g, l) and slots, NT each
-    int32_t *nkl, *nks;
-    int32_t *fs;   // free slots: fs[0, top)
-    ObjEdge *st;   // edge state per slot
-    __device__ __forceinline__ void carve(int32_t *base, uint32_t cap, uint32_t nt) {
-        const size_t s = (size_t)cap + 2;
-        idx = base;
-        aux = base + s;
-        nb = base + 2 * s;
-        bk = base + 3 * s;
-        bk2 = base + 4 * s;
-        int32_t *k = base + kSlotListArrays * s;
-        nkx = reinterpret_cast<float *>(k);
-        nkg = reinterpret_cast<float *>(k + nt);
-        nkl = k + 2 * nt;
-        nks = k + 3 * nt;
-        fs = k + 4 * nt;
-        const size_t off = ((size_t)kSlotListArrays * s + 4 * (size_t)nt + cap) * 4;
-        st = reinterpret_cast<ObjEdge *>(reinterpret_cast<char *>(base) + ((off + 15) & ~(size_t)15));
-    }
-    __device__ __forceinline__ LKey key(int32_t sl) const {
-        return entry_key(st[sl].X, st[sl].G, st[sl].Left);
-    }
-};
-__host__ __device__ constexpr size_t slot_lds_bytes(uint32_t cap) {
-    return ((((size_t)kSlotListArrays * (cap + 2) + 4 * (size_t)slot_threads(cap) + cap) * 4 + 15) & ~(size_t)15) +
-           (size_t)cap * sizeof(ObjEdge);
-}
-// The record calls' slot classes (prk_launch.h): each fills its workgroup, the largest is the LDS capacity.
-static_assert(slot_threads(kAdvWgCaps[0]) == kAdvWgCaps[0] + 2 && slot_threads(kAdvWgCaps[1]) == kAdvWgCaps[1] + 2 &&
-                  slot_threads(kAdvWgCaps[2]) == kAdvWgCaps[2] + 2 && slot_threads(kAdvWgCaps[3]) == kAdvWgCaps[3] + 2 &&
-                  slot_threads(kAdvWgCaps[4]) == kAdvWgCaps[4] + 2 && kAdvWgCaps[4] == kSlotCapLds,
-              "kAdvWgCaps are the slot walk's classes");
-
-// Workgroup reductions and scans over thread order (R: the waves' partials;
-// every caller reaches them with the whole workgroup).
-struct BlockRed {
-    int32_t a[16], b[16], c[16];
-    float x[16], g[16];
-};
-// A workgroup barrier; LO: ordering LDS only (no wait for the workgroup's
-// outstanding device-memory accesses -- for walks whose threads share only
-// LDS, with device-memory stores that nobody in the workgroup reads back).
-template <bool LO = false>
-__device__ __forceinline__ void blk_sync() {
-    if (LO) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    } else {
-        __syncthreads();
-    }
-}
-template <bool LO = false>
-__device__ __forceinline__ int32_t blk_excl_sum(BlockRed &R, int32_t v, int32_t &tot) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int32_t inc = wave_incl_sum_i32(v);
-    if (lane == 63) R.a[w] = inc;
-    blk_sync<LO>();
-    int32_t before = 0, t = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int32_t x = R.a[i];
-        before += i < w ? x : 0;
-        t += x;
-    }
-    blk_sync<LO>();
-    tot = t;
-    return before + inc - v;
-}
-// Two exclusive scans at once (one barrier pair).
-template <bool LO = false>
-__device__ __forceinline__ void blk_excl_sum2(BlockRed &R, int32_t v1, int32_t v2, int32_t &e1, int32_t &e2,
-                                              int32_t &t1, int32_t &t2) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int32_t i1 = wave_incl_sum_i32(v1), i2 = wave_incl_sum_i32(v2);
-    if (lane == 63) { R.a[w] = i1; R.b[w] = i2; }
-    blk_sync<LO>();
-    int32_t b1 = 0, b2 = 0, s1 = 0, s2 = 0;
-    for (int i = 0; i < nw; ++i) {
-        const int32_t x = R.a[i], y = R.b[i];
-        b1 += i < w ? x : 0;
-        b2 += i < w ? y : 0;
-        s1 += x;
-        s2 += y;
-    }
-    blk_sync<LO>();
-    e1 = b1 + i1 - v1;
-    e2 = b2 + i2 - v2;
-    t1 = s1;
-    t2 = s2;
-}
-// Three sums.
-template <bool LO = false>
-__device__ __forceinline__ void blk_sum3(BlockRed &R, int32_t v1, int32_t v2, int32_t v3, int32_t &t1, int32_t &t2,
-                                         int32_t &t3) {
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int32_t s1 = readlane_i(wave_incl_sum_i32(v1), 63), s2 = readlane_i(wave_incl_sum_i32(v2), 63),
-                  s3 = readlane_i(wave_incl_sum_i32(v3), 63);
-    if ((threadIdx.x & 63) == 0) { R.a[w] = s1; R.b[w] = s2; R.c[w] = s3; }
-    blk_sync<LO>();
-    t1 = t2 = t3 = 0;
-    for (int i = 0; i < nw; ++i) { t1 += R.a[i]; t2 += R.b[i]; t3 += R.c[i]; }
-    blk_sync<LO>();
-}
-template <bool LO = false>
-__device__ __forceinline__ int32_t blk_max(BlockRed &R, int32_t v) {
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int32_t m = wave_max_i32(v);
-    if ((threadIdx.x & 63) == 0) R.a[w] = m;
-    blk_sync<LO>();
-    int32_t r = INT32_MIN;
-    for (int i = 0; i < nw; ++i) r = max(r, R.a[i]);
-    blk_sync<LO>();
-    return r;
-}
-// The first thread with b (INT32_MAX: none).
-__device__ __forceinline__ int32_t blk_first(BlockRed &R, bool b) {
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const unsigned long long bal = __ballot(b);
-    if ((threadIdx.x & 63) == 0) R.a[w] = bal ? w * 64 + (int)__builtin_ctzll(bal) : INT32_MAX;
-    __syncthreads();
-    int32_t r = INT32_MAX;
-    for (int i = 0; i < nw; ++i) r = min(r, R.a[i]);
-    __syncthreads();
-    return r;
-}
-// Inclusive prefix maximum of the threads' keys.
-template <bool LO = false>
-__device__ __forceinline__ void blk_key_prefix_max(BlockRed &R, LKey &k) {
-    const int w = threadIdx.x >> 6;
-    int32_t p = 0;
-    wave_key_prefix_max(k, p);
-    if ((threadIdx.x & 63) == 63) { R.x[w] = k.x; R.g[w] = k.g; R.a[w] = k.l; }
-    blk_sync<LO>();
-    LKey c{-INFINITY, -INFINITY, INT32_MIN};
-    for (int i = 0; i < w; ++i) {
-        const LKey o{R.x[i], R.g[i], R.a[i]};
-        if (key_gt(o, c)) c = o;
-    }
-    if (key_gt(c, k)) k = c;
-    blk_sync<LO>();
-}
-
-// One new edge (key c, slot sl) before the first entry it sorts before
-// (3663-3667), else at the tail (thread q: entry q).
-__device__ void insert_one_b(const SlotLds &S, BlockRed &R, int &m, const LKey &c, int32_t sl) {
-    const int q = threadIdx.x;
-    bool b = false;
-    if (q < m) {
-        const int32_t e = S.idx[q];
-        const float x = S.st[e].X, g = S.st[e].G;
-        b = c.x < x || (c.x == x && (c.g < g || (c.g == g && c.l < S.st[e].Left)));
-    }
-    const int p = min(blk_first(R, b), m);
-    const bool mv = q >= p && q < m;  // entries [p, m) move up one
-    const int32_t v = mv ? S.idx[q] : 0;
-    __syncthreads();
-    if (mv) S.idx[q + 1] = v;
-    if (q == 0) S.idx[p] = sl;
-    __syncthreads();
-    ++m;
-}
-
-// The k new edges of the batch (S.nk*[0, k), in insertion order, no NaN key)
-// inserted at once with the result of inserting them one by one (see
-// insert_batch: each new edge lands at its gap + the new edges of earlier
-// gaps + those of its gap ordered before it; entry q moves up by the new
-// edges of gaps <= q).  Thread q: entry q and new edge q.
-__device__ void insert_batch_b(const SlotLds &S, BlockRed &R, int &m, int k) {
-    const int q = threadIdx.x;
-    const bool mine = q < k;
-    // 1. PM(q) = the maximum key of entries [0, q], its (x, g, l) in (nb, bk, aux)
-    float *pmx = reinterpret_cast<float *>(S.nb), *pmg = reinterpret_cast<float *>(S.bk);
-    {
-        LKey kk{-INFINITY, -INFINITY, INT32_MIN};
-        if (q < m) kk = S.key(S.idx[q]);
-        blk_key_prefix_max(R, kk);
-        if (q < m) { pmx[q] = kk.x; pmg[q] = kk.g; S.aux[q] = kk.l; }
-    }
-    __syncthreads();
-    // 2. the gap of new edge q: binary search over the non-decreasing PM
-    LKey kc{0.0f, 0.0f, 0};
-    int32_t rs = 0, gq = 0;
-    if (mine) {
-        kc = LKey{S.nkx[q], S.nkg[q], S.nkl[q]};
-        rs = S.nks[q];
-        int lo = 0, hi = m;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (key_gt(LKey{pmx[mid], pmg[mid], S.aux[mid]}, kc)) hi = mid;
-            else lo = mid + 1;
-        }
-        gq = lo;
-    }
-    __syncthreads();
-    // 3. gap histogram (aux[0, m + 2)), each new edge's arrival slot in its gap
-    if (q < m + 2) S.aux[q] = 0;
-    __syncthreads();
-    int32_t arr = 0;
-    if (mine) arr = atomicAdd(&S.aux[gq], 1);
-    __syncthreads();
-    {  // 4. exclusive scan: aux[g] = new edges of gaps < g
-        const int32_t v = q < m + 2 ? S.aux[q] : 0;
-        int32_t tot;
-        const int32_t ex = blk_excl_sum(R, v, tot);
-        if (q < m + 2) S.aux[q] = ex;
-    }
-    __syncthreads();
-    int32_t s0 = 0, h = 0;
-    if (mine) {  // 5. the new edges grouped by gap
-        s0 = S.aux[gq];
-        h = S.aux[gq + 1] - s0;
-        S.bk2[s0 + arr] = q;
-    }
-    __syncthreads();
-    // 6. final positions: gap + new edges of earlier gaps + those of its gap
-    //    ordered before it (smaller key, or an equal key inserted earlier)
-    //    (a per-thread loop: no barrier inside)
-    int32_t r = 0;
-    for (int32_t j = 0; j < h; ++j) {
-        const int32_t u = S.bk2[s0 + j];
-        if (u != q) {
-            const LKey ku{S.nkx[u], S.nkg[u], S.nkl[u]};
-            r += (key_gt(kc, ku) || (!key_gt(ku, kc) && u < q)) ? 1 : 0;
-        }
-    }
-    // 7. entries move up by the new edges of gaps <= their position; 8. the new edges
-    int32_t v = 0, to = 0;
-    if (q < m) {
-        to = q + S.aux[q + 1];
-        v = S.idx[q];
-    }
-    __syncthreads();
-    if (q < m) S.idx[to] = v;
-    if (mine) S.idx[gq + s0 + r] = rs;
-    __syncthreads();
-    m += k;
-}
-
-// A pair of the slot walk, before its span setup: both edges' values at the
-// row (the fields obj_span / obj_span_scalar read), written by the walk; its
-// SpanPos holds the row, the draw (in minx) and SPAN_RAW until k_span_finish
-// turns it into the span's record (or row -1 when it covers nothing).  The
-// setup's ~300 instructions per span leave the walk's row-serial path.
-constexpr uint32_t SPAN_RAW = 0x40000000u;
-struct PairRaw {
-    float4 l0, l1, l2, r0, r1, r2;  // X Z W U | V N0 N1 N2 | C0 C1 C2 C3, left then right edge
-};
-static_assert(sizeof(PairRaw) == kPairRawBytes, "six dwordx4");
-// One edge's half of a PairRaw (pair_raw_in reads it back).
-__device__ __forceinline__ void pair_raw_half(const ObjEdge &e, float4 &q0, float4 &q1, float4 &q2) {
-    q0 = make_float4(e.X, e.Z, e.W, e.U);
-    q1 = make_float4(e.V, e.N0, e.N1, e.N2);
-    q2 = make_float4(e.C0, e.C1, e.C2, e.C3);
-}
-__device__ __forceinline__ void pair_raw_out(const ObjEdge &a, const ObjEdge &b, PairRaw &o) {
-    pair_raw_half(a, o.l0, o.l1, o.l2);
-    pair_raw_half(b, o.r0, o.r1, o.r2);
-}
-__device__ __forceinline__ ObjEdge pair_raw_in(const float4 &q0, const float4 &q1, const float4 &q2) {
-    ObjEdge e = ObjEdge{};
-    e.X = q0.x; e.Z = q0.y; e.W = q0.z; e.U = q0.w;
-    e.V = q1.x; e.N0 = q1.y; e.N1 = q1.z; e.N2 = q1.w;
-    e.C0 = q2.x; e.C1 = q2.y; e.C2 = q2.z; e.C3 = q2.w;
-    return e;
-}
 __global__ void k_span_finish(FrameParams fp, const PairRaw *__restrict__ raw, uint32_t nslot,
                               SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
                               SpanPos *__restrict__ pos) {
@@ -1963,41 +1287,6 @@ __global__ void k_span_finish(FrameParams fp, const PairRaw *__restrict__ raw, u
     if (!em) p = SpanPos{-1, 0, 0, 0u};  // covers nothing: binned nowhere
     pos[s] = p;
 }
-
-// Read-ahead window of sorted edges as seven dwordx4 (ObjEdge's layout: X, G
-// in q0.xy, YMin, YMax, Left in q4.xyz), named registers (an ObjEdge copy in
-// a loop-carried variable went to scratch).
-#define PRK_WIN(w) float4 w##0, w##1, w##2, w##3, w##4, w##5, w##6
-#define PRK_WIN_LOAD(w, E, i, n)                                                      \
-    do {                                                                              \
-        const float4 *s_ = reinterpret_cast<const float4 *>((E) + min((i), (n) - 1)); \
-        w##0 = s_[0]; w##1 = s_[1]; w##2 = s_[2]; w##3 = s_[3];                       \
-        w##4 = s_[4]; w##5 = s_[5]; w##6 = s_[6];                                     \
-        if ((i) >= (n)) (w##4).x = __int_as_float(INT32_MAX);  /* past the end */     \
-    } while (0)
-// The window's loads complete right where they are issued (s_waitcnt
-// vmcnt(0), once per 64 edges), and the registers are redefined by an empty
-// asm, so no later use waits on the load again: a window register still in
-// flight across the row loop's back edge made the compiler wait for every
-// outstanding access (the previous row's stores included) at the top of
-// every row.
-#define PRK_WIN_WAIT() __builtin_amdgcn_s_waitcnt(0x0F70)  // vmcnt(0) expcnt(7) lgkmcnt(15)
-#define PRK_Q4(q) "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w)
-#define PRK_WIN_LAUNDER(w)                                      \
-    do {                                                        \
-        asm volatile("" : PRK_Q4(w##0), PRK_Q4(w##1));          \
-        asm volatile("" : PRK_Q4(w##2), PRK_Q4(w##3));          \
-        asm volatile("" : PRK_Q4(w##4), PRK_Q4(w##5));          \
-        asm volatile("" : PRK_Q4(w##6));                        \
-    } while (0)
-#define PRK_WIN_COPY(d, w) \
-    do { d##0 = w##0; d##1 = w##1; d##2 = w##2; d##3 = w##3; d##4 = w##4; d##5 = w##5; d##6 = w##6; } while (0)
-#define PRK_WIN_STORE(dst, w)                                                          \
-    do {                                                                               \
-        float4 *d_ = reinterpret_cast<float4 *>(dst);                                  \
-        d_[0] = w##0; d_[1] = w##1; d_[2] = w##2; d_[3] = w##3;                        \
-        d_[4] = w##4; d_[5] = w##5; d_[6] = w##6;                                      \
-    } while (0)
 
 // The slot-list walk of the rows [r0, r1) of an object (r1 <= MaxY), the
 // reference's list operations 3654-3869 once for every caller.
@@ -4197,57 +3486,6 @@ __global__ void __launch_bounds__(256) k_rec_export(const ObjEdge *__restrict__ 
 //   ebase  the first batch edge's slot after the triangle edges (*total0p)
 //   wy     null, or (YMin, YMax) per working-copy slot for k_obj_seg
 // ---------------------------------------------------------------------------
-// (kPrepEdges, prk_launch.h: the edges a workgroup takes)
-struct PrepMap {
-    uint8_t f[28];  // ObjEdge dword -> prk_edge field (27: none, the link)
-};
-constexpr PrepMap prep_map() {
-    // prk_edge field f -> ObjEdge dword (k_rec_export's kWord)
-    constexpr uint8_t kWord[27] = {17, 0, 2, 4, 1, 3, 5, 16, 6, 8, 7, 9, 18, 20, 21, 22, 23,
-                                   24, 25, 26, 27, 10, 11, 12, 13, 14, 15};
-    PrepMap m{};
-    for (int d = 0; d < 28; ++d) m.f[d] = 27;
-    for (int f = 0; f < 27; ++f) m.f[kWord[f]] = (uint8_t)f;
-    return m;
-}
-// The ne records at `rec` (LDS, 27 dwords each) as ObjEdges at dst_edges[0 .. ne):
-// lane t of pass k stores dwordx4 number t + 256 k.
-__device__ __forceinline__ void prep_convert(const uint32_t *rec, uint32_t ne, ObjEdge *__restrict__ dst_edges) {
-    static constexpr PrepMap kMap = prep_map();
-    static_assert(kMap.f[19] == 27 && kMap.f[16] == 7 && kMap.f[17] == 0, "ObjEdge: Next, YMin, YMax");
-    const uint32_t tid = threadIdx.x;
-    float4 *dst = reinterpret_cast<float4 *>(dst_edges);
-    for (uint32_t j = tid; j < 7u * ne; j += (uint32_t)kPrepEdges) {
-        const uint32_t e = j / 7u, q = j - 7u * e;
-        uint32_t v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // (q is not a constant: the map is read from a small table)
-            const uint32_t f = kMap.f[4 * q + k];
-            v[k] = f < 27u ? rec[27u * e + f] : 0xFFFFFFFFu;
-        }
-        dst[j] = make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
-                             __uint_as_float(v[3]));
-    }
-}
-// A workgroup's records into LDS and on into the working copy: edges
-// [e_first, e_first + ne) of the flat input as ObjEdges at dst[0 .. ne)
-// (shared by k_list_prep and k_adv_import; ends in a barrier, so the callers
-// read `rec4` after it).  Returns ne.
-constexpr uint32_t kPrepPieces = 27u * kPrepEdges / 4u;  // 16-byte pieces a full workgroup reads
-static_assert(27 * kPrepEdges % 4 == 0, "a workgroup's records start on a 16-byte boundary");
-__device__ __forceinline__ uint32_t prep_records(const uint4 *__restrict__ in, uint32_t nedge, uint4 *rec4,
-                                                 ObjEdge *__restrict__ dst_edges) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t e_first = blockIdx.x * (uint32_t)kPrepEdges;  // (< nedge: the grid)
-    const uint32_t ne = min((uint32_t)kPrepEdges, nedge - e_first);
-    const uint32_t np = (27u * ne + 3u) / 4u;
-    const uint4 *src = in + (size_t)blockIdx.x * kPrepPieces;
-    for (uint32_t p = tid; p < np; p += (uint32_t)kPrepEdges) rec4[p] = src[p];
-    __syncthreads();
-    prep_convert(reinterpret_cast<const uint32_t *>(rec4), ne, dst_edges);
-    return ne;
-}
 // The rows of a workgroup's ne edges into their lists' sums (lrows): lane t
 // has the record at rec + 27 t (LDS), the pass's batch edge e_first + t, the
 // working-copy slot slot0 + t.
@@ -4436,15 +3674,6 @@ __global__ void __launch_bounds__(256) k_list_rule(const uint32_t *__restrict__ 
 // The records are read where the handle keeps them (any dword address): the
 // three dwords of a record, 108 bytes apart, as in k_list_rule.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off, 64);
-        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 __global__ void __launch_bounds__(256) k_list_stats(const uint32_t *__restrict__ rec, uint32_t nedge,
                                                     const uint32_t *__restrict__ lscan, uint32_t nlist,
                                                     int32_t height, unsigned long long *__restrict__ erows,
@@ -4566,915 +3795,6 @@ __global__ void __launch_bounds__(256) k_list_most(const uint32_t *__restrict__ 
     if (tid == 0) most[blockIdx.x] = (uint32_t)part[0];
 }
 
-// ---------------------------------------------------------------------------
-// prk_advance_edge_lists: the list DrawModel* leaves in the caller's
-// edge_info array (3654-3869), for a batch of sorted lists and no frame:
-// k_adv_import (k_list_prep's import alone: list o's records at slots
-// lscan[o] ..) -> k_adv_walk (a thread per list) -> k_rec_export of the
-// working copy and k_adv_next of its links.
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(kPrepEdges) k_adv_import(const uint4 *__restrict__ in, uint32_t nedge,
-                                                           ObjEdge *__restrict__ work) {
-    __shared__ uint4 rec4[kPrepPieces];
-    prep_records(in, nedge, rec4, work + (size_t)blockIdx.x * kPrepEdges);
-}
-
-// The whole edge step (3811-3829): every field, whatever the draw's mode
-// reads (obj_step<M> steps only those) -- here the stepped record is the
-// result.  The record's quads that hold no stepped field (row range, Left and
-// link; the colour gradient) are not written back.
-//
-// EM is the walk's emission hook: em.half(right, E) sees the record as it
-// stands on the row, before the step -- one end of the line_render_work
-// DrawModelOptimized(RenderQueue) queues for the pair (3756-3809).  AdvNoEmit
-// (prk_advance_edge_lists) compiles to nothing.  em.row(Row) ends every row
-// the walk does not skip, paired or not: DrawModelOptimizedLines queues one
-// buffer_line_render_work there (3604-3609); only AdvRowEmit listens.
-struct AdvNoEmit {
-    __device__ __forceinline__ void half(bool, const ObjEdge &) const {}
-    __device__ __forceinline__ void pair(int32_t) {}
-    __device__ __forceinline__ void row(int32_t) {}
-};
-// (the arithmetic alone: the thread walk steps the record in device memory,
-// the workgroup walk its LDS state -- one text, so one result)
-__device__ __forceinline__ void adv_step_fields(ObjEdge &E) {
-    E.X += E.G;
-    E.Z += E.ZG;
-    E.C0 += E.CG0; E.C1 += E.CG1; E.C2 += E.CG2; E.C3 += E.CG3;
-    float x = E.N0 + E.NG0, y = E.N1 + E.NG1, z = E.N2 + E.NG2;
-    normalize_rcp(x, y, z);
-    E.N0 = x; E.N1 = y; E.N2 = z;
-    E.U += E.UG;
-    E.V += E.VG;
-    E.W += E.WG;
-}
-template <class EM>
-__device__ __forceinline__ void adv_step(ObjEdge *p, const EM &em, bool right) {
-    PRK_ER(w);
-    PRK_ER_LOAD(w, p);
-    ObjEdge E = PRK_ER_EDGE(w);
-    em.half(right, E);
-    adv_step_fields(E);
-    PRK_ER_FROM(w, E);
-    float4 *d = reinterpret_cast<float4 *>(p);
-    d[0] = w0; d[1] = w1; d[2] = w2; d[3] = w3; d[5] = w5;
-}
-
-// walk_object's sorted branch without the frame: the same insertion cursor,
-// expiry, 3722-3749 removal, pairing with both swaps (P3) and empty-list row
-// skip, no span, every field stepped (adv_step), over the rows
-// [YMin[0], min(max YMax, height)) -- prk_advance_edge_records' rows, no band
-// or target clip.  Under the sorted rule (prk.h) the cursor inserts on every
-// row the edges the reference's whole-list scan inserts, in the same order.
-// The list is walked whole: an edge that expires on the row later edges are
-// inserted on is still linked when they are, and its final Next depends on
-// them (k_obj_seg's split would lose that word).  The records are stepped in
-// place; the links are LK's (GLinks: the records' own Next).  Every pair goes
-// to the emission hook before it is stepped: its two ends (adv_step), then
-// em.pair(Row); em.row(Row) once the row's pairs are through.
-template <class LK, class EM>
-__device__ void adv_walk_list(ObjEdge *E, uint32_t n, int32_t height, const LK lk, EM &em) {
-    const int32_t FirstRow = lk.ymin(0);
-    int32_t MaxRow = lk.ymax(0);
-    for (uint32_t i = 1; i < n; ++i) MaxRow = max(MaxRow, lk.ymax((int)i));
-    const int32_t MaxY = min(MaxRow, height);
-    for (uint32_t i = 0; i < n; ++i) lk.set_next((int)i, -1);  // 4094
-    int32_t Head = -1, Tail = -1;
-    uint32_t ins = 0;        // next sorted edge to insert
-    int32_t nym = FirstRow;  // its YMin (INT32_MAX past the end)
-    for (int32_t Row = FirstRow; Row < MaxY; ++Row) {
-        while (ins < n && nym < Row) nym = ++ins < n ? lk.ymin((int)ins) : INT32_MAX;
-        const uint32_t i0 = ins;
-        while (ins < n && nym == Row) nym = ++ins < n ? lk.ymin((int)ins) : INT32_MAX;
-        for (uint32_t ii = i0; ii < ins; ++ii) {  // insertion 3654-3713
-            const int32_t c = (int32_t)ii;
-            if (Head >= 0) {
-                if (lk.before(c, Head)) {
-                    lk.set_next(c, Head);
-                    Head = c;
-                } else {
-                    int32_t Cmp = Head, Prev = Head;
-                    while (Cmp != Tail) {
-                        Cmp = lk.next(Cmp);
-                        if (lk.before(c, Cmp)) {
-                            lk.set_next(c, Cmp);
-                            lk.set_next(Prev, c);
-                            Cmp = Tail;
-                        } else {
-                            Prev = Cmp;
-                        }
-                    }
-                    if (Prev == Cmp) {
-                        lk.set_next(Tail, c);
-                        Tail = c;
-                    }
-                }
-            } else {
-                Head = c;
-                Tail = c;
-            }
-        }
-        while (Head >= 0 && lk.ymax(Head) <= Row) {  // expiry 3715-3720
-            const int32_t Rm = Head;
-            Head = lk.next(Head);
-            lk.set_next(Rm, -1);
-        }
-        if (Head < 0) {  // pin: the row is skipped, and so are the rows before the next insertion
-            Tail = -1;
-            if (ins >= n) break;
-            Row = max(Row, nym - 1);
-            continue;
-        }
-        {
-            int32_t Prev = Head, Chk = Head;  // 3722-3749
-            while (Chk != Tail) {
-                Chk = lk.next(Chk);
-                if (lk.ymax(Chk) <= Row) {
-                    if (Chk == Tail) {
-                        Tail = Prev;
-                        lk.set_next(Tail, -1);
-                        Chk = Tail;
-                    } else {
-                        lk.set_next(Prev, lk.next(Chk));
-                        Chk = Prev;
-                    }
-                }
-                Prev = Chk;
-            }
-        }
-        int32_t PrevCur = -1, PrevNext = -1;  // pairing 3751-3869
-        int32_t Cur = Head, Next = lk.next(Cur);
-        while (Next >= 0) {
-            adv_step(&E[Cur], em, false);  // 3811-3829
-            adv_step(&E[Next], em, true);
-            em.pair(Row);
-            lk.stepped(Cur);
-            lk.stepped(Next);
-            if (lk.x(Cur) > lk.x(Next)) {  // 3831-3841
-                lk.set_next(Cur, lk.next(Next));
-                lk.set_next(Next, Cur);
-                if (PrevNext >= 0) lk.set_next(PrevNext, Next);
-                else Head = Next;              // P3
-                if (Tail == Next) Tail = Cur;  // P3
-                Cur = Next;
-                Next = lk.next(Cur);
-            }
-            if (PrevNext >= 0) {  // 3843-3853
-                if (lk.x(PrevNext) > lk.x(Cur)) {
-                    lk.set_next(PrevNext, lk.next(Cur));
-                    lk.set_next(Cur, PrevNext);
-                    lk.set_next(PrevCur, Cur);
-                    PrevNext = Cur;
-                    Cur = lk.next(PrevNext);
-                }
-            }
-            PrevCur = Cur;
-            PrevNext = Next;
-            if (lk.next(Next) >= 0) {
-                Cur = lk.next(Next);
-                Next = lk.next(Cur);
-            } else {
-                Next = -1;
-            }
-        }
-        em.row(Row);
-    }
-}
-
-// One thread per list; list o: lscan[o + 1] - lscan[o] edges at work +
-// lscan[o].  The list fields are the records' own (GLinks): k_obj_walk's LDS
-// mirrors of short lists were measured here too and left out (DESIGN
-// §4.4.3).  A list of fewer than two edges pairs nothing: it stays as
-// imported, every Next -1.
-__global__ void __launch_bounds__(kLinkThreads) k_adv_walk(ObjEdge *__restrict__ work,
-                                                           const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                           const uint32_t *__restrict__ route, int32_t height) {
-    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist || (route && route[o])) return;  // (routed: a workgroup walks it, k_adv_walk_wg)
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    if (n < 2) return;
-    AdvNoEmit em;
-    adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
-}
-
-// Each edge's Next, an index within its own list or -1, as one flat array.
-__global__ void __launch_bounds__(256) k_adv_next(const ObjEdge *__restrict__ work, uint32_t total,
-                                                  int32_t *__restrict__ next_out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total) next_out[i] = work[i].Next;
-}
-
-// ---------------------------------------------------------------------------
-// prk_span_records: the line_render_work records DrawModelOptimized
-// (RenderQueue) queues for a list (3756-3809), for the same batches and by
-// the same walk: k_adv_import -> k_span_walk (k_adv_walk with the emission
-// hook: a thread per list, each pair's PairRaw and row into the list's slot
-// range, the list's count) -> prk_scan_u32 of the counts -> k_span_pack (the
-// used slots as packed prk_span).
-// ---------------------------------------------------------------------------
-// The hook: pair k of the list at slot at0 + k, both edges as they stand on
-// the row (six dwordx4 stores) and the row.  STORE = false counts only: no
-// slots, the emission compiled out.  A pair past the list's range is counted
-// and not stored (the host's bound rules it out; k_span_walk reports it).
-template <bool STORE>
-struct AdvSpanEmit {
-    PairRaw *raw;
-    int32_t *prow;  // the pairs' rows
-    uint32_t at, end;
-    __device__ __forceinline__ void half(bool right, const ObjEdge &E) const {
-        if constexpr (STORE) {
-            if (at < end) {
-                float4 *q = reinterpret_cast<float4 *>(raw + at) + (right ? 3 : 0);
-                pair_raw_half(E, q[0], q[1], q[2]);
-            }
-        }
-    }
-    __device__ __forceinline__ void pair(int32_t Row) {
-        if constexpr (STORE) {
-            if (at < end) prow[at] = Row;
-        }
-        ++at;
-    }
-    __device__ __forceinline__ void row(int32_t) {}
-};
-
-// sbase: nlist + 1 values, list o's slots [sbase[o], sbase[o + 1]) --
-// floor(edge-rows / 2) of them: a pair uses up one row of each of two listed
-// edges.  cnt[o]: the list's pairs.  err: set when a list passed its range.
-template <bool STORE>
-__global__ void __launch_bounds__(kLinkThreads) k_span_walk(ObjEdge *__restrict__ work,
-                                                            const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                            const uint32_t *__restrict__ route, int32_t height,
-                                                            const uint32_t *__restrict__ sbase,
-                                                            PairRaw *__restrict__ raw, int32_t *__restrict__ row,
-                                                            uint32_t *__restrict__ cnt, uint32_t *__restrict__ err) {
-    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist || (route && route[o])) return;  // (routed: k_span_walk_wg walks and counts it)
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    uint32_t pairs = 0;
-    if (n >= 2) {
-        const uint32_t s0 = STORE ? sbase[o] : 0u, s1 = STORE ? sbase[o + 1] : 0xFFFFFFFFu;
-        AdvSpanEmit<STORE> em{raw, row, s0, s1};
-        adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
-        pairs = em.at - s0;
-        if (STORE && em.at > s1) {
-            pairs = s1 - s0;
-            atomicOr(err, 1u);
-        }
-    }
-    cnt[o] = pairs;
-}
-
-// The used slots as packed prk_span records (25 dwords: Left, Right, Row;
-// an end is XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3], prk.h).
-// A workgroup takes kPackSpans consecutive packed spans; their 25 * kPackSpans
-// dwords are a 16-byte-aligned stretch of the flat output.  Lane t finds span
-// k's list by a binary search of the scanned counts (cscan: nlist + 1 values,
-// the last = total; the list is the last o with cscan[o] <= k, never an empty
-// one), reads its slot sbase[o] + k - cscan[o] (six dwordx4 and the row) and
-// puts the 25 dwords in prk_span's order into LDS at dword 25 t: the stride is
-// odd, so the 32 lanes of a ds_write_b32 group fall on 32 different banks.
-// Then lane t of pass j stores dwordx4 t + 256 j of the stretch from LDS
-// (ds_read_b128 of consecutive 16-byte slots, 1 KiB contiguous a wave
-// instruction).  `out` holds 25 * total dwords rounded up to four; the last
-// piece's spare dwords are zero.
-constexpr int kPackSpans = 256;
-constexpr uint32_t kPackPieces = 25u * kPackSpans / 4u;
-static_assert(25 * kPackSpans % 4 == 0, "a workgroup's spans start on a 16-byte boundary");
-__global__ void __launch_bounds__(kPackSpans) k_span_pack(const PairRaw *__restrict__ raw,
-                                                          const int32_t *__restrict__ row,
-                                                          const uint32_t *__restrict__ sbase,
-                                                          const uint32_t *__restrict__ cscan, uint32_t nlist,
-                                                          uint32_t total, uint4 *__restrict__ out) {
-    __shared__ uint4 st4[kPackPieces];
-    float *st = reinterpret_cast<float *>(st4);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< total: the grid)
-    const uint32_t ns = min((uint32_t)kPackSpans, total - k0);
-    const uint32_t k = k0 + tid;
-    if (tid < ns) {
-        uint32_t lo = 0, hi = nlist;  // cscan[lo] <= k < cscan[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (cscan[mid] <= k) lo = mid;
-            else hi = mid;
-        }
-        const size_t slot = (size_t)sbase[lo] + (k - cscan[lo]);
-        const PairRaw r = raw[slot];
-        float *d = st + 25u * tid;
-        const float4 q[6] = {r.l0, r.l1, r.l2, r.r0, r.r1, r.r2};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 a = q[3 * h], b = q[3 * h + 1], c = q[3 * h + 2];
-            float *e = d + 12 * h;
-            e[0] = a.x; e[1] = a.y; e[2] = a.z; e[3] = a.w; e[4] = b.x;  // X Z W U V
-            e[5] = c.x; e[6] = c.y; e[7] = c.z; e[8] = c.w;              // MinColor
-            e[9] = b.y; e[10] = b.z; e[11] = b.w;                        // MinNormal
-        }
-        d[24] = __int_as_float(row[slot]);
-    } else if (tid < ns + 1u) {
-        st[25u * ns] = st[25u * ns + 1u] = st[25u * ns + 2u] = 0.0f;  // (the last piece's spare dwords; < 25 * 256)
-    }
-    __syncthreads();
-    const uint32_t np = (25u * ns + 3u) / 4u;
-    uint4 *dst = out + (size_t)blockIdx.x * kPackPieces;
-    for (uint32_t p = tid; p < np; p += (uint32_t)kPackSpans) dst[p] = st4[p];
-}
-
-// ---------------------------------------------------------------------------
-// prk_row_records: the buffer_line_render_work records DrawModelOptimizedLines
-// queues for a list (3509-3609: one a row, RowIndex, EdgeCount and EdgeCount
-// thread_edge_info pairs), by the same walk once more: k_adv_import ->
-// k_row_walk (the pairs as k_span_walk leaves them, and a {row, pairs} record
-// at the end of every row the walk does not skip) -> prk_scan_u32 of the row
-// counts and of the pair counts -> k_row_pack (packed prk_row, packed
-// prk_row_pair).  prk_draw_rows' k_rows_unpack turns such records back into
-// prk_draw_spans' input.
-// ---------------------------------------------------------------------------
-// The reference's ThreadEdges[1000] (3403): a row with more pairs writes past it.
-constexpr uint32_t kRowMaxPairs = 1000u;
-// The hook: the halves as AdvSpanEmit's (pair k of the list at slot at0 + k;
-// the row is not stored with the pair), and row(): {Row, pairs since the last
-// row()} into the list's next row slot.  FILL = false counts only: no slot is
-// addressed.  A pair or a row past the list's range is counted and not stored
-// (the host's bounds rule both out; k_row_walk reports it).  over: a row
-// passed kRowMaxPairs.
-template <bool FILL>
-struct AdvRowEmit {
-    PairRaw *raw;
-    int2 *rows;
-    uint32_t at, end;    // pair slots
-    uint32_t rat, rend;  // row slots
-    uint32_t at_row;     // `at` at the last row()
-    uint32_t over;
-    __device__ __forceinline__ void half(bool right, const ObjEdge &E) const {
-        if constexpr (FILL) {
-            if (at < end) {
-                float4 *q = reinterpret_cast<float4 *>(raw + at) + (right ? 3 : 0);
-                pair_raw_half(E, q[0], q[1], q[2]);
-            }
-        }
-    }
-    __device__ __forceinline__ void pair(int32_t) { ++at; }
-    __device__ __forceinline__ void row(int32_t Row) {
-        const uint32_t k = at - at_row;
-        if constexpr (FILL) {
-            if (rat < rend) rows[rat] = make_int2(Row, (int32_t)k);
-        }
-        ++rat;
-        at_row = at;
-        if (k > kRowMaxPairs) over = 1u;
-    }
-};
-
-// sbase / rbase: nlist + 1 values each, list o's pair slots [sbase[o],
-// sbase[o + 1]) (floor(edge-rows / 2), as k_span_walk's) and row slots
-// [rbase[o], rbase[o + 1]) (the rows of its walk, max(0, min(max YMax, height)
-// - YMin[0])).  pcnt[o], rcnt[o]: the list's pairs and rows.  err bit 0: a
-// list passed a range; bit 1: a row passed kRowMaxPairs pairs.  A one-edge
-// list is walked too: its rows pair nothing and are queued all the same.
-template <bool FILL>
-__global__ void __launch_bounds__(kLinkThreads) k_row_walk(ObjEdge *__restrict__ work,
-                                                           const uint32_t *__restrict__ lscan, uint32_t nlist,
-                                                           const uint32_t *__restrict__ route, int32_t height,
-                                                           const uint32_t *__restrict__ sbase,
-                                                           const uint32_t *__restrict__ rbase,
-                                                           PairRaw *__restrict__ raw, int2 *__restrict__ rows,
-                                                           uint32_t *__restrict__ pcnt, uint32_t *__restrict__ rcnt,
-                                                           uint32_t *__restrict__ err) {
-    const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= nlist || (route && route[o])) return;  // (routed: k_row_walk_wg walks and counts it)
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    uint32_t pairs = 0, nrow = 0;
-    if (n >= 1) {
-        const uint32_t s0 = FILL ? sbase[o] : 0u, s1 = FILL ? sbase[o + 1] : 0xFFFFFFFFu;
-        const uint32_t r0 = FILL ? rbase[o] : 0u, r1 = FILL ? rbase[o + 1] : 0xFFFFFFFFu;
-        AdvRowEmit<FILL> em{raw, rows, s0, s1, r0, r1, s0, 0u};
-        adv_walk_list(work + e0, n, height, GLinks{work + e0}, em);
-        pairs = em.at - s0;
-        nrow = em.rat - r0;
-        uint32_t bits = em.over ? 2u : 0u;
-        if (FILL && (em.at > s1 || em.rat > r1)) {
-            pairs = min(pairs, s1 - s0);
-            nrow = min(nrow, r1 - r0);
-            bits |= 1u;
-        }
-        if (bits) atomicOr(err, bits);
-    }
-    pcnt[o] = pairs;
-    rcnt[o] = nrow;
-}
-
-// The used slots as packed records.  Workgroups [0, npb) pack the pairs,
-// kPackSpans consecutive packed pairs each: lane t finds pair k's list as
-// k_span_pack does (pscan: the scanned pair counts), reads its slot (six
-// dwordx4) and puts the 24 dwords in prk_row_pair's interleaved order into LDS
-// at dword kPairStride t.  24 t would put lanes 0, 4, 8, .. of a ds_write_b32
-// group on one bank (24 t mod 32 takes four values); 25 is odd, so the 32
-// lanes fall on 32 banks.  Then lane t of pass j stores dwordx4 t + 256 j of
-// the workgroup's 24 KiB stretch of the output (1 KiB contiguous a wave
-// instruction, every store 16-byte aligned: 96 bytes are six dwordx4), read
-// from LDS as four dwords -- the odd stride leaves no 16-byte alignment for
-// one ds_read_b128.  The workgroups after them copy the rows, one 8-byte
-// record a lane, from list slots to packed position (rscan: the scanned row
-// counts).
-constexpr uint32_t kPairStride = 25u;
-__global__ void __launch_bounds__(kPackSpans) k_row_pack(const PairRaw *__restrict__ raw,
-                                                         const int2 *__restrict__ rows,
-                                                         const uint32_t *__restrict__ sbase,
-                                                         const uint32_t *__restrict__ rbase,
-                                                         const uint32_t *__restrict__ pscan,
-                                                         const uint32_t *__restrict__ rscan, uint32_t nlist,
-                                                         uint32_t npair, uint32_t nrow, uint32_t npb,
-                                                         uint4 *__restrict__ pairs_out, int2 *__restrict__ rows_out) {
-    __shared__ float st[kPairStride * kPackSpans];
-    const uint32_t tid = threadIdx.x;
-    if (blockIdx.x >= npb) {  // (workgroup-uniform)
-        const uint32_t k = (blockIdx.x - npb) * (uint32_t)kPackSpans + tid;
-        if (k >= nrow) return;
-        uint32_t lo = 0, hi = nlist;  // rscan[lo] <= k < rscan[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (rscan[mid] <= k) lo = mid;
-            else hi = mid;
-        }
-        rows_out[k] = rows[(size_t)rbase[lo] + (k - rscan[lo])];
-        return;
-    }
-    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< npair: npb)
-    const uint32_t ns = min((uint32_t)kPackSpans, npair - k0);
-    const uint32_t k = k0 + tid;
-    if (tid < ns) {
-        uint32_t lo = 0, hi = nlist;  // pscan[lo] <= k < pscan[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (pscan[mid] <= k) lo = mid;
-            else hi = mid;
-        }
-        const PairRaw r = raw[(size_t)sbase[lo] + (k - pscan[lo])];
-        float *d = st + kPairStride * tid;
-        d[0] = r.l0.x; d[1] = r.r0.x;  // XMin
-        d[2] = r.l0.y; d[3] = r.r0.y;  // ZMin
-        d[4] = r.l0.z; d[5] = r.r0.z;  // OneOverZMin
-        d[6] = r.l0.w; d[7] = r.r0.w;  // UMin
-        d[8] = r.l1.x; d[9] = r.r1.x;  // VMin
-        d[10] = r.l2.x; d[11] = r.l2.y; d[12] = r.l2.z; d[13] = r.l2.w;  // LeftMinColor
-        d[14] = r.r2.x; d[15] = r.r2.y; d[16] = r.r2.z; d[17] = r.r2.w;  // RightMinColor
-        d[18] = r.l1.y; d[19] = r.l1.z; d[20] = r.l1.w;                  // LeftMinNormal
-        d[21] = r.r1.y; d[22] = r.r1.z; d[23] = r.r1.w;                  // RightMinNormal
-    }
-    __syncthreads();
-    uint4 *dst = pairs_out + (size_t)k0 * 6u;
-    for (uint32_t p = tid; p < 6u * ns; p += (uint32_t)kPackSpans) {
-        const uint32_t t = p / 6u, q = p - 6u * t;
-        const float *sp = st + kPairStride * t + 4u * q;
-        dst[p] = make_uint4(__float_as_uint(sp[0]), __float_as_uint(sp[1]), __float_as_uint(sp[2]),
-                            __float_as_uint(sp[3]));
-    }
-}
-
-// prk_draw_rows: packed rows and pairs back into prk_draw_spans' records
-// (packed prk_span, 25 dwords).  rows: the caller's prk_row records; rscan:
-// their scanned EdgeCounts (nrow + 1 values, the last = npair).  A workgroup
-// takes kPackSpans consecutive pairs: their 24 KiB come in as dwordx4 (lane t
-// of pass j loads piece t + 256 j) and go to LDS at dword kPairStride * pair +
-// word; lane t then reads pair t's 24 dwords (the odd stride: 32 banks for a
-// group's 32 lanes), finds the pair's row -- the last row r with rscan[r] <=
-// k, never one with EdgeCount 0 -- and writes the span's 25 dwords in prk_span's
-// order over them: dwords [25 t, 25 t + 25) are lane t's alone, in and out.
-// The stretch leaves as k_span_pack's does (`out`: 25 * npair dwords rounded
-// up to four, the spare dwords zero).
-__global__ void __launch_bounds__(kPackSpans) k_rows_unpack(const int2 *__restrict__ rows,
-                                                            const uint32_t *__restrict__ rscan, uint32_t nrow,
-                                                            const uint4 *__restrict__ pairs, uint32_t npair,
-                                                            uint4 *__restrict__ out) {
-    static_assert(kPairStride == 25u, "a pair's LDS stretch holds its span");
-    __shared__ uint4 st4[kPackPieces];
-    float *st = reinterpret_cast<float *>(st4);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t k0 = blockIdx.x * (uint32_t)kPackSpans;  // (< npair: the grid)
-    const uint32_t ns = min((uint32_t)kPackSpans, npair - k0);
-    const uint4 *src = pairs + (size_t)k0 * 6u;
-    for (uint32_t p = tid; p < 6u * ns; p += (uint32_t)kPackSpans) {
-        const uint32_t t = p / 6u, q = p - 6u * t;
-        const uint4 v = src[p];
-        float *sp = st + kPairStride * t + 4u * q;
-        sp[0] = __uint_as_float(v.x); sp[1] = __uint_as_float(v.y);
-        sp[2] = __uint_as_float(v.z); sp[3] = __uint_as_float(v.w);
-    }
-    __syncthreads();
-    if (tid < ns) {
-        const uint32_t k = k0 + tid;
-        uint32_t lo = 0, hi = nrow;  // rscan[lo] <= k < rscan[hi]
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (rscan[mid] <= k) lo = mid;
-            else hi = mid;
-        }
-        float *d = st + kPairStride * tid;
-        float w[24];
-#pragma unroll
-        for (int i = 0; i < 24; ++i) w[i] = d[i];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float *e = d + 12 * h;
-            e[0] = w[0 + h]; e[1] = w[2 + h]; e[2] = w[4 + h]; e[3] = w[6 + h]; e[4] = w[8 + h];  // X Z W U V
-            e[5] = w[10 + 4 * h]; e[6] = w[11 + 4 * h]; e[7] = w[12 + 4 * h]; e[8] = w[13 + 4 * h];  // MinColor
-            e[9] = w[18 + 3 * h]; e[10] = w[19 + 3 * h]; e[11] = w[20 + 3 * h];                      // MinNormal
-        }
-        d[24] = __int_as_float(rows[lo].x);
-    } else if (tid < ns + 1u) {
-        st[25u * ns] = st[25u * ns + 1u] = st[25u * ns + 2u] = 0.0f;  // (the last piece's spare dwords; < 25 * 256)
-    }
-    __syncthreads();
-    const uint32_t np = (25u * ns + 3u) / 4u;
-    uint4 *dst = out + (size_t)blockIdx.x * kPackPieces;
-    for (uint32_t p = tid; p < np; p += (uint32_t)kPackSpans) dst[p] = st4[p];
-}
-// The rows' EdgeCounts as one array for the scan (cnt[nrow] = 0: its total).
-__global__ void __launch_bounds__(256) k_rows_counts(const int2 *__restrict__ rows, uint32_t nrow,
-                                                     uint32_t *__restrict__ cnt) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= nrow) cnt[i] = i < nrow ? (uint32_t)rows[i].y : 0u;
-}
-
-// ---------------------------------------------------------------------------
-// Span handles (prk_spans_*, prk_draw_span_records): packed prk_span records
-// that stay in device memory, drawn from where they are.  One launch per
-// recorded draw: spans [first, first + count) of the handle's buffer `spans`
-// are the pass's objects obj0 .. obj0 + count - 1 (kind 4: one slot each, no
-// other walk takes them) and take the winner ids g0 .. g0 + count - 1.
-//
-// The mirror image of k_span_pack.  A workgroup takes kHandleSpans consecutive
-// spans: their 25 * ns dwords start at dword 25 * (first + j0) of the buffer,
-// which is 16-byte aligned only when first + j0 is a multiple of four (25 = 1
-// mod 4: the stretch starts `lead` = (first + j0) & 3 dwords into its first
-// piece).  Lane t of pass j loads piece t + 256 j of the pieces the stretch
-// touches (dwordx4, 1 KiB contiguous a wave instruction; the leading piece's
-// first `lead` dwords and the trailing piece's spare ones belong to the
-// neighbouring spans, or are the buffer's zero padding: read, never used) into
-// LDS as they are (ds_write_b128 of consecutive slots).  Lane t then reads its
-// span's 25 dwords at dword lead + 25 t: the stride is odd, so the 32 lanes of
-// a ds_read_b32 group fall on 32 different banks.  The buffer holds 25 * total
-// dwords rounded up to four (prk_span_pack's / k_rows_unpack's `out`), so the
-// trailing piece is inside it.
-//
-// From there a lane is k_obj_walk's kind-2 branch: the band and target clip
-// on Row, emit_span<MODE_AVX> with the draw's DRAW_ST and texture into the
-// object's slot, row -1 in a slot no span takes.
-constexpr int kHandleSpans = 256;
-constexpr uint32_t kHandlePieces = 25u * kHandleSpans / 4u + 1u;  // (a stretch that starts inside a piece)
-__global__ void __launch_bounds__(kHandleSpans) k_span_handle_walk(FrameParams fp, uint32_t draw, uint32_t g0,
-                                                                   uint32_t obj0, const uint4 *__restrict__ spans,
-                                                                   uint32_t first, uint32_t count,
-                                                                   const unsigned long long *__restrict__ soff,
-                                                                   SpanRecG *__restrict__ recs,
-                                                                   SpanPos *__restrict__ pos,
-                                                                   uint32_t *__restrict__ span_tri) {
-    __shared__ uint4 st4[kHandlePieces];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t j0 = blockIdx.x * (uint32_t)kHandleSpans;  // (< count: the grid)
-    const uint32_t ns = min((uint32_t)kHandleSpans, count - j0);
-    const unsigned long long w0 = 25ull * ((unsigned long long)first + j0);  // the stretch's first dword
-    const uint32_t lead = (uint32_t)(w0 & 3ull);
-    const uint32_t np = (lead + 25u * ns + 3u) / 4u;  // <= kHandlePieces
-    const uint4 *src = spans + (w0 >> 2);
-    for (uint32_t p = tid; p < np; p += (uint32_t)kHandleSpans) st4[p] = src[p];
-    __syncthreads();
-    if (tid >= ns) return;
-    const float *w = reinterpret_cast<const float *>(st4) + lead + 25u * tid;
-    SpanIn sp;
-    {
-        float v[25];
-#pragma unroll
-        for (int i = 0; i < 25; ++i) v[i] = w[i];
-        static_assert(sizeof(SpanIn) == sizeof(v), "prk_span is 25 dwords");
-        __builtin_memcpy(&sp, v, sizeof(sp));
-    }
-    const DrawRec &d = fp.draws[draw];
-    const bool st = (d.flags & DRAW_ST) != 0;
-    const uint32_t o = obj0 + j0 + tid;
-    const uint32_t base = (uint32_t)soff[o], bound = (uint32_t)(soff[o + 1] - soff[o]);
-    uint32_t used = 0;
-    if (sp.Row >= fp.row0 && sp.Row < fp.row1 && sp.Row < fp.H && bound)
-        used = emit_span<MODE_AVX>(fp, span_end_in(sp.L), span_end_in(sp.R), sp.Row, d, st, g0 + j0 + tid, true, base,
-                                   recs, nullptr, pos, span_tri) ? 1u : 0u;
-    for (uint32_t q = used; q < bound; ++q) pos[base + q] = SpanPos{-1, 0, 0, 0u};
-}
-
-// ---------------------------------------------------------------------------
-// Long lists of the three record calls: one workgroup walks one list, the
-// slot-list walk (walk_rows<M, false>'s row loop: read-ahead window,
-// insert_one_b / insert_batch_b, the expiry compaction, the m == 0 row skip,
-// a pair per thread and both swaps) without a frame -- adv_walk_list's rows
-// [YMin[0], min(max YMax, height)), no band or target clip, every field
-// stepped on the LDS state (adv_step_fields) and the thread walk's emission
-// contract: an edge is seen as it stands on the row, before its step.
-//
-// The records' result.  A slot keeps its edge's sorted index in Next (as
-// walk_rows' CHUNK mode does).  An entry's stepped state goes back to
-// work[sorted index] -- the five quads adv_step stores, and its final Next --
-// when it expires, and for the survivors after the last row.  The ordered
-// array gives the reference's Next: on a row, after its insertions and before
-// the removal, an expiring entry in the leading run of expiring entries gets
-// -1 (the head expiry, 3715-3720); any other expiring entry keeps its
-// successor's sorted index, whether that one expires too or not (3722-3749
-// never writes the removed edge's own pointer); the last entry has -1.  After
-// the last walked row every entry still listed gets its successor's sorted
-// index, the last -1.  Edges never inserted stay as imported (Next -1).
-//
-// The hooks (every member holds the same value in every thread):
-//   half(k, right, E, Row)  thread k, pair k of the row: one end before its step
-//   row(Row, P, lead)       a row that is not skipped, P pairs (0 when one
-//                           edge is listed); lead: the one thread that stores
-// ---------------------------------------------------------------------------
-struct WgNoEmit {
-    __device__ __forceinline__ void half(int, bool, const ObjEdge &, int32_t) const {}
-    __device__ __forceinline__ void row(int32_t, uint32_t, bool) {}
-};
-// Pair k of a row at slot at + k (k_span_pack's layout); the row with it.
-template <bool STORE>
-struct WgSpanEmit {
-    PairRaw *raw;
-    int32_t *prow;
-    uint32_t at, end;
-    __device__ __forceinline__ void half(int k, bool right, const ObjEdge &E, int32_t Row) const {
-        if constexpr (STORE) {
-            const uint32_t j = at + (uint32_t)k;
-            if (j < end) {
-                float4 *q = reinterpret_cast<float4 *>(raw + j) + (right ? 3 : 0);
-                pair_raw_half(E, q[0], q[1], q[2]);
-                if (!right) prow[j] = Row;
-            }
-        }
-    }
-    __device__ __forceinline__ void row(int32_t, uint32_t P, bool) { at += P; }
-};
-// The same pair slots (k_row_pack's layout) and {Row, P} into the next row slot.
-template <bool FILL>
-struct WgRowEmit {
-    PairRaw *raw;
-    int2 *rows;
-    uint32_t at, end;    // pair slots
-    uint32_t rat, rend;  // row slots
-    uint32_t over;
-    __device__ __forceinline__ void half(int k, bool right, const ObjEdge &E, int32_t) const {
-        if constexpr (FILL) {
-            const uint32_t j = at + (uint32_t)k;
-            if (j < end) {
-                float4 *q = reinterpret_cast<float4 *>(raw + j) + (right ? 3 : 0);
-                pair_raw_half(E, q[0], q[1], q[2]);
-            }
-        }
-    }
-    __device__ __forceinline__ void row(int32_t Row, uint32_t P, bool lead) {
-        if constexpr (FILL) {
-            if (lead && rat < rend) rows[rat] = make_int2(Row, (int32_t)P);
-        }
-        ++rat;
-        at += P;
-        // (kept with the hook's contract; out of reach while the largest class
-        // holds 1022 edges, 511 pairs: the 1000-pair rule is the thread walk's to test)
-        if (P > kRowMaxPairs) over = 1u;
-    }
-};
-
-// An entry's state back into its record: the quads adv_step stores, and Next.
-__device__ __forceinline__ void adv_write_back(ObjEdge *__restrict__ dst, const ObjEdge &st, int32_t next) {
-    const float4 *q = reinterpret_cast<const float4 *>(&st);
-    float4 *d = reinterpret_cast<float4 *>(dst);
-    d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3]; d[5] = q[5];
-    dst->Next = next;
-}
-
-// E: the list's n >= 1 records (sorted, as imported); cap: the slot class
-// (>= the most edges listed at once: the host's sweep); blockDim.x ==
-// slot_threads(cap).  Every barrier is reached by the whole workgroup: the
-// loop bounds and the branches around them are values every thread holds
-// alike (Row, MaxY, m, ins, wb, top, k, lt, nanc, P).  A row with more new
-// edges than free slots (never) sets err bit 0 and ends the walk for every
-// thread at once; false then.
-template <class EM>
-__device__ bool adv_walk_rows(ObjEdge *__restrict__ E, uint32_t n, int32_t height, const SlotLds &S, BlockRed &R,
-                              uint32_t cap, EM &em, uint32_t *__restrict__ err) {
-    const int tid = threadIdx.x;
-    const uint32_t NT = blockDim.x;
-    int32_t mr = INT32_MIN;
-    for (uint32_t i = tid; i < n; i += NT) mr = max(mr, E[i].YMax);
-    const int32_t MaxY = min(blk_max(R, mr), height);
-    const int32_t FirstRow = E[0].YMin;
-    for (uint32_t q = tid; q < cap; q += NT) S.fs[q] = (int32_t)q;
-    int top = (int)cap;
-    int m = 0;
-    uint32_t ins = 0;
-    // read-ahead window: thread t holds sorted edge wb + t
-    uint32_t wb = 0;
-    PRK_WIN(wa);
-    PRK_WIN_LOAD(wa, E, wb + (uint32_t)tid, n);
-    PRK_WIN_WAIT();
-    PRK_WIN_LAUNDER(wa);
-    __syncthreads();
-    for (int32_t Row = FirstRow; Row < MaxY; ++Row) {
-        // insertion (3654-3713): the edges with YMin == Row, in sorted order,
-        // a window at a time (batches in order == one at a time)
-        for (;;) {
-            if (ins == wb + NT) {
-                wb += NT;
-                PRK_WIN_LOAD(wa, E, wb + tid, n);
-                PRK_WIN_WAIT();
-                PRK_WIN_LAUNDER(wa);
-            }
-            const float wx = wa0.x, wg = wa0.y;
-            const int32_t wymin = __float_as_int(wa4.x), wl = __float_as_int(wa4.z);
-            const int rel = tid - (int)(ins - wb);
-            const bool eqr = rel >= 0 && wymin == Row;
-            int32_t lt, k, nanc;
-            blk_sum3(R, (rel >= 0 && wymin < Row) ? 1 : 0, eqr ? 1 : 0, (eqr && (wx != wx || wg != wg)) ? 1 : 0, lt,
-                     k, nanc);
-            if (lt) {  // (never: the list is sorted and the walk starts on its first row)
-                ins += (uint32_t)lt;
-                continue;
-            }
-            if (k == 0) break;
-            if (k > top) {  // (never: cap >= the most listed edges)
-                if (tid == 0) atomicOr(err, 1u);
-                return false;
-            }
-            if (rel >= 0 && rel < k) {  // the row's new edges take slots; their keys go to nk*
-                const int32_t slot = S.fs[top - 1 - rel];
-                PRK_WIN_STORE(&S.st[slot], wa);
-                S.st[slot].Next = (int32_t)(ins + (uint32_t)rel);  // (its sorted index)
-                S.nkx[rel] = wx;
-                S.nkg[rel] = wg;
-                S.nkl[rel] = wl;
-                S.nks[rel] = slot;
-            }
-            top -= k;
-            __syncthreads();
-            if (k <= 2 || nanc) {  // one at a time (any NaN key), 3654-3713
-                for (int t = 0; t < k; ++t) insert_one_b(S, R, m, LKey{S.nkx[t], S.nkg[t], S.nkl[t]}, S.nks[t]);
-            } else {
-                insert_batch_b(S, R, m, k);
-            }
-            ins += (uint32_t)k;
-            if (ins < wb + NT) break;  // the row's edges end inside the window
-        }
-        {  // expiry 3715-3749: keep entries with YMax > Row, in order; the others' records and slots
-            int32_t e = 0, se = -1;
-            bool keep = false;
-            if (tid < m) {
-                e = S.idx[tid];
-                keep = !(S.st[e].YMax <= Row);
-                if (tid + 1 < m) se = S.idx[tid + 1];  // (its successor before the removal)
-            }
-            const bool gone = tid < m && !keep;
-            int32_t kp, gp, kt, gt;
-            blk_excl_sum2(R, keep ? 1 : 0, gone ? 1 : 0, kp, gp, kt, gt);
-            if (gone) {  // kp == 0: nothing before it stays, the head expiry
-                const int32_t nx = (kp == 0 || se < 0) ? -1 : S.st[se].Next;
-                adv_write_back(&E[S.st[e].Next], S.st[e], nx);
-                S.fs[top + gp] = e;
-            }
-            if (keep) S.idx[kp] = e;
-            m = kt;
-            top += gt;
-            __syncthreads();
-        }
-        if (m == 0) {  // nothing happens on the rows before the next insertion: go there
-            const int32_t nx = ins < n ? E[ins].YMin : INT32_MAX;
-            Row = max(Row, min(nx, MaxY) - 1);
-            continue;
-        }
-        const int P = m / 2;  // pairing 3751-3869: thread k holds pair k
-        const bool valid = tid < P;
-        int32_t i0 = 0, i1 = 0;
-        float x0 = 0.0f, x1 = 0.0f;
-        if (valid) {
-            i0 = S.idx[2 * tid];
-            i1 = S.idx[2 * tid + 1];
-            ObjEdge a = S.st[i0];  // left edge: its values at the row, then its step (3811-3829)
-            em.half(tid, false, a, Row);
-            adv_step_fields(a);
-            S.st[i0] = a;
-            x0 = a.X;
-            ObjEdge b = S.st[i1];  // right edge
-            em.half(tid, true, b, Row);
-            adv_step_fields(b);
-            S.st[i1] = b;
-            x1 = b.X;
-            if (x0 > x1) {  // 3831-3841
-                const int32_t t = i0; i0 = i1; i1 = t;
-                const float f = x0; x0 = x1; x1 = f;
-            }
-            // pair k's entries after its first swap, for its neighbours
-            S.nb[tid] = i0;
-            S.bk[tid] = __float_as_int(x0);
-            S.aux[tid] = i1;
-            S.bk2[tid] = __float_as_int(x1);
-        }
-        __syncthreads();
-        if (valid) {  // 3843-3853: pair k's first entry against pair k-1's second
-            const bool sw = tid >= 1 && __int_as_float(S.bk2[tid - 1]) > x0;
-            const bool swn = tid + 1 < P && x1 > __int_as_float(S.bk[tid + 1]);  // pair k+1's swap takes my second
-            const int32_t nf = sw ? S.aux[tid - 1] : i0, ns = swn ? S.nb[tid + 1] : i1;
-            i0 = nf;
-            i1 = ns;
-        }
-        __syncthreads();
-        if (valid) {
-            S.idx[2 * tid] = i0;
-            S.idx[2 * tid + 1] = i1;
-        }
-        em.row(Row, (uint32_t)P, tid == 0);
-        __syncthreads();
-    }
-    // the list after the last walked row
-    if (tid < m) {
-        const int32_t e = S.idx[tid];
-        const int32_t nx = tid + 1 < m ? S.st[S.idx[tid + 1]].Next : -1;
-        adv_write_back(&E[S.st[e].Next], S.st[e], nx);
-    }
-    return true;
-}
-
-// lists: the indices of the lists of one slot class (`lcap` entries), one
-// workgroup of slot_threads(lcap) threads each; dynamic LDS slot_lds_bytes(lcap).
-__global__ void __launch_bounds__(kSlotMaxThreads) k_adv_walk_wg(ObjEdge *__restrict__ work,
-                                                                 const uint32_t *__restrict__ lscan,
-                                                                 const uint32_t *__restrict__ lists, uint32_t lcap,
-                                                                 int32_t height, uint32_t *__restrict__ err) {
-    extern __shared__ int32_t lds_list[];
-    __shared__ BlockRed R;
-    const uint32_t o = lists[blockIdx.x];
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    if (n == 0) return;  // (the whole workgroup; the host routes no empty list)
-    SlotLds S;
-    S.carve(lds_list, lcap, blockDim.x);
-    WgNoEmit em;
-    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
-}
-template <bool STORE>
-__global__ void __launch_bounds__(kSlotMaxThreads) k_span_walk_wg(ObjEdge *__restrict__ work,
-                                                                  const uint32_t *__restrict__ lscan,
-                                                                  const uint32_t *__restrict__ lists, uint32_t lcap,
-                                                                  int32_t height, const uint32_t *__restrict__ sbase,
-                                                                  PairRaw *__restrict__ raw, int32_t *__restrict__ row,
-                                                                  uint32_t *__restrict__ cnt,
-                                                                  uint32_t *__restrict__ err) {
-    extern __shared__ int32_t lds_list[];
-    __shared__ BlockRed R;
-    const uint32_t o = lists[blockIdx.x];
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    if (n == 0) return;
-    SlotLds S;
-    S.carve(lds_list, lcap, blockDim.x);
-    const uint32_t s0 = STORE ? sbase[o] : 0u, s1 = STORE ? sbase[o + 1] : 0xFFFFFFFFu;
-    WgSpanEmit<STORE> em{raw, row, s0, s1};
-    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
-    if (threadIdx.x == 0) {
-        uint32_t pairs = em.at - s0;
-        if (STORE && em.at > s1) {
-            pairs = s1 - s0;
-            atomicOr(err, 1u);
-        }
-        cnt[o] = pairs;
-    }
-}
-template <bool FILL>
-__global__ void __launch_bounds__(kSlotMaxThreads) k_row_walk_wg(ObjEdge *__restrict__ work,
-                                                                 const uint32_t *__restrict__ lscan,
-                                                                 const uint32_t *__restrict__ lists, uint32_t lcap,
-                                                                 int32_t height, const uint32_t *__restrict__ sbase,
-                                                                 const uint32_t *__restrict__ rbase,
-                                                                 PairRaw *__restrict__ raw, int2 *__restrict__ rows,
-                                                                 uint32_t *__restrict__ pcnt,
-                                                                 uint32_t *__restrict__ rcnt,
-                                                                 uint32_t *__restrict__ err) {
-    extern __shared__ int32_t lds_list[];
-    __shared__ BlockRed R;
-    const uint32_t o = lists[blockIdx.x];
-    const uint32_t e0 = lscan[o], n = lscan[o + 1] - e0;
-    if (n == 0) return;
-    SlotLds S;
-    S.carve(lds_list, lcap, blockDim.x);
-    const uint32_t s0 = FILL ? sbase[o] : 0u, s1 = FILL ? sbase[o + 1] : 0xFFFFFFFFu;
-    const uint32_t r0 = FILL ? rbase[o] : 0u, r1 = FILL ? rbase[o + 1] : 0xFFFFFFFFu;
-    WgRowEmit<FILL> em{raw, rows, s0, s1, r0, r1, 0u};
-    (void)adv_walk_rows(work + e0, n, height, S, R, lcap, em, err);
-    if (threadIdx.x == 0) {
-        uint32_t pairs = em.at - s0, nrow = em.rat - r0;
-        uint32_t bits = em.over ? 2u : 0u;
-        if (FILL && (em.at > s1 || em.rat > r1)) {
-            pairs = min(pairs, s1 - s0);
-            nrow = min(nrow, r1 - r0);
-            bits |= 1u;
-        }
-        if (bits) atomicOr(err, bits);
-        pcnt[o] = pairs;
-        rcnt[o] = nrow;
-    }
-}
-
 }  // namespace prk
 
 extern "C" {
@@ -5507,177 +3827,6 @@ hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total
     const unsigned long long ndw = 27ull * total, nthr = (ndw + 3) / 4;
     hipLaunchKernelGGL(prk::k_rec_export, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s,
                        reinterpret_cast<const prk::ObjEdge *>(edges), ord, ndw, reinterpret_cast<uint4 *>(out));
-    return hipGetLastError();
-}
-
-// The record calls' thread walks.  `total` packed records (readable up to a
-// multiple of 16 bytes) of a->nlist lists (a->lscan: their first edges) into
-// the working copy a->work, walked over a->height rows there by a thread a
-// list (lists with a route word are left to prk_list_walk_wg).
-//   kind 0, prk_advance_edge_lists: prk_rec_export(work, nullptr, ...) packs
-//     the result, prk_adv_next its links.
-//   kind 1, prk_span_records: the walk with the emission: list o's pairs into
-//     PairRaw slots [sbase[o], sbase[o + 1]) and their rows (prow), its count
-//     into cnt[o]; err |= 1 should a list pass its slots.
-//   kind 2, prk_row_records: the walk with the row emission: list o's pairs
-//     into its PairRaw slots, its row records into row slots [rbase[o],
-//     rbase[o + 1]), its counts into cnt[o] / rcnt[o]; err |= 1 as above, |= 2
-//     when a row holds more than 1000 pairs.
-// raw == nullptr (kinds 1, 2): the counts and err alone (no slots are read or
-// written).
-hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const prk::ListWalkArgs *a, hipStream_t s) {
-    if (kind < 0 || kind > 2) return hipErrorInvalidValue;
-    const uint32_t nlist = a->nlist;
-    if (total == 0 || nlist == 0) return hipSuccess;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
-    hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
-                       dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
-    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
-    if (kind == 0)
-        hipLaunchKernelGGL(prk::k_adv_walk, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height);
-    else if (kind == 1 && pr)
-        hipLaunchKernelGGL(prk::k_span_walk<true>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
-                           a->sbase, pr, a->prow, a->cnt, a->err);
-    else if (kind == 1)
-        hipLaunchKernelGGL(prk::k_span_walk<false>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
-                           a->sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, a->cnt, a->err);
-    else if (pr)
-        hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
-                           a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt, a->rcnt, a->err);
-    else
-        hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
-                           a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt, a->rcnt, a->err);
-    return hipGetLastError();
-}
-// The `total` spans the walk left (cscan: the scanned counts, nlist + 1) as
-// packed prk_span; `out` holds 25 * total dwords rounded up to four.
-hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sbase, const uint32_t *cscan,
-                         uint32_t nlist, uint32_t total, void *out, hipStream_t s) {
-    if (total == 0 || nlist == 0) return hipSuccess;
-    hipLaunchKernelGGL(prk::k_span_pack, dim3((total + prk::kPackSpans - 1) / prk::kPackSpans),
-                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const prk::PairRaw *>(raw), row, sbase, cscan,
-                       nlist, total, reinterpret_cast<uint4 *>(out));
-    return hipGetLastError();
-}
-// The npair pairs and nrow rows the walk left (pscan, rscan: the scanned
-// counts, nlist + 1 each) as packed prk_row_pair and prk_row.
-hipError_t prk_row_pack(const void *raw, const void *rows, const uint32_t *sbase, const uint32_t *rbase,
-                        const uint32_t *pscan, const uint32_t *rscan, uint32_t nlist, uint32_t npair, uint32_t nrow,
-                        void *pairs_out, void *rows_out, hipStream_t s) {
-    if (nlist == 0 || (npair == 0 && nrow == 0)) return hipSuccess;
-    const uint32_t npb = (npair + prk::kPackSpans - 1) / prk::kPackSpans;
-    const uint32_t nrb = (nrow + prk::kPackSpans - 1) / prk::kPackSpans;
-    hipLaunchKernelGGL(prk::k_row_pack, dim3(npb + nrb), dim3(prk::kPackSpans), 0, s,
-                       reinterpret_cast<const prk::PairRaw *>(raw), reinterpret_cast<const int2 *>(rows), sbase, rbase,
-                       pscan, rscan, nlist, npair, nrow, npb, reinterpret_cast<uint4 *>(pairs_out),
-                       reinterpret_cast<int2 *>(rows_out));
-    return hipGetLastError();
-}
-// prk_draw_rows: the rows' EdgeCounts (nrow + 1 words, the last 0) for the
-// scan, and npair packed pairs as packed prk_span (`out`: 25 * npair dwords
-// rounded up to four), each on its row's RowIndex.
-hipError_t prk_rows_counts(const void *rows, uint32_t nrow, uint32_t *cnt, hipStream_t s) {
-    hipLaunchKernelGGL(prk::k_rows_counts, dim3(nrow / 256 + 1), dim3(256), 0, s,
-                       reinterpret_cast<const int2 *>(rows), nrow, cnt);
-    return hipGetLastError();
-}
-hipError_t prk_rows_unpack(const void *rows, const uint32_t *rscan, uint32_t nrow, const void *pairs, uint32_t npair,
-                           void *out, hipStream_t s) {
-    if (nrow == 0 || npair == 0) return hipSuccess;
-    hipLaunchKernelGGL(prk::k_rows_unpack, dim3((npair + prk::kPackSpans - 1) / prk::kPackSpans),
-                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const int2 *>(rows), rscan, nrow,
-                       reinterpret_cast<const uint4 *>(pairs), npair, reinterpret_cast<uint4 *>(out));
-    return hipGetLastError();
-}
-// One prk_draw_span_records draw of the pass: spans [first, first + count) of
-// a handle's packed buffer into the slots of objects obj0 .. (k_span_handle_walk).
-hipError_t prk_span_handle_walk(const prk::FrameParams *fp, uint32_t draw, uint32_t g0, uint32_t obj0,
-                                const void *spans, uint32_t first, uint32_t count, const unsigned long long *soff,
-                                void *recs, void *pos, uint32_t *span_tri, hipStream_t s) {
-    if (count == 0) return hipSuccess;
-    hipLaunchKernelGGL(prk::k_span_handle_walk, dim3((count + prk::kHandleSpans - 1) / prk::kHandleSpans),
-                       dim3(prk::kHandleSpans), 0, s, *fp, draw, g0, obj0, reinterpret_cast<const uint4 *>(spans),
-                       first, count, soff, reinterpret_cast<prk::SpanRecG *>(recs),
-                       reinterpret_cast<prk::SpanPos *>(pos), span_tri);
-    return hipGetLastError();
-}
-hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {
-    if (total == 0) return hipSuccess;
-    hipLaunchKernelGGL(prk::k_adv_next, dim3((total + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjEdge *>(work), total, next_out);
-    return hipGetLastError();
-}
-
-// The record calls' workgroup walk (k_adv_walk_wg, k_span_walk_wg,
-// k_row_walk_wg).  prk_adv_wg_lcap: the largest slot class the current device
-// grants them as dynamic LDS (1022, 510 or 254; 0: none, every list stays on
-// the thread walk).  `route` words: 0 the thread walk, c + 1 slot class c.
-uint32_t prk_adv_wg_lcap(void) {
-    static std::atomic<int> cap[64];  // per device: 0 unknown, else cap + 1
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-    int c = cap[dev].load();
-    if (c == 0) {
-        c = 1;
-        const void *fn[5] = {reinterpret_cast<const void *>(&prk::k_adv_walk_wg),
-                             reinterpret_cast<const void *>(&prk::k_span_walk_wg<true>),
-                             reinterpret_cast<const void *>(&prk::k_span_walk_wg<false>),
-                             reinterpret_cast<const void *>(&prk::k_row_walk_wg<true>),
-                             reinterpret_cast<const void *>(&prk::k_row_walk_wg<false>)};
-        for (uint32_t k = prk::kSlotCapLds; k >= 254; k = (k + 2) / 2 - 2) {
-            const size_t bytes = prk::slot_lds_bytes(k);
-            bool ok = true;
-            for (int q = 0; q < 5 && ok; ++q)
-                ok = hipFuncSetAttribute(fn[q], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-            if (ok) {
-                c = (int)k + 1;
-                break;
-            }
-            (void)hipGetLastError();
-        }
-        cap[dev].store(c);
-    }
-    return (uint32_t)(c - 1);
-}
-// The nl lists lists[0, nl) of slot class lcap, a workgroup each, after the
-// call's import (prk_list_walk, whose thread kernels skip them); kind, a->raw
-// and a->err as there.
-hipError_t prk_list_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint32_t nl,
-                            const prk::ListWalkArgs *a, hipStream_t s) {
-    if (nl == 0) return hipSuccess;
-    if (lcap == 0 || lcap > prk_adv_wg_lcap()) return hipErrorInvalidValue;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
-    const dim3 grid(nl), block(prk::slot_threads(lcap));
-    const size_t bytes = prk::slot_lds_bytes(lcap);
-    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
-    switch (kind) {
-        case 0:
-            hipLaunchKernelGGL(prk::k_adv_walk_wg, grid, block, bytes, s, w, a->lscan, lists, lcap, a->height,
-                               a->err);
-            break;
-        case 1:
-            if (pr)
-                hipLaunchKernelGGL(prk::k_span_walk_wg<true>, grid, block, bytes, s, w, a->lscan, lists, lcap,
-                                   a->height, a->sbase, pr, a->prow, a->cnt, a->err);
-            else
-                hipLaunchKernelGGL(prk::k_span_walk_wg<false>, grid, block, bytes, s, w, a->lscan, lists, lcap,
-                                   a->height, a->sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, a->cnt, a->err);
-            break;
-        case 2:
-            if (pr)
-                hipLaunchKernelGGL(prk::k_row_walk_wg<true>, grid, block, bytes, s, w, a->lscan, lists, lcap,
-                                   a->height, a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt,
-                                   a->rcnt, a->err);
-            else
-                hipLaunchKernelGGL(prk::k_row_walk_wg<false>, grid, block, bytes, s, w, a->lscan, lists, lcap,
-                                   a->height, a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt,
-                                   a->rcnt, a->err);
-            break;
-        default: return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 
@@ -6114,8 +4263,6 @@ hipError_t prk_span_finish(const prk::FrameParams *fp, const void *raw, uint32_t
                        reinterpret_cast<prk::ScSpanRecG *>(srecs), reinterpret_cast<prk::SpanPos *>(pos));
     return hipGetLastError();
 }
-
-
 
 // Span -> tile bin entries, pass 0: tcnt[t] = tile t's entries (ntiles + 1
 // values, the last 0: the scan's total).

@@ -7,7 +7,7 @@ The scene is the soup of test_gpu_span_records.py::test_spans_draw_the_lists_fra
 spans).  Every frame comparison is on bits (same_frame: z as uint32, colours
 equal, winners equal) between the handle route and prk_draw_spans in a
 renderer of its own.  k_span_handle_walk's workgroup is 256 spans
-(prk_spans.hip kHandleSpans): the lengths of test 3 are the issue's.
+(prk_records.hip kHandleSpans): the lengths of test 3 are the issue's.
 """
 import ctypes as C
 

@@ -1,5 +1,5 @@
 """CPU test: the rule by which the workgroup walk of the record calls
-(k_adv_walk_wg, prk_spans.hip) gives every record its final Next.
+(k_adv_walk_wg, prk_records.hip) gives every record its final Next.
 
 That walk keeps a list as an ordered array, not as links, so an edge's Next --
 which the reference leaves in the caller's edge_info memory -- has to be read
