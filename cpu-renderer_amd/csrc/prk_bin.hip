@@ -500,7 +500,7 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_band(FrameParams fp, uint
 // k_bin_band a run's ~260 listed triangles (C3b at N = 8) took two rounds of
 // its four waves, 50 k of its 80 k clocks; here every wave but a run's last
 // is full, and the launch runs on the vis stream beside the band's counting
-// sort (prk_api.hip), which does not read the records.
+// sort (prk_flush.hip), which does not read the records.
 __global__ void __launch_bounds__(64) k_band_rec(FrameParams fp, const uint32_t *__restrict__ runlist,
                                                  const uint32_t *__restrict__ run_n) {
     __shared__ float4 stage[64 * 10];

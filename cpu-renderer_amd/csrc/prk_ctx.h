@@ -1,0 +1,397 @@
+// prk_ctx.h — the host runtime's own header: struct prk_context (opaque in
+// include/prk.h) with the resources and scratch it owns, the state a pass is
+// queued with, and the few host functions that cross the host files
+// (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip).  Host
+// only; prk_launch.h stays the seam to the kernel files, and prk_dist.hip
+// keeps the context opaque.
+//
+// Nothing here reaches the library's dynamic symbol table: the helper types
+// and inline functions sit in a hidden-visibility region (one definition for
+// the four files, none exported), the cross-file functions are declared
+// hidden one by one.  Only prk_context itself keeps default visibility.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "../../include/prk.h"
+#include "prk_device.h"
+#include "prk_launch.h"  // the kernel files' launchers, and what the host shares with them
+
+constexpr uint32_t kObjWaveTris = 48;        // objects of this many triangles or more
+// ... and sorted edge lists (prk_draw_edge_lists) of this many edges or more
+// are large objects: the most edges the smallest large triangle object has
+constexpr uint32_t kObjWaveEdges = 3 * kObjWaveTris;
+constexpr uint64_t kPrMaxEntries = 1ull << 23;  // the chunked walk's list entries per pass (~3 GB of scratch)
+
+// Per-frame scratch sets in flight: a frame whose target band has at most
+// kSmallBandPx pixels (64 Mpx) cycles PRK_FRAME_SETS sets, larger ones 2 (the set
+// count nsets; consecutive frames take consecutive sets): with three, frame k+1's binning need not wait for
+// frame k-1's raster (round 2, band of 512 x 4096 px, one rank of 8: 0.284 ->
+// 0.247 ms; 1024 rows: 0.405 -> 0.378; the whole 4096^2 frame then 1-3 %
+// slower, with the host waiting for every frame's count).
+#ifndef PRK_FRAME_SETS
+#define PRK_FRAME_SETS 3
+#endif
+// Round 3 (lazy bin count): three sets for every target up to 64 Mpx (C5
+// included) — the whole C3b frame 1.049-1.053 -> 1.041-1.044 ms (interleaved
+// A/B, three rounds); round 2 measured three sets 1-3 % slower there when the
+// host waited for every frame's count.
+#ifndef PRK_SMALL_BAND_LOG2
+#define PRK_SMALL_BAND_LOG2 26
+#endif
+constexpr size_t kSmallBandPx = (size_t)1 << PRK_SMALL_BAND_LOG2;
+
+#pragma GCC visibility push(hidden)
+
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        size_t want = bytes + bytes / 4 + 256;
+        hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+struct Geometry {
+    const float *V = nullptr, *C = nullptr, *N = nullptr, *UV = nullptr;
+    uint32_t vertex_count = 0;
+    uint32_t cap[4] = {0, 0, 0, 0};  // owned V / C / N / UV buffers hold this many vertices
+    bool owned = false;
+};
+
+struct Texture {
+    uint8_t *mem = nullptr;
+    int32_t w = 0, h = 0, pitch = 0;
+    int32_t filter = 0;  // PRK_FILTER_*
+};
+
+// A target layer (prk_layer_*): a rectangle of (colour, z) pixels in device
+// memory, the library's (prk_layer_alloc) or the caller's (wrapped: read-only).
+struct Layer {
+    uint8_t *color = nullptr;
+    float *z = nullptr;  // rows of w floats
+    int32_t w = 0, h = 0, pitch = 0;
+    bool wrapped = false, live = false;
+};
+
+// A record batch (prk_records_*): lists in prk_edge_records' packed layout,
+// kept in device memory.  The host keeps each list's edge count and whether
+// it takes the sorted walks (flush_spans routes by them) -- no records.
+struct Records {
+    void *rec = nullptr;      // the packed records, readable up to a multiple of 16 bytes
+    uint32_t *tab = nullptr;  // device: the counts (lists + 1 words, the last 0), then the sorted flags
+    std::vector<uint32_t> cnt, flag;
+    uint64_t total = 0;
+    bool live = false;
+    const uint32_t *d_cnt() const { return tab; }
+    const uint32_t *d_flag() const { return tab + cnt.size() + 1; }
+    const void *at(uint64_t r) const { return static_cast<const char *>(rec) + r * sizeof(prk_edge); }  // record r
+};
+
+// A span batch (prk_spans_*): packed prk_span records kept in device memory.
+// The host keeps each list's span count and the total -- no spans.
+struct SpanBatch {
+    void *sp = nullptr;  // the packed spans, readable up to a multiple of 16 bytes (the spare dwords zero)
+    std::vector<uint32_t> cnt;
+    uint64_t total = 0;
+    bool live = false;
+};
+
+inline int status_of(hipError_t e) {
+    if (e == hipSuccess) return PRK_OK;
+    static const bool trace = std::getenv("PRK_TRACE_HIP") != nullptr;  // diagnostics: name the HIP error
+    if (trace) std::fprintf(stderr, "prk: HIP error %d (%s)\n", (int)e, hipGetErrorName(e));
+    if (e == hipErrorOutOfMemory) return PRK_ERR_NOMEM;
+    return PRK_ERR_DEVICE;
+}
+
+// An exclusive scan, or the objects' radix sort, with its temporary storage
+// in `temp`: the size query, the buffer, the run.
+inline hipError_t scan_u32(DevBuf &temp, const uint32_t *in, uint32_t *out, uint32_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_scan_u32(in, out, n, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_scan_u32(in, out, n, temp.p, &tb, s);
+    return e;
+}
+inline hipError_t scan_u64(DevBuf &temp, const unsigned long long *in, unsigned long long *out, uint32_t n, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_scan_u64(in, out, n, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_scan_u64(in, out, n, temp.p, &tb, s);
+    return e;
+}
+inline hipError_t obj_sort(DevBuf &temp, void *keys_in, uint32_t *vals_in, void *keys_out, uint32_t *vals_out, uint32_t n,
+                    uint32_t end_bit, hipStream_t s) {
+    size_t tb = 0;
+    hipError_t e = prk_obj_sort(keys_in, vals_in, keys_out, vals_out, n, end_bit, nullptr, &tb, s);
+    if (e == hipSuccess) e = temp.ensure(std::max<size_t>(tb, 16));
+    if (e == hipSuccess) e = prk_obj_sort(keys_in, vals_in, keys_out, vals_out, n, end_bit, temp.p, &tb, s);
+    return e;
+}
+
+// The state a pass is queued with and an overflow re-run (resolve_count)
+// runs with again: the target, the tile, the cameras and lights, the clear.
+// The context holds its own as its base (prk_context), so this is the one
+// list of these fields: pass_state() copies them out, apply_pass_state() in.
+struct PassState {
+    // target
+    void *color = nullptr;
+    int32_t pitch = 0;
+    float *zbuf = nullptr;
+    int32_t W = 0, H = 0, row0 = 0, row1 = 0;
+    int32_t tile_w = 256, tile_h = 8;  // measured best for C3b
+    // camera + lights: transform / lights set the draws up (FillEdgeTable's
+    // ProjectVertex and Gouraud lighting), shade_* shade their spans (Phong and
+    // UnprojectVertex, read when DrawModel* runs); prk_set_camera sets both
+    prk_transform transform{};
+    prk_light_data lights{};
+    prk_transform shade_transform{};
+    prk_light_data shade_lights{};
+    bool clear_pending = false;  // prk_target_clear_on_flush
+    uint32_t clear_color = 0;
+    float clear_z = 0.0f;
+    bool debug = false;
+};
+
+#pragma GCC visibility pop
+
+struct prk_context : PassState {  // (the target, tile, cameras, lights, clear and debug flag: PassState)
+    int device = 0;
+    hipStream_t own_stream = nullptr;
+    // prk_geometry_write: copies on copy_stream after read_ev (the end of the
+    // last flush); the next flush's streams wait for in_ev
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t in_ev = nullptr, read_ev = nullptr;
+    bool in_wait = false, read_rec = false;
+    // prk_geometry_transform's tables (scan, runs, matrices): staged in pinned
+    // memory, copied on copy_stream ahead of the kernel; xf_ev: that copy is
+    // done (the next call refills the staging)
+    DevBuf d_xform;
+    void *h_xform = nullptr;
+    size_t h_xform_cap = 0;
+    hipEvent_t xf_ev = nullptr, xf_end_ev = nullptr;  // (timed: prk_debug_transform_ms)
+    bool xf_busy = false;
+    bool owns_target = false;
+    bool have_camera = false;
+    // resources
+    std::vector<Geometry> geoms;
+    std::vector<Texture> texs;
+    // record batches by handle (a destroyed one keeps its slot, dead).  A
+    // prk_draw_records DrawRec: src_kind 4, geom the handle, geom_tri0 /
+    // tri_count its lists, src_off / src_n their records within the handle.
+    std::vector<Records> recs;
+    // span batches by handle, their own number space (a destroyed one keeps
+    // its slot, dead).  A prk_draw_span_records DrawRec: src_kind 5, geom the
+    // handle, src_off / src_n its spans within the handle.
+    std::vector<SpanBatch> sbatches;
+    // target layers by handle, their own number space (a destroyed one keeps
+    // its slot, dead)
+    std::vector<Layer> layers;
+    std::vector<prk::DrawRec> draws;
+    uint32_t pending_tris = 0;
+    std::vector<prk_edge> pend_edges;  // prk_draw_edges input of the pending frame
+    std::vector<prk_span> pend_spans;  // prk_draw_spans input of the pending frame
+    // prk_draw_edge_lists input of the pending frame: the batches' records back
+    // to back, and per list its edge count and whether it takes the sorted
+    // walks (list_walks_sorted).  A batch's DrawRec: src_kind 3, src_off /
+    // src_n its records, geom_tri0 its first list, tri_count its lists.
+    std::vector<prk_edge> pend_ledges;
+    std::vector<uint32_t> pend_lcnt, pend_lflag;
+    // Per-frame scratch, nsets of them in use (2, or PRK_FRAME_SETS for small
+    // bands): frame k bins (and, on span-record frames, runs k_vis) into the
+    // set after frame k-1's on bin_stream while frame k-1 shades on the
+    // flush's stream.
+    struct BinSet {
+        DevBuf d_draws, d_texs, d_tri_draw, d_ranges, d_tri_n, d_tri_off, d_pair_tri, d_keys_a, d_vals_a, d_keys_b,
+            d_bins, d_offs, d_temp, d_won, d_list, d_nwin, d_wtag, d_recs, d_trwon, d_wlist, d_seltemp, d_trec,
+            d_ghist, d_tile_tot, d_chunk, d_info, d_runlist, d_run_n;
+        uint32_t *h_info = nullptr;       // pinned: [entry count, overflow] of the set's last binning
+        hipEvent_t counted_ev = nullptr;  // h_info of this set's binning has landed
+        hipEvent_t listed_ev = nullptr;   // a band frame's run lists are written (k_band_rec may start)
+        // bytes last uploaded into d_draws / d_texs and the buffer they went
+        // to: an unchanged table (every frame of a static scene) is not sent again
+        std::vector<uint8_t> h_draws, h_texs;
+        const void *h_draws_at = nullptr, *h_texs_at = nullptr;
+        hipEvent_t free_ev = nullptr;    // the raster that read this set is done
+        hipEvent_t binned_ev = nullptr;  // this set's binning is done
+        bool used = false;
+    };
+    static constexpr int kSets = PRK_FRAME_SETS;
+    BinSet bset[kSets];
+    hipStream_t bin_stream = nullptr;
+    hipStream_t vis_stream = nullptr;  // k_vis of span-record frames
+    DevBuf d_winners, d_anomaly, d_prof;
+    // z early: the last flush was a span-record pass, whose k_vis writes the
+    // final z (k_pix only the colour): a download takes z from the event after
+    // k_vis (ev[z_slot][3]) while the frame shades.  d_negz counts the -0.0
+    // z k_pix wrote over k_vis's +0.0 since the last download.
+    DevBuf d_negz;
+    bool early_z = false;  // prk_set_early_z
+    bool z_early = false;
+    int z_slot = -1;
+    hipEvent_t s_mark = nullptr;  // flush-stream point the bin stream waits for (prior target contents)
+    uint32_t *h_total = nullptr;  // pinned
+    uint32_t pair_hint = 0;       // entry count of the last frame (counting-sort capacity)
+    // Automatic tile (until prk_set_tile): 256x8, or narrower tiles for frames
+    // with few bin entries per tile (under one wave's 64-entry chunk per
+    // tile: 32x8, C2; under 8: 64x8, C1 — the binning's per-tile passes then
+    // cost more than the extra parallelism gains), decided from a frame's
+    // count at 256x8 and kept while the triangle count and the band stay
+    // within 2x of that frame's (measured, profiles/r02b/small_config_tiles.log).
+    bool tile_auto = true;
+    int32_t auto_small = 0;  // 0: 256x8; else the small tile width (64: under 8 entries per tile, 32: under 64)
+    // Wide tiles: an all-AVX frame whose triangles make >= 4.5 bin entries
+    // each at 256x8 (large triangles: C5's radius-32 soup makes 5.6) draws
+    // faster at 512x8 (C5 3.24 -> 2.97 ms, its band of 8 0.474 -> 0.426 ms;
+    // C3b, 3.2 entries a triangle, is fastest at 256x8: 1.021 vs 1.029 ms;
+    // scalar C3a is slower at 512x8), decided and kept like auto_small.
+    int32_t auto_wide = 0;
+    uint32_t auto_T = 0;
+    int32_t auto_px = 0;
+    // all-AVX frames: per-triangle setup records; the AVX k_vis / k_walk read
+    // them (prk_kernels.hip PRK_SETUP_REC), so they are not optional
+    bool setup_rec = true;
+    bool winners_valid = false;
+    prk_stats stats{};
+    // Timing ring: 6 events per flush.
+    static constexpr int kRing = 32;
+    // bin start, bin end (bin_stream); raster end, k_vis end, k_walk end,
+    // raster start (flush stream)
+    hipEvent_t ev[kRing][6] = {};
+    bool pending[kRing] = {};
+    bool split_span[kRing] = {};  // the slot's flush ran k_walk + k_pix
+    uint32_t frame = 0;
+    int last_slot = -1;
+    int last_set = -1;  // scratch set of the last per-triangle pass
+    // The last per-triangle pass, whose bin entry count the host has not read
+    // yet (flush_tris with `defer`): prk_flush returns once the frame is
+    // queued, and the count is read at the next call that needs it
+    // (resolve_count) — by then the binning has long finished, so the host
+    // no longer waits for every frame's binning before queueing the next
+    // frame.  A pass whose entries overflowed the scratch is re-run there,
+    // before anything else is queued or read, with the state it was queued
+    // with (target, camera, tile, clear).
+    struct PendingCount {
+        bool active = false;
+        int set = 0;
+        hipStream_t s = nullptr;
+        std::vector<prk::DrawRec> draws;
+        uint32_t T = 0, win_base = 0, ntiles = 0;
+        bool fuse = false;  // the pass folded a pending clear in: the re-run's clear_pending
+        PassState state;
+    } pcount;
+    // Span path (whole-object AETs) scratch, reused frame to frame.
+    struct SpanScratch {
+        DevBuf d_stage, d_edges, d_ord, d_temp, d_recs, d_pos, d_span_tri, d_scnt, d_soff, d_vals_b,
+            d_offs, d_nwin, d_wtag, d_srecs, d_work, d_ekeys, d_ekeys2, d_evals, d_ecnt, d_escan,
+            d_rcnt, d_rscan, d_bound, d_oslot, d_pool, d_err, d_raw, d_most, d_cls, d_prrow, d_prcnt, d_preoff,
+            d_prfge, d_prccur, d_prkey, d_prest, d_prsst, d_preend, d_preendm, d_prmatch, d_prsidx, d_prsm, d_prstat,
+            d_segcnt, d_segoff, d_segs, d_wy, d_mhuge, d_objtab, d_k0tab, d_lscan, d_lobj, d_lrows,
+            d_ltab,  // a pass with handle draws: its lists' counts and flags (k_list_tables)
+            d_rectab, d_reccnt, d_recout,  // prk_edge_records: its tables, counts and packed records
+            d_spanout,                     // prk_span_records: its packed spans
+            d_rowslot, d_rowcnt, d_rowscan, d_rowout,  // prk_row_records: its row slots, counts, scan, packed rows
+            d_lstat;  // the record walks of a handle: its lists' statistics, the candidates and their most linked
+        // prk_draw_rows' own buffers (frames in flight use the ones above): the
+        // caller's rows and pairs, the EdgeCounts and their scan, the spans
+        DevBuf d_dr_rows, d_dr_pairs, d_dr_cnt, d_dr_scan, d_dr_temp, d_dr_out;
+        // the pass's host tables, packed into pinned memory for one upload
+        // (stage_ev: that upload, before the staging is rewritten)
+        char *h_stage = nullptr;
+        size_t stage_cap = 0;
+        hipEvent_t stage_ev = nullptr;
+        bool stage_busy = false;
+        // host tables of the pass, kept until their asynchronous uploads ran
+        std::vector<prk::ObjRun> h_runs;
+        std::vector<uint32_t> h_big_gl, h_k1src, h_lcnt;
+        std::vector<prk::PrepSeg> h_segs;     // a pass with handle draws: its batch edges' segments
+        std::vector<prk::ListSrc> h_lsrc;     // ... and the handles its runs take their list tables from
+        size_t last_stage_bytes = 0;     // debug (prk_debug_stage_bytes): the last pass's staging upload
+        std::vector<prk::DrawRec> h_draws;
+        std::vector<prk::TexRec> h_texs;
+        uint32_t *h_rb = nullptr;  // pinned readback words
+        char *h_cls = nullptr;     // pinned: the large objects' most active entries, then their walk groups
+        size_t cls_cap = 0;
+        // debug (prk_debug_walk_routes): the last pass with large objects --
+        // objects per walk class, objects sized by k_maxact_huge_*, and the
+        // first large object's (most, rows, entries) as read back
+        uint32_t walk_routes[9] = {};
+        int32_t walk_sizes[3] = {};
+        // debug (prk_debug_list_routes): the most recent record call's lists
+        // on the thread walk, then in each slot class of the workgroup walk
+        uint32_t list_routes[6] = {};
+    } spans;
+    // debug (prk_debug_bins): the last per-triangle pass of the most recent
+    // flush, if it was queued with the debug flag on -- its scratch set and
+    // the frame sizes its binning ran with
+    struct BinsDebug {
+        bool valid = false, rerun = false;
+        int set = 0;
+        uint32_t T = 0, per = 0;
+        int32_t tile_w = 0, tile_h = 0, tiles_x = 0, tiles_y = 0, row0 = 0, row1 = 0;
+    } bdbg;
+};
+
+#define PRK_HIDDEN __attribute__((visibility("hidden")))
+
+PRK_HIDDEN inline PassState pass_state(const prk_context *c) { return *c; }
+PRK_HIDDEN inline void apply_pass_state(prk_context *c, const PassState &p) { static_cast<PassState &>(*c) = p; }
+
+// The texture table as the kernels read it (FrameParams texs), from the
+// context's textures: one entry a handle.
+PRK_HIDDEN inline void tex_table(const prk_context *c, std::vector<prk::TexRec> &out) {
+    out.resize(c->texs.size());
+    for (size_t i = 0; i < out.size(); ++i)
+        out[i] = prk::TexRec{c->texs[i].mem, c->texs[i].w, c->texs[i].h, c->texs[i].pitch, c->texs[i].filter};
+}
+
+// ---- host functions that cross the host files (each defined once; C linkage
+// and hidden, as prk_resolve_pending in prk_launch.h) -------------------------
+extern "C" {
+// prk_flush.hip
+PRK_HIDDEN int resolve_count(prk_context *c);
+PRK_HIDDEN void frame_params(const prk_context *c, prk::FrameParams &fp);
+PRK_HIDDEN hipError_t launch_fill_target(void *color, int32_t pitch, float *z, int32_t W, int32_t rows,
+                                         uint32_t cval, float zval, hipStream_t s);
+// prk_span_pass.hip
+PRK_HIDDEN int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::DrawRec> &draws, uint32_t T,
+                           uint32_t win_base);
+// prk_api.hip
+PRK_HIDDEN void harvest(prk_context *c, int slot);
+PRK_HIDDEN int draw_src(prk_context *c, uint32_t kind, uint32_t off, uint32_t n, uint32_t ids, int32_t semantics,
+                        int32_t phong, int32_t texture);
+PRK_HIDDEN bool list_walks_sorted(const prk_edge *e, uint32_t n);
+PRK_HIDDEN int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_row_pair *pairs,
+                             uint32_t npair, prk_span *out, void *keep = nullptr);
+}  // extern "C"
+
+// Calls that read or replace the target, or change what a re-run of the
+// pending pass would read, first resolve its count (PendingCount).
+#define RESOLVE_COUNT(c)                             \
+    do {                                             \
+        const int _rc = resolve_count(c);            \
+        if (_rc != PRK_OK) return _rc;               \
+    } while (0)
+
+#define PRK_TRY(expr)                              \
+    do {                                           \
+        hipError_t _e = (expr);                    \
+        if (_e != hipSuccess) return status_of(_e); \
+    } while (0)

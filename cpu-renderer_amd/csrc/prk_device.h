@@ -1059,7 +1059,7 @@ struct RowWalker {
 };
 
 // The chunked walk of large objects (prk_spans.hip k_pr_*): its pass-wide
-// buffers and sizes, set by flush_spans (prk_api.hip).
+// buffers and sizes, set by flush_spans (prk_span_pass.hip).
 struct PrWalkArgs {
     const void *objs;           // ObjDesc[]
     const void *pro;            // PrObj[npr]

@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "../../include/prk.h"
-#include "prk_launch.h"  // prk_resolve_pending (prk_api.hip)
+#include "prk_launch.h"  // prk_resolve_pending (prk_flush.hip)
 
 static_assert(PRK_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "unique id size");
 

@@ -1997,7 +1997,7 @@ __global__ void k_selftest_ops(int32_t op, uint32_t n, const uint32_t *pa, const
 }  // namespace prk
 
 // ---------------------------------------------------------------------------
-// Launchers (called from prk_api.cpp).
+// Launchers (called from prk_flush.hip and prk_api.hip).
 // ---------------------------------------------------------------------------
 extern "C" {
 

@@ -1,5 +1,6 @@
-// prk_launch.h — the seam between the host runtime (prk_api.hip, prk_dist.hip)
-// and the kernel files: every extern "C" launcher and query that one file
+// prk_launch.h — the seam between the host runtime (prk_api.hip, prk_flush.hip,
+// prk_span_pass.hip and prk_record_api.hip, which share the context through
+// prk_ctx.h, and prk_dist.hip, which keeps it opaque) and the kernel files: every extern "C" launcher and query that one file
 // defines and another calls, the structures the host fills and the device
 // reads, and the sizes both sides rely on.  Every file that defines one of
 // the functions includes this header, so a definition that disagrees with its
@@ -46,7 +47,7 @@ struct ListSrc {
 };
 
 // The record calls' walks (prk_list_walk, prk_list_walk_wg): a call's device
-// buffers, set by walk_begin and the run (prk_api.hip).  A kind reads only
+// buffers, set by walk_begin and the run (prk_record_api.hip).  A kind reads only
 // its own: 0 prk_advance_edge_lists (work, lscan, nlist, route, height, err),
 // 1 prk_span_records (+ sbase, raw, prow, cnt), 2 prk_row_records (+ sbase,
 // rbase, raw, rows, cnt, rcnt).  raw == nullptr: the counting variants (no
@@ -80,7 +81,7 @@ constexpr size_t packed_span_bytes(size_t n) { return ((n * 25 + 3) / 4) * 16; }
 }  // namespace prk
 
 extern "C" {
-// ---- prk_api.hip (library-internal) -------------------------------------------
+// ---- prk_flush.hip (library-internal) ------------------------------------------
 // A context's pending frame count, resolved on `stream`.
 __attribute__((visibility("hidden"))) int prk_resolve_pending(prk_context *c, void *stream);
 
@@ -139,7 +140,7 @@ hipError_t prk_scan_u64(const unsigned long long *in, unsigned long long *out, u
 //     to the next multiple of 8 TAKE PART in the order; only the bits above that are ignored.  Every key bit,
 //     ignored or not, arrives unchanged in keys_out.  end_bit = 0: the input order.
 //   * A caller whose order is defined by exactly end_bit bits keeps the bits [end_bit, 8 * ceil(end_bit / 8))
-//     equal in every key it wants ordered that way.  Both callers (prk_api.hip: the object passes and the edge
+//     equal in every key it wants ordered that way.  Both callers (prk_span_pass.hip's object passes, prk_record_api.hip's edge
 //     records) do: a real key is (object, YMin, path) < 2^end_bit, zero above, and its lowest path bit is 0
 //     (prk_spans.hip merge_path: pbits exceeds the recursion's depth); a pad key is all ones, so under either
 //     mask it is larger than every real key and the pads end up last, in input order.

@@ -22,7 +22,7 @@
 //                 fix), stepping the paired edges row by row.  Every pair
 //                 of the pass's rows takes a slot in submission order (object,
 //                 row, pair; k_obj_bound bounds each object's slots).  The
-//                 host (prk_api.hip flush_spans) picks a walk per object:
+//                 host (prk_span_pass.hip flush_spans) picks a walk per object:
 //     thread walk          k_obj_walk: a thread per caller edge list or span,
 //                          and per small triangle object when segments are off
 //                          (PRK_OBJ_SEGMENTS=0).
@@ -128,7 +128,7 @@ __device__ __forceinline__ bool obj_sorted(const ObjDesc &od) { return od.kind =
 // walked by rows, or failed its check (the workgroup walk takes it).
 constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 
-// A run of objects as the host lists them (prk_api.hip ObjRun): a draw of
+// A run of objects as the host lists them (prk_launch.h ObjRun; prk_span_pass.hip plan()): a draw of
 // kind 0 is `count` objects of `per` triangles (the last one shorter), kind 2
 // one object per span, kind 1 one object; k_obj_tables expands them.  A
 // prk_draw_edge_lists batch is one run of kind 3, `count` lists from the
@@ -483,7 +483,7 @@ __device__ void walk_object(const FrameParams &fp, const ObjDesc &od, const Draw
     uint32_t emitted = 0;
     // The slots the walk leaves unused (spans that cover nothing take none)
     // are marked row -1 at the end, binned nowhere: frames without large
-    // objects skip the memset of every slot (prk_api.hip).
+    // objects skip the memset of every slot (prk_span_pass.hip).
     if (n == 0) {
         for (uint32_t q = 0; q < bound; ++q) pos[base + q] = SpanPos{-1, 0, 0, 0u};
         return;
@@ -3648,7 +3648,7 @@ __global__ void __launch_bounds__(256) k_list_rule(const uint32_t *__restrict__ 
 
 // ---------------------------------------------------------------------------
 // The record walks of a handle (prk_records_advance / _spans / _rows): what
-// prk_api.hip's host pass takes from the caller's records -- list_walk_steps,
+// prk_record_api.hip's host pass takes from the caller's records -- list_walk_steps,
 // list_most_listed, the row slots -- from records that are only on the device
 // (DESIGN §4.4.8).  Every list holds the sorted rule (the handle's flag), so
 // within a list YMin is non-decreasing and 0 <= YMin <= YMax; the records

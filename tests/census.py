@@ -4,7 +4,7 @@ and the comb scenes (prk.scenes.comb) the huge-object walk tests render.
 census() restates k_obj_maxact (prk_spans.hip) on the oracle's edge table:
 FirstRow, the rows the walk visits, the most entries listed at once, the
 entries over all rows, and the new edges per row.  The host picks an
-object's walk from these (prk_api.hip: LDS slot classes up to 1022 entries,
+object's walk from these (prk_span_pass.hip: LDS slot classes up to 1022 entries,
 the huge-object walk in LDS up to 9200 entries and below 16000 rows, in
 device memory beyond, one wave when the rows outgrow the histogram), and
 Renderer.walk_routes() reports them as the device counted them.

@@ -3,7 +3,7 @@
 
   stats_formula   the closed forms the device kernels evaluate (k_list_stats,
                   k_list_most), in NumPy;
-  stats_sweep     a literal port of prk_api.hip's list_walk_steps and
+  stats_sweep     a literal port of prk_record_api.hip's list_walk_steps and
                   list_most_listed -- the heap sweeps of the host-input calls
                   -- without their early exits.
 

@@ -4,7 +4,7 @@ GPU test is about, and the oracle renders it as one object.  The figures
 stand here next to the scenes; the GPU tests assert the same properties and
 compare the device's own sizes (Renderer.walk_routes) with the census.
 
-Where a walk's list sizes decide its path (prk_spans.hip, prk_api.hip):
+Where a walk's list sizes decide its path (prk_spans.hip, prk_span_pass.hip):
   new edges on a row  < 1024: one insertion window; == 1024: a full window,
                       then an empty one; > 1024: several
   most                <= 1022: an LDS slot class; <= 9200 (and rows < 16000):

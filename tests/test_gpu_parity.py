@@ -260,7 +260,7 @@ def test_early_z_after_z_writing_frame(gpu, first):
     scalar (k_shade) or whole-object (k_span_shade / k_pix) frame writes z on
     the flush stream, then a fused-clear per-triangle AVX frame writes its z
     in k_vis on the visibility stream.  k_vis must wait for the earlier
-    frame's z writers (prk_api.hip, the vis stream's wait on s_mark), or
+    frame's z writers (prk_flush.hip, the vis stream's wait on s_mark), or
     their late stores land over the new frame's z.  Debug off (debug frames
     always wait).  z, colour bit for bit against early z off and the oracle."""
     a = scenes.random_soup(60000, 512, 384, radius=40, seed=71, textured=True)

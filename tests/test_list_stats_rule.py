@@ -1,6 +1,6 @@
 """CPU test: the closed forms of the per-list walk statistics (what k_list_stats
 and k_list_most evaluate for the handle record walks) against
-literal ports of the host pass's heap sweeps (prk_api.hip list_walk_steps and
+literal ports of the host pass's heap sweeps (prk_record_api.hip list_walk_steps and
 list_most_listed, without their early exits) -- liststats.py holds both.  The
 proof of the formulas by exhaustion; the device is held to the closed forms in
 tests/test_gpu_record_walks.py.

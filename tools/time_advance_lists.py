@@ -103,7 +103,7 @@ WG_OFF = str(1 << 62)
 
 
 def thread_cost(words, counts, height):
-    """The largest list_walk_steps (prk_api.hip) among the lists: edge-rows
+    """The largest list_walk_steps (prk_record_api.hip) among the lists: edge-rows
     plus the insertion scans' bound n (n - 1) / 2 (the exact sweep, where that
     bound would pass the 2^21 cap, only lowers it)."""
     w = words.view(np.int32)
