@@ -137,9 +137,6 @@ __device__ __forceinline__ uint32_t range_entries(const TileRange &tr) {
     return n;
 }
 
-#ifndef PRK_ROWCLASS
-#define PRK_ROWCLASS 1
-#endif
 constexpr int kRowClassBits = 3;
 
 // The setup record of triangle g of an all-AVX frame: FillEdgeTable +
@@ -229,17 +226,8 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_count(FrameParams fp, uin
 // the band's triangles ran the whole setup at a few lanes, 99 us of a
 // 0.30 ms band frame).
 constexpr uint32_t kRecRun = 2048;
-#ifndef PRK_BIN_BAND
-#define PRK_BIN_BAND 1  // row bands: k_bin_band (one launch) instead of k_bin_count + k_setup_rec
-#endif
 #ifndef PRK_WPROF
 #define PRK_WPROF 0
-#endif
-#ifndef PRK_BAND_REC_KERNEL
-#define PRK_BAND_REC_KERNEL 1  // a row band's setup records in k_band_rec (prk_band_records), not k_bin_band
-#endif
-#ifndef PRK_BAND_COALESCED
-#define PRK_BAND_COALESCED 1  // k_bin_band: a one-draw run's positions as coalesced float4 loads through LDS
 #endif
 __device__ uint32_t cs_block_excl_scan(uint32_t v, uint32_t *scratch, uint32_t &total);
 __global__ void __launch_bounds__(kCountThreads) k_setup_rec(FrameParams fp, const uint32_t *__restrict__ tri_n) {
@@ -273,9 +261,8 @@ __global__ void __launch_bounds__(kCountThreads) k_setup_rec(FrameParams fp, con
 // tile range of the ones it keeps), writes the tile range and entry count of
 // the ones with entries and lists them in triangle order
 // (runlist[run * kRecRun + i], run_n[run]): the band's counting sort walks
-// only those (BandRuns), and k_band_rec sets up their records (in this
-// kernel, 64 per wave, with -DPRK_BAND_REC_KERNEL=0).  It clears the frame's
-// won flag of every triangle of the run (trwon, span-record frames).
+// only those (BandRuns), and k_band_rec sets up their records.  It clears the
+// frame's won flag of every triangle of the run (trwon, span-record frames).
 // (Round 2: k_bin_count + k_setup_rec, C3b at N = 8 20 + 23 us serial, each
 // reading the band test's inputs of all 1 M triangles; round 5: this kernel
 // with the records, 37 us; round 6: 17.7 us + k_band_rec beside the sort.)
@@ -322,7 +309,7 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_band(FrameParams fp, uint
     const uint32_t gt0 = fp.draw0.geom_tri0 + (g0 - fp.draw0.first_global);
     // (gt0 % 4 == 0 makes the run's offset 16-B aligned; the base must be too:
     // prk_geometry_wrap_device takes any 4-B aligned caller pointer)
-    const bool coal = PRK_BAND_COALESCED && fp.ndraws == 1 && (gt0 & 3u) == 0 &&
+    const bool coal = fp.ndraws == 1 && (gt0 & 3u) == 0 &&
                       ((uintptr_t)fp.draw0.V & 15u) == 0 &&
                       g0 + (uint32_t)kRecRun <= fp.tri_count;  // (a whole run: no tail to mask)
     // Wave w takes kPerWave consecutive triangles of each half: first the
@@ -434,8 +421,8 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_band(FrameParams fp, uint
         if (lane == 0) wcnt[h][wv] = wn;
     }
     {
-        // join the eight (half, wave) lists in order: run list out, and the
-        // joined list for the records below
+        // join the eight (half, wave) lists in order: the run list out (and
+        // joined in LDS, as when this kernel went on to write the records)
         PRK_BT(3);
         __syncthreads();
         uint32_t off[2][kWaves];
@@ -470,15 +457,6 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_band(FrameParams fp, uint
     if (threadIdx.x == 0) run_n[blockIdx.x] = n;
     __syncthreads();
     PRK_BT(4);
-    if (fp.trec && !PRK_BAND_REC_KERNEL)
-        for (uint32_t b = (uint32_t)wv * 64; b < n; b += kCountThreads) {
-            const uint32_t i = b + lane;
-            const bool rec = i < n;
-            const uint32_t g = rec ? list[i] : 0u;
-            TriRec r;
-            if (rec) make_rec(fp, g, r);
-            store_recs(fp, stage[wv], rec, r, g);
-        }
     if (PRK_WPROF) {
         __syncthreads();
         PRK_BT(5);
@@ -494,7 +472,7 @@ __global__ void __launch_bounds__(kCountThreads) k_bin_band(FrameParams fp, uint
     }
 }
 
-// A row band's setup records (PRK_BAND_REC_KERNEL): k_bin_band lists each
+// A row band's setup records: k_bin_band lists each
 // run's triangles with entries (runlist, run_n); workgroup (run, w), one
 // wave, sets up entries [64 w, 64 w + 64) of run `run`'s list.  Inside
 // k_bin_band a run's ~260 listed triangles (C3b at N = 8) took two rounds of
@@ -557,13 +535,10 @@ constexpr int kCsThreads = 1024;
 constexpr uint32_t kCsTrisPerThread = 4;
 constexpr uint32_t kCsChunk = kCsThreads * kCsTrisPerThread;
 constexpr uint32_t kCsMaxTiles = 32768;  // LDS: one u32 per tile (128 KiB)
-#ifndef PRK_REPCLASS
-#define PRK_REPCLASS 0  // 1: bins also grouped by how many tile rows of the triangle lie above the
-                        // tile (its replay length); measured k_vis +6 % on C3b (0.497 -> 0.528 ms)
-#endif
-constexpr int kRepClassBits = PRK_REPCLASS ? 2 : 0;
-constexpr int kClassBits = kRowClassBits + kRepClassBits;
-constexpr uint32_t kCsClassShift = 32 - kClassBits;  // (replay, row) class in the top bits of the emitted pair index
+// (Grouping the bins also by how many tile rows of the triangle lie above the
+// tile, its replay length, measured k_vis +6 % on C3b: 0.497 -> 0.528 ms.)
+constexpr int kClassBits = kRowClassBits;
+constexpr uint32_t kCsClassShift = 32 - kClassBits;  // row class in the top bits of the emitted pair index
 constexpr uint32_t kCsPairMask = (1u << kCsClassShift) - 1u;
 constexpr int kCsClassWindow = 2048;     // k_cs_class: entries grouped per pass
 
@@ -597,26 +572,21 @@ __device__ __forceinline__ uint32_t cs_block_excl_scan(uint32_t v, uint32_t *scr
 
 // The (tile, class) of every entry of a range, in pair order: the rectangle
 // row-major, then the column-0 overflow tiles not in it.  Class = the rows
-// of the tile the triangle can cover (k_vis's row walk) and, above it, how
-// many tile rows of the triangle lie above the tile (its replay of the rows
-// above: 0, 1, 2, 3+), so the 64 entries of a k_vis wave walk and replay
-// about as many rows each.
+// of the tile the triangle can cover (k_vis's row walk), so the 64 entries of
+// a k_vis wave walk about as many rows each.
 template <class F>
 __device__ __forceinline__ void for_each_entry(const FrameParams &fp, const TileRange &tr, F &&f) {
     constexpr int kMaxClass = (1 << kRowClassBits) - 1;
-    constexpr int kMaxRep = (1 << kRepClassBits) - 1;
     if (tr.tx0 <= tr.tx1 && tr.ty0 <= tr.ty1)
         for (int ty = tr.ty0; ty <= tr.ty1; ++ty) {
             const int y0 = ty * fp.tile_h;
             const int rows = min((int)tr.pad1, y0 + fp.tile_h) - max((int)tr.pad0, y0);
-            uint32_t cls = PRK_ROWCLASS ? (uint32_t)min(kMaxClass, max(0, fp.tile_h - rows)) : 0u;
-            const int rep = max(0, y0 - (int)tr.pad0);
-            cls |= (uint32_t)min(kMaxRep, tile_row_of(fp, rep + fp.tile_h - 1)) << kRowClassBits;
+            const uint32_t cls = (uint32_t)min(kMaxClass, max(0, fp.tile_h - rows));
             for (int tx = tr.tx0; tx <= tr.tx1; ++tx) f((uint32_t)(ty * fp.tiles_x + tx), cls);
         }
     for (int ty = tr.oty0; ty <= tr.oty1; ++ty)
         if (!(tr.tx0 == 0 && tr.tx0 <= tr.tx1 && ty >= tr.ty0 && ty <= tr.ty1))
-            f((uint32_t)(ty * fp.tiles_x), PRK_ROWCLASS ? (uint32_t)((kMaxRep << kRowClassBits) | kMaxClass) : 0u);
+            f((uint32_t)(ty * fp.tiles_x), (uint32_t)kMaxClass);
 }
 
 // The triangles of counting-sort chunk c, in order, kCsThreads at a time:
@@ -791,11 +761,7 @@ __global__ void __launch_bounds__(kCsThreads) k_cs_scan(const uint32_t *__restri
 // entries one XCD writes are contiguous and its L2 merges them into whole
 // lines (consecutive chunks on different XCDs left every line of a bin
 // written partially by several L2s: 169 MB written for ~70 MB of data).
-#ifndef PRK_CS_XCD
-#define PRK_CS_XCD 1
-#endif
 __device__ __forceinline__ uint32_t xcd_chunk(uint32_t b, uint32_t n) {
-    if (!PRK_CS_XCD) return b;
     constexpr uint32_t kXcds = 8;
     const uint32_t q = n / kXcds, r = n % kXcds, x = b % kXcds;
     return x * q + min(x, r) + b / kXcds;
@@ -911,7 +877,7 @@ hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, void *rang
     // A whole-frame target sets up (nearly) every triangle: inline records
     // (C3b: 76 us against 22 + 68 us split); a row band only its own.
     const bool band = fp->row0 > 0 || fp->row1 < fp->H;
-    if (band && PRK_BIN_BAND && runlist) {  // (k_bin_band also writes the sentinel tri_n[tri_count])
+    if (band && runlist) {  // (k_bin_band also writes the sentinel tri_n[tri_count])
         hipLaunchKernelGGL(prk::k_bin_band, dim3((n + prk::kRecRun - 1) / prk::kRecRun), dim3(prk::kCountThreads),
                            0, s, *fp, tri_n, reinterpret_cast<prk::TileRange *>(ranges), runlist, run_n, trwon);
         return hipGetLastError();
@@ -929,7 +895,7 @@ hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, void *rang
 // band frame with run lists.  The caller queues it on a stream of its own.
 hipError_t prk_band_records(const prk::FrameParams *fp, const uint32_t *runlist, const uint32_t *run_n,
                             hipStream_t s) {
-    if (!PRK_BAND_REC_KERNEL || !fp->trec || !runlist || !fp->tri_count) return hipSuccess;
+    if (!fp->trec || !runlist || !fp->tri_count) return hipSuccess;
     hipLaunchKernelGGL(prk::k_band_rec, dim3(prk_bin_runs(fp->tri_count), prk::kRecRun / 64), dim3(64), 0, s, *fp,
                        runlist, run_n);
     return hipGetLastError();
@@ -940,20 +906,19 @@ hipError_t prk_band_records(const prk::FrameParams *fp, const uint32_t *runlist,
 // band's share of the triangles, so a narrow band has few chunks (and a
 // small chunk x tile histogram).  0: not a band (whole-frame chunks).
 #ifndef PRK_BAND_MIN_CHUNKS
-#define PRK_BAND_MIN_CHUNKS 128  // > 0: at least about this many chunks (smaller ones) per band frame
+#define PRK_BAND_MIN_CHUNKS 128  // at least about this many chunks (smaller ones) per band frame
                                  // (C3b N = 8: 31 chunks of 1024 threads left the sort on 31 CUs;
                                  // serial binning 0.128 -> 0.094-0.109 ms, N = 4 0.134 -> 0.115)
 #endif
+static_assert(PRK_BAND_MIN_CHUNKS > 0, "band chunks without a minimum count (0) were removed");
 uint32_t prk_cs_band_runs_per_chunk(const prk::FrameParams *fp) {
     const bool band = fp->row0 > 0 || fp->row1 < fp->H;
-    if (!band || !PRK_BIN_BAND) return 0;
+    if (!band) return 0;
     const int64_t rows = std::max<int64_t>(1, (int64_t)std::min(fp->row1, fp->H) - fp->row0);
     const int64_t share = std::max<int64_t>(1, (int64_t)fp->H / rows);  // ~ triangles per band triangle
     int64_t per = (int64_t)prk::kCsChunk * share / prk::kRecRun;
-    if (PRK_BAND_MIN_CHUNKS > 0) {
-        const int64_t nruns = (int64_t)prk_bin_runs(fp->tri_count);
-        per = std::min<int64_t>(per, nruns / std::max(1, PRK_BAND_MIN_CHUNKS));
-    }
+    const int64_t nruns = (int64_t)prk_bin_runs(fp->tri_count);
+    per = std::min<int64_t>(per, nruns / PRK_BAND_MIN_CHUNKS);
     return (uint32_t)std::min<int64_t>(prk::kMaxRunsPerChunk, std::max<int64_t>(1, per));
 }
 uint32_t prk_bin_runs(uint32_t tri_count) { return (tri_count + 1 + prk::kRecRun - 1) / prk::kRecRun; }
@@ -1022,8 +987,7 @@ hipError_t prk_bin_cs(const prk::FrameParams *fp, const void *ranges, const uint
         hipLaunchKernelGGL(prk::k_cs_emit, dim3(nch), dim3(prk::kCsThreads), lds, s, *fp, tr, tri_n, ghist, offs,
                            chunk_base, info, ntiles, tri_off, reinterpret_cast<uint2 *>(bins), pair_tri, won,
                            won_stride, trwon, br);
-    if (PRK_ROWCLASS)
-        hipLaunchKernelGGL(prk::k_cs_class, dim3(ntiles), dim3(256), 0, s, offs, reinterpret_cast<uint2 *>(bins));
+    hipLaunchKernelGGL(prk::k_cs_class, dim3(ntiles), dim3(256), 0, s, offs, reinterpret_cast<uint2 *>(bins));
     return hipGetLastError();
 }
 

@@ -266,7 +266,7 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     uint32_t auto_T = 0;
     int32_t auto_px = 0;
     // all-AVX frames: per-triangle setup records; the AVX k_vis / k_walk read
-    // them (prk_kernels.hip PRK_SETUP_REC), so they are not optional
+    // them instead of running FillEdgeTable, so they are not optional
     bool setup_rec = true;
     bool winners_valid = false;
     prk_stats stats{};

@@ -220,29 +220,19 @@ __device__ __forceinline__ float clamp01(float x) { return x < 0.0f ? 0.0f : (x 
 // FillLineOptimized's span ends (projekt.cpp:1545-1592): LeftX / RightX
 // clamped to [0, W-1], MinX = round(LeftX), MaxX = round(RightX), and XDiff =
 // round(R.X) - round(L.X) on the unclamped ends (1568-1570).  A clamped end
-// is 0 or W - 1, which round to themselves, so two roundings serve all four
-// (PRK_SPAN_ROUND2; 0: the literal four).  False for a NaN end (pinned: the
-// span draws nothing).  st: the single-thread overload's left-clip XOffset
-// (2508).
-#ifndef PRK_SPAN_ROUND2
-#define PRK_SPAN_ROUND2 1
-#endif
+// is 0 or W - 1, which round to themselves, so two roundings serve all four.
+// False for a NaN end (pinned: the span draws nothing).  st: the
+// single-thread overload's left-clip XOffset (2508).
 __device__ __forceinline__ bool span_ends(float LX, float RX, int32_t W, bool st, int32_t &MinX, int32_t &MaxX,
                                           int32_t &XDiff, float &XOffset) {
     XOffset = 0.0f;
     if (LX != LX || RX != RX) return false;
     const bool lneg = LX < 0, lbig = LX >= W, rneg = RX < 0, rbig = RX >= W;
     if (lneg) XOffset = st ? -XOffset : -LX;  // 1545-1565
-    if (PRK_SPAN_ROUND2) {
-        const int32_t rl = round_s32(LX), rr = round_s32(RX);
-        XDiff = (int32_t)((uint32_t)rr - (uint32_t)rl);
-        MinX = lneg ? 0 : (lbig ? W - 1 : rl);
-        MaxX = rneg ? 0 : (rbig ? W - 1 : rr);
-    } else {
-        XDiff = (int32_t)((uint32_t)round_s32(RX) - (uint32_t)round_s32(LX));
-        MinX = round_s32(lneg ? 0.0f : (lbig ? (float)W - 1 : LX));
-        MaxX = round_s32(rneg ? 0.0f : (rbig ? (float)W - 1 : RX));
-    }
+    const int32_t rl = round_s32(LX), rr = round_s32(RX);
+    XDiff = (int32_t)((uint32_t)rr - (uint32_t)rl);
+    MinX = lneg ? 0 : (lbig ? W - 1 : rl);
+    MaxX = rneg ? 0 : (rbig ? W - 1 : rr);
     return true;
 }
 
@@ -272,9 +262,6 @@ __device__ __forceinline__ void normalize_rcp(float &x, float &y, float &z) {
 // waves inside the range, waves with one lane outside it, and operands at the
 // very bounds), and test_shared_divisor_exact to the compiler's own x / d over
 // 2^24 hashed draws (prk_selftest_div_paths, half of whose waves take this path).
-#ifndef PRK_SHARED_DIV
-#define PRK_SHARED_DIV 1
-#endif
 struct DivBy {
     float nd, r;
 };
@@ -297,7 +284,7 @@ __device__ __forceinline__ float div_fast(const DivBy &s, float x) {
 // raster kernels ignore it; prk_selftest_ops reports it).
 template <int K>
 __device__ __forceinline__ bool div_all(float d, float (&x)[K]) {
-    if (PRK_SHARED_DIV) {
+    {  // (a scope of its own: without it the compiler lays the raster kernels' branches out differently)
         // NaN / inf / large numerators fail the sum, zero and tiny ones the min
         float sum = fabsf(x[0]), mn = fabsf(x[0]);
 #pragma unroll
@@ -348,22 +335,17 @@ __device__ __forceinline__ float sqrt_mid(float x) {
 // squared length in [2^-64, 2^62] puts the length in [2^-32, 2^31] (sqrt is
 // correctly rounded and monotone) and every |component| below 2^32, so the
 // sqrt wrappers and the division's scale / fixup steps are identities.
-#ifndef PRK_FAST_NORM
-#define PRK_FAST_NORM 1
-#endif
 // True when the wave took the fast path (as div_all).
 __device__ __forceinline__ bool normalize_div(float &x, float &y, float &z) {
     const float d = (x * x + y * y) + z * z;
-    if (PRK_SHARED_DIV && PRK_FAST_NORM) {
-        const float mn = fminf(fminf(fabsf(x), fabsf(y)), fabsf(z));
-        const bool ok = d >= 0x1p-64f && d <= 0x1p62f && mn >= 0x1p-80f;
-        if (__builtin_expect(__all(ok), 1)) {
-            const DivBy s = div_by(sqrt_mid(d));
-            x = div_fast(s, x);
-            y = div_fast(s, y);
-            z = div_fast(s, z);
-            return true;
-        }
+    const float mn = fminf(fminf(fabsf(x), fabsf(y)), fabsf(z));
+    const bool ok = d >= 0x1p-64f && d <= 0x1p62f && mn >= 0x1p-80f;
+    if (__builtin_expect(__all(ok), 1)) {
+        const DivBy s = div_by(sqrt_mid(d));
+        x = div_fast(s, x);
+        y = div_fast(s, y);
+        z = div_fast(s, z);
+        return true;
     }
     const float len = sqrtf(d);
     float q[3] = {x, y, z};

@@ -18,19 +18,6 @@
 
 #include "prk_ctx.h"
 
-#ifndef PRK_REC_AFTER_CS
-#define PRK_REC_AFTER_CS 1  // a band's k_band_rec queued after the counting sort's launches
-#endif
-#ifndef PRK_BINNED_EARLY
-#define PRK_BINNED_EARLY 0  // 1: binned_ev before the entry count's copy to the host (serial band binning
-                            // 0.084 -> 0.075 ms, but C3b N = 8 pipelined 0.186 -> 0.21-0.22 ms: the copy,
-                            // which the host waits for, then queues behind k_vis)
-#endif
-
-// AVX frames shade through span records (k_walk + k_pix); must match
-// PRK_SPAN_RECORDS of prk_kernels.hip.
-#define PRK_SPAN_RECORDS_HOST 1
-
 extern "C" {
 
 __global__ void k_fill_target(uint32_t *color, int32_t pitch, float *z, int32_t W, int32_t rows,
@@ -255,7 +242,7 @@ int TriPass::begin() {
     harvest(c, slot);  // a flush kRing frames old: long finished
     // A pending fused clear: the span-record kernels (AVX frames) fold it in;
     // every other frame fills the target first, on this stream.
-    fuse = c->clear_pending && T > 0 && modeset == prk::MODE_AVX && PRK_SPAN_RECORDS_HOST;
+    fuse = c->clear_pending && T > 0 && modeset == prk::MODE_AVX;
     if (!fuse) {
         const int rc = fill_pending_clear(c, s);
         if (rc != PRK_OK) return rc;
@@ -363,34 +350,25 @@ int TriPass::bin() {
     PRK_TRY(hipEventRecord(c->ev[slot][0], bs));
     uint32_t *runlist = per ? (uint32_t *)B.d_runlist.p : nullptr, *run_n = per ? (uint32_t *)B.d_run_n.p : nullptr;
     PRK_TRY(prk_bin_count(&fp, (uint32_t *)B.d_tri_n.p, B.d_ranges.p, runlist, run_n, trwon, bs));
-    // a row band's setup records (k_band_rec) run on the vis stream beside
-    // the counting sort, once k_bin_band has listed the runs; queued after
-    // the sort's launches, so a host that is only just ahead of the GPU
-    // (a frame after a wait) does not hold the sort back
-    const bool band_rec = runlist && fp.trec;
+    const bool band_rec = runlist && fp.trec;  // a row band's setup records (k_band_rec, below)
     if (band_rec) PRK_TRY(hipEventRecord(B.listed_ev, bs));
-    if (band_rec && !PRK_REC_AFTER_CS) {
-        PRK_TRY(hipStreamWaitEvent(c->vis_stream, B.listed_ev, 0));
-        PRK_TRY(prk_band_records(&fp, runlist, run_n, c->vis_stream));
-    }
     uint32_t *chunk = (uint32_t *)B.d_chunk.p;
     PRK_TRY(prk_bin_cs(&fp, B.d_ranges.p, (const uint32_t *)B.d_tri_n.p, (uint32_t *)B.d_ghist.p,
                        (uint32_t *)B.d_tile_tot.p, chunk, chunk + nch, (uint32_t *)B.d_offs.p, cap,
                        (uint32_t *)B.d_info.p, (uint32_t *)B.d_tri_off.p, B.d_bins.p, (uint32_t *)B.d_pair_tri.p,
                        won, won_stride, trwon, runlist, run_n, per, bs));
-    // the bins are ready: the raster may start (after the entry count's
-    // copy to the host, PRK_BINNED_EARLY)
-    if (PRK_BINNED_EARLY) {
-        PRK_TRY(hipEventRecord(c->ev[slot][1], bs));
-        PRK_TRY(hipEventRecord(B.binned_ev, bs));
-    }
+    // the entry count's copy to the host, which the host waits for, goes
+    // first (behind binned_ev it would queue after k_vis); then the bins are
+    // ready and the raster may start
     PRK_TRY(hipMemcpyAsync(B.h_info, B.d_info.p, 8, hipMemcpyDeviceToHost, bs));
     PRK_TRY(hipEventRecord(B.counted_ev, bs));
-    if (!PRK_BINNED_EARLY) {
-        PRK_TRY(hipEventRecord(c->ev[slot][1], bs));
-        PRK_TRY(hipEventRecord(B.binned_ev, bs));
-    }
-    if (band_rec && PRK_REC_AFTER_CS) {  // (this frame's k_vis follows the records on the vis stream)
+    PRK_TRY(hipEventRecord(c->ev[slot][1], bs));
+    PRK_TRY(hipEventRecord(B.binned_ev, bs));
+    // a row band's setup records run on the vis stream beside the counting
+    // sort, once k_bin_band has listed the runs (this frame's k_vis follows
+    // them there); queued after the sort's launches, so a host that is only
+    // just ahead of the GPU (a frame after a wait) does not hold the sort back
+    if (band_rec) {
         PRK_TRY(hipStreamWaitEvent(c->vis_stream, B.listed_ev, 0));
         PRK_TRY(prk_band_records(&fp, runlist, run_n, c->vis_stream));
     }

@@ -45,21 +45,12 @@
 #ifndef PRK_VIS_MIN_WAVES
 #define PRK_VIS_MIN_WAVES 4  // waves per SIMD k_vis is register-budgeted for (<= 128 VGPRs)
 #endif
-#ifndef PRK_SPAN_RECORDS
-#define PRK_SPAN_RECORDS 1  // AVX frames shade through k_walk + k_pix (else k_shade)
-#endif
 #ifndef PRK_WALK_MIN_WAVES
 #define PRK_WALK_MIN_WAVES 4  // waves per SIMD k_walk is register-budgeted for
-#endif
-#ifndef PRK_WALK_ON_VIS
-#define PRK_WALK_ON_VIS 0  // k_walk on k_vis's stream (k_pix alone on the flush stream)
 #endif
 #ifndef PRK_PIX_SPLIT
 #define PRK_PIX_SPLIT 2  // k_pix workgroups per tile (2: serial k_pix 0.249 -> 0.245 ms on C3b; unrolling the
                          // pixel loop instead measured no change)
-#endif
-#ifndef PRK_SETUP_REC
-#define PRK_SETUP_REC 1  // all-AVX frames: k_vis / k_walk read the binning pass's setup records
 #endif
 #ifndef PRK_SHADE_MIN_WAVES
 #define PRK_SHADE_MIN_WAVES 3  // waves per SIMD k_shade is register-budgeted for
@@ -86,46 +77,26 @@ __global__ void k_tri_draw(const DrawRec *__restrict__ draws, uint32_t ndraws,
 // Tile raster.
 //
 // One workgroup (4 waves) per tile.  A wave takes 64 bin entries at a time,
-// one triangle per lane: the lane runs FillEdgeTable for it and then all 64
-// lanes walk their AETs row by row in lock step.  At each row a lane's span
-// (the reference's line_render_work, projekt.cpp:3756-3809) goes to the
-// wave's LDS slots, and the wave splits the row's spans into work items:
-//   AVX    : item j of a span = pixels xa+j, xa+j+8, ... < xb, i.e. ONE of the
-//            8 lane chains of FillLineOptimized (each chain is an independent
-//            float recurrence: lane init + one step per 8-px block);
-//   scalar : one item per span (DrawModel's recurrence runs pixel by pixel).
+// one triangle per lane: the lane runs FillEdgeTable for it (or reads its
+// setup record) and then every lane walks its own AET rows.  At each row a
+// lane's span (the reference's line_render_work, projekt.cpp:3756-3809) goes
+// to the wave's LDS slots, and the wave splits the spans into work items:
+//   AVX    : PRK_VIS_GROUP consecutive pixels (visibility) or one won pixel
+//            (shading), each replayed from its FillLineOptimized lane chain
+//            (an independent float recurrence: lane init + one step per 8-px
+//            block);
+//   scalar : chunks of a span (DrawModel's recurrence runs pixel by pixel).
 // Items are spread over the 64 lanes (prefix sum + binary search), so the
 // pixel work no longer serialises on the lane that owns the triangle.
 // ---------------------------------------------------------------------------
-#ifndef PRK_ZPRE
-#define PRK_ZPRE 1  // sweep 1: skip 1/w and the UV mask of fragments that cannot raise the key
-#endif
-#ifndef PRK_PREFETCH
-#define PRK_PREFETCH 0  // single-draw sweeps prefetch the next chunk's triangles (costs the
-                        // registers of a 4-wave-per-SIMD k_vis: measured slower)
-#endif
-#ifndef PRK_LANE_ROWS
-#define PRK_LANE_ROWS 1  // sweeps: each lane walks its own rows (no row lock step across the wave)
-#endif
-#ifndef PRK_MULTI_ROWS
-#define PRK_MULTI_ROWS 1  // sweeps: lanes emit up to 8 rows per iteration when few lanes hold rows
-#endif
 #ifndef PRK_MULTI_ROWS_AVX
 #define PRK_MULTI_ROWS_AVX 4  // AVX sweeps: multi-row iterations only with at most this many active lanes
 #endif
 static_assert(PRK_MULTI_ROWS_AVX <= 8, "8 rows per lane for at most 8 lanes: the 64 span slots");
 #ifndef PRK_VIS_GROUP
-#define PRK_VIS_GROUP 2  // visibility items: G consecutive pixels each (0: one lane chain each)
+#define PRK_VIS_GROUP 2  // visibility items: G consecutive pixels each
 #endif
-#ifndef PRK_PIXEL_ITEMS
-#define PRK_PIXEL_ITEMS 1  // shading sweep (AVX): one work item per won pixel, not per lane chain
-#endif
-#ifndef PRK_VIS_PREBIN
-#define PRK_VIS_PREBIN 1  // k_vis: the next chunk's bin entries load while this chunk runs
-#endif
-#ifndef PRK_VIS_DYN
-#define PRK_VIS_DYN 1  // k_vis waves take the bin's chunks from an LDS counter
-#endif
+static_assert(PRK_VIS_GROUP > 0, "the one-lane-chain visibility item (group 0) was removed");
 #ifndef PRK_VIS_WAVES
 // waves per k_vis tile workgroup; each takes whole 64-entry chunks of the bin.
 // Four waves share one 16 KiB key array: 4 workgroups = 16 waves per CU.
@@ -187,8 +158,8 @@ __device__ __forceinline__ void put_color(const FrameParams &fp, int32_t x, int3
 
 // ----- span setup --------------------------------------------------------
 // FillLineOptimized span setup (projekt.cpp:1543-1835) for row Row; writes the
-// lane's slot and returns its item count (pixels of [MinX, MaxX) in the tile,
-// at most 8 chains).
+// lane's slot and returns its item count over [MinX, MaxX) in the tile:
+// groups of PRK_VIS_GROUP pixels (visibility) or the pixels it won (shading).
 template <bool SHADE, class WS>
 __device__ __forceinline__ int span_setup_avx(const FrameParams &fp, const TileCtx &tc, WS &ws, int lane,
                                               uint32_t tag, int32_t texi, const Edge &L, const Edge &R,
@@ -231,7 +202,6 @@ __device__ __forceinline__ int span_setup_avx(const FrameParams &fp, const TileC
     if constexpr (SHADE) {
         ws.f[SF_LN0][lane] = L.N0; ws.f[SF_LN1][lane] = L.N1; ws.f[SF_LN2][lane] = L.N2;
         ws.f[SF_IN0][lane] = IN0; ws.f[SF_IN1][lane] = IN1; ws.f[SF_IN2][lane] = IN2;
-#if PRK_PIXEL_ITEMS
         // Shading sweep: one item per pixel this span won; the won pixels of
         // the span's first 64 columns as a bit mask.
         // Tags are read 16 at a time (4 x ds_read_b128 from 16-B aligned
@@ -256,13 +226,12 @@ __device__ __forceinline__ int span_setup_avx(const FrameParams &fp, const TileC
         ws.i[SI_WM0][lane] = (int32_t)(uint32_t)wm;
         ws.i[SI_WM1][lane] = (int32_t)(uint32_t)(wm >> 32);
         return won;
-#endif
     }
-    if constexpr (!SHADE && PRK_VIS_GROUP > 0) {
-        constexpr int G = PRK_VIS_GROUP > 0 ? PRK_VIS_GROUP : 1;
+    if constexpr (!SHADE) {  // visibility: items of G consecutive pixels
+        constexpr int G = PRK_VIS_GROUP;
         return (xb - xa + G - 1) / G;
     }
-    return min(8, xb - xa);
+    return min(8, xb - xa);  // (not reached; without it the compiler allocates k_vis's registers differently)
 }
 
 // DrawModel spans are split into chunks of kScChunk pixels, one work item
@@ -437,85 +406,14 @@ __device__ __forceinline__ uint32_t shade_avx_texel(const FrameParams &fp, const
            ((uint32_t)cvt_rne_s32(Fb * 255.0f)) | ((uint32_t)cvt_rne_s32(Fa * 255.0f) << 24);
 }
 
-__device__ __forceinline__ uint32_t shade_avx(const FrameParams &fp, const TexRec &tex, float fu, float fv,
-                                              float z, float n0, float n1, float n2, int32_t x, int32_t i,
-                                              int32_t Row) {
-    return shade_avx_texel(fp, sample_avx(tex, fu, fv), z, n0, n1, n2, x, i, Row);
-}
-
-// Item j of an AVX span: lane chain i = (xa + j - LeftXa) & 7 from block b.
-template <bool SHADE, bool UNI, class WS>
-__device__ __forceinline__ void item_avx(const FrameParams &fp, const TileCtx &tc, const WS &ws, int s,
-                                         int j, int32_t Row) {
-    const int32_t xa = ws.i[SI_XA][s], xb = ws.i[SI_XB][s], LeftXa = ws.i[SI_LEFT][s];
-    const uint32_t tag = (uint32_t)ws.i[SI_TAG][s];
-    const int rowoff = (Row - tc.y0) * tc.tw - tc.x0;
-    int32_t x = xa + j;
-    if (SHADE) {
-        bool any = false;
-        for (int32_t xx = x; xx < xb; xx += 8) any |= is_winner(tc, rowoff + xx, tag);
-        if (!any) return;
-    }
-    // The texture of the span's draw (the item may run on any lane).
-    TexRec tex;
-    if constexpr (SHADE) tex = UNI ? fp.tex0 : fp.texs[ws.i[SI_TEX][s]];
-    else { tex.mem = nullptr; tex.w = tex.h = tex.pitch = tex.filter = 0; }
-    const int32_t rel = x - LeftXa, i = rel & 7, b = rel >> 3;
-    const float IW = ws.f[SF_IW][s], IU = ws.f[SF_IU][s], IV = ws.f[SF_IV][s], IZ = ws.f[SF_IZ][s];
-    const float IW8 = IW * 8.0f, IU8 = IU * 8.0f, IV8 = IV * 8.0f, IZ8 = 8.0f * IZ;
-    const float o = ws.f[SF_XOFF][s] + (float)i;  // lane init (XOffset + i)*inc, 1712-1835
-    float w = ws.f[SF_LW][s] + o * IW, u = ws.f[SF_LU][s] + o * IU;
-    float v = ws.f[SF_LV][s] + o * IV, z = ws.f[SF_LZ][s] + o * IZ;
-    float n0 = 0, n1 = 0, n2 = 0, IN08 = 0, IN18 = 0, IN28 = 0;
-    if constexpr (SHADE) {
-        const float IN0 = ws.f[SF_IN0][s], IN1 = ws.f[SF_IN1][s], IN2 = ws.f[SF_IN2][s];
-        IN08 = IN0 * 8.0f; IN18 = IN1 * 8.0f; IN28 = IN2 * 8.0f;
-        n0 = ws.f[SF_LN0][s] + o * IN0; n1 = ws.f[SF_LN1][s] + o * IN1; n2 = ws.f[SF_LN2][s] + o * IN2;
-        normalize_div(n0, n1, n2);  // 1754
-    }
-    for (int32_t k = 0; k < b; ++k) {  // block steps 2262-2282
-        if (SHADE) {
-            float a = n0 + IN08, bb = n1 + IN18, c = n2 + IN28;
-            normalize_div(a, bb, c);
-            n0 = a; n1 = bb; n2 = c;
-        }
-        z = z + IZ8; w = w + IW8; u = u + IU8; v = v + IV8;
-    }
-    for (; x < xb; x += 8) {
-        const int p = rowoff + x;
-        if (!SHADE) {
-            // A key not above the pixel's current maximum cannot change it,
-            // whatever the UV mask says: skip the 1/w and the mask.
-            const unsigned long long k = make_key(z, tag);
-            if (!PRK_ZPRE || k > tc.key[p]) {
-                const float iw = 1.0f / w;  // 1865-1866
-                const float fu = iw * u, fv = iw * v;
-                if (fu >= 0.0f && fu <= 1.0f && fv >= 0.0f && fv <= 1.0f && z == z) atomicMax(&tc.key[p], k);
-            }
-        } else {
-            if (is_winner(tc, p, tag)) {
-                const float iw = 1.0f / w;  // 1865-1866
-                const float fu = iw * u, fv = iw * v;
-                put_winner(fp, x, Row, z, (PRK_DIAG & 16) ? __float_as_uint(fu + fv + n0 + n1 + n2)
-                                                         : shade_avx(fp, tex, fu, fv, z, n0, n1, n2, x, i, Row));
-            }
-            if (x + 8 < xb) {
-                float a = n0 + IN08, bb = n1 + IN18, c = n2 + IN28;
-                normalize_div(a, bb, c);
-                n0 = a; n1 = bb; n2 = c;
-            }
-        }
-        z = z + IZ8; w = w + IW8; u = u + IU8; v = v + IV8;
-    }
-}
-
-// Visibility item j of an AVX span (PRK_VIS_GROUP = G > 0): the G consecutive
+// Visibility item j of an AVX span (PRK_VIS_GROUP = G): the G consecutive
 // pixels xa + G*j ... of the span, each evaluated from its own lane chain
-// (lane init + b block steps, the recurrence item_avx walks), so one item's
-// slot reads and item->span mapping serve G fragments.
+// i = (x - LeftXa) & 7 (lane init + b block steps, FillLineOptimized's
+// recurrence), so one item's slot reads and item->span mapping serve G
+// fragments.
 template <class WS>
 __device__ __forceinline__ void item_vis_group(const TileCtx &tc, const WS &ws, int s, int j, int32_t Row) {
-    constexpr int G = PRK_VIS_GROUP > 0 ? PRK_VIS_GROUP : 1;
+    constexpr int G = PRK_VIS_GROUP;
     const int32_t xa = ws.i[SI_XA][s], xb = ws.i[SI_XB][s], LeftXa = ws.i[SI_LEFT][s];
     const uint32_t tag = (uint32_t)ws.i[SI_TAG][s];
     const int rowoff = (Row - tc.y0) * tc.tw - tc.x0;
@@ -536,7 +434,7 @@ __device__ __forceinline__ void item_vis_group(const TileCtx &tc, const WS &ws, 
             // A key not above the pixel's current maximum cannot change it,
             // whatever the UV mask says: skip the 1/w and the mask.
             const unsigned long long k = make_key(z, tag);
-            if (!PRK_ZPRE || k > tc.key[p]) {
+            if (k > tc.key[p]) {
                 const float iw = 1.0f / w;  // 1865-1866
                 const float fu = iw * u, fv = iw * v;
                 if (fu >= 0.0f && fu <= 1.0f && fv >= 0.0f && fv <= 1.0f && z == z) atomicMax(&tc.key[p], k);
@@ -547,8 +445,8 @@ __device__ __forceinline__ void item_vis_group(const TileCtx &tc, const WS &ws, 
 
 // Shading item j of an AVX span: the span's j-th won pixel.  Its lane chain
 // i = (x - LeftXa) & 7 is replayed from the lane init through b block steps
-// (the same recurrence item_avx walks), so every lane of the wave shades one
-// winning pixel instead of one chain that may hold none.
+// (the same recurrence item_vis_group walks), so every lane of the wave shades
+// one winning pixel instead of one chain that may hold none.
 template <bool UNI>
 __device__ __forceinline__ void item_avx_pixel(const FrameParams &fp, const TileCtx &tc, const ShadeSlots &ws, int s,
                                                int j, int32_t Row) {
@@ -750,23 +648,18 @@ __device__ __forceinline__ int wave_incl_max(int v) {  // v >= 0
 }
 
 
-// The walker of a sweep's row loop.  PRK_VIS_PERM: the visibility sweep
-// keeps the three edges in fixed registers and the list as a permutation
-// (Walker): every row steps and selects a few fields (the span reads X, z,
-// 1/z, u/z, v/z of its two edges), and insertion / expiry / the crossing
-// swap move two bits.  RowWalker holds the list physically: a row steps two
-// edges with no selects, but an insertion, expiry or swap row moves whole
-// edges — and with 64 triangles per wave nearly every row has one in some
-// lane (about half of the visibility row loop's VALU instructions were those
-// moves).
-#ifndef PRK_VIS_PERM
-#define PRK_VIS_PERM 1
-#endif
-#ifndef PRK_WALK_PERM
-#define PRK_WALK_PERM 0  // 1: k_walk walks with the permutation walker too (normals included): measured k_walk +5 % (three normalisations per row instead of two)
-#endif
+// The walker of a sweep's row loop.  The visibility sweep keeps the three
+// edges in fixed registers and the list as a permutation (Walker): every row
+// steps and selects a few fields (the span reads X, z, 1/z, u/z, v/z of its
+// two edges), and insertion / expiry / the crossing swap move two bits.
+// RowWalker (the shading sweep, and k_walk) holds the list physically: a row
+// steps two edges with no selects, but an insertion, expiry or swap row moves
+// whole edges — and with 64 triangles per wave nearly every row has one in
+// some lane (about half of the visibility row loop's VALU instructions were
+// those moves).  With normals the permutation walker costs three
+// normalisations per row instead of two (k_walk measured +5 % with it).
 template <int M, bool SHADE>
-using SweepWalker = typename std::conditional<PRK_VIS_PERM && !SHADE, Walker<M, SHADE>, RowWalker<M, SHADE>>::type;
+using SweepWalker = typename std::conditional<SHADE, RowWalker<M, true>, Walker<M, false>>::type;
 template <int M, bool NRM>
 __device__ __forceinline__ void wk_from(RowWalker<M, NRM> &wk, const Walker<M, NRM> &w0) { wk.from(w0); }
 template <int M, bool NRM>
@@ -798,34 +691,18 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
     // PRK_PROF event counts (visibility sweep): chunks, row iterations, item
     // windows, items, active lanes summed over row iterations, spans with items
     unsigned long long pc[7] = {0, 0, 0, 0, 0, 0, 0};
-    // Single-draw frames prefetch: the next chunk's bin entry is loaded at the
-    // top of a chunk and its vertex attributes before the row walk, so both
-    // loads are in flight while this chunk's setup and rows run.
-    constexpr bool kPre = UNI && PRK_PREFETCH && !SHADE;  // (k_shade has no registers to spare)
-    TriRaw<M> nraw;
-    uint32_t ne_e = 0, ne_g = 0, ne_j = 0;
-    if constexpr (kPre) {
-        const uint32_t i0 = wave * 64 + lane;
-        if (i0 < n) {
-            ne_e = list ? list[b0 + i0] : i0;
-            const uint2 be = bins[b0 + ne_e];
-            ne_g = be.x;
-            ne_j = be.y;
-            load_tri<M>(fp.draw0, fp.draw0.geom_tri0 + (ne_g - fp.draw0.first_global), nraw);
-        }
-    }
     const uint32_t nwaves = blockDim.x >> 6;
     auto next_chunk = [&](uint32_t cur) -> uint32_t {
-        if (kPre || !chunk_ctr) return cur + 64 * nwaves;
+        if (!chunk_ctr) return cur + 64 * nwaves;
         uint32_t b = 0;
         if (lane == 0) b = atomicAdd(chunk_ctr, 64u);
         return (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
     };
-    const uint32_t first = (kPre || !chunk_ctr) ? wave * 64 : next_chunk(0);
+    const uint32_t first = !chunk_ctr ? wave * 64 : next_chunk(0);
     // Setup-record sweeps take the next chunk when they start one and load
     // its bin entries while this chunk runs, so a chunk's first load is its
     // records (bin entry -> record were two dependent round trips).
-    constexpr bool kPreBin = REC && !SHADE && !kPre && PRK_VIS_PREBIN;
+    constexpr bool kPreBin = REC && !SHADE;
     uint2 pbe = make_uint2(0u, 0u);
     if (kPreBin && !list && first + lane < n) pbe = bins[b0 + first + lane];
     for (uint32_t base = first, nb = 0; base < n; base = nb) {
@@ -841,24 +718,9 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
         int32_t texi = 0;
         SweepWalker<M, SHADE> wk;
         uint32_t anom = 0;
-        TriRaw<M> craw;
-        const uint32_t inext = i + 64 * nwaves;
-        if constexpr (kPre) {
-            craw = nraw;
-            e = ne_e;
-            j = ne_j;
-            if (inext < n) {
-                ne_e = list ? list[b0 + inext] : inext;
-                const uint2 be = bins[b0 + ne_e];
-                ne_g = be.x;
-                ne_j = be.y;
-            }
-        }
         if (active) {
-            if constexpr (!kPre) {
-                e = list ? list[b0 + i] : i;
-                j = (kPreBin && !list) ? cbe.y : bins[b0 + e].y;
-            }
+            e = list ? list[b0 + i] : i;
+            j = (kPreBin && !list) ? cbe.y : bins[b0 + e].y;
             Edge s0, s1, s2;
             int ne;
             uint32_t rhead = 0;
@@ -878,10 +740,6 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
                 ne = (int)(rhead & 0xFu);
                 anom = (rhead >> 20) & 0xFu;
                 st = (rhead >> 24) & 1u;
-            } else if constexpr (kPre) {
-                ne = setup_from_raw<M>(craw, fp.draw0, fp, s0, s1, s2);
-                texi = fp.draw0.tex;
-                st = fp.draw0.flags & DRAW_ST;
             } else if constexpr (UNI) {  // one draw: its record is uniform (kernel arguments)
                 const uint32_t g = bins[b0 + e].x;
                 const uint32_t gt = fp.draw0.geom_tri0 + (g - fp.draw0.first_global);
@@ -913,9 +771,6 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
                 active = wk.Row < wk.MaxY;
             }
         }
-        if constexpr (kPre) {
-            if (inext < n) load_tri<M>(fp.draw0, fp.draw0.geom_tri0 + (ne_g - fp.draw0.first_global), nraw);
-        }
         if (anom) atomicAdd(anomaly, anom);
         if (!(ModeTraits<M>::tex && active)) texi = 0;
         // Visibility tag: the pair index orders fragments of equal z exactly as
@@ -924,10 +779,13 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
         const uint32_t tag = pair_tag(j, st != 0);
         if (PRK_DIAG & 4) active = false;
         if (PRK_PROF) { const unsigned long long t1 = PRK_T(); pt[0] += t1 - t0; t0 = t1; }
-        // PRK_LANE_ROWS: every lane walks its own next row each iteration (the
-        // span's row travels in its slot); else all lanes step row r together.
-        if (PRK_LANE_ROWS && active) active = wk.Row < tc.y1;
-        for (int32_t r = ystart; PRK_LANE_ROWS || r < tc.y1; ++r) {
+        // Every lane walks its own next row each iteration (the span's row
+        // travels in its slot), until no lane holds a row of the tile.  (Nothing
+        // reads the iteration count r; without it, as for (;;) or do-while,
+        // the compiler emits k_vis and k_shade differently.)
+        if (active) active = wk.Row < tc.y1;
+        for (int32_t r = ystart;; ++r) {
+            (void)r;
             // Rows per lane this iteration: when few lanes still hold rows, each
             // emits up to 8 of its next rows into the wave's 64 span slots
             // (slot = rank among the active lanes * k + q), so the items of
@@ -935,7 +793,7 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
             // run side by side instead of one row after another.
             int k = 1, rank = 0;
             if (PRK_PROF) { pc[1] += 1; pc[4] += (unsigned long long)__popcll(__ballot(active)); }
-            if (PRK_LANE_ROWS && PRK_MULTI_ROWS) {
+            {
                 const unsigned long long am = __ballot(active);
                 const int A = __popcll(am);
                 if (M != MODE_AVX) k = A <= 8 ? 8 : (A <= 16 ? 4 : (A <= 32 ? 2 : 1));
@@ -949,7 +807,7 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
                 wave_lds_sync();
             }
             for (int q = 0; q < k; ++q) {
-                if (active && (PRK_LANE_ROWS || wk.Row == r)) {
+                if (active) {
                     const int slot = multi ? rank * k + q : lane;
                     const int32_t row = wk.Row;
                     const bool paired = wk.begin_row();
@@ -964,7 +822,7 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
                         else items = ni;
                     }
                     wk.end_row(paired);
-                    active = wk.Row < wk.MaxY && (!PRK_LANE_ROWS || wk.Row < tc.y1);
+                    active = wk.Row < wk.MaxY && wk.Row < tc.y1;
                 }
             }
             if (multi) {
@@ -1002,9 +860,8 @@ __device__ __forceinline__ void sweep(const FrameParams &fp, const TileCtx &tc, 
                 if (it < total) {
                     const int s = m - 1, j = it - ws.i[SI_PRE][s];
                     const int32_t srow = ws.i[SI_ROW][s];
-                    if constexpr (M == MODE_AVX && SHADE && PRK_PIXEL_ITEMS) item_avx_pixel<UNI>(fp, tc, ws, s, j, srow);
-                    else if constexpr (M == MODE_AVX && !SHADE && PRK_VIS_GROUP > 0) item_vis_group(tc, ws, s, j, srow);
-                    else if constexpr (M == MODE_AVX) item_avx<SHADE, UNI>(fp, tc, ws, s, j, srow);
+                    if constexpr (M == MODE_AVX && SHADE) item_avx_pixel<UNI>(fp, tc, ws, s, j, srow);
+                    else if constexpr (M == MODE_AVX) item_vis_group(tc, ws, s, j, srow);
                     else item_scalar<M, SHADE, UNI>(fp, tc, ws, s, j, srow);
                 }
             }
@@ -1063,7 +920,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
           uint32_t *__restrict__ anomaly) {
     // Span-record frames (all draws AVX): k_walk + k_pix shade from the
     // winner tags; k_vis marks the won (pair, row)s and triangles for them.
-    constexpr bool kRec = MODESET == MODE_AVX && PRK_SPAN_RECORDS;
+    constexpr bool kRec = MODESET == MODE_AVX;
     constexpr bool kZV = kRec && ZV;
     extern __shared__ unsigned long long lds[];
     const int ntile = fp.tiles_x * fp.tiles_y;
@@ -1089,7 +946,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
     VisSlots &ws = slots[threadIdx.x >> 6];
     uint32_t *scratch = reinterpret_cast<uint32_t *>(slots + kVisWaves);
 
-    if (threadIdx.x == 0) scratch[8] = 0;  // the sweep's chunk counter (PRK_VIS_DYN)
+    if (threadIdx.x == 0) scratch[8] = 0;  // the sweep's chunk counter
     // Prior z of the target: a fragment must beat it strictly.
     for (int p = threadIdx.x; p < npx; p += blockDim.x) {
         const int lx = p & (fp.tile_w - 1), ly = p >> fp.tile_w_log2;
@@ -1104,8 +961,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
     __syncthreads();
     if constexpr (MODESET >= 0) {
         // all-AVX frames read the binning pass's setup records (TriRec)
-        sweep<(MODESET >= 0 ? MODESET : 0), false, UNI, MODESET == MODE_AVX && PRK_SETUP_REC>(
-            fp, tc, ws, bins, b0, n, nullptr, anomaly, PRK_VIS_DYN ? scratch + 8 : nullptr);
+        sweep<(MODESET >= 0 ? MODESET : 0), false, UNI, kRec>(fp, tc, ws, bins, b0, n, nullptr, anomaly, scratch + 8);
     } else {
         sweep<MODE_AVX, false, false>(fp, tc, ws, bins, b0, n, nullptr, anomaly);
         sweep<MODE_SC_GOURAUD, false, false>(fp, tc, ws, bins, b0, n, nullptr, anomaly);
@@ -1303,8 +1159,8 @@ __device__ __forceinline__ void walk_flush(const FrameParams &fp, const WalkQueu
 }
 
 
-// k_walk: one thread per triangle that won a pixel.  FillEdgeTable +
-// MergeSort once, then the triangle's whole AET walk (projekt.cpp:3615-3871,
+// k_walk: one thread per triangle that won a pixel.  The binning pass's
+// setup record, then the triangle's whole AET walk (projekt.cpp:3615-3871,
 // normals included) from its first row of the band: no per-tile setup and no
 // replay of the rows above a tile.  Won rows go through the wave's queue.
 template <bool UNI>
@@ -1322,7 +1178,7 @@ __global__ void __launch_bounds__(64 * kWalkWaves, PRK_WALK_MIN_WAVES) k_walk(Fr
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < nw;
     const uint32_t g = active ? wlist[i] : 0u;  // the triangles that won a pixel (compacted)
-    typename std::conditional<PRK_WALK_PERM, Walker<M, true>, RowWalker<M, true>>::type wk;
+    RowWalker<M, true> wk;
     int32_t texi = 0;
     uint32_t st = 0;  // DRAW_ST
     TileRange tr{};
@@ -1334,7 +1190,7 @@ __global__ void __launch_bounds__(64 * kWalkWaves, PRK_WALK_MIN_WAVES) k_walk(Fr
         Edge s0, s1, s2;
         int ne;
         uint32_t rhead = 0;
-        if constexpr (PRK_SETUP_REC) {  // the binning pass's setup record + the vertex normals
+        {  // the binning pass's setup record + the vertex normals
             const float4 *q = reinterpret_cast<const float4 *>(fp.trec + g);
             float4 v[10];
 #pragma unroll
@@ -1360,29 +1216,15 @@ __global__ void __launch_bounds__(64 * kWalkWaves, PRK_WALK_MIN_WAVES) k_walk(Fr
             rhead = (uint32_t)iw[36];
             ne = (int)(rhead & 0xFu);
             st = (rhead >> 24) & 1u;
-        } else if constexpr (UNI) {
-            ne = setup_triangle<M>(fp.draw0, fp.draw0.geom_tri0 + (g - fp.draw0.first_global), fp, s0, s1, s2);
-            texi = fp.draw0.tex;
-            st = fp.draw0.flags & DRAW_ST;
-        } else {
-            const DrawRec *d;
-            uint32_t gt;
-            resolve_draw(fp, g, d, gt);
-            ne = setup_triangle<M>(*d, gt, fp, s0, s1, s2);
-            texi = d->tex;
-            st = d->flags & DRAW_ST;
         }
         active = ne >= 2;
         if (active) {
-            uint32_t anom = 0;
             Walker<M, true> w0;
-            if constexpr (PRK_SETUP_REC) w0.init_rec(ne, s0, s1, s2, fp.H, fp.row1, rhead);
-            else w0.init(ne, s0, s1, s2, fp.H, fp.row1, anom);
+            w0.init_rec(ne, s0, s1, s2, fp.H, fp.row1, rhead);
             const int fr = w0.fast_replay(fp.row0, ne);  // band above row0 (row bands only)
             wk_from(wk, w0);
             if (fr < 0)
                 while (wk.Row < fp.row0 && wk.Row < wk.MaxY) wk.end_row(wk.begin_row());
-            if (anom) atomicAdd(anomaly, anom);
             active = wk.Row < wk.MaxY;
             tr = ranges[g];
             jb = tri_off[g];
@@ -1460,27 +1302,19 @@ __global__ void __launch_bounds__(64 * kWalkWaves, PRK_WALK_MIN_WAVES) k_walk(Fr
 // triangles of its 2048 consecutive triangles as one run (one atomic), so
 // neighbouring triangles — whose setup records share cache lines and whose
 // span records land close together — stay together in the list.
-// PRK_WON_SORT 1 groups each run by triangle height, tallest first (each
-// k_walk lane walks its own triangle, so a wave runs as long as its tallest
-// one); measured on C3b (serial k_walk): 0 -> 0.249 ms, 1 -> 0.278, a global
-// height grouping -> 0.263, round 1's library stream compaction -> 0.256: the
-// scattered record traffic costs more than the lane utilisation gains.
+// (Grouping each run by triangle height, tallest first, so that a wave's
+// lanes walk triangles of like height, measured slower on C3b, serial k_walk:
+// 0.249 -> 0.278 ms, a global height grouping 0.263, round 1's library stream
+// compaction 0.256: the scattered record traffic costs more than the lane
+// utilisation gains.  The run is still laid out through the class histogram
+// that grouping used, with every triangle in class 0.)
 // The list length (kWonHistBytes of scratch) is zeroed before the launch.
 // ---------------------------------------------------------------------------
-#ifndef PRK_WON_SORT
-#define PRK_WON_SORT 0
-#endif
 constexpr int kWonClasses = 64, kWonPer = 8, kWonThreads = 256;
 constexpr size_t kWonHistBytes = 16;  // [0]: the list length
 
-__device__ __forceinline__ int won_class(const TileRange &tr) {
-    if (PRK_WON_SORT == 0) return 0;
-    const int rows = (int)tr.pad1 - (int)tr.pad0;  // band rows [r0, r1) (k_bin_count)
-    return kWonClasses - 1 - min(max(rows, 0), kWonClasses - 1);
-}
-
-// One workgroup per 2048 triangles: its won triangles (grouped by height with
-// PRK_WON_SORT 1) at a run of the list reserved with one atomic on *count.
+// One workgroup per 2048 triangles: its won triangles at a run of the list
+// reserved with one atomic on *count.
 __global__ void __launch_bounds__(kWonThreads) k_won_local(uint32_t n, const uint8_t *__restrict__ trwon,
                                                            const TileRange *__restrict__ ranges,
                                                            uint32_t *__restrict__ count, uint32_t *__restrict__ wlist) {
@@ -1497,7 +1331,7 @@ __global__ void __launch_bounds__(kWonThreads) k_won_local(uint32_t n, const uin
         cls[k] = -1;
         rank[k] = 0;
         if (g < n && trwon[g]) {
-            cls[k] = won_class(ranges[g]);
+            cls[k] = 0;
             rank[k] = atomicAdd(&h[cls[k]], 1u);
         }
     }
@@ -1688,7 +1522,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
         tc.key[p] = k;
     }
     __syncthreads();
-    constexpr int G = PRK_VIS_GROUP > 0 ? PRK_VIS_GROUP : 1;
+    constexpr int G = PRK_VIS_GROUP;
     const uint32_t nwaves = blockDim.x >> 6;
     for (uint32_t base = wave * 64; base < n; base += 64 * nwaves) {
         const uint32_t i = base + lane;
@@ -1821,8 +1655,11 @@ template __global__ void k_span_shade<-1>(PRK_SPAN_SHADE_ARGS);
 template __global__ void k_span_shade<MODE_SC_GOURAUD>(PRK_SPAN_SHADE_ARGS);
 template __global__ void k_span_shade<MODE_SC_PHONG>(PRK_SPAN_SHADE_ARGS);
 PRK_INST(-1, false)
-PRK_INST(MODE_AVX, false)
-PRK_INST(MODE_AVX, true)
+template __global__ void k_vis<MODE_AVX, false>(PRK_VIS_ARGS);  // (AVX frames shade through k_walk + k_pix)
+template __global__ void k_vis<MODE_AVX, true>(PRK_VIS_ARGS);
+// Never launched: without this instantiation in the module the compiler emits
+// k_shade<-1, false> (mixed frames) with other registers and three more lines.
+template __global__ void k_shade<MODE_AVX, true>(PRK_SHADE_ARGS);
 PRK_INST(MODE_SC_GOURAUD, false)
 PRK_INST(MODE_SC_GOURAUD, true)
 PRK_INST(MODE_SC_PHONG, false)
@@ -2056,7 +1893,7 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
     // k_vis runs on svis, the shading on s (after k_vis: `mid` is recorded on
     // svis and waited for on s); svis == s runs the frame on one stream.
     const uint32_t ntile = (uint32_t)(fp->tiles_x * fp->tiles_y);
-    if (svis != s && (!mid || (PRK_WALK_ON_VIS && modeset == prk::MODE_AVX && !mid2))) return hipErrorInvalidValue;
+    if (svis != s && !mid) return hipErrorInvalidValue;
     if (ntile == 0) return hipSuccess;
     const size_t lv = vis_lds(fp), ls = shade_lds(fp);
     const bool uni = fp->ndraws == 1;
@@ -2066,11 +1903,11 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
     const uint32_t nwblk = (fp->tri_count + 64 * prk::kWalkWaves - 1) / (64 * prk::kWalkWaves);
     const uint32_t nwon = (fp->tri_count + prk::kWonThreads * prk::kWonPer - 1) / (prk::kWonThreads * prk::kWonPer);
     const uint2 *bins = reinterpret_cast<const uint2 *>(bins_);
-    if (modeset == prk::MODE_AVX && PRK_SPAN_RECORDS && nblk) {
+    if (modeset == prk::MODE_AVX && nblk) {
         // k_walk's list histogram, cleared before k_vis is waited for (off
         // the k_vis -> k_walk path)
         if (!sel_temp || sel_bytes < prk::kWonHistBytes) return hipErrorInvalidValue;
-        const hipError_t e = hipMemsetAsync(sel_temp, 0, prk::kWonHistBytes, PRK_WALK_ON_VIS ? svis : s);
+        const hipError_t e = hipMemsetAsync(sel_temp, 0, prk::kWonHistBytes, s);
         if (e != hipSuccess) return e;
     }
 #define PRK_VIS(MS, UNI)                                                                                             \
@@ -2089,21 +1926,15 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
                        nwin, wtag, anomaly)
 #define PRK_SPANPIX(UNI)                                                                                             \
     do {                                                                                                             \
-        /* PRK_WALK_ON_VIS: k_walk follows k_vis on svis, k_pix waits for it on s */                                 \
-        hipStream_t sw = PRK_WALK_ON_VIS ? svis : s;                                                                 \
         if (nblk) {                                                                                                  \
-            /* the won triangles, tallest first; the count stays on the device */                                  \
-            uint32_t *nsel = wlist + fp->tri_count;                                                                  \
-            uint32_t *hist_ = reinterpret_cast<uint32_t *>(sel_temp);                                                \
-            nsel = hist_; /* the run counter is the list length */                                                   \
-            hipLaunchKernelGGL(prk::k_won_local, dim3(nwon), dim3(prk::kWonThreads), 0, sw, fp->tri_count, trwon,     \
-                               tr, hist_, wlist);                                                                    \
-            hipLaunchKernelGGL((prk::k_walk<UNI>), dim3(nwblk), dim3(64 * prk::kWalkWaves), 0, sw, *fp, wlist, nsel,    \
-                               tri_off, tr, won,                                                                     \
-                               rp, anomaly);                                                                         \
+            /* the won triangles; the count stays on the device (the run counter is the list length) */              \
+            uint32_t *nsel = reinterpret_cast<uint32_t *>(sel_temp);                                                 \
+            hipLaunchKernelGGL(prk::k_won_local, dim3(nwon), dim3(prk::kWonThreads), 0, s, fp->tri_count, trwon,     \
+                               tr, nsel, wlist);                                                                     \
+            hipLaunchKernelGGL((prk::k_walk<UNI>), dim3(nwblk), dim3(64 * prk::kWalkWaves), 0, s, *fp, wlist, nsel,  \
+                               tri_off, tr, won, rp, anomaly);                                                       \
         }                                                                                                            \
-        if (mid2) (void)hipEventRecord(mid2, sw);                                                                    \
-        if (sw != s) (void)hipStreamWaitEvent(s, mid2, 0);                                                           \
+        if (mid2) (void)hipEventRecord(mid2, s);                                                                     \
         if (fp->z_in_vis)                                                                                            \
             hipLaunchKernelGGL((prk::k_pix<UNI, false, true>), dim3(ntile * PRK_PIX_SPLIT), dim3(256), 0, s, *fp, nwin, \
                                wtag, rp);                                                                            \
@@ -2114,10 +1945,10 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
         case prk::MODE_AVX:
             if (uni) {
                 PRK_VIS(prk::MODE_AVX, true);
-                if (PRK_SPAN_RECORDS) PRK_SPANPIX(true); else PRK_SHADE(prk::MODE_AVX, true);
+                PRK_SPANPIX(true);
             } else {
                 PRK_VIS(prk::MODE_AVX, false);
-                if (PRK_SPAN_RECORDS) PRK_SPANPIX(false); else PRK_SHADE(prk::MODE_AVX, false);
+                PRK_SPANPIX(false);
             }
             break;
         case prk::MODE_SC_GOURAUD:

@@ -425,10 +425,7 @@ struct LLinksT {
         return ax < bx || (ax == bx && (ag < bg || (ag == bg && L->left[at(a)] < L->left[at(b)])));
     }
     __device__ __forceinline__ void stepped(int i) const { L->x[at(i)] += L->g[at(i)]; }  // E.X += E.G (obj_step)
-#ifndef PRK_OBJ_PAIR_CACHE
-#define PRK_OBJ_PAIR_CACHE 1
-#endif
-    static constexpr bool kCache = PRK_OBJ_PAIR_CACHE;
+    static constexpr bool kCache = true;  // (walk_object keeps the last pair's records in registers)
 };
 using LLinks = LLinksT<kLinkCap>;
 
@@ -658,9 +655,6 @@ __device__ void walk_object(const FrameParams &fp, const ObjDesc &od, const Draw
     for (uint32_t q = emitted; q < bound; ++q) pos[base + q] = SpanPos{-1, 0, 0, 0u};
 }
 
-#ifndef PRK_OBJ_LDS_LINKS
-#define PRK_OBJ_LDS_LINKS 1
-#endif
 // LINKS: the launch holds triangle objects small enough for LDS links (the
 // 40-KB mirror is allocated only then: it limits a CU to four workgroups).
 template <bool LINKS>
@@ -2284,9 +2278,6 @@ __global__ void __launch_bounds__(kBigThreads) k_obj_walk_big(FrameParams fp, co
 //     swaps them as big_pair does, writes entries 2k, 2k + 1 after a barrier,
 //     with the next row's per-16 key maxima.
 // ---------------------------------------------------------------------------
-#ifndef PRK_LDS_WINCOUNT
-#define PRK_LDS_WINCOUNT 1  // the LDS walk counts the next row's window in the pairing pass
-#endif
 constexpr int kLdsCap = 9200;                      // list entries (< 577 * 16: 576 coarse bins)
 constexpr int kLdsPer = (kLdsCap + kBigThreads - 1) / kBigThreads;  // old entries a thread owns (9)
 constexpr int kLdsSamp = 576;                      // per-16 maxima (>= kLdsCap / 16)
@@ -2624,7 +2615,7 @@ __global__ void __launch_bounds__(kBigThreads) k_obj_walk_lds(FrameParams fp, co
     unsigned long long wpa[16] = {}, *wp = PRK_WPROF && tid == 0 ? wpa : nullptr;
     unsigned long long tw0 = PRK_WT(), twall = tw0;
     uint32_t pf = UINT32_MAX;  // the window of sorted edges at pf, loaded a row ahead
-    int32_t pre_row = INT32_MIN;  // PRK_LDS_WINCOUNT: W.wc holds row pre_row's counts of the window at pre_pf
+    int32_t pre_row = INT32_MIN;  // (the pairing pass counts the next row's window:) W.wc holds row pre_row's counts of the window at pre_pf
     uint32_t pre_pf = UINT32_MAX;
     int32_t y = INT32_MAX, l = 0, ym = 0;
     float x = 0.0f, g = 0.0f;
@@ -2644,7 +2635,7 @@ __global__ void __launch_bounds__(kBigThreads) k_obj_walk_lds(FrameParams fp, co
         for (;;) {  // the row's new edges, a window of kBigThreads at a time (3654-3713)
             if (pf != ins) fetch(ins);
             int32_t lt, kb, nanc;
-            if (PRK_LDS_WINCOUNT && pre_row == Row && pre_pf == pf) {  // (counted by the last row's pairing)
+            if (pre_row == Row && pre_pf == pf) {  // (counted by the last row's pairing)
                 lt = kb = nanc = 0;
 #pragma unroll
                 for (int w = 0; w < kBigThreads / 64; ++w) {
@@ -2705,7 +2696,7 @@ __global__ void __launch_bounds__(kBigThreads) k_obj_walk_lds(FrameParams fp, co
             bad = true;
             break;
         }
-        const bool pre = PRK_LDS_WINCOUNT && Row + 1 < MaxY;
+        const bool pre = Row + 1 < MaxY;
         lds_pair(W, L, m, rrel, emit, emitted, off, pre ? Row + 1 : INT32_MIN, y, x, g, wp);
         if (pre) {
             pre_row = Row + 1;
@@ -4047,7 +4038,7 @@ hipError_t prk_obj_walk(const prk::FrameParams *fp, const void *objs, uint32_t n
                        reinterpret_cast<prk::SpanRecG *>(recs), reinterpret_cast<prk::ScSpanRecG *>(srecs),        \
                        reinterpret_cast<prk::SpanPos *>(pos), span_tri,                                            \
                        reinterpret_cast<const prk::SpanIn *>(spans_in), err, segmented)
-    if (links && PRK_OBJ_LDS_LINKS) PRK_OBJ_WALK_LAUNCH(true);
+    if (links) PRK_OBJ_WALK_LAUNCH(true);
     else PRK_OBJ_WALK_LAUNCH(false);
 #undef PRK_OBJ_WALK_LAUNCH
     return hipGetLastError();

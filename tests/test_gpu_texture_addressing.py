@@ -92,7 +92,7 @@ def _shapes():
 def test_mixed_semantics_frame_each_draw_its_own_texture(gpu):
     """AVX, scalar and single-thread draws in one flush, as
     test_mixed_semantics_one_frame has them (the AVX items then shade in
-    k_shade / item_avx), each with a texture of another shape: padded nearest,
+    k_shade / item_avx_pixel), each with a texture of another shape: padded nearest,
     24 x 40 under DrawModel, 40 x 24 bilinear, and the padded one again for
     objects of five triangles."""
     s, padded, wide, wide_bilinear, tall = _shapes()
