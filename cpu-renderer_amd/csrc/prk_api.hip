@@ -331,9 +331,9 @@ int prk_destroy(prk_context *c) {
     }
     for (auto &B : c->bset) {
         DevBuf *bb[] = {&B.d_draws, &B.d_texs, &B.d_tri_draw, &B.d_ranges, &B.d_tri_n, &B.d_tri_off, &B.d_pair_tri,
-                        &B.d_keys_a, &B.d_vals_a, &B.d_keys_b, &B.d_bins, &B.d_offs, &B.d_temp, &B.d_won,
-                        &B.d_list, &B.d_nwin, &B.d_wtag, &B.d_recs, &B.d_trwon, &B.d_wlist, &B.d_seltemp,
-                        &B.d_trec, &B.d_ghist, &B.d_tile_tot, &B.d_chunk, &B.d_info, &B.d_runlist, &B.d_run_n};
+                        &B.d_bins, &B.d_offs, &B.d_won, &B.d_list, &B.d_nwin, &B.d_wtag, &B.d_recs, &B.d_trwon,
+                        &B.d_wlist, &B.d_seltemp, &B.d_trec, &B.d_ghist, &B.d_tile_tot, &B.d_chunk, &B.d_info,
+                        &B.d_runlist, &B.d_run_n};
         for (DevBuf *b : bb) b->release();
         if (B.free_ev) (void)hipEventDestroy(B.free_ev);
         if (B.binned_ev) (void)hipEventDestroy(B.binned_ev);
@@ -1419,6 +1419,7 @@ int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_
     hipStream_t s = c->own_stream;
     prk_context::SpanScratch &S = c->spans;
     const size_t out_bytes = packed_span_bytes(npair);
+    static_assert(sizeof(prk_row) == sizeof(prk::RowRec), "the kernels read a prk_row as {row, pairs}");
     PRK_TRY(S.d_dr_rows.ensure((size_t)nrow * sizeof(prk_row)));
     PRK_TRY(S.d_dr_pairs.ensure((size_t)npair * sizeof(prk_row_pair)));
     PRK_TRY(S.d_dr_cnt.ensure(((size_t)nrow + 1) * 4));
@@ -1426,9 +1427,9 @@ int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_
     if (!keep) PRK_TRY(S.d_dr_out.ensure(out_bytes));
     PRK_TRY(hipMemcpyAsync(S.d_dr_rows.p, rows, (size_t)nrow * sizeof(prk_row), hipMemcpyHostToDevice, s));
     PRK_TRY(hipMemcpyAsync(S.d_dr_pairs.p, pairs, (size_t)npair * sizeof(prk_row_pair), hipMemcpyHostToDevice, s));
-    PRK_TRY(prk_rows_counts(S.d_dr_rows.p, nrow, (uint32_t *)S.d_dr_cnt.p, s));
+    PRK_TRY(prk_rows_counts(S.d_dr_rows.as<prk::RowRec>(), nrow, (uint32_t *)S.d_dr_cnt.p, s));
     PRK_TRY(scan_u32(S.d_dr_temp, (const uint32_t *)S.d_dr_cnt.p, (uint32_t *)S.d_dr_scan.p, nrow + 1, s));
-    PRK_TRY(prk_rows_unpack(S.d_dr_rows.p, (const uint32_t *)S.d_dr_scan.p, nrow, S.d_dr_pairs.p, npair,
+    PRK_TRY(prk_rows_unpack(S.d_dr_rows.as<prk::RowRec>(), (const uint32_t *)S.d_dr_scan.p, nrow, S.d_dr_pairs.p, npair,
                             keep ? keep : S.d_dr_out.p, s));
     if (!keep) PRK_TRY(hipMemcpyAsync(out, S.d_dr_out.p, (size_t)npair * sizeof(prk_span), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));  // (the caller's arrays are copied at the call)

@@ -871,7 +871,7 @@ extern "C" {
 // no pair written; the caller re-runs the frame with more room).
 // ghist: nchunks * ntiles u32; tile_tot: ntiles; chunk_tot / chunk_base: nchunks.
 // All-AVX frames (fp->trec): the setup records are computed by k_setup_rec.
-hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, void *ranges, uint32_t *runlist,
+hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, prk::TileRange *ranges, uint32_t *runlist,
                          uint32_t *run_n, uint8_t *trwon, hipStream_t s) {
     const uint32_t n = fp->tri_count + 1;
     // A whole-frame target sets up (nearly) every triangle: inline records
@@ -879,11 +879,11 @@ hipError_t prk_bin_count(const prk::FrameParams *fp, uint32_t *tri_n, void *rang
     const bool band = fp->row0 > 0 || fp->row1 < fp->H;
     if (band && runlist) {  // (k_bin_band also writes the sentinel tri_n[tri_count])
         hipLaunchKernelGGL(prk::k_bin_band, dim3((n + prk::kRecRun - 1) / prk::kRecRun), dim3(prk::kCountThreads),
-                           0, s, *fp, tri_n, reinterpret_cast<prk::TileRange *>(ranges), runlist, run_n, trwon);
+                           0, s, *fp, tri_n, ranges, runlist, run_n, trwon);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(prk::k_bin_count, dim3((n + prk::kCountThreads - 1) / prk::kCountThreads),
-                       dim3(prk::kCountThreads), 0, s, *fp, tri_n, reinterpret_cast<prk::TileRange *>(ranges), !band);
+                       dim3(prk::kCountThreads), 0, s, *fp, tri_n, ranges, !band);
     if (band && fp->trec && fp->tri_count)
         hipLaunchKernelGGL(prk::k_setup_rec, dim3((fp->tri_count + prk::kRecRun - 1) / prk::kRecRun),
                            dim3(prk::kCountThreads), 0, s, *fp, tri_n);
@@ -959,9 +959,9 @@ uint32_t prk_cs_nchunks(uint32_t tri_count, uint32_t per) {
 uint32_t prk_cs_max_tiles(void) { return prk::kCsMaxTiles; }
 uint32_t prk_cs_max_pairs(void) { return prk::kCsPairMask; }
 
-hipError_t prk_bin_cs(const prk::FrameParams *fp, const void *ranges, const uint32_t *tri_n, uint32_t *ghist,
+hipError_t prk_bin_cs(const prk::FrameParams *fp, const prk::TileRange *ranges, const uint32_t *tri_n, uint32_t *ghist,
                       uint32_t *tile_tot, uint32_t *chunk_tot, uint32_t *chunk_base, uint32_t *offs, uint32_t cap,
-                      uint32_t *info, uint32_t *tri_off, void *bins, uint32_t *pair_tri, uint8_t *won,
+                      uint32_t *info, uint32_t *tri_off, prk::BinSlot *bins, uint32_t *pair_tri, uint8_t *won,
                       uint32_t won_stride, uint8_t *trwon, const uint32_t *runlist, const uint32_t *run_n,
                       uint32_t per, hipStream_t s) {
     const uint32_t ntiles = (uint32_t)(fp->tiles_x * fp->tiles_y);
@@ -969,12 +969,11 @@ hipError_t prk_bin_cs(const prk::FrameParams *fp, const void *ranges, const uint
     prk::BandRuns br{nullptr, nullptr, 0u, 0u};
     if (per && runlist) br = prk::BandRuns{runlist, run_n, prk_bin_runs(fp->tri_count), per};
     const uint32_t nch = prk_cs_nchunks(fp->tri_count, br.list ? per : 0u);
-    const prk::TileRange *tr = reinterpret_cast<const prk::TileRange *>(ranges);
     const size_t lds = (size_t)ntiles * 4;
     if (!prk_cs_ready(ntiles)) return hipErrorNotSupported;
     if (nch) {
-        hipLaunchKernelGGL(prk::k_cs_hist, dim3(nch), dim3(prk::kCsThreads), lds, s, *fp, tr, tri_n, ghist, chunk_tot,
-                           ntiles, br);
+        hipLaunchKernelGGL(prk::k_cs_hist, dim3(nch), dim3(prk::kCsThreads), lds, s, *fp, ranges, tri_n, ghist,
+                           chunk_tot, ntiles, br);
         hipLaunchKernelGGL(prk::k_cs_colscan, dim3((ntiles + 63) / 64), dim3(64 * prk::kColSegs), 0, s, ghist, nch,
                            ntiles, tile_tot);
     } else {
@@ -984,10 +983,9 @@ hipError_t prk_bin_cs(const prk::FrameParams *fp, const void *ranges, const uint
     hipLaunchKernelGGL(prk::k_cs_scan, dim3(1), dim3(prk::kCsThreads), 0, s, tile_tot, ntiles, chunk_tot, nch, offs,
                        chunk_base, std::min(cap, prk::kCsPairMask), info);
     if (nch)
-        hipLaunchKernelGGL(prk::k_cs_emit, dim3(nch), dim3(prk::kCsThreads), lds, s, *fp, tr, tri_n, ghist, offs,
-                           chunk_base, info, ntiles, tri_off, reinterpret_cast<uint2 *>(bins), pair_tri, won,
-                           won_stride, trwon, br);
-    hipLaunchKernelGGL(prk::k_cs_class, dim3(ntiles), dim3(256), 0, s, offs, reinterpret_cast<uint2 *>(bins));
+        hipLaunchKernelGGL(prk::k_cs_emit, dim3(nch), dim3(prk::kCsThreads), lds, s, *fp, ranges, tri_n, ghist, offs,
+                           chunk_base, info, ntiles, tri_off, bins, pair_tri, won, won_stride, trwon, br);
+    hipLaunchKernelGGL(prk::k_cs_class, dim3(ntiles), dim3(256), 0, s, offs, bins);
     return hipGetLastError();
 }
 

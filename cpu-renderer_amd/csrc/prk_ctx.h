@@ -2,8 +2,8 @@
 // include/prk.h) with the resources and scratch it owns, the state a pass is
 // queued with, and the few host functions that cross the host files
 // (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip).  Host
-// only; prk_launch.h stays the seam to the kernel files, and prk_dist.hip
-// keeps the context opaque.
+// only; prk_launch.h stays the seam to the kernel files (prk_types.h: the
+// records the buffers here hold), and prk_dist.hip keeps the context opaque.
 //
 // Nothing here reaches the library's dynamic symbol table: the helper types
 // and inline functions sit in a hidden-visibility region (one definition for
@@ -66,6 +66,9 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+    // The buffer as n records of T (prk_types.h): sized by the type, read through it.
+    template <class T> hipError_t ensure_n(size_t n) { return ensure(n * sizeof(T)); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
 struct Geometry {
@@ -219,9 +222,9 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     // set after frame k-1's on bin_stream while frame k-1 shades on the
     // flush's stream.
     struct BinSet {
-        DevBuf d_draws, d_texs, d_tri_draw, d_ranges, d_tri_n, d_tri_off, d_pair_tri, d_keys_a, d_vals_a, d_keys_b,
-            d_bins, d_offs, d_temp, d_won, d_list, d_nwin, d_wtag, d_recs, d_trwon, d_wlist, d_seltemp, d_trec,
-            d_ghist, d_tile_tot, d_chunk, d_info, d_runlist, d_run_n;
+        DevBuf d_draws, d_texs, d_tri_draw, d_ranges, d_tri_n, d_tri_off, d_pair_tri, d_bins, d_offs, d_won, d_list,
+            d_nwin, d_wtag, d_recs, d_trwon, d_wlist, d_seltemp, d_trec, d_ghist, d_tile_tot, d_chunk, d_info,
+            d_runlist, d_run_n;
         uint32_t *h_info = nullptr;       // pinned: [entry count, overflow] of the set's last binning
         hipEvent_t counted_ev = nullptr;  // h_info of this set's binning has landed
         hipEvent_t listed_ev = nullptr;   // a band frame's run lists are written (k_band_rec may start)

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "prk_types.h"  // TileRange and the other records the files share
+
 // Diagnostic builds only (prk_kernels.hip lists the bits); never set in a product build.
 #ifndef PRK_DIAG
 #define PRK_DIAG 0
@@ -187,12 +189,6 @@ __device__ __forceinline__ float u8_unit(uint32_t k) {
     const float rem = __builtin_fmaf(-255.0f, q0, kf);  // exact residual
     return __builtin_fmaf(rem, c, q0);
 }
-
-// Tiles a triangle may touch: the rectangle [tx0..tx1] x [ty0..ty1], plus
-// for scalar semantics the column-0 tiles of rows [oty0..oty1] that receive
-// DrawModel's one-past-the-row store (see span_setup_scalar).
-// pad0 / pad1: the triangle's band rows [r0, r1) (prk_bin.hip: row classes)
-struct TileRange { uint16_t tx0, ty0, tx1, ty1, oty0, oty1, pad0, pad1; };
 
 // ---------------------------------------------------------------------------
 // Conversions with x86 semantics (the reference runs on x86).
@@ -1038,29 +1034,5 @@ struct RowWalker {
         }
         ++Row;
     }
-};
-
-// The chunked walk of large objects (prk_spans.hip k_pr_*): its pass-wide
-// buffers and sizes, set by flush_spans (prk_span_pass.hip).
-struct PrWalkArgs {
-    const void *objs;           // ObjDesc[]
-    const void *pro;            // PrObj[npr]
-    uint32_t npr;               // objects
-    uint32_t warmup;            // chunks start one chunk early (0: from their own first row)
-    uint32_t nchunks;           // their chunks
-    uint32_t max_edges;         // most edges of one object
-    const uint32_t *escan, *total0p;
-    const void *work;           // the walk's working copy (ObjEdge[])
-    void *prrow;                // PrRow[npr]
-    uint32_t *cnt, *eoff, *fge; // per row: rows + 1 per object
-    uint32_t *ccur;             // per chunk: its first row's entries
-    void *key;                  // float4 per entry (chunk j of an object: ent_off + j * most)
-    void *est, *sst, *eend;     // ObjEdge per entry: arrival order / canonical list / a walk's end list
-    uint32_t *eend_m, *match;   // per chunk
-    uint32_t *sidx, *s_m;       // per entry / per chunk: a chunk's list at its first row (edge indices)
-    uint32_t *prstat;           // per object of the pass
-    const unsigned long long *soff;
-    void *raw, *pos;            // PairRaw / SpanPos per span slot
-    uint32_t *span_tri, *err;
 };
 }  // namespace prk

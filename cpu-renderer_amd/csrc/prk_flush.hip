@@ -198,10 +198,10 @@ hipError_t TriPass::upload_table(DevBuf &d, std::vector<uint8_t> &mirror, const 
 // pairs the set's per-pair arrays hold now (they never shrink)
 size_t TriPass::pairs_held() const {
     const prk_context::BinSet &B = *set;
-    size_t m = std::min(B.d_pair_tri.cap / 4, B.d_bins.cap / 8);
+    size_t m = std::min(B.d_pair_tri.cap / 4, B.d_bins.cap / sizeof(prk::BinSlot));
     m = std::min(m, B.d_list.cap / 4);
     m = std::min(m, B.d_won.cap / won_stride);
-    if (span_rec) m = std::min(m, B.d_recs.cap / ((size_t)won_stride * 64));
+    if (span_rec) m = std::min(m, B.d_recs.cap / (won_stride * sizeof(prk::SpanRec)));
     return m;
 }
 
@@ -211,11 +211,11 @@ hipError_t TriPass::ensure_pairs(size_t np) {
     const size_t ne = std::max<size_t>(np, 1);
     hipError_t e = hipSuccess;
     if (e == hipSuccess) e = bset_ensure(B.d_pair_tri, ne * 4);
-    if (e == hipSuccess) e = bset_ensure(B.d_bins, ne * 8);  // (triangle, pair) per bin slot
+    if (e == hipSuccess) e = bset_ensure(B.d_bins, ne * sizeof(prk::BinSlot));
     if (e == hipSuccess) e = bset_ensure(B.d_list, ne * 4);
     if (e == hipSuccess) e = bset_ensure(B.d_won, ne * won_stride);
-    // span records: 64 B per (pair, row in tile); only won ones are written
-    if (e == hipSuccess && span_rec) e = bset_ensure(B.d_recs, ne * won_stride * 64);
+    // span records: one per (pair, row in tile); only won ones are written
+    if (e == hipSuccess && span_rec) e = bset_ensure(B.d_recs, ne * won_stride * sizeof(prk::SpanRec));
     return e;
 }
 
@@ -288,7 +288,7 @@ int TriPass::tables() {
 // anomaly counters, stays in raster().
 int TriPass::scratch() {
     prk_context::BinSet &B = *set;
-    PRK_TRY(bset_ensure(B.d_ranges, (size_t)T * 16));
+    PRK_TRY(bset_ensure(B.d_ranges, (size_t)T * sizeof(prk::TileRange)));
     PRK_TRY(bset_ensure(B.d_tri_n, (size_t)(T + 1) * 4));
     PRK_TRY(bset_ensure(B.d_tri_off, (size_t)(T + 1) * 4));
     PRK_TRY(bset_ensure(B.d_offs, (size_t)(ntiles + 1) * 4));
@@ -349,14 +349,14 @@ int TriPass::bin() {
     uint8_t *trwon = span_rec ? (uint8_t *)B.d_trwon.p : nullptr;
     PRK_TRY(hipEventRecord(c->ev[slot][0], bs));
     uint32_t *runlist = per ? (uint32_t *)B.d_runlist.p : nullptr, *run_n = per ? (uint32_t *)B.d_run_n.p : nullptr;
-    PRK_TRY(prk_bin_count(&fp, (uint32_t *)B.d_tri_n.p, B.d_ranges.p, runlist, run_n, trwon, bs));
+    PRK_TRY(prk_bin_count(&fp, (uint32_t *)B.d_tri_n.p, B.d_ranges.as<prk::TileRange>(), runlist, run_n, trwon, bs));
     const bool band_rec = runlist && fp.trec;  // a row band's setup records (k_band_rec, below)
     if (band_rec) PRK_TRY(hipEventRecord(B.listed_ev, bs));
     uint32_t *chunk = (uint32_t *)B.d_chunk.p;
-    PRK_TRY(prk_bin_cs(&fp, B.d_ranges.p, (const uint32_t *)B.d_tri_n.p, (uint32_t *)B.d_ghist.p,
+    PRK_TRY(prk_bin_cs(&fp, B.d_ranges.as<prk::TileRange>(), (const uint32_t *)B.d_tri_n.p, (uint32_t *)B.d_ghist.p,
                        (uint32_t *)B.d_tile_tot.p, chunk, chunk + nch, (uint32_t *)B.d_offs.p, cap,
-                       (uint32_t *)B.d_info.p, (uint32_t *)B.d_tri_off.p, B.d_bins.p, (uint32_t *)B.d_pair_tri.p,
-                       won, won_stride, trwon, runlist, run_n, per, bs));
+                       (uint32_t *)B.d_info.p, (uint32_t *)B.d_tri_off.p, B.d_bins.as<prk::BinSlot>(),
+                       (uint32_t *)B.d_pair_tri.p, won, won_stride, trwon, runlist, run_n, per, bs));
     // the entry count's copy to the host, which the host waits for, goes
     // first (behind binned_ev it would queue after k_vis); then the bins are
     // ready and the raster may start
@@ -405,11 +405,12 @@ int TriPass::raster() {
         PRK_TRY(hipStreamWaitEvent(s, B.binned_ev, 0));
     }
     PRK_TRY(hipEventRecord(c->ev[slot][5], sv));
-    PRK_TRY(prk_launch_raster(&fp, modeset, (const uint32_t *)B.d_offs.p, B.d_bins.p,
-                              (const uint32_t *)B.d_pair_tri.p, (const uint32_t *)B.d_tri_off.p, B.d_ranges.p,
+    PRK_TRY(prk_launch_raster(&fp, modeset, (const uint32_t *)B.d_offs.p, B.d_bins.as<prk::BinSlot>(),
+                              (const uint32_t *)B.d_pair_tri.p, (const uint32_t *)B.d_tri_off.p,
+                              B.d_ranges.as<prk::TileRange>(),
                               (uint8_t *)B.d_won.p, (uint8_t *)B.d_trwon.p, (uint32_t *)B.d_wlist.p,
                               B.d_seltemp.p, sel_bytes, (uint32_t *)B.d_list.p,
-                              (uint32_t *)B.d_nwin.p, (uint32_t *)B.d_wtag.p, B.d_recs.p,
+                              (uint32_t *)B.d_nwin.p, (uint32_t *)B.d_wtag.p, B.d_recs.as<prk::SpanRec>(),
                               (uint32_t *)c->d_anomaly.p, c->ev[slot][3], span_rec ? c->ev[slot][4] : nullptr, sv,
                               s));
     PRK_TRY(hipEventRecord(c->ev[slot][2], s));
@@ -649,7 +650,7 @@ int prk_debug_bins(prk_context *c, prk_bins_info *info, uint32_t *tri_n, uint16_
     if (offs && tile_capacity < ntiles) return PRK_ERR_ARG;
     if ((bins || pair_tri) && entry_capacity < total) return PRK_ERR_ARG;
     if (tri_n) PRK_TRY(hipMemcpy(tri_n, B.d_tri_n.p, (size_t)T * 4, hipMemcpyDeviceToHost));
-    if (ranges) PRK_TRY(hipMemcpy(ranges, B.d_ranges.p, (size_t)T * 16, hipMemcpyDeviceToHost));
+    if (ranges) PRK_TRY(hipMemcpy(ranges, B.d_ranges.p, (size_t)T * sizeof(prk::TileRange), hipMemcpyDeviceToHost));
     if (tri_off) PRK_TRY(hipMemcpy(tri_off, B.d_tri_off.p, ((size_t)T + 1) * 4, hipMemcpyDeviceToHost));
     if (listed) std::memset(listed, D.per ? 0 : 1, T);
     if (D.per && (tri_n || ranges || tri_off || listed)) {
@@ -675,7 +676,8 @@ int prk_debug_bins(prk_context *c, prk_bins_info *info, uint32_t *tri_n, uint16_
         }
     }
     if (offs) PRK_TRY(hipMemcpy(offs, B.d_offs.p, ((size_t)ntiles + 1) * 4, hipMemcpyDeviceToHost));
-    if (bins && total) PRK_TRY(hipMemcpy(bins, B.d_bins.p, (size_t)total * 8, hipMemcpyDeviceToHost));
+    if (bins && total) PRK_TRY(hipMemcpy(bins, B.d_bins.p, (size_t)total * sizeof(prk::BinSlot),
+                                         hipMemcpyDeviceToHost));
     if (pair_tri && total) PRK_TRY(hipMemcpy(pair_tri, B.d_pair_tri.p, (size_t)total * 4, hipMemcpyDeviceToHost));
     return PRK_OK;
 }

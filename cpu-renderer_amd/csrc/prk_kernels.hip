@@ -1075,12 +1075,6 @@ __global__ void __launch_bounds__(64 * kShadeWaves, PRK_SHADE_MIN_WAVES)
 // set it up per tile and replay the rows above every tile), and the shading
 // runs at full lane occupancy with no walker registers.
 // ---------------------------------------------------------------------------
-struct SpanRec {  // one won row span (FillLineOptimized span setup, 1543-1835)
-    int32_t left_tex;  // LeftXa (low 16 bits) | texture index << 16
-    float xoff, lw, lu, lv, lz, iw, iu, iv, iz, ln0, ln1, ln2, in0, in1, in2;
-};
-static_assert(sizeof(SpanRec) == 64, "span record is four dwordx4");
-
 // k_walk: FillLineOptimized span setup (projekt.cpp:1543-1835) of one row of
 // the triangle; for every tile the span crosses whose (pair, row) won a pixel
 // in k_vis, write the span's record at recs[pair * tile_h + row-in-tile].
@@ -1425,9 +1419,6 @@ __global__ void __launch_bounds__(256) k_pix(FrameParams fp, const uint32_t *__r
 // DrawModel spans (ScSpanRec, SPAN_SCALAR) its scalar chunk items
 // (item_scalar), the one-past-the-row pixel included.
 // ---------------------------------------------------------------------------
-struct SpanPosK { int32_t row, minx, maxx; uint32_t flags; };  // == prk_spans_dev.h SpanPos
-struct ScSpanRec { float f[22]; int32_t tex, pad; };          // == prk_spans_dev.h ScSpanRecG
-static_assert(sizeof(ScSpanRec) == 96, "scalar span record");
 constexpr int32_t kAvxSlot = -2;  // SI_OVF of a slot holding a FillLineOptimized span
 
 // The wave's items: every lane holds `items` work items of the span in its
@@ -1463,8 +1454,7 @@ __device__ __forceinline__ void wave_items(WS &ws, int items, int lane, F &&f) {
 // item count.
 template <bool SHADE, class WS>
 __device__ __forceinline__ int span_slot_scalar(const FrameParams &fp, const TileCtx &tc, WS &ws, int lane,
-                                                const SpanPosK &sp, const ScSpanRec *__restrict__ srecs,
-                                                uint32_t sidx) {
+                                                const SpanPos &sp, const ScSpanRec *__restrict__ srecs, uint32_t sidx) {
     const int32_t W = fp.W;
     const int32_t MinX = sp.minx, MaxX = sp.maxx - 1;
     const bool in_rows = sp.row >= tc.y0 && sp.row < tc.y1;
@@ -1492,7 +1482,7 @@ __device__ __forceinline__ int span_slot_scalar(const FrameParams &fp, const Til
 
 __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
     k_span_vis(FrameParams fp, const uint32_t *__restrict__ offs, const uint32_t *__restrict__ bins,
-               const SpanPosK *__restrict__ pos, const SpanRec *__restrict__ recs,
+               const SpanPos *__restrict__ pos, const SpanRec *__restrict__ recs,
                const ScSpanRec *__restrict__ srecs, const uint32_t *__restrict__ span_tri,
                uint32_t *__restrict__ nwin_out, uint32_t *__restrict__ wtag) {
     extern __shared__ unsigned long long lds[];
@@ -1529,7 +1519,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
         int items = 0;
         if (i < n) {
             const uint32_t sidx = bins[b0 + i];
-            const SpanPosK sp = pos[sidx];
+            const SpanPos sp = pos[sidx];
             if (sp.flags & SPAN_SCALAR) {
                 items = span_slot_scalar<false>(fp, tc, ws, lane, sp, srecs, sidx);
             } else if (sp.row >= tc.y0 && sp.row < tc.y1) {
@@ -1581,8 +1571,7 @@ __global__ void __launch_bounds__(64 * kVisWaves, PRK_VIS_MIN_WAVES)
 template <int M>
 __device__ __forceinline__ void span_shade_sweep(const FrameParams &fp, const TileCtx &tc, ShadeSlots &ws,
                                                  const uint32_t *__restrict__ bins, uint32_t b0, uint32_t n,
-                                                 const SpanPosK *__restrict__ pos,
-                                                 const ScSpanRec *__restrict__ srecs) {
+                                                 const SpanPos *__restrict__ pos, const ScSpanRec *__restrict__ srecs) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t nwaves = blockDim.x >> 6;
     for (uint32_t base = wave * 64; base < n; base += 64 * nwaves) {
@@ -1590,7 +1579,7 @@ __device__ __forceinline__ void span_shade_sweep(const FrameParams &fp, const Ti
         int items = 0;
         if (i < n) {
             const uint32_t sidx = bins[b0 + i];
-            const SpanPosK sp = pos[sidx];
+            const SpanPos sp = pos[sidx];
             if ((sp.flags & SPAN_SCALAR) && (int)((sp.flags >> 8) & 0xFFu) == M)
                 items = span_slot_scalar<true>(fp, tc, ws, lane, sp, srecs, sidx);
         }
@@ -1602,7 +1591,7 @@ __device__ __forceinline__ void span_shade_sweep(const FrameParams &fp, const Ti
 template <int MODESET>
 __global__ void __launch_bounds__(64 * kShadeWaves, PRK_SHADE_MIN_WAVES)
     k_span_shade(FrameParams fp, const uint32_t *__restrict__ offs, const uint32_t *__restrict__ bins,
-                 const SpanPosK *__restrict__ pos, const ScSpanRec *__restrict__ srecs,
+                 const SpanPos *__restrict__ pos, const ScSpanRec *__restrict__ srecs,
                  const uint32_t *__restrict__ nwin_in, const uint32_t *__restrict__ wtag) {
     extern __shared__ unsigned long long lds[];
     const int ntile = fp.tiles_x * fp.tiles_y;
@@ -1649,7 +1638,7 @@ template __global__ void k_pix<true>(PRK_PIX_ARGS);
 template __global__ void k_pix<false, true>(PRK_PIX_ARGS);
 template __global__ void k_pix<false, false, true>(PRK_PIX_ARGS);
 template __global__ void k_pix<true, false, true>(PRK_PIX_ARGS);
-#define PRK_SPAN_SHADE_ARGS FrameParams, const uint32_t *, const uint32_t *, const SpanPosK *, const ScSpanRec *, \
+#define PRK_SPAN_SHADE_ARGS FrameParams, const uint32_t *, const uint32_t *, const SpanPos *, const ScSpanRec *, \
                             const uint32_t *, const uint32_t *
 template __global__ void k_span_shade<-1>(PRK_SPAN_SHADE_ARGS);
 template __global__ void k_span_shade<MODE_SC_GOURAUD>(PRK_SPAN_SHADE_ARGS);
@@ -1885,10 +1874,11 @@ static size_t shade_lds(const prk::FrameParams *fp) {
 // and k_pix.  won: per bin entry (k_shade frames) or per (pair, row) (AVX
 // frames) won flags; trwon: per triangle; recs: span records, 64 B per
 // (pair, row); tri_off / ranges: the binning's pair offsets and tile ranges.
-hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint32_t *offs, const void *bins_,
-                             const uint32_t *pair_tri, const uint32_t *tri_off, const void *ranges, uint8_t *won,
+hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint32_t *offs, const prk::BinSlot *bins,
+                             const uint32_t *pair_tri, const uint32_t *tri_off, const prk::TileRange *ranges,
+                             uint8_t *won,
                              uint8_t *trwon, uint32_t *wlist, void *sel_temp, size_t sel_bytes, uint32_t *list,
-                             uint32_t *nwin, uint32_t *wtag, void *recs, uint32_t *anomaly, hipEvent_t mid,
+                             uint32_t *nwin, uint32_t *wtag, prk::SpanRec *recs, uint32_t *anomaly, hipEvent_t mid,
                              hipEvent_t mid2, hipStream_t svis, hipStream_t s) {
     // k_vis runs on svis, the shading on s (after k_vis: `mid` is recorded on
     // svis and waited for on s); svis == s runs the frame on one stream.
@@ -1897,12 +1887,9 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
     if (ntile == 0) return hipSuccess;
     const size_t lv = vis_lds(fp), ls = shade_lds(fp);
     const bool uni = fp->ndraws == 1;
-    prk::SpanRec *rp = reinterpret_cast<prk::SpanRec *>(recs);
-    const prk::TileRange *tr = reinterpret_cast<const prk::TileRange *>(ranges);
     const uint32_t nblk = (fp->tri_count + 255) / 256;
     const uint32_t nwblk = (fp->tri_count + 64 * prk::kWalkWaves - 1) / (64 * prk::kWalkWaves);
     const uint32_t nwon = (fp->tri_count + prk::kWonThreads * prk::kWonPer - 1) / (prk::kWonThreads * prk::kWonPer);
-    const uint2 *bins = reinterpret_cast<const uint2 *>(bins_);
     if (modeset == prk::MODE_AVX && nblk) {
         // k_walk's list histogram, cleared before k_vis is waited for (off
         // the k_vis -> k_walk path)
@@ -1912,11 +1899,11 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
     }
 #define PRK_VIS(MS, UNI)                                                                                             \
     do {                                                                                                             \
-        if (MS == prk::MODE_AVX && fp->z_in_vis)                                                                   \
+        if (MS == prk::MODE_AVX && fp->z_in_vis)                                                                     \
             hipLaunchKernelGGL((prk::k_vis<MS, UNI, true>), dim3(ntile), dim3(64 * prk::kVisWaves), lv, svis, *fp,   \
                                offs, bins, won, list, nwin, wtag, pair_tri, trwon, anomaly);                         \
         else                                                                                                         \
-            hipLaunchKernelGGL((prk::k_vis<MS, UNI>), dim3(ntile), dim3(64 * prk::kVisWaves), lv, svis, *fp, offs,    \
+            hipLaunchKernelGGL((prk::k_vis<MS, UNI>), dim3(ntile), dim3(64 * prk::kVisWaves), lv, svis, *fp, offs,   \
                                bins, won, list, nwin, wtag, pair_tri, trwon, anomaly);                               \
         if (mid) (void)hipEventRecord(mid, svis);                                                                    \
         if (svis != s) (void)hipStreamWaitEvent(s, mid, 0);                                                          \
@@ -1930,16 +1917,16 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
             /* the won triangles; the count stays on the device (the run counter is the list length) */              \
             uint32_t *nsel = reinterpret_cast<uint32_t *>(sel_temp);                                                 \
             hipLaunchKernelGGL(prk::k_won_local, dim3(nwon), dim3(prk::kWonThreads), 0, s, fp->tri_count, trwon,     \
-                               tr, nsel, wlist);                                                                     \
+                               ranges, nsel, wlist);                                                                 \
             hipLaunchKernelGGL((prk::k_walk<UNI>), dim3(nwblk), dim3(64 * prk::kWalkWaves), 0, s, *fp, wlist, nsel,  \
-                               tri_off, tr, won, rp, anomaly);                                                       \
+                               tri_off, ranges, won, recs, anomaly);                                                 \
         }                                                                                                            \
         if (mid2) (void)hipEventRecord(mid2, s);                                                                     \
         if (fp->z_in_vis)                                                                                            \
             hipLaunchKernelGGL((prk::k_pix<UNI, false, true>), dim3(ntile * PRK_PIX_SPLIT), dim3(256), 0, s, *fp, nwin, \
-                               wtag, rp);                                                                            \
+                               wtag, recs);                                                                          \
         else                                                                                                         \
-            hipLaunchKernelGGL((prk::k_pix<UNI>), dim3(ntile * PRK_PIX_SPLIT), dim3(256), 0, s, *fp, nwin, wtag, rp); \
+            hipLaunchKernelGGL((prk::k_pix<UNI>), dim3(ntile * PRK_PIX_SPLIT), dim3(256), 0, s, *fp, nwin, wtag, recs); \
     } while (0)
     switch (modeset) {
         case prk::MODE_AVX:
@@ -1970,24 +1957,23 @@ hipError_t prk_launch_raster(const prk::FrameParams *fp, int modeset, const uint
 // Span path: visibility then shading of the pass's spans.  scalar_modes: bit
 // m set when the pass holds DrawModel spans of mode m (srecs non-null then);
 // bit MODE_AVX when it holds FillLineOptimized spans.
-hipError_t prk_launch_spans(const prk::FrameParams *fp, const uint32_t *offs, const uint32_t *bins, const void *pos,
-                            const void *recs, const void *srecs, uint32_t modes, const uint32_t *span_tri,
-                            uint32_t *nwin, uint32_t *wtag, hipStream_t s) {
+hipError_t prk_launch_spans(const prk::FrameParams *fp, const uint32_t *offs, const uint32_t *bins,
+                            const prk::SpanPos *pos,
+                            const prk::SpanRec *recs, const prk::ScSpanRec *srecs, uint32_t modes,
+                            const uint32_t *span_tri, uint32_t *nwin, uint32_t *wtag, hipStream_t s) {
     const uint32_t ntile = (uint32_t)(fp->tiles_x * fp->tiles_y);
     if (ntile == 0) return hipSuccess;
     const uint32_t sc = modes & ~(1u << prk::MODE_AVX);
     if (sc && !srecs) return hipErrorInvalidValue;
     const size_t lv = vis_lds(fp), ls = shade_lds(fp);
-    const prk::SpanPosK *P = reinterpret_cast<const prk::SpanPosK *>(pos);
-    const prk::ScSpanRec *SR = reinterpret_cast<const prk::ScSpanRec *>(srecs);
-    hipLaunchKernelGGL(prk::k_span_vis, dim3(ntile), dim3(64 * prk::kVisWaves), lv, s, *fp, offs, bins, P,
-                       reinterpret_cast<const prk::SpanRec *>(recs), SR, span_tri, nwin, wtag);
+    hipLaunchKernelGGL(prk::k_span_vis, dim3(ntile), dim3(64 * prk::kVisWaves), lv, s, *fp, offs, bins, pos,
+                       recs, srecs, span_tri, nwin, wtag);
     if ((modes & (1u << prk::MODE_AVX)) || fp->clear_fused)
         hipLaunchKernelGGL((prk::k_pix<false, true>), dim3(ntile * PRK_PIX_SPLIT), dim3(256), 0, s, *fp, nwin, wtag,
-                           reinterpret_cast<const prk::SpanRec *>(recs));
+                           recs);
 #define PRK_SPAN_SHADE(MS) \
-    hipLaunchKernelGGL((prk::k_span_shade<MS>), dim3(ntile), dim3(64 * prk::kShadeWaves), ls, s, *fp, offs, bins, P, \
-                       SR, nwin, wtag)
+    hipLaunchKernelGGL((prk::k_span_shade<MS>), dim3(ntile), dim3(64 * prk::kShadeWaves), ls, s, *fp, offs, bins, pos, \
+                       srecs, nwin, wtag)
     if (sc == (1u << prk::MODE_SC_GOURAUD)) PRK_SPAN_SHADE(prk::MODE_SC_GOURAUD);
     else if (sc == (1u << prk::MODE_SC_PHONG)) PRK_SPAN_SHADE(prk::MODE_SC_PHONG);
     else if (sc) PRK_SPAN_SHADE(-1);

@@ -19,10 +19,10 @@
 
 #include "../../include/prk_edge_count.h"
 using prk::ObjDesc;
+using prk::ObjEdge;
 using prk::ObjRun;
+using prk::PairRaw;
 using prk::kAdvWgCaps;
-using prk::kObjEdgeBytes;
-using prk::kPairRawBytes;
 using prk::packed_edge_bytes;
 using prk::packed_span_bytes;
 
@@ -114,13 +114,13 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
     PRK_TRY(hipStreamSynchronize(s));  // (tab is on this stack)
     fp.draws = (const prk::DrawRec *)S.d_rectab.p;
     fp.draw0 = d;
-    PRK_TRY(S.d_objtab.ensure((size_t)nobj * sizeof(ObjDesc)));
+    PRK_TRY(S.d_objtab.ensure_n<ObjDesc>(nobj));
     PRK_TRY(S.d_k0tab.ensure((size_t)nobj * 8));
-    void *d_objs = S.d_objtab.p;
+    ObjDesc *d_objs = S.d_objtab.as<ObjDesc>();
     uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
     const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nobj;
-    PRK_TRY(prk_obj_tables(static_cast<char *>(S.d_rectab.p) + kRunOff, 1, nobj, kObjWaveTris, d_objs, k0tab,
-                           k0tab + nobj, nullptr, nullptr, nullptr, 0u, nullptr, s));
+    PRK_TRY(prk_obj_tables(reinterpret_cast<const ObjRun *>(S.d_rectab.as<char>() + kRunOff), 1, nobj, kObjWaveTris,
+                           d_objs, k0tab, k0tab + nobj, nullptr, nullptr, nullptr, 0u, nullptr, s));
     const size_t es = 3 * (size_t)nt;
     PRK_TRY(S.d_ecnt.ensure(((size_t)nt + 1) * 4));
     PRK_TRY(S.d_escan.ensure(((size_t)nt + 1) * 4));
@@ -140,7 +140,7 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
     *total_out = total;
     const bool fill = keep || (records != nullptr && capacity >= total);
     if (fill && total) {
-        PRK_TRY(S.d_edges.ensure(es * kObjEdgeBytes));
+        PRK_TRY(S.d_edges.ensure_n<ObjEdge>(es));
         PRK_TRY(S.d_ekeys.ensure(es * 8));
         PRK_TRY(S.d_evals.ensure(es * 4));
         const size_t out_bytes = packed_edge_bytes(total);
@@ -155,19 +155,20 @@ static int edge_records_run(prk_context *c, int32_t geometry, uint32_t first_tri
         // MergeSort per object: at most 64 edges by one wave each
         // (k_obj_sort_local, into the working copy), else one radix sort
         const bool local_sort = maxn <= 64;
-        PRK_TRY(prk_rec_emit(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, escan, setup, pbits, S.d_edges.p,
-                             S.d_ekeys.p, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
+        unsigned long long *ekeys = S.d_ekeys.as<unsigned long long>();
+        PRK_TRY(prk_rec_emit(&fp, d_objs, d_k0obj, d_k0tri0, nobj, nt, escan, setup, pbits, S.d_edges.as<ObjEdge>(),
+                             ekeys, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
         if (local_sort) {
-            PRK_TRY(S.d_work.ensure(es * kObjEdgeBytes));
-            PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nobj, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, nullptr,
-                                       (uint32_t *)S.d_err.p, s));
-            PRK_TRY(prk_rec_export(S.d_work.p, nullptr, total, d_out, s));
+            PRK_TRY(S.d_work.ensure_n<ObjEdge>(es));
+            PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nobj, escan, ekeys, S.d_edges.as<ObjEdge>(),
+                                       S.d_work.as<ObjEdge>(), nullptr, (uint32_t *)S.d_err.p, s));
+            PRK_TRY(prk_rec_export(S.d_work.as<ObjEdge>(), nullptr, total, d_out, s));
         } else {
             PRK_TRY(S.d_ekeys2.ensure(es * 8));
             PRK_TRY(S.d_ord.ensure(es * 4));
-            PRK_TRY(obj_sort(S.d_temp, S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
+            PRK_TRY(obj_sort(S.d_temp, ekeys, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, (uint32_t *)S.d_ord.p, 3 * nt,
                              obits + ybits + pbits, s));
-            PRK_TRY(prk_rec_export(S.d_edges.p, (const uint32_t *)S.d_ord.p, total, d_out, s));
+            PRK_TRY(prk_rec_export(S.d_edges.as<ObjEdge>(), (const uint32_t *)S.d_ord.p, total, d_out, s));
         }
         uint32_t err = 0;
         PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
@@ -594,7 +595,7 @@ static int walk_begin(prk_context *c, WalkPlan &plan, const void *records, hipMe
     prk_context::SpanScratch &S = c->spans;
     const uint32_t n = plan.n;
     PRK_TRY(S.d_recout.ensure(packed_edge_bytes(n)));
-    PRK_TRY(S.d_work.ensure((size_t)n * kObjEdgeBytes));
+    PRK_TRY(S.d_work.ensure_n<ObjEdge>(n));
     PRK_TRY(S.d_escan.ensure((tab.size() + router.words.size()) * 4));
     if (tables > 1) {
         PRK_TRY(S.d_scnt.ensure(nl1 * 4));
@@ -606,9 +607,9 @@ static int walk_begin(prk_context *c, WalkPlan &plan, const void *records, hipMe
     }
     if (use_err) PRK_TRY(S.d_err.ensure(16));
     if (fill) {
-        PRK_TRY(S.d_raw.ensure(std::max<size_t>((size_t)plan.nslot * kPairRawBytes, 16)));
+        PRK_TRY(S.d_raw.ensure(std::max<size_t>(plan.nslot * sizeof(PairRaw), 16)));
         if (tables == 2) PRK_TRY(S.d_pos.ensure(std::max<size_t>((size_t)plan.nslot * 4, 16)));      // the slots' rows
-        if (tables == 3) PRK_TRY(S.d_rowslot.ensure(std::max<size_t>((size_t)plan.nrslot * 8, 16)));  // {row, pairs}
+        if (tables == 3) PRK_TRY(S.d_rowslot.ensure(std::max<size_t>(plan.nrslot * sizeof(prk::RowRec), 16)));
     }
     PRK_TRY(hipMemcpyAsync(S.d_recout.p, records, (size_t)n * sizeof(prk_edge), kind, s));
     PRK_TRY(hipMemcpyAsync(S.d_escan.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
@@ -621,16 +622,16 @@ static int walk_begin(prk_context *c, WalkPlan &plan, const void *records, hipMe
     PRK_TRY(hipStreamSynchronize(s));  // (tab is this call's; records may be an output)
     const uint32_t *d_lscan = (const uint32_t *)S.d_escan.p, *d_route = wg ? d_lscan + tab.size() : nullptr;
     *d_lists = wg ? d_route + nl1 : nullptr;
-    a->work = S.d_work.p;
+    a->work = S.d_work.as<ObjEdge>();
     a->lscan = d_lscan;
     a->nlist = plan.list_count;
     a->route = d_route;
     a->height = height;
     a->sbase = tables > 1 ? d_lscan + nl1 : nullptr;
     a->rbase = tables > 2 ? d_lscan + 2 * nl1 : nullptr;
-    a->raw = fill ? S.d_raw.p : nullptr;
+    a->raw = fill ? S.d_raw.as<PairRaw>() : nullptr;
     a->prow = fill && tables == 2 ? (int32_t *)S.d_pos.p : nullptr;
-    a->rows = fill && tables == 3 ? S.d_rowslot.p : nullptr;
+    a->rows = fill && tables == 3 ? S.d_rowslot.as<prk::RowRec>() : nullptr;
     a->cnt = tables > 1 ? (uint32_t *)S.d_scnt.p : nullptr;
     a->rcnt = tables > 2 ? (uint32_t *)S.d_rowcnt.p : nullptr;
     a->err = (uint32_t *)S.d_err.p;
@@ -670,8 +671,8 @@ static int advance_run(prk_context *c, WalkPlan &plan, const void *records, hipM
         d_out = keep->rec;
     }
     PRK_TRY(walk_launch(c, plan, a, d_lists));
-    if (records_out || keep) PRK_TRY(prk_rec_export(S.d_work.p, nullptr, n, d_out, s));
-    if (next_out) PRK_TRY(prk_adv_next(S.d_work.p, n, (int32_t *)S.d_evals.p, s));
+    if (records_out || keep) PRK_TRY(prk_rec_export(S.d_work.as<ObjEdge>(), nullptr, n, d_out, s));
+    if (next_out) PRK_TRY(prk_adv_next(S.d_work.as<ObjEdge>(), n, (int32_t *)S.d_evals.p, s));
     uint32_t err = 0;
     if (wg) PRK_TRY(hipMemcpyAsync(&err, S.d_err.p, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernels ran
@@ -738,7 +739,8 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
         void *buf = nullptr;
         if (nspan) {
             PRK_TRY(hipMalloc(&buf, packed_span_bytes(nspan)));
-            hipError_t e = prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, buf, s);
+            hipError_t e = prk_span_pack(S.d_raw.as<PairRaw>(), (const int32_t *)S.d_pos.p, d_sbase, d_cscan,
+                                         list_count, nspan, buf, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) {
                 (void)hipFree(buf);
@@ -754,7 +756,8 @@ static int spans_run(prk_context *c, WalkPlan &plan, const void *records, hipMem
     if (capacity < nspan) return PRK_ERR_ARG;
     if (nspan == 0) return PRK_OK;
     PRK_TRY(S.d_spanout.ensure(packed_span_bytes(nspan)));
-    PRK_TRY(prk_span_pack(S.d_raw.p, (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan, S.d_spanout.p, s));
+    PRK_TRY(prk_span_pack(S.d_raw.as<PairRaw>(), (const int32_t *)S.d_pos.p, d_sbase, d_cscan, list_count, nspan,
+                          S.d_spanout.p, s));
     PRK_TRY(hipStreamSynchronize(s));  // nothing is written to `spans` unless the kernel ran
     PRK_TRY(hipMemcpyAsync(spans, S.d_spanout.p, (size_t)nspan * sizeof(prk_span), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
@@ -822,8 +825,8 @@ static int rows_run(prk_context *c, WalkPlan &plan, const void *records, hipMemc
     if (fill && !is_short && (npair || nrow)) {
         PRK_TRY(S.d_spanout.ensure(std::max<size_t>((size_t)npair * sizeof(prk_row_pair), 16)));
         PRK_TRY(S.d_rowout.ensure(std::max<size_t>((size_t)nrow * sizeof(prk_row), 16)));
-        PRK_TRY(prk_row_pack(S.d_raw.p, S.d_rowslot.p, d_sbase, d_rbase, d_pscan, d_rscan, list_count, npair, nrow,
-                             S.d_spanout.p, S.d_rowout.p, s));
+        PRK_TRY(prk_row_pack(S.d_raw.as<PairRaw>(), S.d_rowslot.as<prk::RowRec>(), d_sbase, d_rbase, d_pscan, d_rscan,
+                             list_count, npair, nrow, S.d_spanout.p, S.d_rowout.as<prk::RowRec>(), s));
         PRK_TRY(hipStreamSynchronize(s));  // nothing is written to the outputs unless the kernel ran
     }
     *row_total_out = nrow;
@@ -890,19 +893,21 @@ static int records_plan(prk_context *c, const Records &R, uint32_t first_list, u
     for (uint32_t o = 0; o < nlist; at += cnt[o], ++o) lscan[o] = at;
     lscan[nlist] = at;
     const void *rec = R.at(r0);
-    // device: lscan | the statistics (24 bytes a list) | the candidates | their most linked
-    const size_t stat_off = (plan.nl1 * 4 + 7) & ~(size_t)7, cand_off = stat_off + (size_t)nlist * 24;
+    // device: lscan | the statistics (ListStatsLayout) | the candidates | their most linked
+    const prk::ListStatsLayout lay{nlist};
+    const size_t stat_off = (plan.nl1 * 4 + 7) & ~(size_t)7, cand_off = stat_off + lay.bytes();
     PRK_TRY(S.d_lstat.ensure(cand_off + (size_t)nlist * 8));
     char *base = static_cast<char *>(S.d_lstat.p);
     const uint32_t *d_lscan = reinterpret_cast<const uint32_t *>(base);
     uint32_t *d_cand = reinterpret_cast<uint32_t *>(base + cand_off), *d_most = d_cand + nlist;
     PRK_TRY(hipMemcpyAsync(base, lscan.data(), plan.nl1 * 4, hipMemcpyHostToDevice, s));
     PRK_TRY(prk_list_stats(rec, at, d_lscan, nlist, height, base + stat_off, s));
-    std::vector<uint64_t> raw(3 * (size_t)nlist);  // edge-rows, scans, {ymin0 ..., ymax_max ...}
-    PRK_TRY(hipMemcpyAsync(raw.data(), base + stat_off, (size_t)nlist * 24, hipMemcpyDeviceToHost, s));
+    std::vector<unsigned long long> raw(lay.bytes() / 8);
+    PRK_TRY(hipMemcpyAsync(raw.data(), base + stat_off, lay.bytes(), hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
-    const uint64_t *erows = raw.data(), *scans = erows + nlist;
-    const int32_t *ymin0 = reinterpret_cast<const int32_t *>(scans + nlist), *ymax_max = ymin0 + nlist;
+    const prk::ListStatsView st = lay.view(raw.data());
+    const unsigned long long *erows = st.erows, *scans = st.scans;
+    const int32_t *ymin0 = st.ymin0, *ymax_max = st.ymaxmax;
     ListRouter &router = plan.router;
     std::vector<uint32_t> cand, most;
     for (uint32_t o = 0; o < nlist; ++o)

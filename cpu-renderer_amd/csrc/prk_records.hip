@@ -939,13 +939,13 @@ hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const pr
     if (kind < 0 || kind > 2) return hipErrorInvalidValue;
     const uint32_t nlist = a->nlist;
     if (total == 0 || nlist == 0) return hipSuccess;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
+    prk::ObjEdge *w = a->work;
     hipLaunchKernelGGL(prk::k_adv_import, dim3((total + prk::kPrepEdges - 1) / prk::kPrepEdges),
                        dim3(prk::kPrepEdges), 0, s, reinterpret_cast<const uint4 *>(records), total, w);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const dim3 grid((nlist + prk::kLinkThreads - 1) / prk::kLinkThreads), block(prk::kLinkThreads);
-    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
+    prk::PairRaw *pr = a->raw;
     if (kind == 0)
         hipLaunchKernelGGL(prk::k_adv_walk, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height);
     else if (kind == 1 && pr)
@@ -956,7 +956,7 @@ hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const pr
                            a->sbase, (prk::PairRaw *)nullptr, (int32_t *)nullptr, a->cnt, a->err);
     else if (pr)
         hipLaunchKernelGGL(prk::k_row_walk<true>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
-                           a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt, a->rcnt, a->err);
+                           a->sbase, a->rbase, pr, a->rows, a->cnt, a->rcnt, a->err);
     else
         hipLaunchKernelGGL(prk::k_row_walk<false>, grid, block, 0, s, w, a->lscan, nlist, a->route, a->height,
                            a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt, a->rcnt, a->err);
@@ -964,41 +964,40 @@ hipError_t prk_list_walk(int kind, const void *records, uint32_t total, const pr
 }
 // The `total` spans the walk left (cscan: the scanned counts, nlist + 1) as
 // packed prk_span; `out` holds 25 * total dwords rounded up to four.
-hipError_t prk_span_pack(const void *raw, const int32_t *row, const uint32_t *sbase, const uint32_t *cscan,
+hipError_t prk_span_pack(const prk::PairRaw *raw, const int32_t *row, const uint32_t *sbase, const uint32_t *cscan,
                          uint32_t nlist, uint32_t total, void *out, hipStream_t s) {
     if (total == 0 || nlist == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_span_pack, dim3((total + prk::kPackSpans - 1) / prk::kPackSpans),
-                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const prk::PairRaw *>(raw), row, sbase, cscan,
+                       dim3(prk::kPackSpans), 0, s, raw, row, sbase, cscan,
                        nlist, total, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }
 // The npair pairs and nrow rows the walk left (pscan, rscan: the scanned
 // counts, nlist + 1 each) as packed prk_row_pair and prk_row.
-hipError_t prk_row_pack(const void *raw, const void *rows, const uint32_t *sbase, const uint32_t *rbase,
+hipError_t prk_row_pack(const prk::PairRaw *raw, const prk::RowRec *rows, const uint32_t *sbase, const uint32_t *rbase,
                         const uint32_t *pscan, const uint32_t *rscan, uint32_t nlist, uint32_t npair, uint32_t nrow,
-                        void *pairs_out, void *rows_out, hipStream_t s) {
+                        void *pairs_out, prk::RowRec *rows_out, hipStream_t s) {
     if (nlist == 0 || (npair == 0 && nrow == 0)) return hipSuccess;
     const uint32_t npb = (npair + prk::kPackSpans - 1) / prk::kPackSpans;
     const uint32_t nrb = (nrow + prk::kPackSpans - 1) / prk::kPackSpans;
     hipLaunchKernelGGL(prk::k_row_pack, dim3(npb + nrb), dim3(prk::kPackSpans), 0, s,
-                       reinterpret_cast<const prk::PairRaw *>(raw), reinterpret_cast<const int2 *>(rows), sbase, rbase,
-                       pscan, rscan, nlist, npair, nrow, npb, reinterpret_cast<uint4 *>(pairs_out),
-                       reinterpret_cast<int2 *>(rows_out));
+                       raw, rows, sbase, rbase,
+                       pscan, rscan, nlist, npair, nrow, npb, reinterpret_cast<uint4 *>(pairs_out), rows_out);
     return hipGetLastError();
 }
 // prk_draw_rows: the rows' EdgeCounts (nrow + 1 words, the last 0) for the
 // scan, and npair packed pairs as packed prk_span (`out`: 25 * npair dwords
 // rounded up to four), each on its row's RowIndex.
-hipError_t prk_rows_counts(const void *rows, uint32_t nrow, uint32_t *cnt, hipStream_t s) {
+hipError_t prk_rows_counts(const prk::RowRec *rows, uint32_t nrow, uint32_t *cnt, hipStream_t s) {
     hipLaunchKernelGGL(prk::k_rows_counts, dim3(nrow / 256 + 1), dim3(256), 0, s,
-                       reinterpret_cast<const int2 *>(rows), nrow, cnt);
+                       rows, nrow, cnt);
     return hipGetLastError();
 }
-hipError_t prk_rows_unpack(const void *rows, const uint32_t *rscan, uint32_t nrow, const void *pairs, uint32_t npair,
-                           void *out, hipStream_t s) {
+hipError_t prk_rows_unpack(const prk::RowRec *rows, const uint32_t *rscan, uint32_t nrow, const void *pairs,
+                           uint32_t npair, void *out, hipStream_t s) {
     if (nrow == 0 || npair == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_rows_unpack, dim3((npair + prk::kPackSpans - 1) / prk::kPackSpans),
-                       dim3(prk::kPackSpans), 0, s, reinterpret_cast<const int2 *>(rows), rscan, nrow,
+                       dim3(prk::kPackSpans), 0, s, rows, rscan, nrow,
                        reinterpret_cast<const uint4 *>(pairs), npair, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }
@@ -1006,18 +1005,17 @@ hipError_t prk_rows_unpack(const void *rows, const uint32_t *rscan, uint32_t nro
 // a handle's packed buffer into the slots of objects obj0 .. (k_span_handle_walk).
 hipError_t prk_span_handle_walk(const prk::FrameParams *fp, uint32_t draw, uint32_t g0, uint32_t obj0,
                                 const void *spans, uint32_t first, uint32_t count, const unsigned long long *soff,
-                                void *recs, void *pos, uint32_t *span_tri, hipStream_t s) {
+                                prk::SpanRecG *recs, prk::SpanPos *pos, uint32_t *span_tri, hipStream_t s) {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_span_handle_walk, dim3((count + prk::kHandleSpans - 1) / prk::kHandleSpans),
                        dim3(prk::kHandleSpans), 0, s, *fp, draw, g0, obj0, reinterpret_cast<const uint4 *>(spans),
-                       first, count, soff, reinterpret_cast<prk::SpanRecG *>(recs),
-                       reinterpret_cast<prk::SpanPos *>(pos), span_tri);
+                       first, count, soff, recs, pos, span_tri);
     return hipGetLastError();
 }
-hipError_t prk_adv_next(const void *work, uint32_t total, int32_t *next_out, hipStream_t s) {
+hipError_t prk_adv_next(const prk::ObjEdge *work, uint32_t total, int32_t *next_out, hipStream_t s) {
     if (total == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_adv_next, dim3((total + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjEdge *>(work), total, next_out);
+                       work, total, next_out);
     return hipGetLastError();
 }
 
@@ -1059,10 +1057,10 @@ hipError_t prk_list_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint
                             const prk::ListWalkArgs *a, hipStream_t s) {
     if (nl == 0) return hipSuccess;
     if (lcap == 0 || lcap > prk_adv_wg_lcap()) return hipErrorInvalidValue;
-    prk::ObjEdge *w = reinterpret_cast<prk::ObjEdge *>(a->work);
+    prk::ObjEdge *w = a->work;
     const dim3 grid(nl), block(prk::slot_threads(lcap));
     const size_t bytes = prk::slot_lds_bytes(lcap);
-    prk::PairRaw *pr = reinterpret_cast<prk::PairRaw *>(a->raw);
+    prk::PairRaw *pr = a->raw;
     switch (kind) {
         case 0:
             hipLaunchKernelGGL(prk::k_adv_walk_wg, grid, block, bytes, s, w, a->lscan, lists, lcap, a->height,
@@ -1079,8 +1077,7 @@ hipError_t prk_list_walk_wg(int kind, uint32_t lcap, const uint32_t *lists, uint
         case 2:
             if (pr)
                 hipLaunchKernelGGL(prk::k_row_walk_wg<true>, grid, block, bytes, s, w, a->lscan, lists, lcap,
-                                   a->height, a->sbase, a->rbase, pr, reinterpret_cast<int2 *>(a->rows), a->cnt,
-                                   a->rcnt, a->err);
+                                   a->height, a->sbase, a->rbase, pr, a->rows, a->cnt, a->rcnt, a->err);
             else
                 hipLaunchKernelGGL(prk::k_row_walk_wg<false>, grid, block, bytes, s, w, a->lscan, lists, lcap,
                                    a->height, a->sbase, a->rbase, (prk::PairRaw *)nullptr, (int2 *)nullptr, a->cnt,

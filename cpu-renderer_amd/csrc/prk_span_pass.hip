@@ -16,15 +16,23 @@
 
 #include "prk_ctx.h"
 
+using prk::EdgeIn;
 using prk::ListSrc;
+using prk::MaxactLayout;
 using prk::ObjDesc;
+using prk::ObjEdge;
 using prk::ObjRun;
+using prk::ObjSeg;
+using prk::PairRaw;
+using prk::PrObj;
+using prk::PrRow;
 using prk::PrepSeg;
+using prk::ScSpanRec;
+using prk::SpanPos;
+using prk::SpanRec;
+using prk::SpanRecG;
 using prk::kAdvWgCaps;
-using prk::kObjEdgeBytes;
-using prk::kPairRawBytes;
 using prk::kPrepEdges;
-using prk::kScSpanRecBytes;
 using prk::kWaveListArrays;
 
 namespace {
@@ -83,24 +91,26 @@ uint32_t slot_class(int32_t most, uint32_t lcap) {
 
 // The classification block of a pass with n large objects (SpanScratch
 // h_cls, d_cls), one layout for the host's pinned copy and the device's:
-// (most, rows, entries) as k_obj_maxact writes them (12 n bytes), then the
+// (most, rows, entries) as k_obj_maxact writes them (MaxactLayout), then the
 // walk groups' objects, pool offsets and list capacities, the chunked walk's
-// table (prk_spans.hip PrObj, 8 words an object) and its objects by group,
-// and the huge walk's (rows, entries) per object in walk-group order.
+// table (PrObj) and its objects by group, and the huge walk's (rows, entries)
+// per object in walk-group order.
 struct ClsView {
     int32_t *most, *rows, *ents;
     uint32_t *big;
     unsigned long long *off;
-    uint32_t *cap, *pr, *grp, *meta;
+    uint32_t *cap;
+    PrObj *pr;
+    uint32_t *grp, *meta;
 };
 struct ClsLayout {
     size_t n, big, off, cap, pr, grp, meta, end;
     explicit ClsLayout(uint32_t nbig = 0) : n(nbig) {
-        big = 12 * n;
+        big = MaxactLayout{n}.bytes();
         off = (big + 4 * n + 7) & ~(size_t)7;
         cap = off + 8 * n;
         pr = cap + 4 * n;
-        grp = pr + 32 * n;
+        grp = pr + sizeof(PrObj) * n;
         meta = grp + 4 * n;
         end = meta + 8 * n;
     }
@@ -109,14 +119,14 @@ struct ClsLayout {
     size_t upload_bytes() const { return end - big; }
     ClsView view(void *base) const {
         char *b = static_cast<char *>(base);
-        int32_t *m = reinterpret_cast<int32_t *>(b);
-        return ClsView{m,
-                       m + n,
-                       m + 2 * n,
+        const prk::MaxactView m = MaxactLayout{n}.view(b);
+        return ClsView{m.most,
+                       m.rows,
+                       m.ents,
                        reinterpret_cast<uint32_t *>(b + big),
                        reinterpret_cast<unsigned long long *>(b + off),
                        reinterpret_cast<uint32_t *>(b + cap),
-                       reinterpret_cast<uint32_t *>(b + pr),
+                       reinterpret_cast<PrObj *>(b + pr),
                        reinterpret_cast<uint32_t *>(b + grp),
                        reinterpret_cast<uint32_t *>(b + meta)};
     }
@@ -243,14 +253,14 @@ static void classify_chunked(const SpanSwitches &sw, uint32_t lcap, const BigObj
                 if (out.pr_ents + ents > kPrMaxEntries || out.npr >= 65535 ||
                     (uint64_t)out.pr_rows + rows + 1 > 0x7FFFFFFFull)
                     continue;
-                uint32_t *q = h.pr + 8 * (size_t)out.npr;
-                q[0] = big_gl[bi];
-                q[1] = out.pr_rows;
-                q[2] = (uint32_t)rows;
-                q[3] = out.pr_chunks;
-                q[4] = (uint32_t)most;
-                q[5] = (uint32_t)out.pr_ents;
-                q[6] = q[7] = 0;
+                PrObj &q = h.pr[out.npr];
+                q.o = big_gl[bi];
+                q.row_off = out.pr_rows;
+                q.rows = (uint32_t)rows;
+                q.chunk_off = out.pr_chunks;
+                q.most = (uint32_t)most;
+                q.ent_off = (uint32_t)out.pr_ents;
+                q.pad0 = q.pad1 = 0;
                 h.grp[out.npr] = out.npr;
                 out.pr_rows += (uint32_t)rows + 1;
                 out.pr_chunks += nch;
@@ -297,7 +307,7 @@ struct SpanPass {
     uint32_t modes = 0;
     bool scalar = false, local_sort = false, segmented = false;
     uint64_t max_segs = 0;
-    void *d_objs = nullptr;
+    ObjDesc *d_objs = nullptr;
     uint32_t *escan = nullptr;
     const uint32_t *total0p = nullptr;
     unsigned long long *oslot = nullptr;
@@ -309,9 +319,9 @@ struct SpanPass {
 
     SpanPass(prk_context *ctx, hipStream_t stream, const std::vector<prk::DrawRec> &d)
         : c(ctx), S(ctx->spans), s(stream), draws(d) {}
-    void *dev(const StagePart &p) const { return static_cast<char *>(S.d_stage.p) + p.off; }
-    void *srecs() const { return scalar ? S.d_srecs.p : nullptr; }  // DrawModel span records
-    void *wy() const { return segmented ? S.d_wy.p : nullptr; }
+    void *dev(const StagePart &p) const { return S.d_stage.as<char>() + p.off; }
+    ScSpanRec *srecs() const { return scalar ? S.d_srecs.as<ScSpanRec>() : nullptr; }  // DrawModel span records
+    int2 *wy() const { return segmented ? S.d_wy.as<int2>() : nullptr; }
     int plan();
     int upload();
     int edges();
@@ -534,9 +544,9 @@ int SpanPass::upload() {
 // and its scan into the objects' first span slots.
 int SpanPass::edges() {
     // the objects (ObjDesc), the kind-0 objects' indices and first triangles
-    PRK_TRY(S.d_objtab.ensure((size_t)std::max<uint32_t>(nobj, 1) * sizeof(ObjDesc)));
+    PRK_TRY(S.d_objtab.ensure_n<ObjDesc>(std::max<uint32_t>(nobj, 1)));
     PRK_TRY(S.d_k0tab.ensure((size_t)std::max<uint32_t>(nk0, 1) * 8));
-    d_objs = S.d_objtab.p;
+    d_objs = S.d_objtab.as<ObjDesc>();
     uint32_t *k0tab = (uint32_t *)S.d_k0tab.p;
     const uint32_t *d_k0obj = k0tab, *d_k0tri0 = k0tab + nk0;
     // the batch lists' first edges: the scan of their counts
@@ -552,15 +562,15 @@ int SpanPass::edges() {
         if (handles) {  // the lists' tables from their sources, on the device
             PRK_TRY(S.d_ltab.ensure((2 * (size_t)nlist + 1) * 4));
             uint32_t *lt = (uint32_t *)S.d_ltab.p;
-            PRK_TRY(prk_list_tables(dev(st_runs), (uint32_t)S.h_runs.size(), nobj, d_lcnt, d_lflag, dev(st_lsrc), nlist,
-                                    lt, lt + nlist + 1, s));
+            PRK_TRY(prk_list_tables(static_cast<const ObjRun *>(dev(st_runs)), (uint32_t)S.h_runs.size(), nobj, d_lcnt,
+                                    d_lflag, static_cast<const ListSrc *>(dev(st_lsrc)), nlist, lt, lt + nlist + 1, s));
             d_lcnt = lt;
             d_lflag = lt + nlist + 1;
         }
         PRK_TRY(scan_u32(S.d_temp, d_lcnt, lscan, nlist + 1, s));
     }
-    PRK_TRY(prk_obj_tables(dev(st_runs), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris, d_objs, k0tab, k0tab + nk0,
-                           d_lcnt, d_lflag, lscan, kObjWaveEdges, lobj, s));
+    PRK_TRY(prk_obj_tables(static_cast<const ObjRun *>(dev(st_runs)), (uint32_t)S.h_runs.size(), nobj, kObjWaveTris,
+                           d_objs, k0tab, k0tab + nk0, d_lcnt, d_lflag, lscan, kObjWaveEdges, lobj, s));
     const uint32_t *d_k1src = (const uint32_t *)dev(st_k1src);
     for (const auto &d : draws) modes |= 1u << d.mode;
     scalar = (modes & ~(1u << prk::MODE_AVX)) != 0;
@@ -570,7 +580,7 @@ int SpanPass::edges() {
     PRK_TRY(S.d_escan.ensure(((size_t)nt + 1) * 4));
     PRK_TRY(S.d_rcnt.ensure(((size_t)nt + 1) * 8));
     PRK_TRY(S.d_rscan.ensure(((size_t)nt + 1) * 8));
-    PRK_TRY(S.d_edges.ensure(es * kObjEdgeBytes));
+    PRK_TRY(S.d_edges.ensure_n<ObjEdge>(es));
     PRK_TRY(S.d_ekeys.ensure(es * 8));
     PRK_TRY(S.d_ekeys2.ensure(es * 8));
     PRK_TRY(S.d_evals.ensure(es * 4));
@@ -579,6 +589,8 @@ int SpanPass::edges() {
     PRK_TRY(hipMemsetAsync(S.d_err.p, 0, 16, s));  // (error bits, then the chunked walk's tally)
     escan = (uint32_t *)S.d_escan.p;
     uint32_t *ord = (uint32_t *)S.d_ord.p;
+    ObjEdge *d_edges = S.d_edges.as<ObjEdge>();
+    unsigned long long *ekeys = S.d_ekeys.as<unsigned long long>();
     unsigned long long *rscan = (unsigned long long *)S.d_rscan.p;
     total0p = escan + nt;
     if (nt) {
@@ -594,10 +606,10 @@ int SpanPass::edges() {
     // edges (k_obj_sort_local, with the gather), else one radix sort of the
     // padded keys (prk_spans.hip)
     local_sort = nt && maxn <= 64 && sw.local_sort;
-    PRK_TRY(prk_objtri_emit(&fp, d_objs, d_k0obj, d_k0tri0, nk0, nt, escan, pbits, ybits, c->H, S.d_edges.p,
-                            S.d_ekeys.p, (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
+    PRK_TRY(prk_objtri_emit(&fp, d_objs, d_k0obj, d_k0tri0, nk0, nt, escan, pbits, ybits, c->H, d_edges, ekeys,
+                            (uint32_t *)S.d_evals.p, local_sort ? 0 : 1, s));
     if (nt && !local_sort)
-        PRK_TRY(obj_sort(S.d_temp, S.d_ekeys.p, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt,
+        PRK_TRY(obj_sort(S.d_temp, ekeys, (uint32_t *)S.d_evals.p, S.d_ekeys2.p, ord, 3 * nt,
                          obits + ybits + pbits, s));
     PRK_TRY(S.d_bound.ensure(((size_t)nobj + 1) * 8));
     PRK_TRY(S.d_oslot.ensure(((size_t)nobj + 1) * 8));
@@ -605,28 +617,31 @@ int SpanPass::edges() {
     // The walk's working copy (the triangle edges, the prk_draw_edges lists,
     // the batch lists).
     const uint32_t nwork = 3 * nt + (uint32_t)nk1 + nledge;
-    PRK_TRY(S.d_work.ensure(std::max<size_t>(nwork, 1) * kObjEdgeBytes));
+    PRK_TRY(S.d_work.ensure_n<ObjEdge>(std::max<size_t>(nwork, 1)));
+    ObjEdge *work = S.d_work.as<ObjEdge>();
     // The small triangle objects' segments (prk_spans.hip k_obj_seg, walk()):
     // a thread per stretch of rows with a non-empty list.
     max_segs = 3 * small_tris + small_ledges;  // (a segment has an edge at least)
     segmented = max_segs && max_segs < 0x7FFFFFFFull && sw.segments;
     if (segmented) PRK_TRY(S.d_wy.ensure((size_t)std::max<uint32_t>(nwork, 1) * 8));
     if (local_sort)
-        PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nk0, escan, S.d_ekeys.p, S.d_edges.p, S.d_work.p, wy(),
+        PRK_TRY(prk_obj_sort_local(d_objs, d_k0obj, nk0, escan, ekeys, d_edges, work, wy(),
                                    (uint32_t *)S.d_err.p, s));
     if (!local_sort || nk1)
-        PRK_TRY(prk_obj_gather(S.d_edges.p, local_sort ? nullptr : ord, total0p, dev(st_edges), d_k1src, (uint32_t)nk1,
-                               S.d_work.p, 3 * nt + (uint32_t)nk1, wy(), s));
+        PRK_TRY(prk_obj_gather(d_edges, local_sort ? nullptr : ord, total0p,
+                               static_cast<const EdgeIn *>(dev(st_edges)), d_k1src,
+                               (uint32_t)nk1, work, 3 * nt + (uint32_t)nk1, wy(), s));
     // the batch lists' records into it, with their lists' row sums; then the
     // span slots: each object's bound, exclusive-scanned into its first slot
     if (handles)
-        PRK_TRY(prk_list_prep_segs(&fp, dev(st_lseg), (uint32_t)S.h_segs.size(), nsegblk, lscan, nlist, lobj, d_objs,
-                                   total0p, (uint32_t)nk1, S.d_work.p, wy(), (unsigned long long *)S.d_lrows.p, s));
+        PRK_TRY(prk_list_prep_segs(&fp, static_cast<const PrepSeg *>(dev(st_lseg)), (uint32_t)S.h_segs.size(), nsegblk,
+                                   lscan, nlist, lobj,
+                                   d_objs, total0p, (uint32_t)nk1, work, wy(), (unsigned long long *)S.d_lrows.p, s));
     else
         PRK_TRY(prk_list_prep(&fp, dev(st_ledges), nledge, lscan, nlist, lobj, d_objs, total0p, (uint32_t)nk1,
-                              S.d_work.p, wy(), (unsigned long long *)S.d_lrows.p, s));
-    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, dev(st_edges), (const unsigned long long *)S.d_lrows.p,
-                          (unsigned long long *)S.d_bound.p, s));
+                              work, wy(), (unsigned long long *)S.d_lrows.p, s));
+    PRK_TRY(prk_obj_bound(&fp, d_objs, nobj, rscan, static_cast<const EdgeIn *>(dev(st_edges)),
+                          (const unsigned long long *)S.d_lrows.p, (unsigned long long *)S.d_bound.p, s));
     PRK_TRY(scan_u64(S.d_temp, (const unsigned long long *)S.d_bound.p, oslot, nobj + 1, s));
     return PRK_OK;
 }
@@ -644,20 +659,21 @@ int SpanPass::sizes() {
         PRK_TRY(hipHostMalloc((void **)&S.h_cls, want, hipHostMallocDefault));
         S.cls_cap = want;
     }
+    const size_t most_bytes = MaxactLayout{nbig}.bytes();
     if (nbig) {
         const uint32_t *d_big = (const uint32_t *)dev(st_big);
-        PRK_TRY(S.d_most.ensure((size_t)nbig * 12));
-        PRK_TRY(prk_obj_maxact(&fp, d_objs, d_big, nbig, escan, total0p, S.d_work.p, (int32_t *)S.d_most.p,
+        PRK_TRY(S.d_most.ensure(most_bytes));
+        PRK_TRY(prk_obj_maxact(&fp, d_objs, d_big, nbig, escan, total0p, S.d_work.as<ObjEdge>(), S.d_most.as<int32_t>(),
                                sw.huge_edges, s));
         for (uint32_t &r : S.walk_routes) r = 0;  // (prk_debug_walk_routes: this pass's)
         for (uint32_t b = 0; b < nbig; ++b)  // (objects of sw.huge_edges edges or more: many workgroups each)
             if (big.all_edges[b] >= sw.huge_edges) {
                 ++S.walk_routes[8];
                 PRK_TRY(S.d_mhuge.ensure(prk_maxact_huge_scratch()));
-                PRK_TRY(prk_obj_maxact_huge(&fp, d_objs, d_big, b, nbig, big.all_edges[b], escan, total0p, S.d_work.p,
-                                            (int32_t *)S.d_most.p, S.d_mhuge.p, s));
+                PRK_TRY(prk_obj_maxact_huge(&fp, d_objs, d_big, b, nbig, big.all_edges[b], escan, total0p,
+                                            S.d_work.as<ObjEdge>(), S.d_most.as<int32_t>(), S.d_mhuge.p, s));
             }
-        PRK_TRY(hipMemcpyAsync(S.h_cls, S.d_most.p, (size_t)nbig * 12, hipMemcpyDeviceToHost, s));
+        PRK_TRY(hipMemcpyAsync(S.h_cls, S.d_most.p, most_bytes, hipMemcpyDeviceToHost, s));
     }
     PRK_TRY(hipMemcpyAsync(S.h_rb, oslot + nobj, 8, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipStreamSynchronize(s));
@@ -666,17 +682,17 @@ int SpanPass::sizes() {
     if (nslot64 >= prk::kMaxPairs) return PRK_ERR_LIMIT;  // 31-bit span tags
     nslot = (uint32_t)nslot64;
     const size_t ns = std::max<uint32_t>(nslot, 1);
-    PRK_TRY(S.d_recs.ensure(ns * 64));
-    PRK_TRY(S.d_pos.ensure(ns * 16));
+    PRK_TRY(S.d_recs.ensure_n<SpanRec>(ns));
+    PRK_TRY(S.d_pos.ensure_n<SpanPos>(ns));
     PRK_TRY(S.d_span_tri.ensure(ns * 4));
-    if (scalar) PRK_TRY(S.d_srecs.ensure(ns * kScSpanRecBytes));
-    if (nbig) PRK_TRY(S.d_raw.ensure(ns * kPairRawBytes));  // the slot walks' pairs
+    if (scalar) PRK_TRY(S.d_srecs.ensure_n<ScSpanRec>(ns));
+    if (nbig) PRK_TRY(S.d_raw.ensure_n<PairRaw>(ns));  // the slot walks' pairs
     // slots no span takes stay row -1: binned nowhere.  Without large objects
     // every slot belongs to the thread or segment walks (walk_object,
     // k_obj_seg), which mark their unused ones themselves (C3b as 16-triangle
     // objects: ~21 M slots, a 0.34-GB memset); the large objects' walks rely
     // on this one.
-    if (nbig || sw.pos_memset) PRK_TRY(hipMemsetAsync(S.d_pos.p, 0xFF, ns * 16, s));
+    if (nbig || sw.pos_memset) PRK_TRY(hipMemsetAsync(S.d_pos.p, 0xFF, ns * sizeof(SpanPos), s));
     return PRK_OK;
 }
 
@@ -700,7 +716,7 @@ int SpanPass::chunked() {
     ObjWalks &w = walks;
     if (!w.npr) return PRK_OK;
     hipError_t ae = S.d_prstat.ensure((size_t)nobj * 4);
-    if (ae == hipSuccess) ae = S.d_prrow.ensure((size_t)w.npr * 8);
+    if (ae == hipSuccess) ae = S.d_prrow.ensure_n<PrRow>(w.npr);
     if (ae == hipSuccess) ae = S.d_prcnt.ensure((size_t)w.pr_rows * 4);
     if (ae == hipSuccess) ae = S.d_preoff.ensure((size_t)w.pr_rows * 4);
     if (ae == hipSuccess) ae = S.d_prfge.ensure((size_t)w.pr_rows * 4);
@@ -709,10 +725,10 @@ int SpanPass::chunked() {
     if (ae == hipSuccess) ae = S.d_prmatch.ensure((size_t)w.pr_chunks * 4);
     if (ae == hipSuccess) ae = S.d_prsm.ensure((size_t)w.pr_chunks * 4);
     if (ae == hipSuccess) ae = S.d_prsidx.ensure(w.pr_ents * 4);
-    if (ae == hipSuccess) ae = S.d_prkey.ensure(w.pr_ents * 16);
-    if (ae == hipSuccess) ae = S.d_prest.ensure(w.pr_ents * kObjEdgeBytes);
-    if (ae == hipSuccess) ae = S.d_prsst.ensure(w.pr_ents * kObjEdgeBytes);
-    if (ae == hipSuccess) ae = S.d_preend.ensure(w.pr_ents * kObjEdgeBytes);
+    if (ae == hipSuccess) ae = S.d_prkey.ensure_n<float4>(w.pr_ents);
+    if (ae == hipSuccess) ae = S.d_prest.ensure_n<ObjEdge>(w.pr_ents);
+    if (ae == hipSuccess) ae = S.d_prsst.ensure_n<ObjEdge>(w.pr_ents);
+    if (ae == hipSuccess) ae = S.d_preend.ensure_n<ObjEdge>(w.pr_ents);
     if (ae == hipErrorOutOfMemory) {
         (void)hipGetLastError();
         DevBuf *bufs[] = {&S.d_prsidx, &S.d_prkey, &S.d_prest, &S.d_prsst, &S.d_preend};
@@ -731,24 +747,24 @@ int SpanPass::chunked() {
     pa.max_edges = w.pr_max_edges;
     pa.escan = escan;
     pa.total0p = total0p;
-    pa.work = S.d_work.p;
-    pa.prrow = S.d_prrow.p;
+    pa.work = S.d_work.as<ObjEdge>();
+    pa.prrow = S.d_prrow.as<PrRow>();
     pa.cnt = (uint32_t *)S.d_prcnt.p;
     pa.eoff = (uint32_t *)S.d_preoff.p;
     pa.fge = (uint32_t *)S.d_prfge.p;
     pa.ccur = (uint32_t *)S.d_prccur.p;
-    pa.key = S.d_prkey.p;
-    pa.est = S.d_prest.p;
-    pa.sst = S.d_prsst.p;
-    pa.eend = S.d_preend.p;
+    pa.key = S.d_prkey.as<float4>();
+    pa.est = S.d_prest.as<ObjEdge>();
+    pa.sst = S.d_prsst.as<ObjEdge>();
+    pa.eend = S.d_preend.as<ObjEdge>();
     pa.eend_m = (uint32_t *)S.d_preendm.p;
     pa.match = (uint32_t *)S.d_prmatch.p;
     pa.sidx = (uint32_t *)S.d_prsidx.p;
     pa.s_m = (uint32_t *)S.d_prsm.p;
     pa.prstat = (uint32_t *)S.d_prstat.p;
     pa.soff = oslot;
-    pa.raw = S.d_raw.p;
-    pa.pos = S.d_pos.p;
+    pa.raw = S.d_raw.as<PairRaw>();
+    pa.pos = S.d_pos.as<SpanPos>();
     pa.span_tri = (uint32_t *)S.d_span_tri.p;
     pa.err = (uint32_t *)S.d_err.p;
     pa.warmup = sw.chunk_warmup;
@@ -766,7 +782,7 @@ int SpanPass::chunked() {
 int SpanPass::walk() {
     if (nbig) {
         PRK_TRY(S.d_cls.ensure(cls.end));
-        PRK_TRY(hipMemcpyAsync(static_cast<char *>(S.d_cls.p) + cls.big, S.h_cls + cls.big, cls.upload_bytes(),
+        PRK_TRY(hipMemcpyAsync(S.d_cls.as<char>() + cls.big, S.h_cls + cls.big, cls.upload_bytes(),
                                hipMemcpyHostToDevice, s));
         if (walks.pool) PRK_TRY(S.d_pool.ensure(walks.pool * 4));
     }
@@ -774,39 +790,43 @@ int SpanPass::walk() {
         const int rc = chunked();
         if (rc != PRK_OK) return rc;
     }
-    const void *d_segs = nullptr;  // (the segments)
+    ObjEdge *work = S.d_work.as<ObjEdge>();
+    SpanRecG *recs = S.d_recs.as<SpanRecG>();  // (the walks store a span record as its four quads)
+    SpanPos *pos = S.d_pos.as<SpanPos>();
+    PairRaw *raw = S.d_raw.as<PairRaw>();
+    const ObjSeg *d_segs = nullptr;  // (the segments)
     const uint32_t *d_nseg = nullptr;
     if (segmented) {
         PRK_TRY(S.d_segcnt.ensure(((size_t)nobj + 1) * 4));
         PRK_TRY(S.d_segoff.ensure(((size_t)nobj + 1) * 4));
-        PRK_TRY(S.d_segs.ensure((size_t)max_segs * 24));  // prk_spans.hip ObjSeg
+        PRK_TRY(S.d_segs.ensure_n<ObjSeg>(max_segs));
         uint32_t *segcnt = (uint32_t *)S.d_segcnt.p, *segoff = (uint32_t *)S.d_segoff.p;
-        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, nullptr, nullptr, s));
+        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, wy(), oslot, segcnt, segoff, nullptr, nullptr, s));
         PRK_TRY(scan_u32(S.d_temp, segcnt, segoff, nobj + 1, s));
-        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, S.d_wy.p, oslot, segcnt, segoff, S.d_segs.p, S.d_pos.p,
+        PRK_TRY(prk_obj_seg(&fp, d_objs, nobj, escan, total0p, wy(), oslot, segcnt, segoff, S.d_segs.as<ObjSeg>(), pos,
                             s));
-        d_segs = S.d_segs.p;
+        d_segs = S.d_segs.as<ObjSeg>();
         d_nseg = segoff + nobj;
     }
     uint32_t *span_tri = (uint32_t *)S.d_span_tri.p, *err = (uint32_t *)S.d_err.p;
-    PRK_TRY(prk_obj_walk(&fp, d_objs, nobj, escan, total0p, S.d_work.p, oslot, S.d_recs.p, srecs(), S.d_pos.p, span_tri,
-                         dev(st_spans), err, thread_links ? 1 : 0, d_segs, d_nseg, (uint32_t)max_segs, s));
+    PRK_TRY(prk_obj_walk(&fp, d_objs, nobj, escan, total0p, work, oslot, recs, srecs(), pos, span_tri,
+                         static_cast<const prk::SpanIn *>(dev(st_spans)), err, thread_links ? 1 : 0, d_segs, d_nseg,
+                         (uint32_t)max_segs, s));
     for (const HandleRun &h : hruns)  // the span handles' draws, from their own buffers
-        PRK_TRY(prk_span_handle_walk(&fp, h.draw, h.g0, h.obj0, h.sp, h.first, h.n, oslot, S.d_recs.p, S.d_pos.p,
-                                     span_tri, s));
+        PRK_TRY(prk_span_handle_walk(&fp, h.draw, h.g0, h.obj0, h.sp, h.first, h.n, oslot, recs, pos, span_tri, s));
     const ClsView d = cls.view(S.d_cls.p);
     for (const WalkGroup &g : walks.groups) {
         if (g.big)
             PRK_TRY(prk_big_walk(&fp, g.mode, g.lds ? 1 : 0, d_objs, d.big + g.start, d.off + g.start, d.cap + g.start,
                                  d.meta + 2 * (size_t)g.start, g.count, g.max_rows, (int32_t *)S.d_pool.p, escan,
-                                 total0p, S.d_work.p, oslot, S.d_raw.p, S.d_pos.p, span_tri, err, d_prstat, s));
+                                 total0p, work, oslot, raw, pos, span_tri, err, d_prstat, s));
         else
             PRK_TRY(prk_obj_walk_group(&fp, g.mode, g.lcap, d_objs, d.big + g.start, d.off + g.start, d.cap + g.start,
-                                       g.count, (int32_t *)S.d_pool.p, escan, total0p, S.d_work.p, oslot, S.d_recs.p,
-                                       srecs(), S.d_raw.p, S.d_pos.p, span_tri, err, d_prstat, s));
+                                       g.count, (int32_t *)S.d_pool.p, escan, total0p, work, oslot, recs, srecs(), raw,
+                                       pos, span_tri, err, d_prstat, s));
     }
     if (nbig)  // the slot walks' pairs into span records
-        PRK_TRY(prk_span_finish(&fp, S.d_raw.p, nslot, S.d_recs.p, srecs(), S.d_pos.p, s));
+        PRK_TRY(prk_span_finish(&fp, raw, nslot, recs, srecs(), pos, s));
     return PRK_OK;
 }
 
@@ -817,7 +837,7 @@ int SpanPass::bin_shade(uint32_t T) {
     PRK_TRY(S.d_scnt.ensure(((size_t)ntiles + 1) * 4));
     PRK_TRY(S.d_offs.ensure(((size_t)ntiles + 1) * 4));
     uint32_t *tcnt = (uint32_t *)S.d_scnt.p, *toff = (uint32_t *)S.d_offs.p;
-    PRK_TRY(prk_span_count(&fp, S.d_pos.p, nslot, tcnt, s));
+    PRK_TRY(prk_span_count(&fp, S.d_pos.as<SpanPos>(), nslot, tcnt, s));
     PRK_TRY(scan_u32(S.d_temp, tcnt, toff, ntiles + 1, s));
     PRK_TRY(hipMemcpyAsync(S.h_rb + 2, toff + ntiles, 4, hipMemcpyDeviceToHost, s));
     PRK_TRY(hipMemcpyAsync(S.h_rb + 3, S.d_err.p, 16, hipMemcpyDeviceToHost, s));
@@ -835,12 +855,12 @@ int SpanPass::bin_shade(uint32_t T) {
     c->stats.tiles = ntiles;
     c->stats.bin_entries = total;
     PRK_TRY(S.d_vals_b.ensure((size_t)std::max<uint32_t>(total, 1) * 4));
-    PRK_TRY(prk_span_bin(&fp, S.d_pos.p, nslot, toff, tcnt, (uint32_t *)S.d_vals_b.p, s));
+    PRK_TRY(prk_span_bin(&fp, S.d_pos.as<SpanPos>(), nslot, toff, tcnt, (uint32_t *)S.d_vals_b.p, s));
     PRK_TRY(S.d_nwin.ensure((size_t)ntiles * 4));
     PRK_TRY(S.d_wtag.ensure((size_t)ntiles * fp.tile_w * fp.tile_h * 4));
-    PRK_TRY(prk_launch_spans(&fp, (const uint32_t *)S.d_offs.p, (const uint32_t *)S.d_vals_b.p, S.d_pos.p, S.d_recs.p,
-                             srecs(), modes, (const uint32_t *)S.d_span_tri.p, (uint32_t *)S.d_nwin.p,
-                             (uint32_t *)S.d_wtag.p, s));
+    PRK_TRY(prk_launch_spans(&fp, (const uint32_t *)S.d_offs.p, (const uint32_t *)S.d_vals_b.p, S.d_pos.as<SpanPos>(),
+                             S.d_recs.as<SpanRec>(), srecs(), modes, (const uint32_t *)S.d_span_tri.p,
+                             (uint32_t *)S.d_nwin.p, (uint32_t *)S.d_wtag.p, s));
     return PRK_OK;
 }
 }  // namespace

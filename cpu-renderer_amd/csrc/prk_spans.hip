@@ -69,7 +69,8 @@
 //   k_pix (prk_kernels.hip, span records indexed by span)  shading.
 //
 // Where things are:
-//   prk_spans_dev.h  the types and row arithmetic shared with prk_records.hip
+//   prk_types.h      the records shared with the host and with prk_kernels.hip
+//   prk_spans_dev.h  the device functions and row arithmetic shared with prk_records.hip
 //   prk_wave.h       wave and workgroup primitives (DPP scans, LKey, blk_*)
 //   prk_slot.h       the slot list of the workgroup walks, here and there
 //   prk_spans.hip    every kernel of a pass named above, and prk_edge_records'
@@ -119,7 +120,7 @@ namespace prk {
 //           as they leave every large object, and the host lists it for no
 //           other walk; like kind 2 it takes one slot (k_obj_bound).
 // g0 is the winner id (pass-local) of what it draws.
-// (struct ObjDesc: prk_launch.h)
+// (struct ObjDesc: prk_types.h)
 constexpr uint32_t kObjWave = 0x80000000u;
 constexpr uint32_t kListSrc = 0xFFFFFFFFu;  // ObjDesc::src of a batch's list
 // Kinds whose edges are sorted by YMin: every walk but the whole-list scan.
@@ -128,7 +129,7 @@ __device__ __forceinline__ bool obj_sorted(const ObjDesc &od) { return od.kind =
 // walked by rows, or failed its check (the workgroup walk takes it).
 constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 
-// A run of objects as the host lists them (prk_launch.h ObjRun; prk_span_pass.hip plan()): a draw of
+// A run of objects as the host lists them (prk_types.h ObjRun; prk_span_pass.hip plan()): a draw of
 // kind 0 is `count` objects of `per` triangles (the last one shorter), kind 2
 // one object per span, kind 1 one object; k_obj_tables expands them.  A
 // prk_draw_edge_lists batch is one run of kind 3, `count` lists from the
@@ -141,7 +142,7 @@ constexpr uint32_t kPrDone = 1u, kPrFailed = 2u;
 // its first list there (per), for k_list_tables to gather lcnt / lflag.  A
 // prk_draw_span_records draw is a run of kind 4: one object per span, from
 // span src_off of its handle on.
-// (struct ObjRun: prk_launch.h)
+// (struct ObjRun: prk_types.h)
 __global__ void k_obj_tables(const ObjRun *__restrict__ runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris,
                              ObjDesc *__restrict__ objs, uint32_t *__restrict__ k0obj, uint32_t *__restrict__ k0tri0,
                              const uint32_t *__restrict__ lcnt, const uint32_t *__restrict__ lflag,
@@ -472,7 +473,7 @@ __global__ void __launch_bounds__(256) k_obj_sort_local(const ObjDesc *__restric
 template <int M, class LK>
 __device__ void walk_object(const FrameParams &fp, const ObjDesc &od, const DrawRec &d, ObjEdge *__restrict__ E,
                             uint32_t n, uint32_t base, uint32_t bound, SpanRecG *__restrict__ recs,
-                            ScSpanRecG *__restrict__ srecs, SpanPos *__restrict__ pos,
+                            ScSpanRec *__restrict__ srecs, SpanPos *__restrict__ pos,
                             uint32_t *__restrict__ span_tri, uint32_t *__restrict__ err, const LK lk) {
     constexpr bool kScalar = M != MODE_AVX;
     const bool st = (d.flags & DRAW_ST) != 0;
@@ -662,7 +663,7 @@ __global__ void __launch_bounds__(kLinkThreads, 1) k_obj_walk(FrameParams fp, co
                                                  const uint32_t *__restrict__ escan,
                                                  const uint32_t *__restrict__ total0p, ObjEdge *__restrict__ work,
                                                  const unsigned long long *__restrict__ soff,
-                                                 SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
+                                                 SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs,
                                                  SpanPos *__restrict__ pos, uint32_t *__restrict__ span_tri,
                                                  const SpanIn *__restrict__ spans_in, uint32_t *__restrict__ err,
                                                  uint32_t segmented) {
@@ -739,12 +740,7 @@ __global__ void __launch_bounds__(kLinkThreads, 1) k_obj_walk(FrameParams fp, co
 // (half their edges' active rows, as k_obj_bound's), a slot a segment leaves
 // unused stays row -1.  Random scattered triangles grouped 16 at a time
 // (C3b as 16-triangle objects) make ~12 segments of a few edges per object.
-struct ObjSeg {
-    uint32_t o;      // object
-    uint32_t e0, n;  // its sorted edges [e0, e0 + n) (object-relative)
-    uint32_t base, bound;  // span slots
-    uint32_t pad;
-};
+// (ObjSeg: prk_types.h)
 // One thread per object: the segments' count (WRITE false; segcnt[nobj] = 0)
 // or descriptors (at segoff[o]), in object order.  (Ordering them by length
 // instead, so a wave's segments end together, made the walk slower.)
@@ -804,7 +800,7 @@ __global__ void __launch_bounds__(kLinkThreads) k_obj_walk_seg(FrameParams fp, c
                                                   const uint32_t *__restrict__ nsegp,
                                                   const uint32_t *__restrict__ escan,
                                                   const uint32_t *__restrict__ total0p, ObjEdge *__restrict__ work,
-                                                  SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
+                                                  SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs,
                                                   SpanPos *__restrict__ pos, uint32_t *__restrict__ span_tri,
                                                   uint32_t *__restrict__ err) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1077,7 +1073,7 @@ __device__ void insert_batch(const WaveList &L, int &m, const ObjEdge *__restric
 template <int M, bool GL>
 __device__ void walk_object_wave(const FrameParams &fp, const ObjDesc &od, const DrawRec &d,
                                  ObjEdge *__restrict__ E, uint32_t n, uint32_t base, uint32_t bound,
-                                 const WaveList &L, SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
+                                 const WaveList &L, SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs,
                                  SpanPos *__restrict__ pos, uint32_t *__restrict__ span_tri,
                                  uint32_t *__restrict__ err) {
     constexpr bool kScalar = M != MODE_AVX;
@@ -1169,7 +1165,7 @@ __device__ void walk_object_wave(const FrameParams &fp, const ObjDesc &od, const
             int32_t ia = 0, ib = 0;
             SpanPos sp;
             SpanRecG rec;
-            ScSpanRecG srec;
+            ScSpanRec srec;
             if (valid) {
                 ia = L.idx[2 * kk];
                 ib = L.idx[2 * kk + 1];
@@ -1240,8 +1236,7 @@ __device__ void walk_object_wave(const FrameParams &fp, const ObjDesc &od, const
 }
 
 __global__ void k_span_finish(FrameParams fp, const PairRaw *__restrict__ raw, uint32_t nslot,
-                              SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
-                              SpanPos *__restrict__ pos) {
+                              SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs, SpanPos *__restrict__ pos) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nslot) return;
     SpanPos p = pos[s];
@@ -1260,7 +1255,7 @@ __global__ void k_span_finish(FrameParams fp, const PairRaw *__restrict__ raw, u
         }
 #define PRK_FINISH_SC(MM)                                                          \
     case MM: {                                                                     \
-        ScSpanRecG srec;                                                           \
+        ScSpanRec srec;                                                            \
         em = obj_span_scalar<MM>(fp, L, R, Row, d.tex, srec, p);                   \
         if (em) {                                                                  \
             SpanRecG mark;                                                         \
@@ -1657,7 +1652,7 @@ __global__ void __launch_bounds__(kSlotMaxThreads) k_obj_walk_wave(FrameParams f
                                                       uint32_t lcap, const uint32_t *__restrict__ escan,
                                                       const uint32_t *__restrict__ total0p, ObjEdge *__restrict__ work,
                                                       const unsigned long long *__restrict__ soff,
-                                                      SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
+                                                      SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs,
                                                       PairRaw *__restrict__ raw, SpanPos *__restrict__ pos,
                                                       uint32_t *__restrict__ span_tri, uint32_t *__restrict__ err,
                                                       const uint32_t *__restrict__ prstat) {
@@ -2812,18 +2807,7 @@ __global__ void __launch_bounds__(256) k_big_replay(FrameParams fp, const ObjDes
 #endif
 constexpr int32_t kPrChunk = PRK_PR_CHUNK;  // rows per chunk
 constexpr int32_t kPrMaxM = 1022;           // most entries of a list (the workgroup walk's largest LDS list)
-struct PrObj {                              // per object of the walk (host: flush_spans)
-    uint32_t o;                             // object index
-    uint32_t row_off;                       // its first row in the pass's row arrays (rows + 1 each)
-    uint32_t rows;                          // MaxY - FirstRow (k_obj_maxact)
-    uint32_t chunk_off;                     // its first chunk in the pass's chunk arrays
-    uint32_t most;                          // k_obj_maxact's most entries (the list stride per chunk)
-    uint32_t ent_off;                       // its first list entry: chunk j's lists at ent_off + j * most
-    uint32_t pad0, pad1;
-};
-struct PrRow {                              // per object, set by k_pr_hist
-    int32_t first_row, max_y;
-};
+// (PrObj, the host's per-object table, PrRow and PrWalkArgs: prk_types.h)
 __device__ __forceinline__ uint32_t pr_chunks(const PrObj &P) { return (P.rows + kPrChunk - 1) / kPrChunk; }
 __device__ __forceinline__ bool pr_key_lt(float ax, float ag, int32_t al, uint32_t ai, float bx, float bg, int32_t bl,
                                           uint32_t bi) {
@@ -3548,7 +3532,7 @@ __global__ void __launch_bounds__(kPrepEdges) k_list_prep(FrameParams fp, const 
 //                  list there in per
 //   k_list_rule    prk_api.hip's list_walks_sorted for every list of a handle
 // ---------------------------------------------------------------------------
-// (struct PrepSeg, struct ListSrc: prk_launch.h)
+// (struct PrepSeg, struct ListSrc: prk_types.h)
 __global__ void __launch_bounds__(kPrepEdges) k_list_prep_segs(FrameParams fp, const PrepSeg *__restrict__ segs,
                                                                uint32_t nseg, const uint32_t *__restrict__ lscan,
                                                                uint32_t nlist, const uint32_t *__restrict__ lobj,
@@ -3793,83 +3777,79 @@ extern "C" {
 // prk_edge_records: the edges of every object triangle with all their fields
 // and true-YMin MergeSort keys (as prk_objtri_emit otherwise), the objects'
 // edge counts, and the sorted edges as packed prk_edge records.
-hipError_t prk_rec_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj, const uint32_t *k0tri0,
+hipError_t prk_rec_emit(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *k0obj,
+                        const uint32_t *k0tri0,
                         uint32_t nk0, uint32_t ntri, const uint32_t *escan, int32_t setup, uint32_t pbits,
-                        void *edges, void *keys, uint32_t *vals, int pad, hipStream_t s) {
+                        prk::ObjEdge *edges, unsigned long long *keys, uint32_t *vals, int pad, hipStream_t s) {
     if (ntri == 0) return hipSuccess;
     if (pad) {  // (the radix sort reads every slot)
         const hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)3 * ntri * 8, s);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(prk::k_rec_emit, dim3((ntri + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, k0tri0, nk0, ntri, escan, setup, pbits,
-                       reinterpret_cast<prk::ObjEdge *>(edges), reinterpret_cast<unsigned long long *>(keys), vals);
+                       objs, k0obj, k0tri0, nk0, ntri, escan, setup, pbits, edges, keys, vals);
     return hipGetLastError();
 }
-hipError_t prk_rec_counts(const void *objs, const uint32_t *k0obj, uint32_t nk0, const uint32_t *escan,
+hipError_t prk_rec_counts(const prk::ObjDesc *objs, const uint32_t *k0obj, uint32_t nk0, const uint32_t *escan,
                           uint32_t *counts, hipStream_t s) {
     if (nk0 == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_rec_counts, dim3((nk0 + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, nk0, escan, counts);
+                       objs, k0obj, nk0, escan, counts);
     return hipGetLastError();
 }
-hipError_t prk_rec_export(const void *edges, const uint32_t *ord, uint64_t total, void *out, hipStream_t s) {
+hipError_t prk_rec_export(const prk::ObjEdge *edges, const uint32_t *ord, uint64_t total, void *out, hipStream_t s) {
     if (total == 0) return hipSuccess;
     const unsigned long long ndw = 27ull * total, nthr = (ndw + 3) / 4;
     hipLaunchKernelGGL(prk::k_rec_export, dim3((uint32_t)((nthr + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjEdge *>(edges), ord, ndw, reinterpret_cast<uint4 *>(out));
+                       edges, ord, ndw, reinterpret_cast<uint4 *>(out));
     return hipGetLastError();
 }
 
 // The pass's objects (ObjDesc) and kind-0 object tables from the host's runs.
 // (lcnt, lflag, lscan, lobj: the batch lists' tables, k_obj_tables; null
 // without runs of kind 3)
-hipError_t prk_obj_tables(const void *runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris, void *objs,
+hipError_t prk_obj_tables(const prk::ObjRun *runs, uint32_t nruns, uint32_t nobj, uint32_t wave_tris,
+                          prk::ObjDesc *objs,
                           uint32_t *k0obj, uint32_t *k0tri0, const uint32_t *lcnt, const uint32_t *lflag,
                           const uint32_t *lscan, uint32_t wave_edges, uint32_t *lobj, hipStream_t s) {
     if (nobj == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_obj_tables, dim3((nobj + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjRun *>(runs), nruns, nobj, wave_tris,
-                       reinterpret_cast<prk::ObjDesc *>(objs), k0obj, k0tri0, lcnt, lflag, lscan, wave_edges, lobj);
+                       runs, nruns, nobj, wave_tris, objs, k0obj, k0tri0, lcnt, lflag, lscan, wave_edges, lobj);
     return hipGetLastError();
 }
 // The batch lists' records into the working copy, and each list's row sum
 // (k_list_prep; lrows: nlist values, zeroed here).
 hipError_t prk_list_prep(const prk::FrameParams *fp, const void *records, uint32_t nedge, const uint32_t *lscan,
-                         uint32_t nlist, const uint32_t *lobj, const void *objs, const uint32_t *total0p,
-                         uint32_t ebase, void *work, void *wy, unsigned long long *lrows, hipStream_t s) {
+                         uint32_t nlist, const uint32_t *lobj, const prk::ObjDesc *objs, const uint32_t *total0p,
+                         uint32_t ebase, prk::ObjEdge *work, int2 *wy, unsigned long long *lrows, hipStream_t s) {
     if (nlist == 0) return hipSuccess;
     const hipError_t e = hipMemsetAsync(lrows, 0, (size_t)nlist * 8, s);
     if (e != hipSuccess || nedge == 0) return e;
     hipLaunchKernelGGL(prk::k_list_prep, dim3((nedge + prk::kPrepEdges - 1) / prk::kPrepEdges),
                        dim3(prk::kPrepEdges), 0, s, *fp, reinterpret_cast<const uint4 *>(records), nedge, lscan, nlist,
-                       lobj, reinterpret_cast<const prk::ObjDesc *>(objs), total0p, ebase,
-                       reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy), lrows);
+                       lobj, objs, total0p, ebase, work, wy, lrows);
     return hipGetLastError();
 }
 // k_list_prep for a pass that draws from record handles: `segs` (PrepSeg, nseg
 // of them, nblk workgroups in all) instead of one flat input.
-hipError_t prk_list_prep_segs(const prk::FrameParams *fp, const void *segs, uint32_t nseg, uint32_t nblk,
-                              const uint32_t *lscan, uint32_t nlist, const uint32_t *lobj, const void *objs,
-                              const uint32_t *total0p, uint32_t ebase, void *work, void *wy,
+hipError_t prk_list_prep_segs(const prk::FrameParams *fp, const prk::PrepSeg *segs, uint32_t nseg, uint32_t nblk,
+                              const uint32_t *lscan, uint32_t nlist, const uint32_t *lobj, const prk::ObjDesc *objs,
+                              const uint32_t *total0p, uint32_t ebase, prk::ObjEdge *work, int2 *wy,
                               unsigned long long *lrows, hipStream_t s) {
     if (nlist == 0) return hipSuccess;
     const hipError_t e = hipMemsetAsync(lrows, 0, (size_t)nlist * 8, s);
     if (e != hipSuccess || nseg == 0 || nblk == 0) return e;
     hipLaunchKernelGGL(prk::k_list_prep_segs, dim3(nblk), dim3(prk::kPrepEdges), 0, s, *fp,
-                       reinterpret_cast<const prk::PrepSeg *>(segs), nseg, lscan, nlist, lobj,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), total0p, ebase,
-                       reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy), lrows);
+                       segs, nseg, lscan, nlist, lobj, objs, total0p, ebase, work, wy, lrows);
     return hipGetLastError();
 }
 // The pass's list counts (nlist + 1, the last 0) and sorted flags from the
 // staged tables and the handles' (k_list_tables).
-hipError_t prk_list_tables(const void *runs, uint32_t nruns, uint32_t nobj, const uint32_t *cnt0,
-                           const uint32_t *flag0, const void *srcs, uint32_t nlist, uint32_t *lcnt, uint32_t *lflag,
-                           hipStream_t s) {
+hipError_t prk_list_tables(const prk::ObjRun *runs, uint32_t nruns, uint32_t nobj, const uint32_t *cnt0,
+                           const uint32_t *flag0, const prk::ListSrc *srcs, uint32_t nlist, uint32_t *lcnt,
+                           uint32_t *lflag, hipStream_t s) {
     hipLaunchKernelGGL(prk::k_list_tables, dim3(((nobj ? nobj : 1u) + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjRun *>(runs), nruns, nobj, cnt0, flag0,
-                       reinterpret_cast<const prk::ListSrc *>(srcs), nlist, lcnt, lflag);
+                       runs, nruns, nobj, cnt0, flag0, srcs, nlist, lcnt, lflag);
     return hipGetLastError();
 }
 // The sorted rule of every list of `nedge` packed records (k_list_rule);
@@ -3884,19 +3864,18 @@ hipError_t prk_list_rule(const void *records, uint32_t nedge, const uint32_t *ls
     return hipGetLastError();
 }
 // The walk statistics of every list of `nedge` packed records, which hold
-// the sorted rule (k_list_stats).  stats: 24 bytes a list, zeroed here --
-// nlist edge-row sums (u64), nlist insertion-scan sums (u64), nlist YMin of
-// the first record (i32), nlist largest YMax (i32).
+// the sorted rule (k_list_stats).  stats: a ListStatsLayout(nlist) block
+// (prk_types.h), zeroed here.
 hipError_t prk_list_stats(const void *records, uint32_t nedge, const uint32_t *lscan, uint32_t nlist, int32_t height,
                           void *stats, hipStream_t s) {
     if (nlist == 0) return hipSuccess;
-    const hipError_t e = hipMemsetAsync(stats, 0, (size_t)nlist * 24, s);
+    const prk::ListStatsLayout lay{nlist};
+    const hipError_t e = hipMemsetAsync(stats, 0, lay.bytes(), s);
     if (e != hipSuccess || nedge == 0) return e;
-    unsigned long long *erows = reinterpret_cast<unsigned long long *>(stats), *scans = erows + nlist;
-    int32_t *ymin0 = reinterpret_cast<int32_t *>(scans + nlist), *ymaxmax = ymin0 + nlist;
+    const prk::ListStatsView v = lay.view(stats);
     hipLaunchKernelGGL(prk::k_list_stats, dim3((nedge + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const uint32_t *>(records), nedge, lscan, nlist, height, erows, scans, ymin0,
-                       ymaxmax);
+                       reinterpret_cast<const uint32_t *>(records), nedge, lscan, nlist, height, v.erows, v.scans,
+                       v.ymin0, v.ymaxmax);
     return hipGetLastError();
 }
 // The most edges linked at once of the `ncand` lists cand[] names, among the
@@ -3910,19 +3889,19 @@ hipError_t prk_list_most(const void *records, const uint32_t *lscan, const uint3
 }
 // FillEdgeTable of the pass's object triangles: per-triangle edge and
 // active-row counts (ntri + 1 values each, the last 0) ...
-hipError_t prk_objtri_count(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj,
+hipError_t prk_objtri_count(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *k0obj,
                             const uint32_t *k0tri0, uint32_t nk0, uint32_t ntri, uint32_t *ecnt,
                             unsigned long long *rcnt, hipStream_t s) {
     hipLaunchKernelGGL(prk::k_objtri_count, dim3((ntri + 1 + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, k0tri0, nk0, ntri, ecnt, rcnt);
+                       objs, k0obj, k0tri0, nk0, ntri, ecnt, rcnt);
     return hipGetLastError();
 }
 // ... then the edges at their exclusive scan, with their MergeSort keys
 // (keys: 3 * ntri slots, those past the visible edges all ones).
-hipError_t prk_objtri_emit(const prk::FrameParams *fp, const void *objs, const uint32_t *k0obj,
+hipError_t prk_objtri_emit(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *k0obj,
                            const uint32_t *k0tri0, uint32_t nk0, uint32_t ntri, const uint32_t *escan,
-                           uint32_t pbits, uint32_t ybits, int32_t ycap, void *edges, void *keys, uint32_t *vals,
-                           int pad, hipStream_t s) {
+                           uint32_t pbits, uint32_t ybits, int32_t ycap, prk::ObjEdge *edges, unsigned long long *keys,
+                           uint32_t *vals, int pad, hipStream_t s) {
     if (ntri == 0) return hipSuccess;
     if (pad) {  // (the radix sort reads every slot; k_obj_sort_local only the visible edges')
         const hipError_t e = hipMemsetAsync(keys, 0xFF, (size_t)3 * ntri * 8, s);
@@ -3930,42 +3909,38 @@ hipError_t prk_objtri_emit(const prk::FrameParams *fp, const void *objs, const u
     }
     const prk::SortKeyBits kb{pbits, ybits, ycap};
     hipLaunchKernelGGL(prk::k_objtri_emit, dim3((ntri + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, k0tri0, nk0, ntri, escan, kb,
-                       reinterpret_cast<prk::ObjEdge *>(edges), reinterpret_cast<unsigned long long *>(keys), vals);
+                       objs, k0obj, k0tri0, nk0, ntri, escan, kb, edges, keys, vals);
     return hipGetLastError();
 }
 // The walk's working copy (n slots: total0 triangle edges, then nk1 caller edges).
 // (wy: null, or the triangle edges' (YMin, YMax) as int2, for prk_obj_seg)
-hipError_t prk_obj_gather(const void *edges, const uint32_t *ord, const uint32_t *total0p, const void *edges_in,
-                          const uint32_t *k1src, uint32_t nk1, void *work, uint32_t n, void *wy, hipStream_t s) {
+hipError_t prk_obj_gather(const prk::ObjEdge *edges, const uint32_t *ord, const uint32_t *total0p,
+                          const prk::EdgeIn *edges_in,
+                          const uint32_t *k1src, uint32_t nk1, prk::ObjEdge *work, uint32_t n, int2 *wy,
+                          hipStream_t s) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_obj_gather, dim3((n + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjEdge *>(edges), ord, total0p,
-                       reinterpret_cast<const prk::EdgeIn *>(edges_in), k1src, nk1,
-                       reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<int2 *>(wy));
+                       edges, ord, total0p, edges_in, k1src, nk1, work, wy);
     return hipGetLastError();
 }
 
 // MergeSort + gather of objects of at most 64 edges (k_obj_sort_local).
-hipError_t prk_obj_sort_local(const void *objs, const uint32_t *k0obj, uint32_t nk0, const uint32_t *escan,
-                              const void *keys, const void *edges, void *work, void *wy, uint32_t *err,
-                              hipStream_t s) {
+hipError_t prk_obj_sort_local(const prk::ObjDesc *objs, const uint32_t *k0obj, uint32_t nk0, const uint32_t *escan,
+                              const unsigned long long *keys, const prk::ObjEdge *edges, prk::ObjEdge *work, int2 *wy,
+                              uint32_t *err, hipStream_t s) {
     if (nk0 == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_obj_sort_local, dim3((nk0 + 3) / 4), dim3(256), 0, s,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), k0obj, nk0, escan,
-                       reinterpret_cast<const unsigned long long *>(keys),
-                       reinterpret_cast<const prk::ObjEdge *>(edges), reinterpret_cast<prk::ObjEdge *>(work),
-                       reinterpret_cast<int2 *>(wy), err);
+                       objs, k0obj, nk0, escan, keys, edges, work, wy, err);
     return hipGetLastError();
 }
 // Span slots per object (nobj + 1 values, the last 0; exclusive-scanned by
 // the caller into each object's first slot).
-hipError_t prk_obj_bound(const prk::FrameParams *fp, const void *objs, uint32_t nobj, const unsigned long long *rscan,
-                         const void *edges_in, const unsigned long long *lrows, unsigned long long *bound,
+hipError_t prk_obj_bound(const prk::FrameParams *fp, const prk::ObjDesc *objs, uint32_t nobj,
+                         const unsigned long long *rscan,
+                         const prk::EdgeIn *edges_in, const unsigned long long *lrows, unsigned long long *bound,
                          hipStream_t s) {
     hipLaunchKernelGGL(prk::k_obj_bound, dim3((nobj + 1 + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), nobj, rscan,
-                       reinterpret_cast<const prk::EdgeIn *>(edges_in), lrows, bound);
+                       objs, nobj, rscan, edges_in, lrows, bound);
     return hipGetLastError();
 }
 // The LDS capacity of the workgroup walk on the current device (listed edges;
@@ -4015,29 +3990,27 @@ uint32_t prk_obj_walk_lcap(void) {
 // The object walk: a thread per small object or caller edge list ...
 // (segs: the small triangle objects' segments, prk_obj_seg, walked a thread
 // each; null: a thread per object)
-hipError_t prk_obj_walk(const prk::FrameParams *fp, const void *objs, uint32_t nobj, const uint32_t *escan,
-                        const uint32_t *total0p, void *work, const unsigned long long *soff, void *recs, void *srecs,
-                        void *pos, uint32_t *span_tri, const void *spans_in, uint32_t *err, int links,
-                        const void *segs, const uint32_t *nsegp, uint32_t max_segs, hipStream_t s) {
+hipError_t prk_obj_walk(const prk::FrameParams *fp, const prk::ObjDesc *objs, uint32_t nobj, const uint32_t *escan,
+                        const uint32_t *total0p, prk::ObjEdge *work, const unsigned long long *soff,
+                        prk::SpanRecG *recs, prk::ScSpanRec *srecs,
+                        prk::SpanPos *pos, uint32_t *span_tri, const prk::SpanIn *spans_in, uint32_t *err, int links,
+                        const prk::ObjSeg *segs, const uint32_t *nsegp, uint32_t max_segs, hipStream_t s) {
     if (nobj == 0) return hipSuccess;
     const uint32_t segmented = segs ? 1u : 0u;
     if (segs && max_segs) {
         hipLaunchKernelGGL(prk::k_obj_walk_seg, dim3((max_segs + prk::kLinkThreads - 1) / prk::kLinkThreads),
-                           dim3(prk::kLinkThreads), 0, s, *fp, reinterpret_cast<const prk::ObjDesc *>(objs),
-                           reinterpret_cast<const prk::ObjSeg *>(segs), nsegp, escan, total0p,
-                           reinterpret_cast<prk::ObjEdge *>(work), reinterpret_cast<prk::SpanRecG *>(recs),
-                           reinterpret_cast<prk::ScSpanRecG *>(srecs), reinterpret_cast<prk::SpanPos *>(pos), span_tri,
-                           err);
+                           dim3(prk::kLinkThreads), 0, s, *fp, objs, segs, nsegp, escan, total0p, work, recs,
+                           srecs, pos, span_tri, err);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
 #define PRK_OBJ_WALK_LAUNCH(LK)                                                                                    \
     hipLaunchKernelGGL(prk::k_obj_walk<LK>, dim3((nobj + prk::kLinkThreads - 1) / prk::kLinkThreads),              \
-                       dim3(prk::kLinkThreads), 0, s, *fp, reinterpret_cast<const prk::ObjDesc *>(objs), nobj, escan, \
-                       total0p, reinterpret_cast<prk::ObjEdge *>(work), soff,                                      \
-                       reinterpret_cast<prk::SpanRecG *>(recs), reinterpret_cast<prk::ScSpanRecG *>(srecs),        \
-                       reinterpret_cast<prk::SpanPos *>(pos), span_tri,                                            \
-                       reinterpret_cast<const prk::SpanIn *>(spans_in), err, segmented)
+                       dim3(prk::kLinkThreads), 0, s, *fp, objs, nobj, escan,                                      \
+                       total0p, work, soff,                                                                        \
+                       recs, srecs,                                                                                \
+                       pos, span_tri,                                                                              \
+                       spans_in, err, segmented)
     if (links) PRK_OBJ_WALK_LAUNCH(true);
     else PRK_OBJ_WALK_LAUNCH(false);
 #undef PRK_OBJ_WALK_LAUNCH
@@ -4048,50 +4021,45 @@ uint32_t prk_obj_link_cap(void) { return (uint32_t)prk::kLinkCap; }
 // the last 0) when segs is null, else the descriptors at segoff[o].
 // With the descriptors it also marks each object's slots past its segments'
 // row -1 (pos).
-hipError_t prk_obj_seg(const prk::FrameParams *fp, const void *objs, uint32_t nobj, const uint32_t *escan,
-                       const uint32_t *total0p, const void *wy, const unsigned long long *soff, uint32_t *segcnt,
-                       const uint32_t *segoff, void *segs, void *pos, hipStream_t s) {
+hipError_t prk_obj_seg(const prk::FrameParams *fp, const prk::ObjDesc *objs, uint32_t nobj, const uint32_t *escan,
+                       const uint32_t *total0p, const int2 *wy, const unsigned long long *soff, uint32_t *segcnt,
+                       const uint32_t *segoff, prk::ObjSeg *segs, prk::SpanPos *pos, hipStream_t s) {
     const dim3 g((nobj + 1 + 255) / 256), b(256);
-    const prk::ObjDesc *O = reinterpret_cast<const prk::ObjDesc *>(objs);
-    const int2 *W = reinterpret_cast<const int2 *>(wy);
     if (!segs)
-        hipLaunchKernelGGL(prk::k_obj_seg<false>, g, b, 0, s, *fp, O, nobj, escan, total0p, W, soff, segcnt, segoff,
+        hipLaunchKernelGGL(prk::k_obj_seg<false>, g, b, 0, s, *fp, objs, nobj, escan, total0p, wy, soff, segcnt, segoff,
                            nullptr, nullptr);
     else
-        hipLaunchKernelGGL(prk::k_obj_seg<true>, g, b, 0, s, *fp, O, nobj, escan, total0p, W, soff, segcnt, segoff,
-                           reinterpret_cast<prk::ObjSeg *>(segs), reinterpret_cast<prk::SpanPos *>(pos));
+        hipLaunchKernelGGL(prk::k_obj_seg<true>, g, b, 0, s, *fp, objs, nobj, escan, total0p, wy, soff, segcnt, segoff,
+                           segs, pos);
     return hipGetLastError();
 }
 // ... the most active entries of the large ones (big[0, nbig)) ...
-// (most: 3 * nbig values, see k_obj_maxact)
-hipError_t prk_obj_maxact(const prk::FrameParams *fp, const void *objs, const uint32_t *big, uint32_t nbig,
-                          const uint32_t *escan, const uint32_t *total0p, const void *work, int32_t *most,
+// (most: a MaxactLayout(nbig) block, prk_types.h; see k_obj_maxact)
+hipError_t prk_obj_maxact(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *big, uint32_t nbig,
+                          const uint32_t *escan, const uint32_t *total0p, const prk::ObjEdge *work, int32_t *most,
                           uint32_t huge_min, hipStream_t s) {
     if (nbig == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_obj_maxact, dim3(nbig), dim3(prk::kSlotMaxThreads), 0, s, *fp,
-                       reinterpret_cast<const prk::ObjDesc *>(objs), big, nbig, escan, total0p,
-                       reinterpret_cast<const prk::ObjEdge *>(work), most, huge_min);
+                       objs, big, nbig, escan, total0p, work, most, huge_min);
     return hipGetLastError();
 }
 // ... and those of the huge object big[b] (3 * tris >= huge_min, at most
 // `edges` edges) over many workgroups: scratch = (kMaxactRows + 2) ints + 3
 // words (prk_maxact_huge_scratch bytes), zeroed here.
 size_t prk_maxact_huge_scratch(void) { return (size_t)(prk::kMaxactRows + 2) * 4 + 3 * 8; }
-hipError_t prk_obj_maxact_huge(const prk::FrameParams *fp, const void *objs, const uint32_t *big, uint32_t b,
+hipError_t prk_obj_maxact_huge(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *big, uint32_t b,
                                uint32_t nbig, uint32_t edges, const uint32_t *escan, const uint32_t *total0p,
-                               const void *work, int32_t *most, void *scratch, hipStream_t s) {
+                               const prk::ObjEdge *work, int32_t *most, void *scratch, hipStream_t s) {
     if (edges == 0) return hipSuccess;
     const size_t hb = (size_t)(prk::kMaxactRows + 2) * 4;
     hipError_t e = hipMemsetAsync(scratch, 0, prk_maxact_huge_scratch(), s);
     if (e != hipSuccess) return e;
     int32_t *hist = static_cast<int32_t *>(scratch);
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(static_cast<char *>(scratch) + hb);
-    const prk::ObjDesc *O = reinterpret_cast<const prk::ObjDesc *>(objs);
-    const prk::ObjEdge *W = reinterpret_cast<const prk::ObjEdge *>(work);
     hipLaunchKernelGGL(prk::k_maxact_huge_part, dim3((edges + prk::kMaxactChunk - 1) / prk::kMaxactChunk),
-                       dim3(prk::kSlotMaxThreads), 0, s, *fp, O, big, b, escan, total0p, W, hist, acc);
-    hipLaunchKernelGGL(prk::k_maxact_huge_fin, dim3(1), dim3(prk::kSlotMaxThreads), 0, s, *fp, O, big, b, nbig,
-                       escan, total0p, W, hist, acc, most);
+                       dim3(prk::kSlotMaxThreads), 0, s, *fp, objs, big, b, escan, total0p, work, hist, acc);
+    hipLaunchKernelGGL(prk::k_maxact_huge_fin, dim3(1), dim3(prk::kSlotMaxThreads), 0, s, *fp, objs, big, b, nbig,
+                       escan, total0p, work, hist, acc, most);
     return hipGetLastError();
 }
 // ... and a workgroup per large object of mode `mode` (big[0, nbig)): lcap > 0
@@ -4100,11 +4068,12 @@ hipError_t prk_obj_maxact_huge(const prk::FrameParams *fp, const void *objs, con
 // slots soff[o] + k.  err: bit 0 a pool slice smaller than its object, bit 1
 // an object emitted past its bound (neither can happen).
 uint32_t prk_obj_walk_threads(uint32_t lcap) { return lcap ? prk::slot_threads(lcap) : 64u; }
-hipError_t prk_obj_walk_group(const prk::FrameParams *fp, int32_t mode, uint32_t lcap, const void *objs,
+hipError_t prk_obj_walk_group(const prk::FrameParams *fp, int32_t mode, uint32_t lcap, const prk::ObjDesc *objs,
                               const uint32_t *big, const unsigned long long *big_off, const uint32_t *big_cap,
                               uint32_t nbig, int32_t *pool, const uint32_t *escan, const uint32_t *total0p,
-                              void *work, const unsigned long long *soff, void *recs, void *srecs, void *raw,
-                              void *pos, uint32_t *span_tri, uint32_t *err, const uint32_t *prstat,
+                              prk::ObjEdge *work, const unsigned long long *soff, prk::SpanRecG *recs,
+                              prk::ScSpanRec *srecs, prk::PairRaw *raw,
+                              prk::SpanPos *pos, uint32_t *span_tri, uint32_t *err, const uint32_t *prstat,
                               hipStream_t s) {
     if (nbig == 0) return hipSuccess;
     const size_t bytes = lcap ? prk::slot_lds_bytes(lcap) : 0;
@@ -4112,11 +4081,11 @@ hipError_t prk_obj_walk_group(const prk::FrameParams *fp, int32_t mode, uint32_t
     switch (mode) {
 #define PRK_WALK_WAVE(MM)                                                                                           \
     case MM:                                                                                                        \
-        hipLaunchKernelGGL(prk::k_obj_walk_wave<MM>, dim3(nbig), dim3(nt), bytes, s, *fp,                          \
-                           reinterpret_cast<const prk::ObjDesc *>(objs), big, big_off, big_cap, pool, lcap, escan,  \
-                           total0p, reinterpret_cast<prk::ObjEdge *>(work), soff,                                   \
-                           reinterpret_cast<prk::SpanRecG *>(recs), reinterpret_cast<prk::ScSpanRecG *>(srecs),     \
-                           reinterpret_cast<prk::PairRaw *>(raw), reinterpret_cast<prk::SpanPos *>(pos), span_tri,  \
+        hipLaunchKernelGGL(prk::k_obj_walk_wave<MM>, dim3(nbig), dim3(nt), bytes, s, *fp,                           \
+                           objs, big, big_off, big_cap, pool, lcap, escan,                                          \
+                           total0p, work, soff,                                                                     \
+                           recs, srecs,                                                                             \
+                           raw, pos, span_tri,                                                                      \
                            err, prstat);                                                                            \
         break;
         PRK_WALK_WAVE(prk::MODE_AVX)
@@ -4137,30 +4106,28 @@ hipError_t prk_obj_walk_group(const prk::FrameParams *fp, int32_t mode, uint32_t
 uint32_t prk_big_max_entries(void) { return prk::kBigMaxM; }
 uint64_t prk_big_slice_ints(uint32_t cap, uint32_t rows, uint32_t ents) { return prk::big_slice_ints(cap, rows, ents); }
 uint32_t prk_big_lds_cap(void) { return (uint32_t)prk::kLdsCap; }
-hipError_t prk_big_walk(const prk::FrameParams *fp, int32_t mode, int lds, const void *objs, const uint32_t *big,
+hipError_t prk_big_walk(const prk::FrameParams *fp, int32_t mode, int lds, const prk::ObjDesc *objs,
+                        const uint32_t *big,
                         const unsigned long long *big_off, const uint32_t *big_cap, const uint32_t *big_meta,
                         uint32_t nbig, uint32_t max_rows, int32_t *pool, const uint32_t *escan,
-                        const uint32_t *total0p, const void *work, const unsigned long long *soff, void *raw,
-                        void *pos, uint32_t *span_tri, uint32_t *err, const uint32_t *prstat, hipStream_t s) {
+                        const uint32_t *total0p, const prk::ObjEdge *work, const unsigned long long *soff,
+                        prk::PairRaw *raw,
+                        prk::SpanPos *pos, uint32_t *span_tri, uint32_t *err, const uint32_t *prstat, hipStream_t s) {
     if (nbig == 0) return hipSuccess;
     if (nbig > 65535) return hipErrorInvalidValue;
-    const prk::ObjDesc *O = reinterpret_cast<const prk::ObjDesc *>(objs);
-    const prk::ObjEdge *W = reinterpret_cast<const prk::ObjEdge *>(work);
     if (lds)
-        hipLaunchKernelGGL(prk::k_obj_walk_lds, dim3(nbig), dim3(prk::kBigThreads), 0, s, *fp, O, big, big_off,
-                           big_cap, big_meta, pool, escan, total0p, W, soff, err, prstat);
+        hipLaunchKernelGGL(prk::k_obj_walk_lds, dim3(nbig), dim3(prk::kBigThreads), 0, s, *fp, objs, big, big_off,
+                           big_cap, big_meta, pool, escan, total0p, work, soff, err, prstat);
     else
-        hipLaunchKernelGGL(prk::k_obj_walk_big, dim3(nbig), dim3(prk::kBigThreads), 0, s, *fp, O, big, big_off,
-                           big_cap, big_meta, pool, escan, total0p, W, soff, err, prstat);
+        hipLaunchKernelGGL(prk::k_obj_walk_big, dim3(nbig), dim3(prk::kBigThreads), 0, s, *fp, objs, big, big_off,
+                           big_cap, big_meta, pool, escan, total0p, work, soff, err, prstat);
     if (max_rows == 0) return hipGetLastError();
     const dim3 g(max_rows, nbig), b(256);
-    prk::PairRaw *R = reinterpret_cast<prk::PairRaw *>(raw);
-    prk::SpanPos *P = reinterpret_cast<prk::SpanPos *>(pos);
     switch (mode) {
 #define PRK_BIG_REPLAY(MM)                                                                                      \
     case MM:                                                                                                    \
-        hipLaunchKernelGGL(prk::k_big_replay<MM>, g, b, 0, s, *fp, O, big, big_off, big_cap, big_meta, pool,    \
-                           escan, total0p, W, soff, R, P, span_tri, prstat);                                    \
+        hipLaunchKernelGGL(prk::k_big_replay<MM>, g, b, 0, s, *fp, objs, big, big_off, big_cap, big_meta, pool, \
+                           escan, total0p, work, soff, raw, pos, span_tri, prstat);                             \
         break;
         PRK_BIG_REPLAY(prk::MODE_AVX)
         PRK_BIG_REPLAY(prk::MODE_SC_GOURAUD)
@@ -4180,22 +4147,20 @@ hipError_t prk_big_walk(const prk::FrameParams *fp, int32_t mode, int lds, const
 hipError_t prk_pr_walk_begin(const prk::FrameParams *fp, const prk::PrWalkArgs *a, hipStream_t s) {
     if (a->npr == 0) return hipSuccess;
     if (a->npr > 65535 || a->max_edges == 0) return hipErrorInvalidValue;
-    const prk::PrObj *P = reinterpret_cast<const prk::PrObj *>(a->pro);
-    prk::PrRow *PR = reinterpret_cast<prk::PrRow *>(a->prrow);
-    const prk::ObjDesc *O = reinterpret_cast<const prk::ObjDesc *>(a->objs);
-    const prk::ObjEdge *W = reinterpret_cast<const prk::ObjEdge *>(a->work);
+    const prk::PrObj *P = a->pro;
+    prk::PrRow *PR = a->prrow;
+    const prk::ObjDesc *O = a->objs;
+    const prk::ObjEdge *W = a->work;
     hipLaunchKernelGGL(prk::k_pr_hist, dim3(a->npr), dim3(prk::kSlotMaxThreads), 0, s, *fp, O, P, a->escan,
                        a->total0p, W, PR, a->cnt, a->eoff, a->fge, a->prstat);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemsetAsync(a->ccur, 0, (size_t)a->nchunks * 4, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(prk::k_pr_fill, dim3((a->max_edges + 255) / 256, a->npr), dim3(256), 0, s, *fp, O, P, PR,
-                       a->escan, a->total0p, W, a->ccur, reinterpret_cast<float4 *>(a->key),
-                       reinterpret_cast<prk::ObjEdge *>(a->est), a->prstat);
+                       a->escan, a->total0p, W, a->ccur, a->key, a->est, a->prstat);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(prk::k_pr_start, dim3(a->nchunks), dim3(prk::kPrStartThreads), 0, s, P, a->npr, a->ccur,
-                       reinterpret_cast<const float4 *>(a->key), reinterpret_cast<const prk::ObjEdge *>(a->est),
-                       reinterpret_cast<prk::ObjEdge *>(a->sst), a->prstat);
+                       a->key, a->est, a->sst, a->prstat);
     return hipGetLastError();
 }
 hipError_t prk_pr_walk_group(const prk::FrameParams *fp, const prk::PrWalkArgs *a, int32_t mode, uint32_t cap,
@@ -4204,27 +4169,27 @@ hipError_t prk_pr_walk_group(const prk::FrameParams *fp, const prk::PrWalkArgs *
     if (cap == 0 || ngroup > 65535) return hipErrorInvalidValue;
     const size_t bytes = prk::slot_lds_bytes(cap);
     const uint32_t nt = prk::slot_threads(cap);
-    const prk::PrObj *P = reinterpret_cast<const prk::PrObj *>(a->pro);
-    const prk::PrRow *PR = reinterpret_cast<const prk::PrRow *>(a->prrow);
-    const prk::ObjDesc *O = reinterpret_cast<const prk::ObjDesc *>(a->objs);
-    const prk::ObjEdge *W = reinterpret_cast<const prk::ObjEdge *>(a->work);
-    const prk::ObjEdge *SST = reinterpret_cast<const prk::ObjEdge *>(a->sst);
-    prk::ObjEdge *EE = reinterpret_cast<prk::ObjEdge *>(a->eend);
-    prk::PairRaw *RAW = reinterpret_cast<prk::PairRaw *>(a->raw);
-    prk::SpanPos *POS = reinterpret_cast<prk::SpanPos *>(a->pos);
+    const prk::PrObj *P = a->pro;
+    const prk::PrRow *PR = a->prrow;
+    const prk::ObjDesc *O = a->objs;
+    const prk::ObjEdge *W = a->work;
+    const prk::ObjEdge *SST = a->sst;
+    prk::ObjEdge *EE = a->eend;
+    prk::PairRaw *RAW = a->raw;
+    prk::SpanPos *POS = a->pos;
     switch (mode) {
-#define PRK_PR_GROUP(MM)                                                                                             \
-    case MM:                                                                                                         \
+#define PRK_PR_GROUP(MM)                                                                                            \
+    case MM:                                                                                                        \
         hipLaunchKernelGGL(prk::k_pr_chunk<MM>, dim3(max_chunks, ngroup), dim3(nt), bytes, s, *fp, O, P, grp, cap,  \
                            PR, a->cnt, a->eoff, a->fge, a->escan, a->total0p, W, a->soff, SST, EE, a->eend_m,       \
-                           a->sidx, a->s_m, a->prstat, RAW, POS, a->span_tri, a->err, a->warmup);                    \
+                           a->sidx, a->s_m, a->prstat, RAW, POS, a->span_tri, a->err, a->warmup);                   \
         if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                          \
-        hipLaunchKernelGGL(prk::k_pr_cmp, dim3(a->nchunks), dim3(256), 0, s, P, a->npr, a->prstat, EE, a->eend_m,    \
-                           a->sidx, a->s_m, a->match);                                                               \
+        hipLaunchKernelGGL(prk::k_pr_cmp, dim3(a->nchunks), dim3(256), 0, s, P, a->npr, a->prstat, EE, a->eend_m,   \
+                           a->sidx, a->s_m, a->match);                                                              \
         if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                          \
         hipLaunchKernelGGL(prk::k_pr_fix<MM>, dim3(ngroup), dim3(nt), bytes, s, *fp, O, P, grp, cap, PR, a->cnt,    \
                            a->eoff, a->fge, a->escan, a->total0p, W, a->soff, EE, a->eend_m, a->sidx, a->s_m,       \
-                           a->match, a->prstat, RAW, POS, a->span_tri, a->err);                                      \
+                           a->match, a->prstat, RAW, POS, a->span_tri, a->err);                                     \
         break;
         PRK_PR_GROUP(prk::MODE_AVX)
         PRK_PR_GROUP(prk::MODE_SC_GOURAUD)
@@ -4238,7 +4203,7 @@ hipError_t prk_pr_walk_group(const prk::FrameParams *fp, const prk::PrWalkArgs *
 }
 hipError_t prk_pr_walk_end(const prk::PrWalkArgs *a, hipStream_t s) {
     if (a->npr == 0) return hipSuccess;
-    hipLaunchKernelGGL(prk::k_pr_tally, dim3(1), dim3(256), 0, s, reinterpret_cast<const prk::PrObj *>(a->pro),
+    hipLaunchKernelGGL(prk::k_pr_tally, dim3(1), dim3(256), 0, s, a->pro,
                        a->npr, a->prstat, a->err);
     return hipGetLastError();
 }
@@ -4246,36 +4211,35 @@ uint32_t prk_pr_chunk_rows(void) { return (uint32_t)prk::kPrChunk; }
 int32_t prk_pr_max_row_entries(void) { return prk::kPrMaxM; }
 int32_t prk_pr_max_rows(void) { return prk::kMaxactRows - 1; }
 // The slot walk's pairs (SPAN_RAW) into span records, one thread per slot.
-hipError_t prk_span_finish(const prk::FrameParams *fp, const void *raw, uint32_t nslot, void *recs, void *srecs,
-                           void *pos, hipStream_t s) {
+hipError_t prk_span_finish(const prk::FrameParams *fp, const prk::PairRaw *raw, uint32_t nslot, prk::SpanRecG *recs,
+                           prk::ScSpanRec *srecs, prk::SpanPos *pos, hipStream_t s) {
     if (nslot == 0) return hipSuccess;
     hipLaunchKernelGGL(prk::k_span_finish, dim3((nslot + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::PairRaw *>(raw), nslot, reinterpret_cast<prk::SpanRecG *>(recs),
-                       reinterpret_cast<prk::ScSpanRecG *>(srecs), reinterpret_cast<prk::SpanPos *>(pos));
+                       raw, nslot, recs, srecs, pos);
     return hipGetLastError();
 }
 
 // Span -> tile bin entries, pass 0: tcnt[t] = tile t's entries (ntiles + 1
 // values, the last 0: the scan's total).
-hipError_t prk_span_count(const prk::FrameParams *fp, const void *pos, uint32_t nspan, uint32_t *tcnt,
+hipError_t prk_span_count(const prk::FrameParams *fp, const prk::SpanPos *pos, uint32_t nspan, uint32_t *tcnt,
                           hipStream_t s) {
     const uint32_t ntiles = (uint32_t)(fp->tiles_x * fp->tiles_y);
     hipError_t e = hipMemsetAsync(tcnt, 0, ((size_t)ntiles + 1) * 4, s);
     if (e != hipSuccess || nspan == 0) return e;
     hipLaunchKernelGGL(prk::k_span_tiles<false>, dim3((nspan + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::SpanPos *>(pos), nspan, tcnt, nullptr, nullptr);
+                       pos, nspan, tcnt, nullptr, nullptr);
     return hipGetLastError();
 }
 
 // Pass 1: bins[offs[t] ...] = the spans of tile t (offs: the counts'
 // exclusive scan; tcur: ntiles cursors, zeroed here).
-hipError_t prk_span_bin(const prk::FrameParams *fp, const void *pos, uint32_t nspan, const uint32_t *offs,
+hipError_t prk_span_bin(const prk::FrameParams *fp, const prk::SpanPos *pos, uint32_t nspan, const uint32_t *offs,
                         uint32_t *tcur, uint32_t *bins, hipStream_t s) {
     const uint32_t ntiles = (uint32_t)(fp->tiles_x * fp->tiles_y);
     hipError_t e = hipMemsetAsync(tcur, 0, (size_t)ntiles * 4, s);
     if (e != hipSuccess || nspan == 0) return e;
     hipLaunchKernelGGL(prk::k_span_tiles<true>, dim3((nspan + 255) / 256), dim3(256), 0, s, *fp,
-                       reinterpret_cast<const prk::SpanPos *>(pos), nspan, tcur, offs, bins);
+                       pos, nspan, tcur, offs, bins);
     return hipGetLastError();
 }
 

@@ -1,58 +1,14 @@
-// prk_spans_dev.h — the span path's device types and row arithmetic that
-// prk_spans.hip and prk_records.hip share, each defined here once.
+// prk_spans_dev.h — the span path's device functions and row arithmetic that
+// prk_spans.hip and prk_records.hip share, each defined here once.  The
+// records they read and write (ObjEdge, SpanPos, SpanRecG, ScSpanRec, PairRaw,
+// EdgeIn, SpanIn) are prk_types.h's.
 #pragma once
 
 #include "prk_device.h"
 #include "prk_launch.h"
 
 namespace prk {
-// Caller edges (prk_edge = edge_info without Next, prk.h) and spans (prk_span).
-struct EdgeIn {
-    int32_t YMax;
-    float XMin, ZMin, OneOverZMin, Gradient, ZGradient, OneOverZGradient;
-    int32_t YMin;
-    float UMin, VMin, UGradient, VGradient;
-    int32_t Left;
-    float MinColor[4], ColorGradient[4], MinNormal[3], NormalGradient[3];
-};
-struct SpanEndIn {
-    float XMin, ZMin, OneOverZMin, UMin, VMin, MinColor[4], MinNormal[3];
-};
-struct SpanIn {
-    SpanEndIn L, R;
-    int32_t Row;
-};
-
-// Mutable edge_info of the object's AET (projekt.h:17-37) in global memory.
-struct ObjEdge {
-    float X, G, Z, ZG, W, WG, U, UG, V, VG;
-    float N0, N1, N2, NG0, NG1, NG2;
-    int32_t YMin, YMax, Left, Next;
-    float C0, C1, C2, C3, CG0, CG1, CG2, CG3;  // MinColor / ColorGradient (DrawModel's Gouraud colour)
-};
-static_assert(sizeof(ObjEdge) == kObjEdgeBytes, "ObjEdge is seven dwordx4");
-
-// Span of the span path: its row and pixel range [minx, maxx) (half-open,
-// 1588-1592), DRAW_ST in flags.
-struct SpanPos {
-    int32_t row, minx, maxx;
-    uint32_t flags;
-};
-
-struct SpanRecG {  // == SpanRec of prk_kernels.hip (FillLineOptimized lane init)
-    float4 q0, q1, q2, q3;
-};
-// A DrawModel span (scalar semantics) of the span path: the values at MinX
-// after the left clip (308-412) and the per-pixel increments, in the float
-// slot order of the scalar sweeps (prk_kernels.hip SS_*), plus its texture.
-// Its SpanRecG slot carries kScalarSpan in its first word, its SpanPos the
-// half-open [MinX, MaxX + 1) and SPAN_SCALAR | mode << 8 (prk_device.h).
-struct ScSpanRecG {
-    float f[22];
-    int32_t tex, pad;
-};
-static_assert(sizeof(ScSpanRecG) == kScSpanRecBytes, "scalar span record is six dwordx4");
-
+// An ObjEdge from FillEdgeTable's edge.
 __device__ __forceinline__ void obj_edge_store(ObjEdge &o, const Edge &E) {
     o.X = E.X; o.G = E.G; o.Z = E.Z; o.ZG = E.ZG; o.W = E.W; o.WG = E.WG;
     o.U = E.U; o.UG = E.UG; o.V = E.V; o.VG = E.VG;
@@ -130,7 +86,7 @@ __device__ __forceinline__ bool obj_span(const FrameParams &fp, const ObjEdge &L
 // draws nothing (a NaN end: pinned).
 template <int M>
 __device__ __forceinline__ bool obj_span_scalar(const FrameParams &fp, const ObjEdge &L, const ObjEdge &R, int32_t Row,
-                                                int32_t texi, ScSpanRecG &rec, SpanPos &pos) {
+                                                int32_t texi, ScSpanRec &rec, SpanPos &pos) {
     using TR = ModeTraits<M>;
     const int32_t W = fp.W;
     float XOffset = 0.0f;
@@ -215,11 +171,11 @@ __device__ __forceinline__ ObjEdge span_end_in(const SpanEndIn &e) {  // FillLin
 template <int M>
 __device__ __forceinline__ bool emit_span(const FrameParams &fp, const ObjEdge &L, const ObjEdge &R, int32_t Row,
                                           const DrawRec &d, bool st, uint32_t g0, bool write, uint32_t at,
-                                          SpanRecG *__restrict__ recs, ScSpanRecG *__restrict__ srecs,
+                                          SpanRecG *__restrict__ recs, ScSpanRec *__restrict__ srecs,
                                           SpanPos *__restrict__ pos, uint32_t *__restrict__ span_tri) {
     SpanPos sp;
     if constexpr (M != MODE_AVX) {
-        ScSpanRecG srec;
+        ScSpanRec srec;
         if (!obj_span_scalar<M>(fp, L, R, Row, d.tex, srec, sp)) return false;
         if (write) {
             SpanRecG mark;
@@ -314,10 +270,6 @@ __device__ __forceinline__ ObjEdge er_edge(float4 q0, float4 q1, float4 q2, floa
 // turns it into the span's record (or row -1 when it covers nothing).  The
 // setup's ~300 instructions per span leave the walk's row-serial path.
 constexpr uint32_t SPAN_RAW = 0x40000000u;
-struct PairRaw {
-    float4 l0, l1, l2, r0, r1, r2;  // X Z W U | V N0 N1 N2 | C0 C1 C2 C3, left then right edge
-};
-static_assert(sizeof(PairRaw) == kPairRawBytes, "six dwordx4");
 // One edge's half of a PairRaw (pair_raw_in reads it back).
 __device__ __forceinline__ void pair_raw_half(const ObjEdge &e, float4 &q0, float4 &q1, float4 &q2) {
     q0 = make_float4(e.X, e.Z, e.W, e.U);
