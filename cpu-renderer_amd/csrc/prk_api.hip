@@ -255,6 +255,57 @@ int prk_selftest_scan(int32_t device, int32_t width, uint32_t n, const void *in,
     return PRK_OK;
 }
 
+// The visibility reduction on the caller's words (prk.h): prk_visibility_*'s
+// kernels with no context, every device buffer guarded, the histogram in its
+// counting instantiation.
+int prk_selftest_visibility(int32_t device, uint32_t n, const int32_t *winners, uint32_t id_count, uint32_t *counts,
+                            uint32_t *pix_prefix, uint32_t *vis_prefix, uint32_t *ids, uint32_t *visible_out,
+                            uint64_t *atomics_out, uint32_t *damage) {
+    if (device < 0 || (!winners && n) || ((!counts || !ids) && id_count) || !pix_prefix || !vis_prefix ||
+        !visible_out || !atomics_out || !damage || id_count > 0xFFFFFFF0u)
+        return PRK_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(device));
+    const size_t wb = (size_t)n * 4, ib = (size_t)id_count * 4, mb = ib + 4;
+    size_t tb = 0;
+    PRK_TRY(prk_vis_reduce(nullptr, n, id_count, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &tb, nullptr,
+                           nullptr));
+    GuardedBuf win, cnt, flg, pix, vis, idl, temp, nat;
+    const uint32_t zero = 0;
+    PRK_TRY(win.fill(wb, winners));
+    PRK_TRY(cnt.fill(mb, nullptr));
+    PRK_TRY(flg.fill(mb, nullptr));
+    PRK_TRY(pix.fill(mb, nullptr));
+    PRK_TRY(vis.fill(mb, nullptr));
+    PRK_TRY(idl.fill(ib, nullptr));
+    PRK_TRY(temp.fill(tb, nullptr));
+    PRK_TRY(nat.fill(4, &zero));
+    PRK_TRY(prk_vis_reduce((const int32_t *)win.p, n, id_count, (uint32_t *)cnt.p, (uint32_t *)flg.p, (uint32_t *)pix.p,
+                           (uint32_t *)vis.p, (uint32_t *)idl.p, temp.p, &tb, (uint32_t *)nat.p, nullptr));
+    PRK_TRY(hipDeviceSynchronize());
+    GuardedBuf *all[] = {&win, &cnt, &flg, &pix, &vis, &idl, &temp, &nat};
+    for (GuardedBuf *b : all) PRK_TRY(b->read());
+    *damage = (win.holds(winners) && win.guard_intact() ? 0u : PRK_DAMAGE_INPUT) |
+              (cnt.guard_intact() && pix.guard_intact() && vis.guard_intact() && idl.guard_intact() &&
+                       nat.guard_intact()
+                   ? 0u
+                   : PRK_DAMAGE_OUTPUT_GUARD) |
+              (temp.guard_intact() && flg.guard_intact() ? 0u : PRK_DAMAGE_TEMP_GUARD);
+    uint32_t visible = 0, atomics = 0;
+    std::memcpy(&visible, vis.host.data() + ib, 4);
+    std::memcpy(&atomics, nat.host.data(), 4);
+    if (visible > id_count) visible = id_count;  // (a damaged run: nothing past the caller's arrays)
+    if (ib) std::memcpy(counts, cnt.host.data(), ib);
+    std::memcpy(pix_prefix, pix.host.data(), mb);
+    std::memcpy(vis_prefix, vis.host.data(), mb);
+    if (visible) std::memcpy(ids, idl.host.data(), (size_t)visible * 4);
+    *visible_out = visible;
+    *atomics_out = atomics;
+    return PRK_OK;
+}
+
 int prk_create(int device, prk_context **out) {
     if (!out) return PRK_ERR_ARG;
     *out = nullptr;
@@ -341,7 +392,9 @@ int prk_destroy(prk_context *c) {
         if (B.listed_ev) (void)hipEventDestroy(B.listed_ev);
         if (B.h_info) (void)hipHostFree(B.h_info);
     }
-    DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz, &c->d_xform};
+    DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz, &c->d_xform,
+                      &c->vis.d_counts, &c->vis.d_flags, &c->vis.d_pix, &c->vis.d_vis, &c->vis.d_ids,
+                      &c->vis.d_temp, &c->vis.d_starts, &c->vis.d_gout};
     for (DevBuf *b : bufs) b->release();
     if (c->h_xform) (void)hipHostFree(c->h_xform);
     if (c->xf_ev) (void)hipEventDestroy(c->xf_ev);

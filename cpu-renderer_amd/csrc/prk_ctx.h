@@ -1,7 +1,8 @@
 // prk_ctx.h — the host runtime's own header: struct prk_context (opaque in
 // include/prk.h) with the resources and scratch it owns, the state a pass is
 // queued with, and the few host functions that cross the host files
-// (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip).  Host
+// (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip,
+// prk_visibility_api.hip).  Host
 // only; prk_launch.h stays the seam to the kernel files (prk_types.h: the
 // records the buffers here hold), and prk_dist.hip keeps the context opaque.
 //
@@ -149,6 +150,21 @@ inline hipError_t obj_sort(DevBuf &temp, void *keys_in, uint32_t *vals_in, void 
     return e;
 }
 
+// Visibility feedback (prk_visibility_*, prk_visibility_api.hip): the winner
+// map of the last flush reduced to per-id pixel counts.  prk_flush says
+// whether its frame has an answer (draws, and the winner map of debug mode)
+// and how many ids it handed out; the first query reduces the map, later ones
+// of the same frame reuse the arrays.  The buffers grow with ensure and are
+// reused frame to frame.
+struct VisState {
+    DevBuf d_counts, d_flags, d_pix, d_vis, d_ids, d_temp;  // id_count + 1 words each (d_ids: id_count)
+    DevBuf d_starts, d_gout;                                // prk_visibility_groups: its ranges, its two outputs
+    bool frame = false;  // the last prk_flush drew, with the winner map on
+    bool done = false;   // ... and has been reduced
+    uint32_t id_count = 0, visible = 0;
+    uint64_t covered = 0;
+};
+
 // The state a pass is queued with and an overflow re-run (resolve_count)
 // runs with again: the target, the tile, the cameras and lights, the clear.
 // The context holds its own as its base (prk_context), so this is the one
@@ -272,6 +288,7 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     // them instead of running FillEdgeTable, so they are not optional
     bool setup_rec = true;
     bool winners_valid = false;
+    VisState vis;
     prk_stats stats{};
     // Timing ring: 6 events per flush.
     static constexpr int kRing = 32;

@@ -569,6 +569,8 @@ int prk_flush(prk_context *c, void *stream) {
     }
     c->z_early = false;  // (the passes below say whether the frame's last one allows it)
     c->bdbg.valid = false;  // (prk_debug_bins: this flush's last per-triangle pass, if any)
+    c->vis.frame = c->vis.done = false;  // (prk_visibility_*: this flush's frame, if it draws with the winner map)
+    const uint32_t frame_ids = c->pending_tris;  // the ids this flush hands out
     if (c->debug) {
         PRK_TRY(c->d_winners.ensure((size_t)c->W * (c->row1 - c->row0) * 4));
         PRK_TRY(hipMemsetAsync(c->d_winners.p, 0xFF, (size_t)c->W * (c->row1 - c->row0) * 4, s));
@@ -614,6 +616,10 @@ int prk_flush(prk_context *c, void *stream) {
     }
     // the frame's last reader of the geometry (the flush stream ends every pass)
     c->read_rec = hipEventRecord(c->read_ev, s) == hipSuccess;
+    if (rc == PRK_OK && c->debug) {  // the frame prk_visibility_* answers for
+        c->vis.frame = true;
+        c->vis.id_count = frame_ids;
+    }
     return rc;
 }
 

@@ -147,6 +147,17 @@ hipError_t prk_layer_launch(const void *src_color, size_t src_cpitch, const floa
                             void *dst_color, size_t dst_cpitch, float *dst_z, size_t dst_zpitch, uint32_t w,
                             uint32_t h, int32_t rule, hipStream_t s);
 
+// ---- prk_visibility.hip -------------------------------------------------------
+// prk_visibility_*: n winner words reduced over id_count ids (temp == nullptr: the scratch size only) -- counts,
+// flags, pix_prefix and vis_prefix of id_count + 1 words each, ids of id_count (written up to the visible count).
+// natomics: nullptr, or a zeroed word that counts the histogram's atomic adds (the self-test's instantiation).
+hipError_t prk_vis_reduce(const int32_t *winners, uint32_t n, uint32_t id_count, uint32_t *counts, uint32_t *flags,
+                          uint32_t *pix_prefix, uint32_t *vis_prefix, uint32_t *ids, void *temp, size_t *temp_bytes,
+                          uint32_t *natomics, hipStream_t s);
+// pixels[g] / visible[g] (either may be null) of the ngroup id ranges [starts[g], starts[g + 1]): prefix differences.
+hipError_t prk_vis_groups(const uint32_t *starts, uint32_t ngroup, const uint32_t *pix_prefix,
+                          const uint32_t *vis_prefix, uint32_t *pixels, uint32_t *visible, hipStream_t s);
+
 // ---- prk_spans.hip: prk_edge_records ---------------------------------------------
 // prk_edge_records: the object triangles' edges with their true-YMin MergeSort keys ...
 hipError_t prk_rec_emit(const prk::FrameParams *fp, const prk::ObjDesc *objs, const uint32_t *k0obj,

@@ -170,6 +170,7 @@ _SIGS.update({name: (C.c_int, args) for name, args in abi.GEOMETRY_TRANSFORM_SIG
 _SIGS.update({name: (C.c_int, args) for name, args in abi.TEXTURE_TARGET_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.TARGET_LAYER_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.SORT_SELFTEST_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.VISIBILITY_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
@@ -345,6 +346,24 @@ def selftest_scan(x, width, device=0):
     _check("prk_selftest_scan", lib().prk_selftest_scan(device, int(width), a.shape[0], _ptr(a), _ptr(out),
                                                         C.byref(dmg)))
     return out, dmg.value
+
+
+def selftest_visibility(winners, id_count, device=0):
+    """prk_selftest_visibility: the visibility reduction (prk_visibility_*'s
+    kernels) of the int32 winner words over id_count ids, no context.
+    Returns a dict: counts [id_count], pix_prefix and vis_prefix
+    [id_count + 1], ids [visible] (all uint32), visible, atomics (the atomic
+    adds the histogram issued) and damage (0 or abi.PRK_DAMAGE_* bits)."""
+    w = np.ascontiguousarray(winners, np.int32).reshape(-1)
+    m = int(id_count)
+    counts, ids = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+    pix, vis = np.zeros(m + 1, np.uint32), np.zeros(m + 1, np.uint32)
+    nvis, nat, dmg = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0xFFFFFFFF)
+    _check("prk_selftest_visibility", lib().prk_selftest_visibility(
+        device, w.shape[0], _ptr(w), m, _ptr(counts), _ptr(pix), _ptr(vis), _ptr(ids), C.byref(nvis), C.byref(nat),
+        C.byref(dmg)))
+    return dict(counts=counts, pix_prefix=pix, vis_prefix=vis, ids=ids[:nvis.value], visible=nvis.value,
+                atomics=nat.value, damage=dmg.value)
 
 
 def band_rows(height, rank, nranks):
@@ -660,6 +679,54 @@ class Renderer:
         w = np.empty((rows, self.width), np.int32)
         _check("prk_download_winners", self._L.prk_download_winners(self._h, _ptr(w)))
         return w
+
+    # ---- visibility feedback ----------------------------------------------
+    def visibility(self):
+        """prk_visibility_info: (id_count, covered, visible_ids) of the last
+        frame -- the ids its flush handed out, the pixels of this context's
+        band that any of them won, and how many ids won at least one.  Needs
+        set_debug(True) at the flush; the first call after a flush reduces
+        the winner map on the device, later ones reuse the result."""
+        n, cov, vis = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        _check("prk_visibility_info", self._L.prk_visibility_info(self._h, C.byref(n), C.byref(cov), C.byref(vis)))
+        return n.value, cov.value, vis.value
+
+    def visibility_counts(self, first=0, count=None):
+        """prk_visibility_counts: uint32 [count], the pixels ids first ...
+        first + count won (None: to the frame's last id)."""
+        if count is None:
+            count = self.visibility()[0] - int(first)
+        out = np.zeros(max(0, int(count)), np.uint32)
+        _check("prk_visibility_counts", self._L.prk_visibility_counts(self._h, int(first), int(count), _ptr(out)))
+        return out
+
+    def visibility_groups(self, starts):
+        """prk_visibility_groups: for the groups of ids [starts[g],
+        starts[g + 1]) (uint32 [groups + 1], non-decreasing), (pixels, visible):
+        uint32 [groups] each -- a group's pixels, and how many of its ids won any."""
+        st = np.ascontiguousarray(starts, np.uint32).reshape(-1)
+        if st.shape[0] < 1:
+            raise ValueError("visibility_groups: starts needs groups + 1 words")
+        g = st.shape[0] - 1
+        pix, vis = np.zeros(g, np.uint32), np.zeros(g, np.uint32)
+        _check("prk_visibility_groups", self._L.prk_visibility_groups(self._h, _ptr(st), g, _ptr(pix), _ptr(vis)))
+        return pix, vis
+
+    def visibility_ids(self):
+        """prk_visibility_ids: uint32 [visible_ids], the ids that won a pixel, ascending."""
+        total = C.c_uint64(0)
+        _check("prk_visibility_ids", self._L.prk_visibility_ids(self._h, None, 0, C.byref(total)))
+        out = np.zeros(total.value, np.uint32)
+        _check("prk_visibility_ids", self._L.prk_visibility_ids(self._h, _ptr(out), total.value, C.byref(total)))
+        return out
+
+    def visibility_device(self):
+        """prk_visibility_device: (counts_ptr, pix_prefix_ptr, id_count) -- the
+        library's device arrays of id_count and id_count + 1 uint32 words,
+        complete, read-only, valid until the next flush or target change."""
+        cp, pp, n = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        _check("prk_visibility_device", self._L.prk_visibility_device(self._h, C.byref(cp), C.byref(pp), C.byref(n)))
+        return cp.value or 0, pp.value or 0, n.value
 
     # ---- state ------------------------------------------------------------
     def set_camera(self, transform, lights):

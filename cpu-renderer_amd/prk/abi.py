@@ -146,6 +146,17 @@ TARGET_LAYER_SIGS = {
     "prk_layer_destroy": [C.c_void_p, C.c_int32],
 }
 
+# Visibility feedback (prk.h): each entry point and its argument types
+VISIBILITY_SIGS = {
+    "prk_visibility_info": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)],
+    "prk_visibility_counts": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
+    "prk_visibility_groups": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p],
+    "prk_visibility_ids": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+    "prk_visibility_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)],
+    "prk_selftest_visibility": [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)],
+}
+
 
 # prk_row_pair word w holds prk_span word ROW_PAIR_SPAN_WORD[w] (an end is
 # XMin ZMin OneOverZMin UMin VMin MinColor[4] MinNormal[3]; Right at +12)

@@ -403,6 +403,66 @@ int prk_layer_download(prk_context *ctx, int32_t layer, uint32_t *color_host, in
 int prk_layer_info(prk_context *ctx, int32_t layer, int32_t *width, int32_t *height, int32_t *pitch_bytes, int32_t *wrapped);
 int prk_layer_destroy(prk_context *ctx, int32_t layer);
 
+/* Visibility feedback: what the last frame showed, per id, without moving the
+ * frame to the host -- which draws, objects or triangles won pixels, and how
+ * many.  An EXTENSION of this build with its own definition:
+ * the reference has no such query.
+ *
+ * THE FRAME is the most recent prk_flush, if it had draws and was queued with
+ * prk_set_debug(ctx, 1) (prk_download_winners' precondition: the answer is a
+ * reduction of that winner map, on the device).  A flush without draws or with
+ * debug off leaves no frame, and neither does a target bound or allocated
+ * since.
+ * IDS are the frame's winner numbering, in submission order from 0: one per
+ * triangle of prk_draw and of prk_draw_objects' range (an object's pixels
+ * carry the id of its first triangle; its other ids stay at 0 pixels), one
+ * per prk_draw_edges call, per list of prk_draw_edge_lists / prk_draw_records
+ * (an empty list takes its id all the same), per span of prk_draw_spans /
+ * prk_draw_span_records and per pair of prk_draw_rows.  id_count is the number
+ * of ids that flush handed out.
+ * pixels[i] is the number of pixels of the context's band, rows [row0, row1),
+ * whose winner word is i.  A pixel that kept an earlier flush's contents
+ * belongs to no id.  covered is the sum of pixels[i], visible_ids the number
+ * of ids with pixels[i] > 0.  A band context answers for its own rows, so a
+ * frame's counts are the sums of its ranks'.  Winner ids are not merged by
+ * prk_target_from_layer (above), so a later merge does not change the answer.
+ *
+ * prk_visibility_info: id_count, covered and visible_ids (all three required).
+ * prk_visibility_counts: pixels[0 .. count) = the counts of ids first_id ...
+ * prk_visibility_groups: for group g = ids [starts[g], starts[g + 1]) -- an
+ * object's triangles, a batch's lists; starts has group_count + 1 words --
+ * pixels[g] = the sum of the group's counts and visible[g] = how many of its
+ * ids have any.  Either output may be NULL, not both; an empty group gets 0.
+ * prk_visibility_ids: the ids with pixels[i] > 0, ascending.  *total_out is
+ * always written (0 where there is no frame); ids == NULL: the size only; a
+ * capacity below the total: PRK_ERR_ARG with `ids` untouched.
+ * prk_visibility_device: the library's own device arrays, complete when the
+ * call returns: counts of id_count words and pix_prefix of id_count + 1
+ * (pix_prefix[i] = pixels[0] + ... + pixels[i - 1]; the last word is covered).
+ * Read-only, valid until the next prk_flush, prk_target_alloc / prk_target_bind
+ * or prk_destroy: for a caller that wants the counts as a tensor, no copy.
+ *
+ * Ordering and cost: every call resolves the pending frame first (an
+ * overflowed one is re-run, as prk_download_winners does).  The first call
+ * after a flush waits for the frame, queues the reduction (a histogram of the
+ * map, two scans, a compaction) and waits for it; later calls for the same
+ * frame reuse the result: host copies, and one small kernel for the groups.
+ * Nothing here touches the flush: a frame queued without the winner map costs
+ * what it did.  The winner map is debug mode's, which forgoes the fused clear
+ * (prk_target_clear_on_flush then fills before the frame).
+ *
+ * PRK_ERR_ARG: a NULL context, no such frame, a NULL required pointer,
+ * first_id + count > id_count, starts not non-decreasing or
+ * starts[group_count] > id_count.  PRK_ERR_LIMIT: a band of 2^32 pixels or
+ * more.  count == 0 or group_count == 0: PRK_OK, nothing written.  On any
+ * error nothing is written, except *total_out as stated. */
+int prk_visibility_info(prk_context *ctx, uint32_t *id_count, uint64_t *covered, uint32_t *visible_ids);
+int prk_visibility_counts(prk_context *ctx, uint32_t first_id, uint32_t count, uint32_t *pixels);
+int prk_visibility_groups(prk_context *ctx, const uint32_t *starts, uint32_t group_count,
+                          uint32_t *pixels, uint32_t *visible); /* either output may be NULL, not both */
+int prk_visibility_ids(prk_context *ctx, uint32_t *ids, uint64_t capacity, uint64_t *total_out);
+int prk_visibility_device(prk_context *ctx, const uint32_t **counts, const uint32_t **pix_prefix, uint32_t *id_count);
+
 /* Geometry: non-indexed SoA vertex arrays exactly as render_entry_3d_object
  * (projekt.h:2-15): positions v3, colours v4, normals v3, uvs v2, three
  * vertices per triangle.  Copied to HBM once; a draw references a range. */
@@ -806,6 +866,20 @@ enum { PRK_DAMAGE_INPUT = 1, PRK_DAMAGE_OUTPUT_GUARD = 2, PRK_DAMAGE_TEMP_GUARD 
 int prk_selftest_sort(int32_t device, uint32_t n, uint32_t end_bit, const uint64_t *keys, const uint32_t *vals,
                       uint32_t repeats, uint64_t *keys_out, uint32_t *vals_out, uint32_t *damage);
 int prk_selftest_scan(int32_t device, int32_t width, uint32_t n, const void *in, void *out, uint32_t *damage);
+/* Test: prk_visibility_*'s kernels (csrc/prk_visibility.hip) on the caller's
+ * n winner words and id_count ids, synchronously on `device`, no context
+ * needed, guarded and compared as above (the flags the scans read count as
+ * temp).  counts: id_count words; pix_prefix, vis_prefix: id_count + 1 words;
+ * ids: room for id_count words, *visible_out (= vis_prefix[id_count]) of them
+ * written.  *atomics_out: the atomic adds the histogram issued -- counted by
+ * an instantiation of its own, which this call alone runs (the one behind
+ * prk_visibility_* carries no counter).  PRK_ERR_ARG: a NULL pointer (winners
+ * with n > 0, counts / ids with id_count > 0, any other), a bad device,
+ * id_count > 2^32 - 16.  tests/test_gpu_visibility.py holds every word to
+ * tests/visref.py, *damage == 0. */
+int prk_selftest_visibility(int32_t device, uint32_t n, const int32_t *winners, uint32_t id_count,
+                            uint32_t *counts, uint32_t *pix_prefix, uint32_t *vis_prefix, uint32_t *ids,
+                            uint32_t *visible_out, uint64_t *atomics_out, uint32_t *damage);
 
 /* The bound target (any pointer may be NULL) and the context's device and
  * own stream (a hipStream_t; prk_flush(ctx, NULL) runs on it). */
