@@ -306,6 +306,94 @@ int prk_selftest_visibility(int32_t device, uint32_t n, const int32_t *winners, 
     return PRK_OK;
 }
 
+// prk_geometry_select's three stages on the caller's tables and arrays
+// (prk.h): the launchers the call itself queues, with no context, every
+// device buffer guarded, the outputs starting out as the guard pattern.
+int prk_selftest_select(int32_t device, const uint32_t *pix_prefix, uint32_t id_count, const prk_select_item *items,
+                        uint32_t item_count, const prk_select_level *levels, uint32_t level_count,
+                        const prk_xform *xforms, uint32_t xform_count, const uint32_t *item_pixels,
+                        const float *src_vertices, const float *src_colors, const float *src_normals,
+                        const float *src_uvs, uint32_t src_tris, uint32_t dst_first_tri, uint32_t dst_tris,
+                        float *dst_vertices, float *dst_colors, float *dst_normals, float *dst_uvs, int32_t *chosen,
+                        uint32_t *out_first, uint64_t *total_tris_out, uint32_t *damage) {
+    if (device < 0 || (item_count && (!items || !chosen)) || !out_first || !total_tris_out || !damage ||
+        (!item_pixels && !pix_prefix) || id_count == UINT32_MAX || item_count == UINT32_MAX)
+        return PRK_ERR_ARG;
+    const float *src[4] = {src_vertices, src_colors, src_normals, src_uvs};
+    float *dst[4] = {dst_vertices, dst_colors, dst_normals, dst_uvs};
+    const size_t comp[4] = {3, 4, 3, 2};
+    for (int k = 0; k < 4; ++k)
+        if (src[k] && !dst[k]) return PRK_ERR_ARG;
+    uint64_t worst = 0;
+    {
+        const int rc = select_check(items, item_count, levels, level_count, xforms, xform_count, src_tris,
+                                    item_pixels ? nullptr : &id_count, &worst);
+        if (rc != PRK_OK) return rc;
+    }
+    if (worst && !src_vertices) return PRK_ERR_ARG;
+    if (worst > (1ull << 31)) return PRK_ERR_LIMIT;
+    if ((uint64_t)dst_first_tri + worst > dst_tris || (uint64_t)dst_tris * 3 > 0xFFFFFFF0ull) return PRK_ERR_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(device));
+    const size_t wb = ((size_t)item_count + 1) * 4;
+    size_t tb = 0;
+    PRK_TRY(prk_scan_u32(nullptr, nullptr, item_count + 1, nullptr, &tb, nullptr));
+    GuardedBuf pix, itm, lev, xfm, ipx, sa[4], da[4], cho, cnt, sta, run, temp;
+    PRK_TRY(pix.fill(item_pixels ? 0 : ((size_t)id_count + 1) * 4, pix_prefix));
+    PRK_TRY(itm.fill((size_t)item_count * sizeof(prk_select_item), items));
+    PRK_TRY(lev.fill(levels ? (size_t)level_count * sizeof(prk_select_level) : 0, levels));
+    PRK_TRY(xfm.fill(xforms ? (size_t)xform_count * sizeof(prk_xform) : 0, xforms));
+    PRK_TRY(ipx.fill(item_pixels ? (size_t)item_count * 4 : 0, item_pixels));
+    for (int k = 0; k < 4; ++k) {
+        PRK_TRY(sa[k].fill(src[k] ? (size_t)src_tris * 3 * comp[k] * 4 : 0, src[k]));
+        PRK_TRY(da[k].fill(src[k] ? (size_t)dst_tris * 3 * comp[k] * 4 : 0, nullptr));
+    }
+    PRK_TRY(cho.fill((size_t)item_count * 4, nullptr));
+    PRK_TRY(cnt.fill(wb, nullptr));
+    PRK_TRY(sta.fill(wb, nullptr));
+    PRK_TRY(run.fill((size_t)item_count * sizeof(prk::SelRun), nullptr));
+    PRK_TRY(temp.fill(tb, nullptr));
+    PRK_TRY(prk_sel_choose((const prk_select_item *)itm.p, item_count, (const prk_select_level *)lev.p,
+                           item_pixels ? nullptr : (const uint32_t *)pix.p,
+                           item_pixels ? (const uint32_t *)ipx.p : nullptr, (int32_t *)cho.p, (uint32_t *)cnt.p,
+                           (prk::SelRun *)run.p, nullptr));
+    PRK_TRY(prk_scan_u32((const uint32_t *)cnt.p, (uint32_t *)sta.p, item_count + 1, temp.p, &tb, nullptr));
+    uint32_t total = 0;
+    PRK_TRY(hipMemcpy(&total, sta.p + (size_t)item_count * 4, 4, hipMemcpyDeviceToHost));  // (waits for both)
+    if (total > worst) return PRK_ERR_DEVICE;  // (never: the emit pass would leave the destination)
+    const float *ds[4];
+    float *dd[4];
+    for (int k = 0; k < 4; ++k) {
+        ds[k] = src[k] ? (const float *)sa[k].p : nullptr;
+        dd[k] = src[k] ? (float *)da[k].p : nullptr;
+    }
+    PRK_TRY(prk_sel_emit((const uint32_t *)sta.p, (const prk::SelRun *)run.p, item_count, total, dst_first_tri,
+                         (const prk_xform *)xfm.p, ds[0], ds[1], ds[2], ds[3], dd[0], dd[1], dd[2], dd[3], nullptr));
+    PRK_TRY(hipDeviceSynchronize());
+    GuardedBuf *all[] = {&pix, &itm, &lev, &xfm, &ipx, &sa[0], &sa[1], &sa[2], &sa[3], &da[0], &da[1],
+                         &da[2], &da[3], &cho, &cnt, &sta, &run, &temp};
+    for (GuardedBuf *b : all) PRK_TRY(b->read());
+    bool in_ok = pix.holds(pix_prefix) && pix.guard_intact() && itm.holds(items) && itm.guard_intact() &&
+                 lev.holds(levels) && lev.guard_intact() && xfm.holds(xforms) && xfm.guard_intact() &&
+                 ipx.holds(item_pixels) && ipx.guard_intact();
+    bool out_ok = cho.guard_intact() && sta.guard_intact();
+    for (int k = 0; k < 4; ++k) {
+        in_ok = in_ok && sa[k].holds(src[k]) && sa[k].guard_intact();
+        out_ok = out_ok && da[k].guard_intact();
+    }
+    *damage = (in_ok ? 0u : PRK_DAMAGE_INPUT) | (out_ok ? 0u : PRK_DAMAGE_OUTPUT_GUARD) |
+              (cnt.guard_intact() && run.guard_intact() && temp.guard_intact() ? 0u : PRK_DAMAGE_TEMP_GUARD);
+    if (item_count) std::memcpy(chosen, cho.host.data(), (size_t)item_count * 4);
+    std::memcpy(out_first, sta.host.data(), wb);
+    for (uint32_t i = 0; i <= item_count; ++i) out_first[i] += dst_first_tri;
+    for (int k = 0; k < 4; ++k)
+        if (src[k] && da[k].bytes) std::memcpy(dst[k], da[k].host.data(), da[k].bytes);
+    *total_tris_out = total;
+    return PRK_OK;
+}
+
 int prk_create(int device, prk_context **out) {
     if (!out) return PRK_ERR_ARG;
     *out = nullptr;
@@ -394,11 +482,14 @@ int prk_destroy(prk_context *c) {
     }
     DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz, &c->d_xform,
                       &c->vis.d_counts, &c->vis.d_flags, &c->vis.d_pix, &c->vis.d_vis, &c->vis.d_ids,
-                      &c->vis.d_temp, &c->vis.d_starts, &c->vis.d_gout};
+                      &c->vis.d_temp, &c->vis.d_starts, &c->vis.d_gout, &c->sel.d_tab, &c->sel.d_out,
+                      &c->sel.d_temp};
     for (DevBuf *b : bufs) b->release();
     if (c->h_xform) (void)hipHostFree(c->h_xform);
     if (c->xf_ev) (void)hipEventDestroy(c->xf_ev);
     if (c->xf_end_ev) (void)hipEventDestroy(c->xf_end_ev);
+    for (hipEvent_t e : c->sel.ev)
+        if (e) (void)hipEventDestroy(e);
     {
         auto &S = c->spans;
         DevBuf *sb[] = {&S.d_stage, &S.d_edges, &S.d_ord, &S.d_temp, &S.d_recs, &S.d_pos, &S.d_span_tri, &S.d_scnt,
@@ -1043,8 +1134,6 @@ int prk_geometry_update(prk_context *c, int32_t handle, const float *v, const fl
     return PRK_OK;
 }
 
-static int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end);
-
 int prk_geometry_write(prk_context *c, int32_t handle, uint32_t first_vertex, uint32_t vertex_count,
                        const float *v, const float *col, const float *n, const float *uv) {
     if (!c || handle < 0 || (size_t)handle >= c->geoms.size() || first_vertex % 3 || vertex_count % 3)
@@ -1085,8 +1174,9 @@ int prk_geometry_write(prk_context *c, int32_t handle, uint32_t first_vertex, ui
 // are wanted now (prk_geometry_write, prk_geometry_transform): buffers that
 // must grow do so by half again at least, so a frame streamed in chunks
 // reallocates rarely; contents kept, zeros past them (a new array: all zeros),
-// recorded draws repointed.  Growing waits for the device.
-static int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end) {
+// recorded draws repointed.  Growing waits for the device.  (Hidden,
+// prk_ctx.h: prk_geometry_select grows its destination the same way.)
+int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end) {
     Geometry &g = c->geoms[handle];
     const float **dst[4] = {&g.V, &g.C, &g.N, &g.UV};
     const size_t comp[4] = {3, 4, 3, 2};

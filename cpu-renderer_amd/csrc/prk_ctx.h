@@ -2,7 +2,7 @@
 // include/prk.h) with the resources and scratch it owns, the state a pass is
 // queued with, and the few host functions that cross the host files
 // (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip,
-// prk_visibility_api.hip).  Host
+// prk_visibility_api.hip, prk_select_api.hip).  Host
 // only; prk_launch.h stays the seam to the kernel files (prk_types.h: the
 // records the buffers here hold), and prk_dist.hip keeps the context opaque.
 //
@@ -165,6 +165,16 @@ struct VisState {
     uint64_t covered = 0;
 };
 
+// prk_geometry_select (prk_select_api.hip): the call's tables as uploaded, what
+// the device builds from them (chosen, n, start, the runs) and the scan's
+// scratch, all reused call to call; the emit pass of one call reads them
+// until the next call's uploads, which the geometry stream orders behind it.
+struct SelState {
+    DevBuf d_tab, d_out, d_temp;
+    hipEvent_t ev[4] = {};  // (timed: prk_debug_select_ms) before the uploads, after the total's copy; around the emit pass
+    bool timed = false, emitted = false;
+};
+
 // The state a pass is queued with and an overflow re-run (resolve_count)
 // runs with again: the target, the tile, the cameras and lights, the clear.
 // The context holds its own as its base (prk_context), so this is the one
@@ -289,6 +299,7 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     bool setup_rec = true;
     bool winners_valid = false;
     VisState vis;
+    SelState sel;
     prk_stats stats{};
     // Timing ring: 6 events per flush.
     static constexpr int kRing = 32;
@@ -400,6 +411,14 @@ PRK_HIDDEN int draw_src(prk_context *c, uint32_t kind, uint32_t off, uint32_t n,
 PRK_HIDDEN bool list_walks_sorted(const prk_edge *e, uint32_t n);
 PRK_HIDDEN int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_row_pair *pairs,
                              uint32_t npair, prk_span *out, void *keep = nullptr);
+// Room for `end` vertices in a library-owned geometry's arrays that exist or are wanted now.
+PRK_HIDDEN int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end);
+// prk_visibility_api.hip: the frame's answer, reduced if this is the first query since its flush.
+PRK_HIDDEN int vis_ready(prk_context *c);
+// prk_select_api.hip: prk_geometry_select's table checks (the self-test runs them too).
+PRK_HIDDEN int select_check(const prk_select_item *items, uint32_t item_count, const prk_select_level *levels,
+                            uint32_t level_count, const prk_xform *xforms, uint32_t xform_count, uint32_t src_tris,
+                            const uint32_t *frame_ids, uint64_t *worst);
 }  // extern "C"
 
 // Calls that read or replace the target, or change what a re-run of the

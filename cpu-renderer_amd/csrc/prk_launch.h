@@ -19,6 +19,9 @@
 #include "prk_types.h"  // the records both sides rely on
 
 struct prk_context;  // include/prk.h
+struct prk_select_item;   // ... and its plain records that a kernel file reads as they are
+struct prk_select_level;
+struct prk_xform;
 
 namespace prk {
 struct FrameParams;  // prk_device.h
@@ -132,6 +135,22 @@ hipError_t prk_obj_sort(void *keys_in, uint32_t *vals_in, void *keys_out, uint32
 hipError_t prk_xform_launch(const void *tables, size_t runs_off, size_t xf_off, uint32_t nruns, uint32_t total,
                             const float *sV, const float *sC, const float *sN, const float *sUV, float *dV,
                             float *dC, float *dN, float *dUV, hipStream_t s);
+
+// ---- prk_select.hip -----------------------------------------------------------
+// prk_geometry_select, stage 1: for each of nitems items its pixel count (item_pixels[i], or without item_pixels
+// the difference of two pix_prefix words), the first of its levels that the count passes, and from it chosen[i]
+// (the level, or -1), n[i] (its triangles, or 0) and runs[i].  n has nitems + 1 words, the last written 0: the
+// scan's input, whose last output word is the total.
+hipError_t prk_sel_choose(const prk_select_item *items, uint32_t nitems, const prk_select_level *levels,
+                          const uint32_t *pix_prefix, const uint32_t *item_pixels, int32_t *chosen, uint32_t *n,
+                          prk::SelRun *runs, hipStream_t s);
+// Stage 3 (stage 2 is prk_scan_u32 of n into start): output triangle t of [0, total) belongs to the last item i
+// with start[i] <= t; source triangle runs[i].src0 + (t - start[i]) goes through xforms[runs[i].xform] to
+// destination triangle dst_first_tri + t.  total = start[nitems], read back by the caller.
+hipError_t prk_sel_emit(const uint32_t *start, const prk::SelRun *runs, uint32_t nitems, uint32_t total,
+                        uint32_t dst_first_tri, const prk_xform *xforms, const float *sV, const float *sC,
+                        const float *sN, const float *sUV, float *dV, float *dC, float *dN, float *dUV,
+                        hipStream_t s);
 
 // ---- prk_tex.hip --------------------------------------------------------------
 // prk_texture_from_target: the factor*dw x factor*dh pixels at src (rows spitch bytes apart) box-filtered

@@ -44,6 +44,15 @@ struct ListSrc {
 };
 static_assert(sizeof(ListSrc) == 16);
 
+// prk_geometry_select (prk_select.hip): what k_sel_choose leaves for an item
+// and k_sel_emit reads -- the first source triangle of the chosen level and
+// the item's matrix (a dropped item: zeros, never read).  The items and
+// levels themselves are prk.h's prk_select_item / prk_select_level.
+struct SelRun {
+    uint32_t src0, xform;
+};
+static_assert(sizeof(SelRun) == 8);
+
 // Caller edges (prk_edge = edge_info without Next, prk.h) and spans (prk_span).
 struct EdgeIn {
     int32_t YMax;

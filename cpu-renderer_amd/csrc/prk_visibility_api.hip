@@ -12,11 +12,10 @@
 
 #include "prk_ctx.h"
 
-namespace {
-
 // The frame's answer, reduced if this is the first query since its flush.
 // PRK_ERR_ARG: no such frame (prk_download_winners' precondition, and draws).
-int vis_ready(prk_context *c) {
+// (Hidden, prk_ctx.h: prk_geometry_select reads the frame's pix_prefix too.)
+extern "C" int vis_ready(prk_context *c) {
     RESOLVE_COUNT(c);  // (an overflowed frame is re-run: its winner words land first)
     VisState &V = c->vis;
     if (!c->winners_valid || !V.frame || !c->d_winners.p) return PRK_ERR_ARG;
@@ -49,8 +48,6 @@ int vis_ready(prk_context *c) {
     V.done = true;
     return PRK_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "prk_launch.h"
+#include "prk_xform_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -39,30 +40,11 @@ struct Run {
     uint32_t src0, dst0, xform, start;
 };
 
-// Vertex records of the arrays.  A source geometry may be a caller's device
-// pointers (prk_geometry_wrap_device), of which only float alignment is known.
-struct __attribute__((packed, aligned(4))) V3 {
-    float x, y, z;
-};
-struct __attribute__((packed, aligned(4))) V4u {  // colours of a source
-    float x, y, z, w;
-};
-struct __attribute__((packed, aligned(4))) V2u {  // uvs of a source
-    float x, y;
-};
-
-struct Arrays {
-    const float *sV, *sC, *sN, *sUV;  // source (an absent array: nullptr)
-    float *dV, *dC, *dN, *dUV;        // destination: library-owned (hipMalloc alignment)
-};
-
-__device__ __forceinline__ float row3(const float4 m, float x, float y, float z) {
-    return (m.x * x + m.y * y) + m.z * z;
-}
+using prk::XformArrays;  // the arrays and the per-vertex arithmetic: prk_xform_dev.h
 
 __global__ __launch_bounds__(kThreads) void k_xform(const uint32_t *__restrict__ scan, const Run *__restrict__ runs,
                                                     uint32_t nruns, uint32_t total,
-                                                    const float4 *__restrict__ xforms, const Arrays A) {
+                                                    const float4 *__restrict__ xforms, const XformArrays A) {
     __shared__ uint32_t s_src[kTris], s_dst[kTris], s_xf[kTris];
     const uint32_t tid = threadIdx.x;
     const uint32_t t0 = blockIdx.x * kTris;  // (total <= 2^31: no wrap)
@@ -85,32 +67,7 @@ __global__ __launch_bounds__(kThreads) void k_xform(const uint32_t *__restrict__
     if (t0 + lt >= total) return;
     const size_t sv = (size_t)s_src[lt] * 3u + corner;  // source and destination vertex
     const size_t dv = (size_t)s_dst[lt] * 3u + corner;
-    const float4 *M = xforms + (size_t)s_xf[lt] * 3u;
-    const float4 m0 = M[0], m1 = M[1], m2 = M[2];
-    {
-        const V3 p = reinterpret_cast<const V3 *>(A.sV)[sv];
-        V3 o;
-        o.x = row3(m0, p.x, p.y, p.z) + m0.w;
-        o.y = row3(m1, p.x, p.y, p.z) + m1.w;
-        o.z = row3(m2, p.x, p.y, p.z) + m2.w;
-        reinterpret_cast<V3 *>(A.dV)[dv] = o;
-    }
-    if (A.sN) {
-        const V3 p = reinterpret_cast<const V3 *>(A.sN)[sv];
-        V3 o;
-        o.x = row3(m0, p.x, p.y, p.z);
-        o.y = row3(m1, p.x, p.y, p.z);
-        o.z = row3(m2, p.x, p.y, p.z);
-        reinterpret_cast<V3 *>(A.dN)[dv] = o;
-    }
-    if (A.sC) {
-        const V4u c = reinterpret_cast<const V4u *>(A.sC)[sv];
-        reinterpret_cast<float4 *>(A.dC)[dv] = make_float4(c.x, c.y, c.z, c.w);
-    }
-    if (A.sUV) {
-        const V2u c = reinterpret_cast<const V2u *>(A.sUV)[sv];
-        reinterpret_cast<float2 *>(A.dUV)[dv] = make_float2(c.x, c.y);
-    }
+    prk::xform_vertex(A, sv, dv, xforms + (size_t)s_xf[lt] * 3u);
 }
 
 }  // namespace
@@ -125,7 +82,7 @@ extern "C" hipError_t prk_xform_launch(const void *tables, size_t runs_off, size
                                        hipStream_t s) {
     if (!total || !nruns) return hipSuccess;
     const uint8_t *b = static_cast<const uint8_t *>(tables);
-    const Arrays A{sV, sC, sN, sUV, dV, dC, dN, dUV};
+    const XformArrays A{sV, sC, sN, sUV, dV, dC, dN, dUV};
     const uint32_t blocks = (total + kTris - 1) / kTris;
     hipLaunchKernelGGL(k_xform, dim3(blocks), dim3(kThreads), 0, s, reinterpret_cast<const uint32_t *>(b),
                        reinterpret_cast<const Run *>(b + runs_off), nruns, total,

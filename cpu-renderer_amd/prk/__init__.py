@@ -171,6 +171,7 @@ _SIGS.update({name: (C.c_int, args) for name, args in abi.TEXTURE_TARGET_SIGS.it
 _SIGS.update({name: (C.c_int, args) for name, args in abi.TARGET_LAYER_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.SORT_SELFTEST_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.VISIBILITY_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.SELECT_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
@@ -364,6 +365,47 @@ def selftest_visibility(winners, id_count, device=0):
         C.byref(dmg)))
     return dict(counts=counts, pix_prefix=pix, vis_prefix=vis, ids=ids[:nvis.value], visible=nvis.value,
                 atomics=nat.value, damage=dmg.value)
+
+
+def _select_tables(items, levels, xforms):
+    """(items uint32 [n, 5], levels uint32 [m, 3], xforms float32 [k, 3, 4]) and their typed pointers (None: NULL)."""
+    it = np.ascontiguousarray(items, np.uint32).reshape(-1, 5)
+    lv = None if levels is None else np.ascontiguousarray(levels, np.uint32).reshape(-1, 3)
+    xf = None if xforms is None else np.ascontiguousarray(xforms, np.float32).reshape(-1, 3, 4)
+    ptrs = (C.cast(it.ctypes.data, C.POINTER(abi.PrkSelectItem)) if it.shape[0] else None,
+            None if lv is None else C.cast(lv.ctypes.data, C.POINTER(abi.PrkSelectLevel)),
+            None if xf is None else C.cast(xf.ctypes.data, C.POINTER(abi.PrkXform)))
+    return (it, lv, xf), ptrs
+
+
+def selftest_select(items, levels, xforms, src, dst_tris, dst_first_tri=0, pix_prefix=None, item_pixels=None,
+                    device=0):
+    """prk_selftest_select: prk_geometry_select's stages (choice, scan, emit)
+    on host tables, no context.  items uint32 [n, 5] of (first_id, id_count,
+    first_level, level_count, xform), levels uint32 [m, 3] of (min_pixels,
+    src_first_tri, tri_count), xforms float32 [k, 3, 4]; src: (vertices,
+    colors, normals, uvs), None for an absent array; counts from pix_prefix
+    (uint32 [ids + 1]) or item_pixels (uint32 [n]).  Returns a dict: chosen
+    int32 [n], out_first uint32 [n + 1], total, dst (the dst_tris triangles of
+    every array src has, as uint32 words -- 0xA5A5A5A5 where nothing was
+    written), damage (0 or abi.PRK_DAMAGE_* bits)."""
+    (it, lv, xf), (ip, lp, xp) = _select_tables(items, levels, xforms)
+    n = it.shape[0]
+    pp = None if pix_prefix is None else np.ascontiguousarray(pix_prefix, np.uint32).reshape(-1)
+    px = None if item_pixels is None else np.ascontiguousarray(item_pixels, np.uint32).reshape(-1)
+    assert px is None or px.shape[0] == n
+    arrs = [None if a is None else np.ascontiguousarray(a, np.float32) for a in src]
+    src_tris = 0 if arrs[0] is None else arrs[0].shape[0] // 3
+    out = [None if a is None else np.zeros((3 * int(dst_tris), comp), np.float32)
+           for a, comp in zip(arrs, (3, 4, 3, 2))]
+    chosen, first = np.zeros(n, np.int32), np.zeros(n + 1, np.uint32)
+    total, dmg = C.c_uint64(0), C.c_uint32(0xFFFFFFFF)
+    _check("prk_selftest_select", lib().prk_selftest_select(
+        device, _ptr(pp), 0 if pp is None else pp.shape[0] - 1, ip, n, lp, 0 if lv is None else lv.shape[0], xp,
+        0 if xf is None else xf.shape[0], _ptr(px), *[_ptr(a) for a in arrs], src_tris, int(dst_first_tri),
+        int(dst_tris), *[_ptr(a) for a in out], _ptr(chosen), _ptr(first), C.byref(total), C.byref(dmg)))
+    return dict(chosen=chosen, out_first=first, total=total.value,
+                dst=tuple(None if a is None else a.view(np.uint32) for a in out), damage=dmg.value)
 
 
 def band_rows(height, rank, nranks):
@@ -899,6 +941,34 @@ class Renderer:
         _check("prk_geometry_transform", self._L.prk_geometry_transform(
             self._h, src, dst, C.cast(r.ctypes.data, C.POINTER(abi.PrkXformRun)), r.shape[0],
             C.cast(x.ctypes.data, C.POINTER(abi.PrkXform)), x.shape[0]))
+
+    def geometry_select(self, src, dst, items, levels, xforms, dst_first_tri=0, item_pixels=None):
+        """prk_geometry_select: cull and pick a level of detail on the device.
+        items uint32 [n, 5] of (first_id, id_count, first_level, level_count,
+        xform), levels uint32 [m, 3] of (min_pixels, src_first_tri, tri_count),
+        xforms float32 [k, 3, 4]; item_pixels uint32 [n], or None for the last
+        frame's counts (set_debug(True) at its flush).  The chosen triangles
+        go to dst from dst_first_tri on, packed in item order; the call waits
+        for the total, not for the pass that writes them.  Returns (total,
+        chosen int32 [n], out_first uint32 [n + 1])."""
+        (it, lv, xf), (ip, lp, xp) = _select_tables(items, levels, xforms)
+        n = it.shape[0]
+        px = None if item_pixels is None else np.ascontiguousarray(item_pixels, np.uint32).reshape(-1)
+        if px is not None and px.shape[0] != n:
+            raise ValueError("geometry_select: item_pixels needs a word an item")
+        chosen, first = np.zeros(n, np.int32), np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        _check("prk_geometry_select", self._L.prk_geometry_select(
+            self._h, src, dst, int(dst_first_tri), ip, n, lp, 0 if lv is None else lv.shape[0], xp,
+            0 if xf is None else xf.shape[0], _ptr(px), _ptr(chosen), _ptr(first), C.byref(total)))
+        return total.value, chosen, first
+
+    def select_ms(self):
+        """prk_debug_select_ms: (choose_ms, emit_ms), the device times of the
+        last geometry_select's uploads + choice + scan and of its emit pass."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        _check("prk_debug_select_ms", self._L.prk_debug_select_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def geometry_download(self, geom, first_tri=0, tri_count=None, arrays=(True, True, True, True)):
         """prk_geometry_download of triangles [first_tri, first_tri +

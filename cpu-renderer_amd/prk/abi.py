@@ -122,6 +122,32 @@ GEOMETRY_TRANSFORM_SIGS = {
     "prk_debug_transform_ms": [C.c_void_p, C.c_void_p],
 }
 
+class PrkSelectLevel(C.Structure):
+    """prk_select_level: source triangles [src_first_tri, +tri_count), chosen
+    when the item's pixel count is at least min_pixels."""
+    _fields_ = [("min_pixels", C.c_uint32), ("src_first_tri", C.c_uint32), ("tri_count", C.c_uint32)]
+
+
+class PrkSelectItem(C.Structure):
+    """prk_select_item: the item's ids [first_id, +id_count) of the frame, its
+    levels [first_level, +level_count) of the call's table, its matrix."""
+    _fields_ = [("first_id", C.c_uint32), ("id_count", C.c_uint32), ("first_level", C.c_uint32),
+                ("level_count", C.c_uint32), ("xform", C.c_uint32)]
+
+
+# Cull and pick a level of detail on the device (prk.h): each entry point and its argument types
+SELECT_SIGS = {
+    "prk_geometry_select": [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(PrkSelectItem), C.c_uint32,
+                            C.POINTER(PrkSelectLevel), C.c_uint32, C.POINTER(PrkXform), C.c_uint32, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)],
+    "prk_selftest_select": [C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(PrkSelectItem), C.c_uint32,
+                            C.POINTER(PrkSelectLevel), C.c_uint32, C.POINTER(PrkXform), C.c_uint32, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)],
+    "prk_debug_select_ms": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+}
+
 # Render to texture (prk.h): each entry point and its argument types
 TEXTURE_TARGET_SIGS = {
     "prk_texture_alloc": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],

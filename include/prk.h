@@ -566,6 +566,87 @@ int prk_debug_geometry_stream(prk_context *ctx, void **stream);
  * for it.  PRK_ERR_ARG before any transform. */
 int prk_debug_transform_ms(prk_context *ctx, float *kernel_ms);
 
+/* Cull and pick a level of detail on the device.  An EXTENSION of this build
+ * with its own definition: it acts on prk_visibility_*'s
+ * counts without moving them to the host.  For every ITEM (an object, a group
+ * of them) the call decides on the device whether the item is drawn and from
+ * which of its LEVELS (meshes of the source geometry, finest first as a rule),
+ * and writes the chosen triangles, packed in item order and transformed, into
+ * dst.  One word comes back before the draw: the triangle total.  The library
+ * still decides nothing on its own: thresholds and tables are the caller's.
+ *
+ * pixels(i): with item_pixels, item_pixels[i] -- no frame is needed, first_id
+ *   and id_count are ignored.  Without (NULL), the sum of the frame's
+ *   pixels[id] over ids [first_id, first_id + id_count): THE FRAME is
+ *   prk_visibility_*'s, with the same "no such frame" rule; the sum is a
+ *   difference of two pix_prefix words (it fits in 32 bits); id_count == 0
+ *   gives 0.
+ * chosen(i): the smallest l in [0, item.level_count) with
+ *   pixels(i) >= levels[item.first_level + l].min_pixels; -1 when no level
+ *   passes or the item has no levels.  Nothing is assumed about the order of
+ *   the thresholds: the first level that passes wins.  min_pixels == 0 always
+ *   passes: an always-drawn item (a new object, the occluders) has one level
+ *   with min_pixels == 0.
+ * n(i): the chosen level's tri_count, or 0.
+ * out_first[i] = dst_first_tri + n(0) + ... + n(i - 1); out_first[item_count]
+ *   is the end; *total_tris_out = the sum of the n(i).
+ * Triangles [out_first[i], out_first[i] + n(i)) of dst are source triangles
+ *   [level.src_first_tri, +n(i)) through xforms[item.xform], in exactly
+ *   prk_geometry_transform's arithmetic (the same expression order, nothing
+ *   fused, colours and uvs copied bit for bit).  When the total is not 0, dst
+ *   grows and receives the arrays src has by prk_geometry_transform's rule,
+ *   and its vertex count becomes max(old, 3 * end); triangles outside
+ *   [dst_first_tri, end) keep their contents.  A call that chooses nothing
+ *   (total 0) writes nothing and leaves dst as it was.
+ *
+ * Ordering: the choice and the scan run at the call, on the geometry stream,
+ * and the call waits for them -- it needs the total to size dst and the grid,
+ * and returns it.  The emit pass is queued as prk_geometry_transform's pass
+ * is: after the frames already flushed have read dst, before the next
+ * prk_flush's kernels read it; the call does not wait for it.  All tables are
+ * copied at the call.  src is read where the emit pass stands in that order.
+ *
+ * Errors are decided on the host from the arguments and from worst cases; no
+ * status depends on what the device chose, and on any error nothing is
+ * written.  PRK_ERR_ARG: a NULL context or total_tris_out; a bad handle,
+ * src == dst, a wrapped dst; item_count > 0 with NULL items; NULL levels or
+ * xforms where an item has levels; an item's first_level + level_count past
+ * level_count; xform >= xform_count on an item that has levels; a level of a
+ * listed item (with tri_count > 0) whose source range passes the end of src;
+ * without item_pixels, no frame, or an item's first_id + id_count past the
+ * frame's id_count; a worst-case end -- dst_first_tri plus every item's
+ * largest level -- past prk_geometry_write's vertex limit.  PRK_ERR_LIMIT: a
+ * worst-case total above 2^31 (checked before the vertex limit, which such a
+ * total always passes).  item_count == 0: PRK_OK, total 0, out_first[0] =
+ * dst_first_tri.
+ *
+ * Ids after a compacted draw: after prk_draw(dst, dst_first_tri, total, ...)
+ * as the frame's first draw, item i's ids next frame are
+ * [out_first[i] - dst_first_tri, +n(i)).  A dropped item has no ids; it comes
+ * back only if the caller gives it a level with min_pixels == 0 again -- the
+ * caller's policy, every k-th frame for instance.
+ * Band contexts: a band context's frame counts cover its own rows only; ranks
+ * that must draw the same geometry pass the summed counts as item_pixels.
+ *
+ * chosen: item_count words or NULL; out_first: item_count + 1 words or NULL. */
+typedef struct prk_select_level {
+    uint32_t min_pixels, src_first_tri, tri_count;
+} prk_select_level;
+typedef struct prk_select_item {
+    uint32_t first_id, id_count, first_level, level_count, xform; /* xform: index into the call's xforms */
+} prk_select_item;
+int prk_geometry_select(prk_context *ctx, int32_t src, int32_t dst, uint32_t dst_first_tri,
+                        const prk_select_item *items, uint32_t item_count,
+                        const prk_select_level *levels, uint32_t level_count,
+                        const prk_xform *xforms, uint32_t xform_count,
+                        const uint32_t *item_pixels, int32_t *chosen, uint32_t *out_first,
+                        uint64_t *total_tris_out);
+/* Debug/bench: the device times of the most recent prk_geometry_select that
+ * reached the device -- choose_ms from before its table uploads to the copy of
+ * the total (uploads, choice, scan), emit_ms its emit pass alone (0 when the
+ * total was 0); waits for the pass.  PRK_ERR_ARG before any such call. */
+int prk_debug_select_ms(prk_context *ctx, float *choose_ms, float *emit_ms);
+
 /* Record one draw: triangles [first_tri, first_tri+tri_count) of a geometry,
  * object offset P (render_entry_3d_object::P), semantics PRK_SEM_*,
  * PhongShading flag, texture handle (-1 = no Bitmap).
@@ -880,6 +961,32 @@ int prk_selftest_scan(int32_t device, int32_t width, uint32_t n, const void *in,
 int prk_selftest_visibility(int32_t device, uint32_t n, const int32_t *winners, uint32_t id_count,
                             uint32_t *counts, uint32_t *pix_prefix, uint32_t *vis_prefix, uint32_t *ids,
                             uint32_t *visible_out, uint64_t *atomics_out, uint32_t *damage);
+/* Test: prk_geometry_select's three stages (csrc/prk_select.hip: the choice,
+ * the scan, the emit pass) on host-supplied inputs, synchronously on `device`,
+ * no context needed, guarded and compared as above.  pix_prefix: id_count + 1
+ * words, read when item_pixels is NULL (else it may be NULL).  The source is
+ * src_tris triangles of the arrays given (src_vertices required when any
+ * level has triangles; the others may be NULL).  The destination is dst_tris
+ * triangles of every array the source has, on the device pre-filled with the
+ * guard pattern (bytes of 0xA5) and returned whole: the words outside
+ * [dst_first_tri, dst_first_tri + total) come back as that pattern.  A dst_*
+ * pointer is required where the source has the array and ignored where not.
+ * chosen: item_count words; out_first: item_count + 1 words.  *damage: an
+ * input (a table, pix_prefix, item_pixels, a source array) changed or its
+ * guard did; the guard after chosen, the scan's output or a destination array
+ * changed; the guard after the counts, the runs or the scan's scratch changed.
+ * PRK_ERR_ARG: a NULL required pointer, a bad device, prk_geometry_select's
+ * table errors (with id_count as the frame's), a worst-case end past dst_tris.
+ * PRK_ERR_LIMIT as there.  tests/test_gpu_select.py holds every word to
+ * tests/selectref.py, *damage == 0. */
+int prk_selftest_select(int32_t device, const uint32_t *pix_prefix, uint32_t id_count,
+                        const prk_select_item *items, uint32_t item_count,
+                        const prk_select_level *levels, uint32_t level_count,
+                        const prk_xform *xforms, uint32_t xform_count, const uint32_t *item_pixels,
+                        const float *src_vertices, const float *src_colors, const float *src_normals,
+                        const float *src_uvs, uint32_t src_tris, uint32_t dst_first_tri, uint32_t dst_tris,
+                        float *dst_vertices, float *dst_colors, float *dst_normals, float *dst_uvs,
+                        int32_t *chosen, uint32_t *out_first, uint64_t *total_tris_out, uint32_t *damage);
 
 /* The bound target (any pointer may be NULL) and the context's device and
  * own stream (a hipStream_t; prk_flush(ctx, NULL) runs on it). */
