@@ -357,7 +357,7 @@ int prk_selftest_select(int32_t device, const uint32_t *pix_prefix, uint32_t id_
     PRK_TRY(temp.fill(tb, nullptr));
     PRK_TRY(prk_sel_choose((const prk_select_item *)itm.p, item_count, (const prk_select_level *)lev.p,
                            item_pixels ? nullptr : (const uint32_t *)pix.p,
-                           item_pixels ? (const uint32_t *)ipx.p : nullptr, (int32_t *)cho.p, (uint32_t *)cnt.p,
+                           item_pixels ? (const uint32_t *)ipx.p : nullptr, nullptr, (int32_t *)cho.p, (uint32_t *)cnt.p,
                            (prk::SelRun *)run.p, nullptr));
     PRK_TRY(prk_scan_u32((const uint32_t *)cnt.p, (uint32_t *)sta.p, item_count + 1, temp.p, &tb, nullptr));
     uint32_t total = 0;
@@ -391,6 +391,49 @@ int prk_selftest_select(int32_t device, const uint32_t *pix_prefix, uint32_t id_
     for (int k = 0; k < 4; ++k)
         if (src[k] && da[k].bytes) std::memcpy(dst[k], da[k].host.data(), da[k].bytes);
     *total_tris_out = total;
+    return PRK_OK;
+}
+
+// prk_visibility_bounds' two kernels on the caller's z words and tables
+// (prk.h): the launchers the call itself queues, with no context, every device
+// buffer guarded, the z words z_offset floats into their buffer.
+int prk_selftest_bounds(int32_t device, const float *z, int32_t width, int32_t height, int32_t row0, int32_t row1,
+                        uint32_t z_offset, const prk_transform *transform, const float P[3], const prk_bound *bounds,
+                        uint32_t count, const prk_xform *xforms, uint32_t xform_count, float *zmin, uint32_t *pixels,
+                        uint32_t *damage) {
+    if (device < 0 || !z || !transform || !zmin || !damage || (count && (!bounds || !xforms || !pixels)) ||
+        width <= 0 || height <= 0 || row0 < 0 || row1 > height || row0 >= row1 || z_offset > 1024)
+        return PRK_ERR_ARG;
+    for (uint32_t i = 0; i < count; ++i)
+        if (bounds[i].xform >= xform_count) return PRK_ERR_ARG;
+    prk::BoundsFrame B;
+    if (!bounds_frame(width, row0, row1, *transform, P, &B)) return PRK_ERR_LIMIT;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device >= ndev) return PRK_ERR_ARG;
+    PRK_TRY(hipSetDevice(device));
+    const size_t npx = (size_t)width * (size_t)(row1 - row0), nt = (size_t)B.tiles_x * (size_t)B.tiles_y;
+    std::vector<float> zin(z_offset + npx, 0.0f);
+    std::memcpy(zin.data() + z_offset, z, npx * 4);
+    GuardedBuf zb, xfm, bnd, zmn, pix;
+    PRK_TRY(zb.fill(zin.size() * 4, zin.data()));
+    PRK_TRY(xfm.fill(count ? (size_t)xform_count * sizeof(prk_xform) : 0, xforms));
+    PRK_TRY(bnd.fill((size_t)count * sizeof(prk_bound), bounds));
+    PRK_TRY(zmn.fill(nt * 4, nullptr));
+    PRK_TRY(pix.fill((size_t)count * 4, nullptr));
+    PRK_TRY(prk_ztile_min((const float *)zb.p + z_offset, &B, (float *)zmn.p, nullptr));
+    PRK_TRY(prk_bounds_test((const prk_bound *)bnd.p, count, (const prk_xform *)xfm.p, &B, (const float *)zmn.p,
+                            (uint32_t *)pix.p, nullptr));
+    PRK_TRY(hipDeviceSynchronize());
+    GuardedBuf *all[] = {&zb, &xfm, &bnd, &zmn, &pix};
+    for (GuardedBuf *b : all) PRK_TRY(b->read());
+    *damage = (zb.holds(zin.data()) && zb.guard_intact() && xfm.holds(xforms) && xfm.guard_intact() &&
+                       bnd.holds(bounds) && bnd.guard_intact()
+                   ? 0u
+                   : PRK_DAMAGE_INPUT) |
+              (zmn.guard_intact() && pix.guard_intact() ? 0u : PRK_DAMAGE_OUTPUT_GUARD);
+    std::memcpy(zmin, zmn.host.data(), nt * 4);
+    if (count) std::memcpy(pixels, pix.host.data(), (size_t)count * 4);
     return PRK_OK;
 }
 
@@ -483,8 +526,10 @@ int prk_destroy(prk_context *c) {
     DevBuf *bufs[] = {&c->d_winners, &c->d_anomaly, &c->d_prof, &c->d_negz, &c->d_xform,
                       &c->vis.d_counts, &c->vis.d_flags, &c->vis.d_pix, &c->vis.d_vis, &c->vis.d_ids,
                       &c->vis.d_temp, &c->vis.d_starts, &c->vis.d_gout, &c->sel.d_tab, &c->sel.d_out,
-                      &c->sel.d_temp};
+                      &c->sel.d_temp, &c->bnd.d_zmin, &c->bnd.d_tab, &c->bnd.d_pixels};
     for (DevBuf *b : bufs) b->release();
+    for (hipEvent_t e : c->bnd.ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->h_xform) (void)hipHostFree(c->h_xform);
     if (c->xf_ev) (void)hipEventDestroy(c->xf_ev);
     if (c->xf_end_ev) (void)hipEventDestroy(c->xf_end_ev);
@@ -557,6 +602,7 @@ int prk_target_bind(prk_context *c, void *color, int32_t pitch_bytes, float *zbu
     c->row0 = row0;
     c->row1 = row1;
     c->winners_valid = false;
+    c->bnd.answered = false;  // (prk_visibility_bounds' answer was the old target's)
     return PRK_OK;
 }
 
@@ -585,6 +631,7 @@ int prk_target_alloc(prk_context *c, int32_t width, int32_t height, int32_t row0
     c->row1 = row1;
     c->owns_target = true;
     c->winners_valid = false;
+    c->bnd.answered = false;
     if (color_out) *color_out = col;
     if (zbuf_out) *zbuf_out = z;
     return PRK_OK;

@@ -2,7 +2,7 @@
 // include/prk.h) with the resources and scratch it owns, the state a pass is
 // queued with, and the few host functions that cross the host files
 // (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip,
-// prk_visibility_api.hip, prk_select_api.hip).  Host
+// prk_visibility_api.hip, prk_select_api.hip, prk_bounds_api.hip).  Host
 // only; prk_launch.h stays the seam to the kernel files (prk_types.h: the
 // records the buffers here hold), and prk_dist.hip keeps the context opaque.
 //
@@ -175,6 +175,18 @@ struct SelState {
     bool timed = false, emitted = false;
 };
 
+// prk_visibility_bounds (prk_bounds_api.hip): the target's min-z tile map,
+// rebuilt at every call (it belongs to the target, not to a frame's winner
+// map), the call's tables as uploaded, and the answer -- `count` words that
+// stay valid until the next call or until the target is replaced.
+struct BoundsState {
+    DevBuf d_zmin, d_tab, d_pixels;
+    hipEvent_t ev[3] = {};  // (timed: prk_debug_bounds_ms) before k_ztile_min, between the kernels, after k_bounds_test
+    bool answered = false, timed = false, tested = false;  // tested: the timed call ran k_bounds_test (count > 0)
+    uint32_t count = 0;
+    int32_t tiles_x = 0, tiles_y = 0, first_tile_row = 0;  // the map of the last call (prk_debug_ztiles)
+};
+
 // The state a pass is queued with and an overflow re-run (resolve_count)
 // runs with again: the target, the tile, the cameras and lights, the clear.
 // The context holds its own as its base (prk_context), so this is the one
@@ -300,6 +312,7 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     bool winners_valid = false;
     VisState vis;
     SelState sel;
+    BoundsState bnd;
     prk_stats stats{};
     // Timing ring: 6 events per flush.
     static constexpr int kRing = 32;
@@ -419,6 +432,9 @@ PRK_HIDDEN int vis_ready(prk_context *c);
 PRK_HIDDEN int select_check(const prk_select_item *items, uint32_t item_count, const prk_select_level *levels,
                             uint32_t level_count, const prk_xform *xforms, uint32_t xform_count, uint32_t src_tris,
                             const uint32_t *frame_ids, uint64_t *worst);
+// prk_bounds_api.hip: prk_visibility_bounds' band and camera record (false: a band of 2^32 pixels or more).
+PRK_HIDDEN bool bounds_frame(int32_t W, int32_t row0, int32_t row1, const prk_transform &t, const float P[3],
+                             prk::BoundsFrame *out);
 }  // extern "C"
 
 // Calls that read or replace the target, or change what a re-run of the

@@ -22,6 +22,7 @@ struct prk_context;  // include/prk.h
 struct prk_select_item;   // ... and its plain records that a kernel file reads as they are
 struct prk_select_level;
 struct prk_xform;
+struct prk_bound;
 
 namespace prk {
 struct FrameParams;  // prk_device.h
@@ -141,9 +142,10 @@ hipError_t prk_xform_launch(const void *tables, size_t runs_off, size_t xf_off, 
 // the difference of two pix_prefix words), the first of its levels that the count passes, and from it chosen[i]
 // (the level, or -1), n[i] (its triangles, or 0) and runs[i].  n has nitems + 1 words, the last written 0: the
 // scan's input, whose last output word is the total.
+// bound_pixels (prk_geometry_select_bounds; else nullptr): an item with id_count == 0 takes bound_pixels[i].
 hipError_t prk_sel_choose(const prk_select_item *items, uint32_t nitems, const prk_select_level *levels,
-                          const uint32_t *pix_prefix, const uint32_t *item_pixels, int32_t *chosen, uint32_t *n,
-                          prk::SelRun *runs, hipStream_t s);
+                          const uint32_t *pix_prefix, const uint32_t *item_pixels, const uint32_t *bound_pixels,
+                          int32_t *chosen, uint32_t *n, prk::SelRun *runs, hipStream_t s);
 // Stage 3 (stage 2 is prk_scan_u32 of n into start): output triangle t of [0, total) belongs to the last item i
 // with start[i] <= t; source triangle runs[i].src0 + (t - start[i]) goes through xforms[runs[i].xform] to
 // destination triangle dst_first_tri + t.  total = start[nitems], read back by the caller.
@@ -151,6 +153,16 @@ hipError_t prk_sel_emit(const uint32_t *start, const prk::SelRun *runs, uint32_t
                         uint32_t dst_first_tri, const prk_xform *xforms, const float *sV, const float *sC,
                         const float *sN, const float *sUV, float *dV, float *dC, float *dN, float *dUV,
                         hipStream_t s);
+
+// ---- prk_bounds.hip -----------------------------------------------------------
+// prk_visibility_bounds, stage 1: zmin[tiles_y][tiles_x] of the band B describes (z: its first pixel, rows W
+// floats apart, 4-byte aligned) -- per 8 x 8 tile the smallest non-NaN z word, +inf without one.
+// hipErrorInvalidValue when B's tile counts are not the band's.
+hipError_t prk_ztile_min(const float *z, const prk::BoundsFrame *B, float *zmin, hipStream_t s);
+// Stage 2: pixels[i] of the `count` boxes against zmin, under B's camera and P (xforms: 16-byte aligned; every
+// bounds[i].xform inside it -- the host's check).
+hipError_t prk_bounds_test(const prk_bound *bounds, uint32_t count, const prk_xform *xforms,
+                           const prk::BoundsFrame *B, const float *zmin, uint32_t *pixels, hipStream_t s);
 
 // ---- prk_tex.hip --------------------------------------------------------------
 // prk_texture_from_target: the factor*dw x factor*dh pixels at src (rows spitch bytes apart) box-filtered

@@ -6,7 +6,9 @@
 // resident destination geometry.  No table goes back to the host in between.
 //
 //   k_sel_choose   one thread an item: pixels(i) = item_pixels[i], or the
-//                  difference of two pix_prefix words; the first of the item's
+//                  difference of two pix_prefix words, or (with bound_pixels,
+//                  prk_geometry_select_bounds) bound_pixels[i] for an item
+//                  without ids; the first of the item's
 //                  levels with pixels(i) >= min_pixels wins (no order of the
 //                  thresholds is assumed); chosen[i], n[i] and the item's run
 //                  (first source triangle, matrix) are written.  Thread
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(kChooseThreads) void k_sel_choose(const prk_select_
                                                                const prk_select_level *__restrict__ levels,
                                                                const uint32_t *__restrict__ pix_prefix,
                                                                const uint32_t *__restrict__ item_pixels,
+                                                               const uint32_t *__restrict__ bound_pixels,
                                                                int32_t *__restrict__ chosen, uint32_t *__restrict__ n,
                                                                SelRun *__restrict__ runs) {
     const uint64_t i = (uint64_t)blockIdx.x * kChooseThreads + threadIdx.x;
@@ -58,8 +61,10 @@ __global__ __launch_bounds__(kChooseThreads) void k_sel_choose(const prk_select_
     }
     const prk_select_item it = items[i];
     // (the host has checked first_id + id_count against the frame's ids: no wrap, both words inside)
-    const uint32_t pixels =
-        item_pixels ? item_pixels[i] : pix_prefix[it.first_id + it.id_count] - pix_prefix[it.first_id];
+    // (with bound_pixels an item without ids reads no pix_prefix word: there may be no frame)
+    const uint32_t pixels = item_pixels                           ? item_pixels[i]
+                            : (bound_pixels && it.id_count == 0u) ? bound_pixels[i]
+                                                                  : pix_prefix[it.first_id + it.id_count] - pix_prefix[it.first_id];
     int32_t pick = -1;
     uint32_t cnt = 0, src0 = 0;
     for (uint32_t l = 0; l < it.level_count; ++l) {
@@ -108,12 +113,12 @@ __global__ __launch_bounds__(kThreads) void k_sel_emit(const uint32_t *__restric
 extern "C" {
 
 hipError_t prk_sel_choose(const prk_select_item *items, uint32_t nitems, const prk_select_level *levels,
-                          const uint32_t *pix_prefix, const uint32_t *item_pixels, int32_t *chosen, uint32_t *n,
-                          prk::SelRun *runs, hipStream_t s) {
+                          const uint32_t *pix_prefix, const uint32_t *item_pixels, const uint32_t *bound_pixels,
+                          int32_t *chosen, uint32_t *n, prk::SelRun *runs, hipStream_t s) {
     if (nitems == UINT32_MAX) return hipErrorInvalidValue;  // (nitems + 1 words)
     const uint32_t blocks = (uint32_t)(((uint64_t)nitems + 1 + kChooseThreads - 1) / kChooseThreads);
     hipLaunchKernelGGL(k_sel_choose, dim3(blocks), dim3(kChooseThreads), 0, s, items, nitems, levels, pix_prefix,
-                       item_pixels, chosen, n, runs);
+                       item_pixels, bound_pixels, chosen, n, runs);
     return hipGetLastError();
 }
 

@@ -44,17 +44,29 @@ int select_check(const prk_select_item *items, uint32_t item_count, const prk_se
     return PRK_OK;
 }
 
-int prk_geometry_select(prk_context *c, int32_t src, int32_t dst, uint32_t dst_first_tri, const prk_select_item *items,
-                        uint32_t item_count, const prk_select_level *levels, uint32_t level_count,
-                        const prk_xform *xforms, uint32_t xform_count, const uint32_t *item_pixels, int32_t *chosen,
-                        uint32_t *out_first, uint64_t *total_tris_out) {
+}  // extern "C"
+
+// The body of prk_geometry_select and prk_geometry_select_bounds.  `bounds`:
+// the second call -- no item_pixels, an item without ids takes its word of the
+// last prk_visibility_bounds' answer (which must be there, item_count words),
+// and the frame is needed only where some item has ids.
+static int select_body(prk_context *c, int32_t src, int32_t dst, uint32_t dst_first_tri, const prk_select_item *items,
+                       uint32_t item_count, const prk_select_level *levels, uint32_t level_count,
+                       const prk_xform *xforms, uint32_t xform_count, const uint32_t *item_pixels, bool bounds,
+                       int32_t *chosen, uint32_t *out_first, uint64_t *total_tris_out) {
     if (!c || !total_tris_out || (item_count && !items)) return PRK_ERR_ARG;
     if (src < 0 || (size_t)src >= c->geoms.size() || dst < 0 || (size_t)dst >= c->geoms.size() || src == dst)
         return PRK_ERR_ARG;
     if (!c->geoms[dst].owned) return PRK_ERR_ARG;
+    if (bounds && (!c->bnd.answered || c->bnd.count != item_count)) return PRK_ERR_ARG;
     const uint32_t src_tris = c->geoms[src].vertex_count / 3;
     uint32_t frame_ids = 0;
-    if (!item_pixels) {  // the frame's counts: there must be a frame (reduced here if no query has yet)
+    bool frame = !item_pixels;
+    if (bounds) {
+        frame = false;
+        for (uint32_t i = 0; i < item_count && !frame; ++i) frame = items[i].id_count != 0;
+    }
+    if (frame) {  // the frame's counts: there must be a frame (reduced here if no query has yet)
         const int rc = vis_ready(c);
         if (rc != PRK_OK) return rc;
         frame_ids = c->vis.id_count;
@@ -62,7 +74,7 @@ int prk_geometry_select(prk_context *c, int32_t src, int32_t dst, uint32_t dst_f
     uint64_t worst = 0;
     {
         const int rc = select_check(items, item_count, levels, level_count, xforms, xform_count, src_tris,
-                                    item_pixels ? nullptr : &frame_ids, &worst);
+                                    frame ? &frame_ids : nullptr, &worst);
         if (rc != PRK_OK) return rc;
     }
     if (worst && !c->geoms[src].V) return PRK_ERR_ARG;  // (a geometry written without positions)
@@ -110,8 +122,9 @@ int prk_geometry_select(prk_context *c, int32_t src, int32_t dst, uint32_t dst_f
     if (levels && lb) PRK_TRY(hipMemcpyAsync(tab + lev_off, levels, lb, hipMemcpyHostToDevice, s));
     if (xforms && xb) PRK_TRY(hipMemcpyAsync(tab + xf_off, xforms, xb, hipMemcpyHostToDevice, s));
     if (pb) PRK_TRY(hipMemcpyAsync(tab + px_off, item_pixels, pb, hipMemcpyHostToDevice, s));
-    PRK_TRY(prk_sel_choose(d_items, item_count, d_levels, item_pixels ? nullptr : c->vis.d_pix.as<uint32_t>(), d_px,
-                           d_chosen, d_n, d_runs, s));
+    // (the bounds answer was complete when its call returned: no stream has to wait for it)
+    PRK_TRY(prk_sel_choose(d_items, item_count, d_levels, frame ? c->vis.d_pix.as<uint32_t>() : nullptr, d_px,
+                           bounds ? c->bnd.d_pixels.as<uint32_t>() : nullptr, d_chosen, d_n, d_runs, s));
     PRK_TRY(prk_scan_u32(d_n, d_start, item_count + 1, S.d_temp.p, &tb, s));
     uint32_t total = 0;
     PRK_TRY(hipMemcpyAsync(&total, d_start + item_count, 4, hipMemcpyDeviceToHost, s));
@@ -149,6 +162,24 @@ int prk_geometry_select(prk_context *c, int32_t src, int32_t dst, uint32_t dst_f
     }
     *total_tris_out = total;
     return PRK_OK;
+}
+
+extern "C" {
+
+int prk_geometry_select(prk_context *c, int32_t src, int32_t dst, uint32_t dst_first_tri, const prk_select_item *items,
+                        uint32_t item_count, const prk_select_level *levels, uint32_t level_count,
+                        const prk_xform *xforms, uint32_t xform_count, const uint32_t *item_pixels, int32_t *chosen,
+                        uint32_t *out_first, uint64_t *total_tris_out) {
+    return select_body(c, src, dst, dst_first_tri, items, item_count, levels, level_count, xforms, xform_count,
+                       item_pixels, false, chosen, out_first, total_tris_out);
+}
+
+int prk_geometry_select_bounds(prk_context *c, int32_t src, int32_t dst, uint32_t dst_first_tri,
+                               const prk_select_item *items, uint32_t item_count, const prk_select_level *levels,
+                               uint32_t level_count, const prk_xform *xforms, uint32_t xform_count, int32_t *chosen,
+                               uint32_t *out_first, uint64_t *total_tris_out) {
+    return select_body(c, src, dst, dst_first_tri, items, item_count, levels, level_count, xforms, xform_count,
+                       nullptr, true, chosen, out_first, total_tris_out);
 }
 
 int prk_debug_select_ms(prk_context *c, float *choose_ms, float *emit_ms) {

@@ -53,6 +53,18 @@ struct SelRun {
 };
 static_assert(sizeof(SelRun) == 8);
 
+// prk_visibility_bounds (prk_bounds.hip): the band both kernels work on, its
+// 8 x 8 z tiles, and what the test kernel projects with -- prk_set_camera's
+// transform and the call's P, as the host fills them.
+struct BoundsFrame {
+    int32_t W, row0, row1;       // the band: rows [row0, row1) of W pixels, z rows W floats apart
+    int32_t tiles_x, tiles_y;    // (W + 7) / 8, and the tile rows that meet the band
+    int32_t first_tile_row;      // row0 / 8: zmin's first row
+    float D, F, M2P, Cx, Cy;     // ProjectVertex's constants
+    float P[3];
+};
+static_assert(sizeof(BoundsFrame) == 56);
+
 // Caller edges (prk_edge = edge_info without Next, prk.h) and spans (prk_span).
 struct EdgeIn {
     int32_t YMax;

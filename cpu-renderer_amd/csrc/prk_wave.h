@@ -20,6 +20,10 @@ __device__ __forceinline__ float dpp_f(float old, float v) {
 }
 constexpr int kDppShr1 = 0x111, kDppShr2 = 0x112, kDppShr4 = 0x114, kDppShr8 = 0x118;
 constexpr int kDppBcast15 = 0x142, kDppBcast31 = 0x143;
+// Exchanges inside groups of 8 lanes (every lane has a source): quad_perm
+// [1,0,3,2] and [2,3,0,1] swap neighbours and pairs, row_half_mirror reverses
+// the 8 -- after the three, a commutative fold has reached all 8 lanes.
+constexpr int kDppSwap1 = 0xB1, kDppSwap2 = 0x4E, kDppHalfMirror = 0x141;
 __device__ __forceinline__ int32_t wave_incl_sum_i32(int32_t v) {
     v += dpp_i<kDppShr1>(0, v);
     v += dpp_i<kDppShr2>(0, v);

@@ -172,6 +172,7 @@ _SIGS.update({name: (C.c_int, args) for name, args in abi.TARGET_LAYER_SIGS.item
 _SIGS.update({name: (C.c_int, args) for name, args in abi.SORT_SELFTEST_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.VISIBILITY_SIGS.items()})
 _SIGS.update({name: (C.c_int, args) for name, args in abi.SELECT_SIGS.items()})
+_SIGS.update({name: (C.c_int, args) for name, args in abi.BOUNDS_SIGS.items()})
 
 COMM_ID_BYTES = 128  # PRK_COMM_ID_BYTES
 
@@ -406,6 +407,49 @@ def selftest_select(items, levels, xforms, src, dst_tris, dst_first_tri=0, pix_p
         int(dst_tris), *[_ptr(a) for a in out], _ptr(chosen), _ptr(first), C.byref(total), C.byref(dmg)))
     return dict(chosen=chosen, out_first=first, total=total.value,
                 dst=tuple(None if a is None else a.view(np.uint32) for a in out), damage=dmg.value)
+
+
+def _bound_tables(bounds, xforms):
+    """(bounds as float32 [n, 7] rows of lo[3], hi[3] and the xform index as a
+    uint32 word, xforms float32 [k, 3, 4]) and their typed pointers (None: NULL)."""
+    b = np.ascontiguousarray(bounds, np.float32).reshape(-1, 7)
+    xf = None if xforms is None else np.ascontiguousarray(xforms, np.float32).reshape(-1, 3, 4)
+    return (b, xf), (C.cast(b.ctypes.data, C.POINTER(abi.PrkBound)) if b.shape[0] else None,
+                     None if xf is None else C.cast(xf.ctypes.data, C.POINTER(abi.PrkXform)))
+
+
+def pack_bounds(lo, hi, xform):
+    """prk_bound records as float32 [n, 7]: lo, hi float [n, 3], xform the
+    matrix index of each (stored as a uint32 word in the last column)."""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    out = np.zeros((lo.shape[0], 7), np.float32)
+    out[:, 0:3] = lo
+    out[:, 3:6] = np.asarray(hi, np.float32).reshape(-1, 3)
+    out.view(np.uint32)[:, 6] = np.broadcast_to(np.asarray(xform, np.uint32), (lo.shape[0],))
+    return out
+
+
+def selftest_bounds(z, row0, height, transform, bounds, xforms, P=None, z_offset=0, device=0):
+    """prk_selftest_bounds: prk_visibility_bounds' two kernels on host inputs,
+    no context.  z float32 [row1 - row0, W] (the band of a W x height frame
+    from row0 on), placed z_offset floats into its device buffer; transform an
+    abi.PrkTransform; bounds from pack_bounds; xforms float32 [k, 3, 4].
+    Returns a dict: zmin float32 [tiles_y, tiles_x], pixels uint32 [n], damage
+    (0 or abi.PRK_DAMAGE_* bits)."""
+    zz = np.ascontiguousarray(z, np.float32)
+    rows, W = zz.shape
+    row1 = int(row0) + rows
+    (b, xf), (bp, xp) = _bound_tables(bounds, xforms)
+    n = b.shape[0]
+    zmin = np.zeros(((row1 + 7) // 8 - int(row0) // 8, (W + 7) // 8), np.float32)
+    pix = np.zeros(n, np.uint32)
+    Pc = None if P is None else (C.c_float * 3)(*P)
+    dmg = C.c_uint32(0xFFFFFFFF)
+    _check("prk_selftest_bounds", lib().prk_selftest_bounds(
+        device, _ptr(zz), W, int(height), int(row0), row1, int(z_offset), C.byref(transform),
+        None if Pc is None else C.cast(Pc, C.c_void_p), bp, n, xp, 0 if xf is None else xf.shape[0], _ptr(zmin),
+        _ptr(pix), C.byref(dmg)))
+    return dict(zmin=zmin, pixels=pix, damage=dmg.value)
 
 
 def band_rows(height, rank, nranks):
@@ -769,6 +813,59 @@ class Renderer:
         cp, pp, n = C.c_void_p(), C.c_void_p(), C.c_uint32(0)
         _check("prk_visibility_device", self._L.prk_visibility_device(self._h, C.byref(cp), C.byref(pp), C.byref(n)))
         return cp.value or 0, pp.value or 0, n.value
+
+    # ---- bounds occlusion test ---------------------------------------------
+    def visibility_bounds(self, bounds, xforms, P=None):
+        """prk_visibility_bounds: uint32 [n], for every box (pack_bounds rows;
+        xforms float32 [k, 3, 4]) an upper bound on the pixels anything inside
+        it could win over the z the target holds now -- 0: it cannot be seen.
+        Rebuilds the target's min-z tile map, tests on the device, waits."""
+        (b, xf), (bp, xp) = _bound_tables(bounds, xforms)
+        out = np.zeros(b.shape[0], np.uint32)
+        Pc = None if P is None else (C.c_float * 3)(*P)
+        _check("prk_visibility_bounds", self._L.prk_visibility_bounds(
+            self._h, bp, b.shape[0], xp, 0 if xf is None else xf.shape[0],
+            None if Pc is None else C.cast(Pc, C.c_void_p), _ptr(out)))
+        return out
+
+    def visibility_bounds_device(self):
+        """prk_visibility_bounds_device: (pixels_ptr, count) -- the last
+        answer's device array, valid until the next visibility_bounds or
+        target change."""
+        pp, n = C.c_void_p(), C.c_uint32(0)
+        _check("prk_visibility_bounds_device", self._L.prk_visibility_bounds_device(self._h, C.byref(pp), C.byref(n)))
+        return pp.value or 0, n.value
+
+    def ztiles(self):
+        """prk_debug_ztiles: (zmin float32 [tiles_y, tiles_x], first tile row)
+        of the last visibility_bounds."""
+        tx, ty, t0 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _check("prk_debug_ztiles", self._L.prk_debug_ztiles(self._h, None, 0, C.byref(tx), C.byref(ty), C.byref(t0)))
+        out = np.zeros((ty.value, tx.value), np.float32)
+        _check("prk_debug_ztiles", self._L.prk_debug_ztiles(self._h, _ptr(out), out.size, C.byref(tx), C.byref(ty),
+                                                            C.byref(t0)))
+        return out, t0.value
+
+    def bounds_ms(self):
+        """prk_debug_bounds_ms: (ztile_ms, test_ms), the device times of the
+        last visibility_bounds' two kernels."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        _check("prk_debug_bounds_ms", self._L.prk_debug_bounds_ms(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def geometry_select_bounds(self, src, dst, items, levels, xforms, dst_first_tri=0):
+        """prk_geometry_select_bounds: geometry_select from the last frame's
+        counts, except that an item with id_count == 0 takes its word of the
+        last visibility_bounds (one box an item).  Returns (total, chosen
+        int32 [n], out_first uint32 [n + 1])."""
+        (it, lv, xf), (ip, lp, xp) = _select_tables(items, levels, xforms)
+        n = it.shape[0]
+        chosen, first = np.zeros(n, np.int32), np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        _check("prk_geometry_select_bounds", self._L.prk_geometry_select_bounds(
+            self._h, src, dst, int(dst_first_tri), ip, n, lp, 0 if lv is None else lv.shape[0], xp,
+            0 if xf is None else xf.shape[0], _ptr(chosen), _ptr(first), C.byref(total)))
+        return total.value, chosen, first
 
     # ---- state ------------------------------------------------------------
     def set_camera(self, transform, lights):

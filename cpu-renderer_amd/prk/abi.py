@@ -148,6 +148,27 @@ SELECT_SIGS = {
     "prk_debug_select_ms": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)],
 }
 
+class PrkBound(C.Structure):
+    """prk_bound: an axis-aligned box lo .. hi in the space of its matrix."""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("xform", C.c_uint32)]
+
+
+# The bounds occlusion test (prk.h): each entry point and its argument types
+BOUNDS_SIGS = {
+    "prk_visibility_bounds": [C.c_void_p, C.POINTER(PrkBound), C.c_uint32, C.POINTER(PrkXform), C.c_uint32,
+                              C.c_void_p, C.c_void_p],
+    "prk_visibility_bounds_device": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)],
+    "prk_geometry_select_bounds": [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(PrkSelectItem),
+                                   C.c_uint32, C.POINTER(PrkSelectLevel), C.c_uint32, C.POINTER(PrkXform),
+                                   C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)],
+    "prk_debug_ztiles": [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                         C.POINTER(C.c_int32)],
+    "prk_debug_bounds_ms": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "prk_selftest_bounds": [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                            C.POINTER(PrkTransform), C.c_void_p, C.POINTER(PrkBound), C.c_uint32,
+                            C.POINTER(PrkXform), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)],
+}
+
 # Render to texture (prk.h): each entry point and its argument types
 TEXTURE_TARGET_SIGS = {
     "prk_texture_alloc": [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)],

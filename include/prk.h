@@ -622,9 +622,9 @@ int prk_debug_transform_ms(prk_context *ctx, float *kernel_ms);
  *
  * Ids after a compacted draw: after prk_draw(dst, dst_first_tri, total, ...)
  * as the frame's first draw, item i's ids next frame are
- * [out_first[i] - dst_first_tri, +n(i)).  A dropped item has no ids; it comes
- * back only if the caller gives it a level with min_pixels == 0 again -- the
- * caller's policy, every k-th frame for instance.
+ * [out_first[i] - dst_first_tri, +n(i)).  A dropped item has no ids and leaves
+ * no pixels to count: whether it could be seen again is answered by
+ * prk_visibility_bounds, and acted on by prk_geometry_select_bounds (below).
  * Band contexts: a band context's frame counts cover its own rows only; ranks
  * that must draw the same geometry pass the summed counts as item_pixels.
  *
@@ -646,6 +646,103 @@ int prk_geometry_select(prk_context *ctx, int32_t src, int32_t dst, uint32_t dst
  * the total (uploads, choice, scan), emit_ms its emit pass alone (0 when the
  * total was 0); waits for the pass.  PRK_ERR_ARG before any such call. */
 int prk_debug_select_ms(prk_context *ctx, float *choose_ms, float *emit_ms);
+
+/* Bounds occlusion test on the device: bring culled items back.  An EXTENSION
+ * of this build with its own definition.  An item that was
+ * not drawn has no pixels to count; this call tests its bounding box against
+ * the depth the target holds now, without moving the z-buffer to the host.
+ * Pixel counts rule the items that were drawn, this test the ones that were
+ * not.  The library still decides nothing: boxes, padding and thresholds are
+ * the caller's.
+ *
+ * Z TILES.  The target band, rows [row0, row1) of the W x H frame, is cut into
+ * tiles of 8 x 8 pixels aligned to frame coordinates: tile (tx, ty) covers
+ * x in [8tx, 8tx + 8) ^ [0, W) and y in [8ty, 8ty + 8) ^ [row0, row1).
+ * zmin[ty][tx] is the smallest non-NaN z word of the tile's pixels, or +inf if
+ * every word is NaN.  -0.0 and +0.0 are one value (either may be stored);
+ * denormals compare by value.  W need not be a multiple of 8, row0 need not
+ * be one, and the z pointer of a caller-bound target need only be 4-byte
+ * aligned.  The map has tiles_x = (W + 7) / 8 columns and the tile rows
+ * row0 / 8 ... (row1 + 7) / 8 - 1.
+ *
+ * BOUNDS.  Item i has 8 corners, every choice of lo / hi per axis.  Each goes
+ * through xforms[bound.xform] in exactly prk_geometry_transform's position
+ * arithmetic (((M[i][0]*x + M[i][1]*y) + M[i][2]*z) + M[i][3], nothing fused),
+ * then + P component by component as a draw adds its P (a NULL P is 0), then
+ * through ProjectVertex under prk_set_camera's transform as it stands at the
+ * call: d = D - z; if d > 0.2: k = (1 / d) * F, px = Cx + M2P * (k * x),
+ * py = Cy + M2P * (k * y).
+ * znear(i) is the largest camera-space z (after + P, before projection) of the
+ *   8 corners, NaN if any of them is NaN.  The z-buffer holds camera-space z,
+ *   and a larger z is nearer (z > zbuf wins; clears are -FLT_MAX).
+ * rect(i) is x0 = floor(min px) - 1, x1 = floor(max px) + 2 and the same in
+ *   y, half-open, each of the four clamped in float (max with the low edge,
+ *   then min with the high edge) to [0, W] and [row0, row1] before any integer
+ *   conversion.  The pixel of margin on each side absorbs the fill rules.  If
+ *   any corner fails d > 0.2 (a NaN d included) or any projected coordinate
+ *   is NaN, rect(i) is the whole band.
+ * pixels(i) is the sum of area(rect(i) ^ t) over the tiles t that meet rect(i)
+ *   and satisfy !(znear(i) < zmin[t]).  Equality passes: the single-thread
+ *   semantics draw on >=, and an item tested against a frame that holds its
+ *   own flat face must not hide itself.  A NaN znear passes everywhere.  An
+ *   empty rectangle gives 0.
+ * pixels(i) is an upper bound on the pixels any geometry inside the box could
+ * win over the target's current z, and 0 only if the box cannot win a pixel --
+ * exact up to the rounding of the rasteriser's span recurrences (an edge's x
+ * and z are stepped row by row in f32 and may leave the hull of the vertices
+ * by a few ulps).  PADDING THE BOX AGAINST THAT ROUNDING IS THE CALLER'S JOB.
+ * A band context answers for its own rows on band-clipped tiles; the sum over
+ * ranks is again an upper bound, and equals the one-context answer only when
+ * the band edges are multiples of 8.
+ *
+ * prk_visibility_bounds.  Ordering is prk_layer_from_target's, except that the
+ * call waits for its result: the pending frame is resolved first (an
+ * overflowed one is re-run); the two kernels run after the frames already
+ * flushed and after the clears, uploads and layer calls queued so far; a
+ * prk_target_clear_on_flush not flushed yet is not in what the call reads.
+ * The tile map is rebuilt at every call.  The answer -- count words on the
+ * device, and in `pixels` if that is not NULL -- is complete when the call
+ * returns and stays valid until the next prk_visibility_bounds,
+ * prk_target_alloc, prk_target_bind or prk_destroy.  A later prk_flush does
+ * not invalidate it: which z it was tested against is the caller's business.
+ * Errors are decided on the host, nothing written and the previous answer as
+ * it was: PRK_ERR_ARG for a NULL context, NULL bounds or xforms with
+ * count > 0, a bound's xform >= xform_count, a call before any
+ * prk_set_camera; PRK_ERR_NO_TARGET without a target; PRK_ERR_LIMIT for a
+ * band of 2^32 pixels or more.  count == 0: PRK_OK and an empty answer.
+ * prk_visibility_bounds_device: the answer's device array and its count
+ * (read-only; PRK_ERR_ARG when there is none).
+ *
+ * prk_geometry_select_bounds is prk_geometry_select with item_pixels == NULL,
+ * except that an item with id_count == 0 takes pixels(i) = answer[i] of the
+ * last prk_visibility_bounds.  PRK_ERR_ARG if there is no answer or its count
+ * is not item_count.  A frame is needed only when some item has
+ * id_count > 0 (its ids are then checked against the frame's for every item,
+ * as there).  Everything else is prk_geometry_select's, word for word:
+ * chosen, out_first, the emit arithmetic, the errors from worst cases, the
+ * ordering, and dst left untouched when the total is 0.
+ *
+ * Debug/bench: prk_debug_ztiles copies the last call's tile map (row-major,
+ * tiles_y rows of tiles_x; zmin NULL: the sizes only; a capacity in floats
+ * below tiles_x * tiles_y: PRK_ERR_ARG) and says which tile row is its first;
+ * prk_debug_bounds_ms gives the device times of the last call's two kernels
+ * (test_ms 0 when count was 0).  Both are PRK_ERR_ARG before any call. */
+typedef struct prk_bound {
+    float lo[3], hi[3];
+    uint32_t xform; /* index into the call's xforms */
+} prk_bound;
+int prk_visibility_bounds(prk_context *ctx, const prk_bound *bounds, uint32_t count,
+                          const prk_xform *xforms, uint32_t xform_count, const float *P,
+                          uint32_t *pixels);
+int prk_visibility_bounds_device(prk_context *ctx, const uint32_t **pixels, uint32_t *count);
+int prk_geometry_select_bounds(prk_context *ctx, int32_t src, int32_t dst, uint32_t dst_first_tri,
+                               const prk_select_item *items, uint32_t item_count,
+                               const prk_select_level *levels, uint32_t level_count,
+                               const prk_xform *xforms, uint32_t xform_count,
+                               int32_t *chosen, uint32_t *out_first, uint64_t *total_tris_out);
+int prk_debug_ztiles(prk_context *ctx, float *zmin, uint64_t capacity, int32_t *tiles_x, int32_t *tiles_y,
+                     int32_t *first_tile_row);
+int prk_debug_bounds_ms(prk_context *ctx, float *ztile_ms, float *test_ms);
 
 /* Record one draw: triangles [first_tri, first_tri+tri_count) of a geometry,
  * object offset P (render_entry_3d_object::P), semantics PRK_SEM_*,
@@ -987,6 +1084,21 @@ int prk_selftest_select(int32_t device, const uint32_t *pix_prefix, uint32_t id_
                         const float *src_uvs, uint32_t src_tris, uint32_t dst_first_tri, uint32_t dst_tris,
                         float *dst_vertices, float *dst_colors, float *dst_normals, float *dst_uvs,
                         int32_t *chosen, uint32_t *out_first, uint64_t *total_tris_out, uint32_t *damage);
+/* Test: prk_visibility_bounds' two kernels (csrc/prk_bounds.hip) on
+ * host-supplied inputs, synchronously on `device`, no context needed, guarded
+ * and compared as above.  z: the band's width * (row1 - row0) words, placed
+ * z_offset floats (at most 1024) into their device buffer, so that 1 gives the
+ * kernel a base that is only 4-byte aligned.  zmin: (width + 7) / 8 columns by
+ * (row1 + 7) / 8 - row0 / 8 rows; pixels: count words.  *damage: an input
+ * changed or its guard did; the guard after zmin or pixels changed.
+ * PRK_ERR_ARG: a NULL required pointer (P may be NULL: 0), a bad device or
+ * band, a bound's xform >= xform_count.  PRK_ERR_LIMIT as
+ * prk_visibility_bounds.  tests/test_gpu_bounds.py holds every word to
+ * tests/boundsref.py, *damage == 0. */
+int prk_selftest_bounds(int32_t device, const float *z, int32_t width, int32_t height, int32_t row0,
+                        int32_t row1, uint32_t z_offset, const prk_transform *transform, const float *P,
+                        const prk_bound *bounds, uint32_t count, const prk_xform *xforms,
+                        uint32_t xform_count, float *zmin, uint32_t *pixels, uint32_t *damage);
 
 /* The bound target (any pointer may be NULL) and the context's device and
  * own stream (a hipStream_t; prk_flush(ctx, NULL) runs on it). */
