@@ -6,8 +6,8 @@
 // queues its pass -- after the frames already flushed and after the clears,
 // uploads and layer calls queued so far -- and waits.  The tile map belongs to
 // the target and is rebuilt at every call: nothing here reads or writes
-// VisState.  (prk_selftest_bounds, with the other self-tests, is in
-// prk_api.hip; prk_geometry_select_bounds is in prk_select_api.hip.)
+// VisState.  (prk_selftest_bounds is in prk_selftest.hip;
+// prk_geometry_select_bounds is in prk_select_api.hip.)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -61,9 +61,7 @@ int prk_visibility_bounds(prk_context *c, const prk_bound *bounds, uint32_t coun
     S.answered = false;  // (a failure from here on leaves no answer)
     uint8_t *tab = S.d_tab.as<uint8_t>();
     hipStream_t s = c->copy_stream;
-    if (c->read_rec) PRK_TRY(hipStreamWaitEvent(s, c->read_ev, 0));
-    PRK_TRY(hipEventRecord(c->s_mark, c->own_stream));
-    PRK_TRY(hipStreamWaitEvent(s, c->s_mark, 0));
+    PRK_TRY(side_begin(c, true));  // (the target form; no side_end: the pass only reads, and the call waits)
     if (count) {
         PRK_TRY(hipMemcpyAsync(tab, xforms, xb, hipMemcpyHostToDevice, s));
         PRK_TRY(hipMemcpyAsync(tab + b_off, bounds, bb, hipMemcpyHostToDevice, s));

@@ -1,14 +1,16 @@
 // prk_ctx.h — the host runtime's own header: struct prk_context (opaque in
 // include/prk.h) with the resources and scratch it owns, the state a pass is
-// queued with, and the few host functions that cross the host files
-// (prk_api.hip, prk_flush.hip, prk_span_pass.hip, prk_record_api.hip,
-// prk_visibility_api.hip, prk_select_api.hip, prk_bounds_api.hip).  Host
-// only; prk_launch.h stays the seam to the kernel files (prk_types.h: the
-// records the buffers here hold), and prk_dist.hip keeps the context opaque.
+// queued with, the ordering of the side passes between frames (side_begin),
+// and the few host functions that cross the host files (prk_api.hip,
+// prk_target_api.hip, prk_geometry_api.hip, prk_selftest.hip, prk_flush.hip,
+// prk_span_pass.hip, prk_record_api.hip, prk_visibility_api.hip,
+// prk_select_api.hip, prk_bounds_api.hip).  Host only; prk_launch.h stays the
+// seam to the kernel files (prk_types.h: the records the buffers here hold),
+// and prk_dist.hip keeps the context opaque.
 //
 // Nothing here reaches the library's dynamic symbol table: the helper types
 // and inline functions sit in a hidden-visibility region (one definition for
-// the four files, none exported), the cross-file functions are declared
+// the host files, none exported), the cross-file functions are declared
 // hidden one by one.  Only prk_context itself keeps default visibility.
 #pragma once
 
@@ -78,6 +80,7 @@ struct Geometry {
     uint32_t cap[4] = {0, 0, 0, 0};  // owned V / C / N / UV buffers hold this many vertices
     bool owned = false;
 };
+constexpr size_t kGeomComp[4] = {3, 4, 3, 2};  // floats a vertex in V / C / N / UV
 
 struct Texture {
     uint8_t *mem = nullptr;
@@ -165,6 +168,17 @@ struct VisState {
     uint64_t covered = 0;
 };
 
+// prk_geometry_transform (prk_geometry_api.hip): its tables (scan, runs, matrices),
+// staged in pinned memory and copied on copy_stream ahead of the kernel.
+struct XformState {
+    DevBuf d_tab;
+    void *h_tab = nullptr;
+    size_t h_cap = 0;
+    hipEvent_t copied_ev = nullptr;  // the staging has been copied (the next call refills it)
+    hipEvent_t end_ev = nullptr;     // after the kernel (timed from copied_ev: prk_debug_transform_ms)
+    bool busy = false;
+};
+
 // prk_geometry_select (prk_select_api.hip): the call's tables as uploaded, what
 // the device builds from them (chosen, n, start, the runs) and the scan's
 // scratch, all reused call to call; the emit pass of one call reads them
@@ -216,19 +230,25 @@ struct PassState {
 struct prk_context : PassState {  // (the target, tile, cameras, lights, clear and debug flag: PassState)
     int device = 0;
     hipStream_t own_stream = nullptr;
-    // prk_geometry_write: copies on copy_stream after read_ev (the end of the
-    // last flush); the next flush's streams wait for in_ev
+    // Side passes: work queued between frames, without waiting, on what frames
+    // read or write.  It runs on copy_stream between side_begin() and side_end().
+    //   Geometry form (prk_geometry_write, prk_geometry_transform, the emit pass
+    //   of prk_geometry_select): the pass waits for read_ev, which prk_flush (and
+    //   a re-run, resolve_count) records on the flush stream at the frame's end;
+    //   read_rec: there is such a record (geometry_grow drops it once the device
+    //   is idle).  prk_resolve_pending's gather stream waits for it too.
+    //   Target form (prk_target_upload_async, prk_texture_from_target, the layer
+    //   passes, prk_visibility_bounds): the pass touches the target, so it also
+    //   waits for s_mark, recorded on own_stream then: the clears and uploads
+    //   queued so far.  (s_mark is a scratch event; flush_tris' vis stream waits
+    //   on it the same way for the flush stream's work so far.)
+    // side_end() records in_ev after the work and sets in_wait; side_wait() is
+    // the wait for it: the three streams of the next prk_flush, which then
+    // clears in_wait, and prk_target_clear (prk_target_upload joins it on the
+    // host).  prk_visibility_bounds only reads and waits itself: no side_end().
     hipStream_t copy_stream = nullptr;
-    hipEvent_t in_ev = nullptr, read_ev = nullptr;
-    bool in_wait = false, read_rec = false;
-    // prk_geometry_transform's tables (scan, runs, matrices): staged in pinned
-    // memory, copied on copy_stream ahead of the kernel; xf_ev: that copy is
-    // done (the next call refills the staging)
-    DevBuf d_xform;
-    void *h_xform = nullptr;
-    size_t h_xform_cap = 0;
-    hipEvent_t xf_ev = nullptr, xf_end_ev = nullptr;  // (timed: prk_debug_transform_ms)
-    bool xf_busy = false;
+    hipEvent_t read_ev = nullptr, in_ev = nullptr, s_mark = nullptr;
+    bool read_rec = false, in_wait = false;
     bool owns_target = false;
     bool have_camera = false;
     // resources
@@ -287,7 +307,6 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     bool early_z = false;  // prk_set_early_z
     bool z_early = false;
     int z_slot = -1;
-    hipEvent_t s_mark = nullptr;  // flush-stream point the bin stream waits for (prior target contents)
     uint32_t *h_total = nullptr;  // pinned
     uint32_t pair_hint = 0;       // entry count of the last frame (counting-sort capacity)
     // Automatic tile (until prk_set_tile): 256x8, or narrower tiles for frames
@@ -311,6 +330,7 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
     bool setup_rec = true;
     bool winners_valid = false;
     VisState vis;
+    XformState xf;
     SelState sel;
     BoundsState bnd;
     prk_stats stats{};
@@ -398,6 +418,31 @@ struct prk_context : PassState {  // (the target, tile, cameras, lights, clear a
 PRK_HIDDEN inline PassState pass_state(const prk_context *c) { return *c; }
 PRK_HIDDEN inline void apply_pass_state(prk_context *c, const PassState &p) { static_cast<PassState &>(*c) = p; }
 
+// The side passes' ordering (the rule: prk_context::copy_stream); after_own_stream is the target form.
+PRK_HIDDEN inline hipError_t side_begin(prk_context *c, bool after_own_stream) {
+    hipError_t e = c->read_rec ? hipStreamWaitEvent(c->copy_stream, c->read_ev, 0) : hipSuccess;
+    if (e == hipSuccess && after_own_stream) e = hipEventRecord(c->s_mark, c->own_stream);
+    if (e == hipSuccess && after_own_stream) e = hipStreamWaitEvent(c->copy_stream, c->s_mark, 0);
+    return e;
+}
+PRK_HIDDEN inline hipError_t side_end(prk_context *c) {
+    const hipError_t e = hipEventRecord(c->in_ev, c->copy_stream);
+    if (e == hipSuccess) c->in_wait = true;
+    return e;
+}
+PRK_HIDDEN inline hipError_t side_wait(const prk_context *c, hipStream_t s) {
+    return c->in_wait ? hipStreamWaitEvent(s, c->in_ev, 0) : hipSuccess;
+}
+
+// `device` among the devices there are: PRK_ERR_DEVICE without any,
+// PRK_ERR_ARG outside them; it is then made current (unless `set` is off).
+PRK_HIDDEN inline int use_device(int device, bool set = true) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PRK_ERR_DEVICE;
+    if (device < 0 || device >= ndev) return PRK_ERR_ARG;
+    return set ? status_of(hipSetDevice(device)) : PRK_OK;
+}
+
 // The texture table as the kernels read it (FrameParams texs), from the
 // context's textures: one entry a handle.
 PRK_HIDDEN inline void tex_table(const prk_context *c, std::vector<prk::TexRec> &out) {
@@ -417,33 +462,37 @@ PRK_HIDDEN hipError_t launch_fill_target(void *color, int32_t pitch, float *z, i
 // prk_span_pass.hip
 PRK_HIDDEN int flush_spans(prk_context *c, hipStream_t s, const std::vector<prk::DrawRec> &draws, uint32_t T,
                            uint32_t win_base);
-// prk_api.hip
+// prk_api.hip: the draw recorders' and the timing ring's
 PRK_HIDDEN void harvest(prk_context *c, int slot);
 PRK_HIDDEN int draw_src(prk_context *c, uint32_t kind, uint32_t off, uint32_t n, uint32_t ids, int32_t semantics,
                         int32_t phong, int32_t texture);
 PRK_HIDDEN bool list_walks_sorted(const prk_edge *e, uint32_t n);
 PRK_HIDDEN int rows_to_spans(prk_context *c, const prk_row *rows, uint32_t nrow, const prk_row_pair *pairs,
                              uint32_t npair, prk_span *out, void *keep = nullptr);
-// Room for `end` vertices in a library-owned geometry's arrays that exist or are wanted now.
+// prk_geometry_api.hip: room for `end` vertices in a library-owned geometry's arrays that exist or are wanted now.
 PRK_HIDDEN int geometry_grow(prk_context *c, int32_t handle, const bool want[4], uint32_t end);
 // prk_visibility_api.hip: the frame's answer, reduced if this is the first query since its flush.
 PRK_HIDDEN int vis_ready(prk_context *c);
-// prk_select_api.hip: prk_geometry_select's table checks (the self-test runs them too).
+// prk_select_api.hip: prk_geometry_select's table checks (prk_selftest.hip runs them too).
 PRK_HIDDEN int select_check(const prk_select_item *items, uint32_t item_count, const prk_select_level *levels,
                             uint32_t level_count, const prk_xform *xforms, uint32_t xform_count, uint32_t src_tris,
                             const uint32_t *frame_ids, uint64_t *worst);
-// prk_bounds_api.hip: prk_visibility_bounds' band and camera record (false: a band of 2^32 pixels or more).
+// prk_bounds_api.hip: prk_visibility_bounds' band and camera record (false: a band of 2^32 pixels or more;
+// prk_selftest.hip builds its own with it).
 PRK_HIDDEN bool bounds_frame(int32_t W, int32_t row0, int32_t row1, const prk_transform &t, const float P[3],
                              prk::BoundsFrame *out);
 }  // extern "C"
 
+// A status passed on unless it is PRK_OK.
+#define PRK_CHECK(expr)                \
+    do {                               \
+        const int _rc = (expr);        \
+        if (_rc != PRK_OK) return _rc; \
+    } while (0)
+
 // Calls that read or replace the target, or change what a re-run of the
 // pending pass would read, first resolve its count (PendingCount).
-#define RESOLVE_COUNT(c)                             \
-    do {                                             \
-        const int _rc = resolve_count(c);            \
-        if (_rc != PRK_OK) return _rc;               \
-    } while (0)
+#define RESOLVE_COUNT(c) PRK_CHECK(resolve_count(c))
 
 #define PRK_TRY(expr)                              \
     do {                                           \

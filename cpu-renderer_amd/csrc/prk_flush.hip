@@ -547,12 +547,11 @@ int prk_flush(prk_context *c, void *stream) {
         c->tile_h = 8;
     }
     hipStream_t s = stream ? (hipStream_t)stream : c->own_stream;
-    if (c->in_wait) {  // prk_geometry_write copies still in flight: every stream of the frame waits for them
-        PRK_TRY(hipStreamWaitEvent(s, c->in_ev, 0));
-        PRK_TRY(hipStreamWaitEvent(c->bin_stream, c->in_ev, 0));
-        PRK_TRY(hipStreamWaitEvent(c->vis_stream, c->in_ev, 0));
-        c->in_wait = false;
-    }
+    // side passes still in flight: every stream of the frame waits for them
+    PRK_TRY(side_wait(c, s));
+    PRK_TRY(side_wait(c, c->bin_stream));
+    PRK_TRY(side_wait(c, c->vis_stream));
+    c->in_wait = false;
     bool any_avx = false;
     for (const auto &d : c->draws) any_avx |= d.mode == prk::MODE_AVX;
     if (any_avx && (c->W % 8)) return PRK_ERR_UNSUPPORTED;  // aligned 8-wide z load, projekt.cpp:2218

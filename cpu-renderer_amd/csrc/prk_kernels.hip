@@ -1823,7 +1823,7 @@ __global__ void k_selftest_ops(int32_t op, uint32_t n, const uint32_t *pa, const
 }  // namespace prk
 
 // ---------------------------------------------------------------------------
-// Launchers (called from prk_flush.hip and prk_api.hip).
+// Launchers (called from prk_flush.hip and prk_selftest.hip).
 // ---------------------------------------------------------------------------
 extern "C" {
 

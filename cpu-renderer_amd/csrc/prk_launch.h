@@ -1,6 +1,6 @@
-// prk_launch.h — the seam between the host runtime (prk_api.hip, prk_flush.hip,
-// prk_span_pass.hip and prk_record_api.hip, which share the context through
-// prk_ctx.h, and prk_dist.hip, which keeps it opaque) and the kernel files:
+// prk_launch.h — the seam between the host runtime (the host files that share
+// the context through prk_ctx.h, which lists them, and prk_dist.hip, which
+// keeps it opaque) and the kernel files:
 // every extern "C" launcher and query that one file defines and another
 // calls, and the constants both sides rely on.  The records that cross it are
 // prk_types.h's, and the prototypes name them: a buffer of the wrong record

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kLanes *kRows) void k_layer(const uint8_t *__restri
 
 }  // namespace
 
-// The caller (prk_api.hip) has checked both rectangles against the layer and
+// The caller (prk_target_api.hip) has checked both rectangles against the layer and
 // the target's band; rule is a PRK_MERGE_*; w, h > 0.
 extern "C" hipError_t prk_layer_launch(const void *src_color, size_t src_cpitch, const float *src_z, size_t src_zpitch,
                                        void *dst_color, size_t dst_cpitch, float *dst_z, size_t dst_zpitch, uint32_t w,

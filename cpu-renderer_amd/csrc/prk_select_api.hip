@@ -5,8 +5,8 @@
 // and the scan (prk_select.hip) on the geometry stream and waits for one
 // word, the triangle total; it then sizes dst and the grid from it and queues
 // the emit pass as prk_geometry_transform queues its pass, without waiting.
-// (prk_selftest_select, with the other self-tests, is in prk_api.hip; both
-// run select_check and the launchers of prk_launch.h.)
+// (prk_selftest_select is in prk_selftest.hip; both run select_check and the
+// launchers of prk_launch.h.)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -67,16 +67,12 @@ static int select_body(prk_context *c, int32_t src, int32_t dst, uint32_t dst_fi
         for (uint32_t i = 0; i < item_count && !frame; ++i) frame = items[i].id_count != 0;
     }
     if (frame) {  // the frame's counts: there must be a frame (reduced here if no query has yet)
-        const int rc = vis_ready(c);
-        if (rc != PRK_OK) return rc;
+        PRK_CHECK(vis_ready(c));
         frame_ids = c->vis.id_count;
     }
     uint64_t worst = 0;
-    {
-        const int rc = select_check(items, item_count, levels, level_count, xforms, xform_count, src_tris,
-                                    frame ? &frame_ids : nullptr, &worst);
-        if (rc != PRK_OK) return rc;
-    }
+    PRK_CHECK(select_check(items, item_count, levels, level_count, xforms, xform_count, src_tris,
+                           frame ? &frame_ids : nullptr, &worst));
     if (worst && !c->geoms[src].V) return PRK_ERR_ARG;  // (a geometry written without positions)
     // (the total first: 2^31 triangles are past the vertex limit wherever they start)
     if (worst > (1ull << 31)) return PRK_ERR_LIMIT;
@@ -138,19 +134,15 @@ static int select_body(prk_context *c, int32_t src, int32_t dst, uint32_t dst_fi
         const bool has[4] = {sg.V != nullptr, sg.C != nullptr, sg.N != nullptr, sg.UV != nullptr};
         const uint32_t endv = (uint32_t)(((uint64_t)dst_first_tri + total) * 3);
         const uint32_t end = std::max<uint32_t>(c->geoms[dst].vertex_count, endv);
-        {
-            const int rc = geometry_grow(c, dst, has, end);
-            if (rc != PRK_OK) return rc;
-        }
+        PRK_CHECK(geometry_grow(c, dst, has, end));
         Geometry &d = c->geoms[dst];
-        // ordered as prk_geometry_transform's pass: after read_ev, the next flush waits for in_ev
-        if (c->read_rec) PRK_TRY(hipStreamWaitEvent(s, c->read_ev, 0));
+        // a side pass in the geometry form, as prk_geometry_transform's (s is copy_stream)
+        PRK_TRY(side_begin(c, false));
         PRK_TRY(hipEventRecord(S.ev[2], s));
         PRK_TRY(prk_sel_emit(d_start, d_runs, item_count, total, dst_first_tri, d_xf, sg.V, sg.C, sg.N, sg.UV,
                              (float *)d.V, (float *)d.C, (float *)d.N, (float *)d.UV, s));
         PRK_TRY(hipEventRecord(S.ev[3], s));
-        PRK_TRY(hipEventRecord(c->in_ev, s));
-        c->in_wait = true;
+        PRK_TRY(side_end(c));
         d.vertex_count = end;
     }
     S.timed = true;

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kQuads *kRows) void k_tex_from_target(const uint8_t
 
 }  // namespace
 
-// The caller (prk_api.hip) has checked both rectangles against the target's
+// The caller (prk_target_api.hip) has checked both rectangles against the target's
 // band and the texture; factor is 1, 2 or 4; dw, dh > 0.
 extern "C" hipError_t prk_tex_from_target_launch(const void *src, size_t spitch, void *dst, size_t dpitch,
                                                  uint32_t dw, uint32_t dh, int32_t factor, hipStream_t s) {

@@ -5,7 +5,7 @@
 // reduces the map (prk_visibility.hip: histogram, flags, two scans, compact)
 // into the context's VisState and waits; later queries of the same frame are
 // host copies from those arrays, plus k_vis_groups for caller ranges.
-// (prk_selftest_visibility, with the other self-tests, is in prk_api.hip.)
+// (prk_selftest_visibility is in prk_selftest.hip.)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,8 +53,7 @@ extern "C" {
 
 int prk_visibility_info(prk_context *c, uint32_t *id_count, uint64_t *covered, uint32_t *visible_ids) {
     if (!c || !id_count || !covered || !visible_ids) return PRK_ERR_ARG;
-    const int rc = vis_ready(c);
-    if (rc != PRK_OK) return rc;
+    PRK_CHECK(vis_ready(c));
     *id_count = c->vis.id_count;
     *covered = c->vis.covered;
     *visible_ids = c->vis.visible;
@@ -63,8 +62,7 @@ int prk_visibility_info(prk_context *c, uint32_t *id_count, uint64_t *covered, u
 
 int prk_visibility_counts(prk_context *c, uint32_t first_id, uint32_t count, uint32_t *pixels) {
     if (!c || (!pixels && count)) return PRK_ERR_ARG;
-    const int rc = vis_ready(c);
-    if (rc != PRK_OK) return rc;
+    PRK_CHECK(vis_ready(c));
     if ((uint64_t)first_id + count > c->vis.id_count) return PRK_ERR_ARG;
     if (count)
         PRK_TRY(hipMemcpy(pixels, c->vis.d_counts.as<uint32_t>() + first_id, (size_t)count * 4, hipMemcpyDeviceToHost));
@@ -74,8 +72,7 @@ int prk_visibility_counts(prk_context *c, uint32_t first_id, uint32_t count, uin
 int prk_visibility_groups(prk_context *c, const uint32_t *starts, uint32_t group_count, uint32_t *pixels,
                           uint32_t *visible) {
     if (!c || !starts || (!pixels && !visible)) return PRK_ERR_ARG;
-    const int rc = vis_ready(c);
-    if (rc != PRK_OK) return rc;
+    PRK_CHECK(vis_ready(c));
     VisState &V = c->vis;
     for (uint32_t g = 0; g < group_count; ++g)
         if (starts[g] > starts[g + 1]) return PRK_ERR_ARG;
@@ -100,8 +97,7 @@ int prk_visibility_groups(prk_context *c, const uint32_t *starts, uint32_t group
 int prk_visibility_ids(prk_context *c, uint32_t *ids, uint64_t capacity, uint64_t *total_out) {
     if (!c || !total_out) return PRK_ERR_ARG;
     *total_out = 0;
-    const int rc = vis_ready(c);
-    if (rc != PRK_OK) return rc;
+    PRK_CHECK(vis_ready(c));
     const uint32_t total = c->vis.visible;
     *total_out = total;
     if (!ids) return PRK_OK;  // the size only
@@ -112,8 +108,7 @@ int prk_visibility_ids(prk_context *c, uint32_t *ids, uint64_t capacity, uint64_
 
 int prk_visibility_device(prk_context *c, const uint32_t **counts, const uint32_t **pix_prefix, uint32_t *id_count) {
     if (!c || !counts || !pix_prefix || !id_count) return PRK_ERR_ARG;
-    const int rc = vis_ready(c);
-    if (rc != PRK_OK) return rc;
+    PRK_CHECK(vis_ready(c));
     *counts = c->vis.d_counts.as<uint32_t>();
     *pix_prefix = c->vis.d_pix.as<uint32_t>();
     *id_count = c->vis.id_count;

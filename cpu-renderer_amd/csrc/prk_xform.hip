@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kThreads) void k_xform(const uint32_t *__restrict__
 
 }  // namespace
 
-// Host-side layout of the tables in one device buffer (prk_api.hip fills it):
+// Host-side layout of the tables in one device buffer (prk_geometry_api.hip fills it):
 // words [0, nruns]: the scan (nruns + 1 words, the last the total); runs at
 // byte runs_off (16 bytes each); matrices at byte xf_off (48 bytes each);
 // both offsets multiples of 16.
